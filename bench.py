@@ -8,8 +8,15 @@ Contract (driver):  python bench.py --gpus N --steps K --warmup W
   enqueued at once on their own streams) over one clip of synthetic frames per GPU.  Frames shard by rank with no data-path
   collective; the only exchange is the all-gather of the per-frame min/max scalars (RCCL).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`, the per-band completion times of
+the step).  --full adds everything else the line used to carry: the labelled sequential pass behind `roofline` / `kernel_*`, socket
+power, the PCIe-inclusive and batch-1 latency legs, the clock probe, the other precision mode and the CPU baseline.
+--dump-outputs DIR writes what the last timed step computed (rank 0) as float32 .npy files; the inputs are seeded, so two builds
+can be compared output for output.
 """
 import argparse
+import contextlib
 import json
 import os
 import sys
@@ -361,6 +368,19 @@ def pmc_clocks(fam_keys):
 SYMBOLS = {"attention": "attnq_kernel<1, 2, 0, false, 8>", "layernorm": "layernorm_kernel", "elementwise": "(bilinear, instance-norm, lookup, ... kernels)",
            "prepost": "(pre- / post-processing kernels)"}
 PREC_NAME = {0: "f16", 1: "split-f16"}
+DUMP_SAMPLE = 4 << 20          # elements kept of a larger --dump-outputs array: 16 MB of float32 each
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: device tensor} -> out_dir/<name>.npy as float32: whole when it has at most DUMP_SAMPLE elements, otherwise
+    out_dir/<name>_sample.npy = the elements at DUMP_SAMPLE sorted flat positions drawn from a generator seeded by the name (the same
+    positions in every run of the same shape)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        if t.numel() > DUMP_SAMPLE:
+            idx = np.sort(np.random.default_rng(list(name.encode())).integers(0, t.numel(), DUMP_SAMPLE))
+            t, name = t.reshape(-1)[torch.from_numpy(idx).to(t.device)], name + "_sample"
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -385,7 +405,7 @@ def main():
                          "child process next to its GPU work when the host has cores to spare")
     ap.add_argument("--gemm-tile", type=int, default=0, help="A/B switch: 0 auto, 1 128x128, 2 ping-pong 256x256, 9 256x64")
     ap.add_argument("--conv-tile", type=int, default=0)
-    ap.add_argument("--all-legs", action="store_true", help="also run the per-band legs below with their usual sizes (flow 720p, mask, pipeline, PCIe)")
+    ap.add_argument("--all-legs", action="store_true", help="also run the per-band legs below with their usual sizes (flow 720p, mask, pipeline, PCIe); with --full")
     ap.add_argument("--latency", action="store_true", default=True,
                     help="also time one 1280x720 frame at batch 1 (BASELINE configs[1]; on by default since round 4: eight batch-1 calls, ~0.1 s)")
     ap.add_argument("--no-latency", dest="latency", action="store_false")
@@ -403,11 +423,20 @@ def main():
     ap.add_argument("--mask-frames", type=int, default=0, help="frames per step of the mask_mmdet leg")
     ap.add_argument("--gmflow-pairs", type=int, default=0, help="frame pairs per GPU per step of the flow_gmflow leg (1080p x 0.75)")
     ap.add_argument("--flow-pairs", type=int, default=0, help="frame pairs per GPU per step of the 720p flow_raft leg (BASELINE configs[2])")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed steps, run everything else the line can carry: the labelled sequential pass (`sequential`, `roofline`, "
+                         "`kernel_*`), socket power, the PCIe-inclusive and batch-1 latency legs, the clock probe, the other precision mode and the "
+                         "CPU baseline (the switches above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (rank 0) to DIR/<name>.npy as float32: the per-frame depth min / max and flow "
+                         "max displacement in full, and a fixed seeded sample of %d elements of each encoded uint8 output" % DUMP_SAMPLE)
     args = ap.parse_args()
     if args.all_legs:
         args.latency = True
         args.pipeline_frames, args.mask_frames, args.flow_pairs = 32, 32, 8
         args.gmflow_pairs = args.gmflow_pairs or 15
+    if not args.full and (args.flow_pairs > 0 or args.mask_frames > 0 or args.gmflow_pairs > 0 or args.pipeline_frames > 1):
+        ap.error("the per-band legs (--all-legs, --flow-pairs, --mask-frames, --gmflow-pairs, --pipeline-frames) run with --full only")
 
     if args.cpu_baseline_only:
         from prisma_amd import synth
@@ -507,8 +536,8 @@ def main():
         for _ in range(warmup):
             step()
         from prisma_amd.power import PowerSampler
-        seq = None
-        with PowerSampler(local_rank) as ps:
+        seq = fam = None
+        with (PowerSampler(local_rank) if args.full else contextlib.nullcontext()) as ps:
             if args.sequential_only:
                 # every launch of the timed region is bracketed by HIP events on its band's stream; the records accumulate over the K
                 # steps and are read once after the closing barrier, so no event query sits inside the timed region
@@ -516,12 +545,16 @@ def main():
                 fn.set_profiling(timing=True, accumulate=True)
             t0, t1 = timed(step, steps)
         dt = t1 - t0
-        power = ps.window(t0, t1) if rank == 0 else None
+        power = ps.window(t0, t1) if args.full and rank == 0 else None
         depth_s, flow_s = band_s[0], band_s[1]
+        if args.dump_outputs and rank == 0:
+            # what a caller of the timed path receives from its last step, before any later pass writes the same buffers again
+            dump_outputs(args.dump_outputs, {"depth_rgb": d_rgb, "depth_min": scal[0], "depth_max": scal[1],
+                                             "flow_rgb": f_rgb, "flow_max_displacement": scal[2, :B - 1]})
         if args.sequential_only:
             fam = families()
             seq = {"dt": R.max_over_ranks(dt), "steps": steps, "depth_s": depth_s, "flow_s": flow_s}
-        else:
+        elif args.full:
             # the labelled sequential pass: not part of `value`; the per-symbol attribution of the same work on the same warm chip
             ns = max(1, min(args.seq_steps, steps))
             step_seq()
@@ -534,7 +567,7 @@ def main():
         sc = scal.cpu().numpy()
         assert np.isfinite(sc).all() and (sc[1] > sc[0]).all() and (sc[2, :B - 1] > 0).all(), "degenerate depth range / flow"
         res = {"dt": dt, "fam": fam, "depth_s": depth_s, "flow_s": flow_s, "seq": seq, "power": power}
-        if extras and rank == 0:
+        if extras and args.full and rank == 0:
             # PCIe-inclusive rate (never `value`; SURVEY 8(d) config 4: frames "resident in pinned host memory"): the SAME clip through the host-pointer
             # entry points of both bands (abi.hip: H2D, the band and D2H of a chunk on three streams) from page-locked frames into page-locked result
             # arrays, with the library's default chunking (a 32-frame clip is one chunk per band).
@@ -613,7 +646,7 @@ def main():
     # them; the driver's wall clock around this command is then mostly GPU time.  It starts only now: beside the timed
     # region it cost the depth band 20 ms of launch gaps on one box (r05z, first attempt).  Smaller hosts run it at the end, as before.
     cpu_child = None
-    if world == 1 and not args.no_cpu_baseline and (os.cpu_count() or 1) >= 48:
+    if args.full and world == 1 and not args.no_cpu_baseline and (os.cpu_count() or 1) >= 48:
         import subprocess
         cpu_child = subprocess.Popen([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--batch", str(B), "--height", str(H), "--width", str(W),
                                       "--encoder", args.encoder, "--flow-scale", str(args.flow_scale), "--flow-iters", str(args.flow_iters)],
@@ -622,7 +655,7 @@ def main():
     # launch of the ping-pong kernel at the ViT's fc1 + GELU shape, right after the timed region (chip warm).  The 2.5 PF the fractions are
     # quoted against assume 2.4 GHz; on data the part is power-limited (profiles/r04a_clock_mfma_peak.txt: 1.63-1.65 GHz in a bare MFMA loop).
     clock_ghz = None
-    if rank == 0 and not args.no_clock:
+    if args.full and rank == 0 and not args.no_clock:
         try:
             import tempfile
             dump = os.path.join(tempfile.gettempdir(), "prisma_bench_gemm_dbg.%d.bin" % os.getpid())
@@ -639,12 +672,12 @@ def main():
         finally:
             os.environ.pop("PB_GEMM_DBG", None)
     # the other precision mode runs in a child process (single-GPU runs only): its launches then land in their own rocprofv3
-    # per-process file, so the per-symbol averages of `rocprofv3 --stats -- python bench.py` stay those of ONE mode each
+    # per-process file, so the per-symbol averages of `rocprofv3 --stats -- python bench.py --full` stay those of ONE mode each
     other = None
-    if not args.one_precision and world == 1:
+    if args.full and not args.one_precision and world == 1:
         import subprocess
         osteps = max(1, min(args.steps, 3))
-        cmd = [sys.executable, os.path.abspath(__file__), "--precision", str(1 - args.precision), "--one-precision", "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--precision", str(1 - args.precision), "--full", "--one-precision", "--no-cpu-baseline",
                "--host-clips", "0", "--no-latency", "--no-clock", "--steps", str(osteps), "--warmup", "1", "--batch", str(B), "--height", str(H), "--width", str(W), "--encoder", args.encoder,
                "--flow-scale", str(args.flow_scale), "--flow-iters", str(args.flow_iters)] + (["--sequential-only"] if args.sequential_only else ["--seq-steps", "1"])
         r = subprocess.run(cmd, capture_output=True, text=True)
@@ -659,32 +692,15 @@ def main():
     pipe = pipeline_leg(args, R) if args.pipeline_frames > 1 else None
 
     if rank == 0:
-        dt, fam = main_res["dt"], main_res["fam"]
+        dt = main_res["dt"]
         fps = world * B * args.steps / dt
-        # per-symbol attribution = the sequential pass (bands one after the other, every launch bracketed by HIP events): `sq` holds its
-        # wall time, step count and per-band times; the timed region itself when --sequential-only
-        sq = main_res["seq"]
-        qsteps = sq["steps"]
-        # roofline kernel: the family with the most launch time in the sequential pass (bands run one after the other, so this is
-        # the kernel's own time - the criterion rocprofv3's per-symbol totals reproduce)
-        # Two flow-band symbols sit within 1 % of each other, so a bare arg-max would name a different kernel from run to run: among the
-        # symbols within 3 % of the largest time, the one with the most algorithmic FLOPs per step is taken (a property of the launch list).
-        cands = [(k, v) for k, v in fam.items() if v["flops"] > 0]
-        top_ms = max(v["ms"] for _, v in cands)
-        dom_name, g = max(((k, v) for k, v in cands if v["ms"] >= 0.97 * top_ms), key=lambda kv: (kv[1]["flops"], kv[0]))
-        ach = g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
-        dom_sym = dom_name.split("/", 1)[1]
-        dom_sym = SYMBOLS.get(dom_sym, dom_sym)
-        traffic, traffic_src = pmc_traffic(dom_sym)
-        exec_mult = g["exec_flops"] / g["flops"] if g["flops"] > 0 else 1.0     # MFMA passes issued per algorithmic pass (split-fp16: 2 - 3)
-        tot_fl = sum(v["flops"] for v in fam.values())
-        band_fl = {b: sum(v["flops"] for k, v in fam.items() if k.startswith(b + "/")) for b in ("depth", "flow")}
 
         def mode_summary(res, steps):
             return {"value": round(world * B * steps / res["dt"], 3), "unit": "frames/s", "ms_per_step": round(res["dt"] / steps * 1e3, 3),
                     "depth_ms_per_step": round(res["depth_s"] / steps * 1e3, 3), "flow_ms_per_step": round(res["flow_s"] / steps * 1e3, 3),
                     "band_ms_note": "ms from the step's start to the band's completion (in the default timed region both bands run at once)"}
 
+        # the headline: all a plain run measures
         out = {
             "metric": "frames/sec (depth_anything ViT-L + flow_raft, 1080p)",
             "value": round(fps, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -707,6 +723,33 @@ def main():
                              "reached where |ref| is a few per cent of the range; the asserted bound is the range-relative one the min / max-normalised encodes see",
                 "f16": "one fp16 MFMA pass per GEMM / conv, fp32 accumulate; against the fp32 reference depth 1.3e-3 max / 8e-4 L2, flow up to 2.2e-3 / 1.5e-3 "
                        "at 1280x720 - outside the tolerance, reported for comparison with round 1"},
+            "timed_region": ("sequential: depth band, then flow band, per-launch HIP events on (--sequential-only)" if args.sequential_only else
+                             "both bands of a step enqueued at once on their two ctx streams (prisma_amd.engine.run_concurrently), no per-launch events; "
+                             "results byte-identical to the sequential order (tests/test_gpu_edges.py)"),
+        }
+        out["this_precision"] = dict(mode_summary(main_res, args.steps), precision=PREC_NAME[args.precision])
+    if rank == 0 and args.full:
+        dt, fam = main_res["dt"], main_res["fam"]
+        # per-symbol attribution = the sequential pass (bands one after the other, every launch bracketed by HIP events): `sq` holds its
+        # wall time, step count and per-band times; the timed region itself when --sequential-only
+        sq = main_res["seq"]
+        qsteps = sq["steps"]
+        # roofline kernel: the family with the most launch time in the sequential pass (bands run one after the other, so this is
+        # the kernel's own time - the criterion rocprofv3's per-symbol totals reproduce)
+        # Two flow-band symbols sit within 1 % of each other, so a bare arg-max would name a different kernel from run to run: among the
+        # symbols within 3 % of the largest time, the one with the most algorithmic FLOPs per step is taken (a property of the launch list).
+        cands = [(k, v) for k, v in fam.items() if v["flops"] > 0]
+        top_ms = max(v["ms"] for _, v in cands)
+        dom_name, g = max(((k, v) for k, v in cands if v["ms"] >= 0.97 * top_ms), key=lambda kv: (kv[1]["flops"], kv[0]))
+        ach = g["flops"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] > 0 else 0.0
+        dom_sym = dom_name.split("/", 1)[1]
+        dom_sym = SYMBOLS.get(dom_sym, dom_sym)
+        traffic, traffic_src = pmc_traffic(dom_sym)
+        exec_mult = g["exec_flops"] / g["flops"] if g["flops"] > 0 else 1.0     # MFMA passes issued per algorithmic pass (split-fp16: 2 - 3)
+        tot_fl = sum(v["flops"] for v in fam.values())
+        band_fl = {b: sum(v["flops"] for k, v in fam.items() if k.startswith(b + "/")) for b in ("depth", "flow")}
+
+        out.update({
             "roofline": {"bound": "mfma", "kernel": dom_sym, "family": dom_name,
                          "achieved": round(ach, 2), "peak": PEAK_F16_TFLOPS, "unit": "TFLOP/s",
                          "frac": round(ach / PEAK_F16_TFLOPS, 4), "traffic": traffic,
@@ -740,9 +783,6 @@ def main():
                                  "band's flops / its wall time in the sequential pass / peak; step_frac = all launches' flops / timed step wall time / peak"},
             "model_tflops": round(tot_fl / qsteps * args.steps / dt / 1e12, 2),
             "executed_tflops": round(sum(v["exec_flops"] for v in fam.values()) / qsteps * args.steps / dt / 1e12, 2),
-            "timed_region": ("sequential: depth band, then flow band, per-launch HIP events on (--sequential-only)" if args.sequential_only else
-                             "both bands of a step enqueued at once on their two ctx streams (prisma_amd.engine.run_concurrently), no per-launch events; "
-                             "results byte-identical to the sequential order (tests/test_gpu_edges.py)"),
             # the same step with the bands one after the other and every launch timed: what rounds 1-5 reported as `value`
             "sequential": {"value": round(world * B * qsteps / sq["dt"], 3), "unit": "frames/s", "steps": qsteps, "ms_per_step": round(sq["dt"] / qsteps * 1e3, 3),
                            "depth_ms_per_step": round(sq["depth_s"] / qsteps * 1e3, 3), "flow_ms_per_step": round(sq["flow_s"] / qsteps * 1e3, 3),
@@ -779,8 +819,7 @@ def main():
             # algorithmic bytes (A + W + output once) per second of launch time: the figure to hold against HBM's ~8 TB/s for the launches
             # that move more than they compute (the K = 256 correlation-volume GEMMs sit in flow/gemm_kernel<128, 128, 2, 2, 0, 0, ...>)
             "kernel_algorithmic_tbps": {k: round(v["bytes"] / (v["ms"] * 1e-3) / 1e12, 3) for k, v in fam.items() if v["bytes"] > 0 and v["ms"] > 0},
-        }
-        out["this_precision"] = dict(mode_summary(main_res, args.steps), precision=PREC_NAME[args.precision])
+        })
         if other:
             out["other_precision"] = other
         if world == 1 and not args.no_cpu_baseline:
@@ -793,6 +832,7 @@ def main():
                 except Exception:      # noqa: BLE001 - fall back to the in-process baseline
                     cb = None
             out["cpu_baseline"] = cb or cpu_baseline(weights, cfg, rweights, frames, args.flow_scale, args.flow_iters)
+    if rank == 0:
         if flow:
             out["flow_raft_720p"] = flow
         if mask:

@@ -277,12 +277,19 @@ def frame_pair_sequence(n: int, height: int, width: int, seed: int = 0, shift: T
             tex[..., c] += amp[c] * np.sin(fx * xx + fy * yy * (1 if c != 1 else -1) + ph[c])
     tex = (tex - tex.min()) / (tex.max() - tex.min())
     out = np.empty((n, height, width, 3), np.uint8)
+    import os
+    from concurrent.futures import ThreadPoolExecutor
     from scipy.ndimage import map_coordinates
-    for i in range(n):
+
+    def warp(i):
         ys = yy[:height, :width] + 32 + shift[1] * i
         xs = xx[:height, :width] + 32 + shift[0] * i
         for c in range(3):
             out[i, ..., c] = np.clip(map_coordinates(tex[..., c], [ys, xs], order=1) * 255.0, 0, 255).astype(np.uint8)
+
+    # map_coordinates releases the GIL: the frames are warped on up to 16 host threads (a 32-frame 1080p clip takes ~16 s on one core)
+    with ThreadPoolExecutor(max(1, min(16, os.cpu_count() or 1, n))) as ex:
+        list(ex.map(warp, range(n)))
     return out
 
 

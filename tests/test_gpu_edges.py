@@ -110,11 +110,38 @@ def test_bench_nccl_path_under_torch_distributed_run():
     env = dict(os.environ, PRISMA_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "3",
-           "--height", "270", "--width", "480", "--encoder", "vits", "--no-cpu-baseline", "--one-precision"]
+           "--height", "270", "--width", "480", "--encoder", "vits", "--full", "--no-cpu-baseline", "--one-precision"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["value"] > 0 and line["scaling"] == "weak" and "roofline" in line
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_the_last_step(tmp_path):
+    """bench.py without --full: the timed steps and the headline only; --dump-outputs writes what the last step computed, which equals what
+    the host entry point returns for the same seeded clip on a context of the same max_batch."""
+    import json, os, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "3", "--height", "270",
+           "--width", "480", "--encoder", "vits", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "frames/s" and line["dtype"] == "split-f16"
+    assert not {"roofline", "sequential", "other_precision", "cpu_baseline"} & set(line)
+    got = {f[:-4]: np.load(out / f) for f in os.listdir(out)}
+    assert sorted(got) == ["depth_max", "depth_min", "depth_rgb", "flow_max_displacement", "flow_rgb"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    fr = synth.frame_pair_sequence(3, 270, 480, seed=1000)
+    net = engine.DepthAnything(synth.depth_anything_weights("vits", seed=1234), "vits", max_batch=3)
+    _, rgb, mn, mx = net.infer_batch(fr, want_depth=False)
+    net.close()
+    assert np.array_equal(got["depth_rgb"], rgb.astype(np.float32))
+    assert np.array_equal(got["depth_min"], mn) and np.array_equal(got["depth_max"], mx)
+    assert got["flow_rgb"].shape[:1] == (2,) and (got["flow_max_displacement"] > 0).all()
 
 
 def test_depth_host_pipeline_with_page_locked_buffers(depth):

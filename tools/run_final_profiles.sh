@@ -13,9 +13,9 @@ export PYTHONUNBUFFERED=1 TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-.}"
 O=gpurun_out
 mkdir -p $O
-timeout 900 python bench.py > $O/${T}_bench.log 2> $O/${T}_bench.err
+timeout 900 python bench.py --full > $O/${T}_bench.log 2> $O/${T}_bench.err
 tail -1 $O/${T}_bench.log > $O/${T}_default_bench_line.json
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/${T}_seq --output-format csv -- python bench.py --sequential-only --host-clips 0 --no-latency > $O/${T}_seq.log 2> $O/${T}_seq.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/${T}_seq --output-format csv -- python bench.py --full --sequential-only --host-clips 0 --no-latency > $O/${T}_seq.log 2> $O/${T}_seq.err
 tail -1 $O/${T}_seq.log > $O/${T}_sequential_bench_line.json
 i=0
 for f in $(ls $O/${T}_seq/*/*kernel_stats.csv | sort -V); do
@@ -29,6 +29,6 @@ python tools/pmc_summary.py $O/${T}_pmc_fetch $O/${T}_pmc_write $O/${T}_pmc_traf
 timeout 400 rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE -d $O/${T}_pmc_clock --output-format csv -- python bench.py $D > $O/${T}_pmc_clock.log 2>&1
 python tools/pmc_clock.py $O/${T}_pmc_clock $O/${T}_clock_per_symbol.json > $O/${T}_clock_per_symbol.txt 2>&1
 rm -rf $O/${T}_pmc_fetch $O/${T}_pmc_write $O/${T}_pmc_clock $O/${T}_seq
-timeout 900 python bench.py --all-legs --one-precision > $O/${T}_all_legs.log 2> $O/${T}_all_legs.err
+timeout 900 python bench.py --full --all-legs --one-precision > $O/${T}_all_legs.log 2> $O/${T}_all_legs.err
 tail -1 $O/${T}_all_legs.log > $O/${T}_all_legs_bench_line.json
 cut -c1-400 $O/${T}_default_bench_line.json

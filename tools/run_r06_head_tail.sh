@@ -6,7 +6,7 @@ export PYTHONUNBUFFERED=1
 O=gpurun_out; mkdir -p $O
 timeout 1200 python -m pytest tests/test_gpu_depth.py tests/test_gpu_outliers.py tests/test_gpu_edges.py -m gpu -x -q -s 2>&1 | grep -E "relmax|passed|failed|Error|assert" > $O/r06u_head_tail_tests.txt
 tail -25 $O/r06u_head_tail_tests.txt
-D="--steps 10 --warmup 3 --one-precision --no-cpu-baseline --host-clips 0 --no-clock"
+D="--full --steps 10 --warmup 3 --one-precision --no-cpu-baseline --host-clips 0 --no-clock"
 for rep in 1 2; do
   for v in 0 1; do
     PB_HEAD_TAIL=$v timeout 600 python bench.py $D > $O/r06u_head_tail_${v}_${rep}.log 2> $O/r06u_head_tail_${v}_${rep}.err

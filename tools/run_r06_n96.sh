@@ -6,7 +6,7 @@ export PYTHONUNBUFFERED=1
 O=gpurun_out; mkdir -p $O
 timeout 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_raft.py tests/test_gpu_gmflow.py -m gpu -x -q 2>&1 | tail -8 > $O/r06r_n96_tests.txt
 cat $O/r06r_n96_tests.txt
-D="--steps 10 --warmup 3 --one-precision --no-cpu-baseline --host-clips 0 --no-latency --no-clock"
+D="--full --steps 10 --warmup 3 --one-precision --no-cpu-baseline --host-clips 0 --no-latency --no-clock"
 for rep in 1 2; do
   for v in 0 1 2; do
     PB_TILE_N96=$v timeout 600 python bench.py $D > $O/r06r_n96_${v}_${rep}.log 2> $O/r06r_n96_${v}_${rep}.err
