@@ -331,6 +331,20 @@ int pb_op_attention128_split(pb_ctx *ctx, const float *q, const float *k, const 
                              int B, int L, int vcols, int kxor);
 int pb_op_conv2d(pb_ctx *ctx, const float *x, const float *w, const float *bias, float *y,
                  int B, int Ci, int H, int W, int Co, int ksize, int stride, int pad, int relu_in, int relu_out);
+/* One convolution / dense layer in the engines' split precision, through their own weight packers and launch code (EngineBase pack_conv / pack,
+ * set_weights, conv() / dense()).  layout: 0 fp16, 1 split16 (fp16 residual parts; sa = 1: the map is [hi | lo], 0: [hi]), 2 mx3 (maps
+ * [hi | hi8 | lo8] with e4m3 residual parts), 3 mx2 (maps [a16 | a8]: the layer reads channels [ci_off, ci_off + Ci) of a Ctot-channel map).
+ * The map is built on the host from x (NHWC [B, H, W, Ci], or [B, H, W, Ctot] for mx2; dense: A [M, K]) the way the producing epilogues
+ * write it.  w [Co, Ci, kh, kw] (dense: [N, K]), bias [Co]; skip (or NULL) [M, Co] is added in the output's layout.  tapin: slice-major K
+ * order; tile: 0 = the engines' choice (the halo conv included), else a gemm.h TILE_*; split_out: the output is a split map (lo_off = its
+ * channels padded to 64).  `out` receives the raw output buffer, rows_out x ldo halfs (rows_out >= M rounded up to 256), preset to 0xFF
+ * bytes where the launch must not write; info[13] = {pw, map pa, mx3, mx2, sa, sw, tapin, packed K, packed-channel copy, Cseg, ldo, lo8,
+ * lo8 pa}; kernel = the symbol that ran (pb_set_option "op_splitk" lends a split-K workspace). */
+int pb_op_conv2d_split(pb_ctx *ctx, const float *x, const float *w, const float *bias, const float *skip, int B, int H, int W, int Ci, int Ctot,
+                       int ci_off, int Co, int kh, int kw, int stride, int layout, int sa, int tapin, int tile, int split_out, int act,
+                       int pre_relu, int rows_out, void *out, int *info, char *kernel, int kernel_cap);
+int pb_op_dense_split(pb_ctx *ctx, const float *A, const float *w, const float *bias, const float *skip, int M, int K, int N, int layout,
+                      int sa, int tile, int split_out, int act, int rows_out, void *out, int *info, char *kernel, int kernel_cap);
 /* bilinear resize NCHW float32, align_corners 0/1 (torch F.interpolate semantics). */
 int pb_op_bilinear(pb_ctx *ctx, const float *x, float *y, int B, int C, int H, int W, int OH, int OW,
                    int align_corners);

@@ -261,6 +261,132 @@ struct DevMem {
     template <class T> T *as() { return (T *)p; }
 };
 #define PB_TRY(expr) do { int _r = (expr); if (_r) return _r; } while (0)
+
+// ---- one layer through EngineBase's own packing and launch code (pb_op_conv2d_split / pb_op_dense_split) ------------------------------
+// The maps are built on the host the way the producing epilogues write them (gemm_kernels.h lo8_store2 / direct epilogue); the weights go
+// through begin_load / pack_conv / pack / set_weights / conv() / dense() untouched, so the host packers are under test with the kernels.
+enum { SL_F16 = 0, SL_SPLIT16 = 1, SL_MX3 = 2, SL_MX2 = 3 };
+
+class SplitOpEngine : public EngineBase {
+  public:
+    explicit SplitOpEngine(int device) : EngineBase(device) {}
+    int setup(const pb_tensor *t, int n, int layout, int tapin) {
+        PB_TRY(begin_load(t, n));
+        split_w_ = layout != SL_F16; mx_ = layout >= SL_MX3; pack_mx2_ = layout == SL_MX2; pack_tapin_ = tapin;
+        return 0;
+    }
+    int pack_layer(bool is_conv, int sa, int N, int K, PackedW &w) {
+        if (is_conv) return pack_conv("l", true, nullptr, nullptr, w, sa);
+        const pb_tensor *tw = find("l.weight"), *tb = find("l.bias");
+        PB_CHECK(tw && tb, PB_ERR_ARG, "split op: no weights");
+        return pack((const float *)tw->data, N, K, (int)round_up(K, 64), w, (const float *)tb->data, 1, sa);
+    }
+    // host map of P rows of C fp32 values: f16 [hi], split16 [hi | lo (sa)], mx3 [hi | hi8 | lo8], mx2 [a16 | a8] (a8 of the fp16 value)
+    void build_map(const float *x, int64_t P, int C, int Cp, int layout, int sa, int64_t ld, std::vector<f16> &h) const {
+        for (int64_t p = 0; p < P; ++p) {
+            f16 *row = h.data() + p * ld;
+            unsigned char *r8 = (unsigned char *)(row + Cp);
+            for (int c = 0; c < C; ++c) {
+                const float v = x[p * C + c];
+                const f16 hi = (f16)v;
+                row[c] = hi;
+                if (layout == SL_SPLIT16 && sa) row[Cp + c] = (f16)(v - (float)hi);
+                if (layout == SL_MX3) {
+                    r8[c] = pb_f32_to_e4m3(ldexpf((float)hi, kLo8Pa));
+                    r8[Cp + c] = pb_f32_to_e4m3(ldexpf(v - (float)hi, kLo8Pa + 12));
+                }
+                if (layout == SL_MX2) r8[c] = pb_f32_to_e4m3(ldexpf((float)hi, kMx2Pa));
+            }
+        }
+    }
+    // skip tensor in the output's layout: [hi], [hi | lo] (fp16 residual) or [hi | hi8 | lo8] (e4m3 residual), C = lo_off
+    void build_skip(const float *s, int M, int N, int C, int lo_off, bool lo8, int64_t ldo, std::vector<f16> &h) const {
+        for (int m = 0; m < M; ++m) {
+            f16 *row = h.data() + (int64_t)m * ldo;
+            unsigned char *r8 = (unsigned char *)(row + C);
+            for (int n = 0; n < N; ++n) {
+                const float v = s[(int64_t)m * N + n];
+                const f16 hi = (f16)v;
+                row[n] = hi;
+                if (lo_off && lo8) {
+                    r8[n] = pb_f32_to_e4m3(ldexpf((float)hi, kLo8Pa));
+                    r8[C + n] = pb_f32_to_e4m3(ldexpf(v - (float)hi, kLo8Pa + 12));
+                } else if (lo_off) {
+                    row[C + n] = (f16)(v - (float)hi);
+                }
+            }
+        }
+    }
+    int run(bool is_conv, const float *x, const float *skip, int B, int H, int W, int Ci, int Ctot, int ci_off, int Co, int kh, int kw, int stride,
+            int layout, int sa, int tile, int splitk, int split_out, int act, int pre_relu, int rows_out, void *out, int *info, char *kname, int kcap) {
+        PB_CHECK(layout >= SL_F16 && layout <= SL_MX2 && Co % 8 == 0 && Ci > 0 && ci_off >= 0 && ci_off + Ci <= Ctot, PB_ERR_ARG, "split op: bad arguments");
+        if (layout != SL_SPLIT16) sa = layout == SL_MX3;
+        PackedW w;
+        const int K = is_conv ? 0 : Ci;
+        PB_TRY(pack_layer(is_conv, sa, Co, K, w));
+        const int Cp = (int)round_up(Ci, 64);
+        // the map: mx2 carries Ctot channels per pixel [a16 (Ctot) | a8 (Ctot bytes)] and the layer reads the slice [ci_off, ci_off + Ci)
+        const bool m2 = w.mx2 != 0;
+        PB_CHECK(m2 || w.mx3 || (Ctot == Ci && ci_off == 0), PB_ERR_ARG, "split op: a channel slice needs the mx2 layout");
+        PB_CHECK(!m2 || (Ctot % 128 == 0 && ci_off % 16 == 0), PB_ERR_ARG, "split op: mx2 map of %d channels, slice at %d", Ctot, ci_off);
+        const int Cm = m2 ? Ctot : Cp;
+        const int64_t ld = m2 ? Cm + Cm / 2 : (w.mx3 ? 2 * Cp : (w.sa ? 2 * Cp : Cp));
+        const int64_t P = is_conv ? (int64_t)B * H * W : B;
+        const int OH = is_conv ? (H + 2 * (kh / 2) - kh) / stride + 1 : 1, OW = is_conv ? (W + 2 * (kw / 2) - kw) / stride + 1 : 1;
+        const int64_t M = is_conv ? (int64_t)B * OH * OW : B;
+        const int C = (int)round_up(Co, 64), lo_off = split_out ? C : 0;
+        const int64_t ldo = split_out ? 2 * C : C;
+        const bool lo8 = split_out && mx_;
+        PB_CHECK(rows_out >= round_up(M, 256), PB_ERR_ARG, "split op: the output holds %d rows, the launch writes %lld", rows_out, (long long)M);
+        std::vector<f16> hx((size_t)round_up(P, 256) * ld, (f16)0.f);
+        std::vector<float> xpad;
+        const float *xs = x;
+        if (Cm != (m2 ? Ctot : Ci)) {          // channels padded to 64 with zeros
+            xpad.assign((size_t)P * Cm, 0.f);
+            for (int64_t p = 0; p < P; ++p) memcpy(&xpad[(size_t)p * Cm], x + p * Ci, (size_t)Ci * 4);
+            xs = xpad.data();
+        }
+        build_map(xs, P, Cm, m2 ? Cm : Cp, m2 ? SL_MX2 : (w.mx3 ? SL_MX3 : (w.sa ? SL_SPLIT16 : SL_F16)), w.sa, ld, hx);
+        DevMem dx, dout, dskip, dsk;
+        PB_TRY(dx.alloc(hx.size() * 2));
+        PB_HIP(hipMemcpy(dx.p, hx.data(), hx.size() * 2, hipMemcpyHostToDevice));
+        PB_TRY(dout.alloc((size_t)rows_out * ldo * 2));
+        PB_HIP(hipMemset(dout.p, 0xFF, (size_t)rows_out * ldo * 2));            // 0xFFFF: an fp16 NaN, 0xFF: an e4m3 NaN
+        if (skip) {
+            std::vector<f16> hs((size_t)rows_out * ldo, (f16)0.f);
+            build_skip(skip, (int)M, Co, C, lo_off, lo8, ldo, hs);
+            PB_TRY(dskip.alloc(hs.size() * 2));
+            PB_HIP(hipMemcpy(dskip.p, hs.data(), hs.size() * 2, hipMemcpyHostToDevice));
+        }
+        if (splitk) {
+            PB_TRY(dsk.alloc((size_t)512 * 128 * 128 * 4));
+            sk_ws_ = dsk.as<float>(); sk_cap_ = (int64_t)512 * 128 * 128;
+        }
+        PB_HIP(hipDeviceSynchronize());
+        pb_gemm_set_last_kernel("");
+        const f16 *in = dx.as<f16>() + (m2 ? ci_off : 0);
+        int r;
+        if (is_conv) {
+            conv_tile = tile;
+            r = conv(in, Cp, m2 ? (int)ld : 0, B, H, W, kh, kw, stride, w, dout.as<f16>(), (int)ldo, act, pre_relu, dskip.as<f16>(), nullptr, lo_off,
+                     m2 ? Ctot - ci_off / 2 : 0);
+        } else {
+            dense_tile = tile;
+            PB_CHECK(!pre_relu, PB_ERR_ARG, "split op: dense() has no pre_relu");
+            r = dense(in, (int)ld, M, w, dout.as<f16>(), (int)ldo, act, dskip.as<f16>(), 0, -1, lo_off);
+        }
+        sk_ws_ = nullptr; sk_cap_ = 0;
+        if (r) return r;
+        PB_HIP(hipStreamSynchronize(stream));
+        PB_HIP(hipMemcpy(out, dout.p, (size_t)rows_out * ldo * 2, hipMemcpyDeviceToHost));
+        if (info) {
+            const int v[13] = {w.mx_pw, m2 ? kMx2Pa : kLo8Pa, w.mx3, w.mx2, w.sa, w.sw, w.tapin, w.K, w.wcw != nullptr, w.Cseg, (int)ldo, lo8, kLo8Pa};
+            memcpy(info, v, sizeof(v));
+        }
+        if (kname && kcap > 0) snprintf(kname, kcap, "%s", pb_gemm_last_kernel());
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -1257,6 +1383,35 @@ int pb_depth_encode_still(pb_ctx *c, const float *depth, int H, int W, int flip,
     if (min_out) *min_out = mnmx[0];
     if (max_out) *max_out = mnmx[1];
     return 0;
+}
+
+int pb_op_conv2d_split(pb_ctx *c, const float *x, const float *w, const float *bias, const float *skip, int B, int H, int W, int Ci, int Ctot,
+                       int ci_off, int Co, int kh, int kw, int stride, int layout, int sa, int tapin, int tile, int split_out, int act, int pre_relu,
+                       int rows_out, void *out, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && x && w && bias && out && B > 0 && H > 0 && W > 0 && kh >= 1 && kw >= 1 && (stride == 1 || stride == 2), PB_ERR_ARG,
+             "op_conv2d_split: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    pb_tensor t[2] = {};
+    t[0].name = "l.weight"; t[0].dtype = PB_F32; t[0].ndim = 4; t[0].data = (void *)w;
+    t[0].shape[0] = Co; t[0].shape[1] = Ci; t[0].shape[2] = kh; t[0].shape[3] = kw;
+    t[1].name = "l.bias"; t[1].dtype = PB_F32; t[1].ndim = 1; t[1].shape[0] = Co; t[1].data = (void *)bias;
+    SplitOpEngine e(c->device);
+    PB_TRY(e.setup(t, 2, layout, tapin));
+    return e.run(true, x, skip, B, H, W, Ci, Ctot ? Ctot : Ci, ci_off, Co, kh, kw, stride, layout, sa, tile, c->op_splitk, split_out, act, pre_relu,
+                 rows_out, out, info, kernel, kernel_cap);
+}
+
+int pb_op_dense_split(pb_ctx *c, const float *A, const float *w, const float *bias, const float *skip, int M, int K, int N, int layout, int sa,
+                      int tile, int split_out, int act, int rows_out, void *out, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && A && w && bias && out && M > 0 && K > 0, PB_ERR_ARG, "op_dense_split: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    pb_tensor t[2] = {};
+    t[0].name = "l.weight"; t[0].dtype = PB_F32; t[0].ndim = 2; t[0].shape[0] = N; t[0].shape[1] = K; t[0].data = (void *)w;
+    t[1].name = "l.bias"; t[1].dtype = PB_F32; t[1].ndim = 1; t[1].shape[0] = N; t[1].data = (void *)bias;
+    SplitOpEngine e(c->device);
+    PB_TRY(e.setup(t, 2, layout, 0));
+    return e.run(false, A, skip, M, 1, 1, K, K, 0, N, 1, 1, 1, layout, sa, tile, c->op_splitk, split_out, act, 0, rows_out, out, info, kernel,
+                 kernel_cap);
 }
 
 }  // extern "C"

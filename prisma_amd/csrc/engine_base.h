@@ -18,6 +18,9 @@ class EngineBase {
     bool debug = false;
     KernelTimer timer;
     int conv_tile = TILE_AUTO;
+    int dense_tile = TILE_AUTO;  // dense()'s tile (the engines keep TILE_AUTO; the split-precision op entry points force one)
+    float *sk_ws_ = nullptr;     // split-K workspace conv() / dense() lend launch_gemm (gemm.h sk_ws; null in the engines)
+    int64_t sk_cap_ = 0;
     int split_w_ = 0;            // PB_PREC_SPLIT: weights packed as hi + lo fp16, two passes over K (set before load)
     int mx_ = 0;                 // ... and where activations are split too (sa) the residual parts are e4m3: maps [hi | hi8 | lo8],
                                  // weights [w_hi | w_lo8 | w_hi8] per tap, fp8 tiles through the MX-scaled MFMA (PackedW::mx3)

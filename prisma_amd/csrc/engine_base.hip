@@ -293,6 +293,7 @@ int EngineBase::conv(const f16 *in, int cC, int cLd, int n, int H, int W, int kh
     if (fuse) { a.out2 = fuse->out2; a.gru_h = fuse->gru_h; a.gru_z = fuse->gru_z; a.gru_rh = fuse->gru_rh; a.gru_ld = fuse->gru_ld; a.add2 = fuse->add2; }
     if (w.mx2 && a8_rel && a8_rel != cC) { a.kwrap = cC; a.kshift = a8_rel - cC; }      // the fp8 copy of a channel slice is not adjacent
     if (o8_off) { a.o8_off = o8_off; a.o8_scale = (float)(1 << kMx2Pa); }
+    a.sk_ws = sk_ws_; a.sk_cap = sk_cap_;
     PB_CHECK(!w.sw || w.Cseg == cC, PB_ERR_STATE, "split conv: %d channels, weights packed for %d", cC, w.Cseg);
     set_weights(a, w, true);
     PB_CHECK(w.K == kh * kw * a.cC, PB_ERR_STATE, "conv: packed K %d != %d*%d*%d", w.K, kh, kw, a.cC);
@@ -318,8 +319,9 @@ int EngineBase::dense(const f16 *A, int lda, int64_t M, const PackedW &w, f16 *o
     if (lo_off && mx_) { a.lo8 = 1; a.lo8_pa = kLo8Pa; }
     if (o8_off) { a.o8_off = o8_off; a.o8_scale = (float)(1 << kMx2Pa); }
     if (w.mx2 && a_pa >= 0) a.mx_scale_a = 127 - a_pa;
+    a.sk_ws = sk_ws_; a.sk_cap = sk_cap_;
     tic(F_GEMM, 2.0 * M * (double)a.N * w.Kreal, 2.0 * ((double)M * w.Kreal + (double)a.N * w.Kreal + (double)M * a.N), w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
-    int r = launch_gemm(cur_, A_DENSE, EPI_STD, TILE_AUTO, a);
+    int r = launch_gemm(cur_, A_DENSE, EPI_STD, dense_tile, a);
     if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
     toc();
     return r;

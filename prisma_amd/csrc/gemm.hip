@@ -81,7 +81,11 @@ int launch_gemm(hipStream_t stream, int amode, int epi, int tile, const GemmArgs
         // 64 < N <= 96 (RAFT / GMFlow encoder stage 2 carries 96 channels): the 128 x 96 tile - a quarter fewer MFMAs, B rows and fragment reads than
         // the 128-wide tile spends on 32 padding columns; its third column block has a plain single-column epilogue (gemm_kernels.h single_col_epilogue)
         if (g_n96 < 0) pb_gemm_set_n96(pb_env_int("PB_TILE_N96", 2));
-        if (tile == TILE_128 && g_n96 && amode == A_CONV && epi == EPI_STD && a.N > 64 && a.N <= 96 && (a.act == ACT_NONE || a.act == ACT_RELU) && !a.out2 && !a.o8_off)
+        // ... only when its chunk table holds the launch's K tiles (counted on the packed-channel K axis where that copy applies below): a deeper
+        // layer (3 x 3 over 512 mx3 / 1024 fp16 channels: 144 K tiles) stays on the 128 x 128 tile instead of failing the check further down
+        const int k96 = (a.Wcw && g_n96 >= 2 && !a.cTapInner ? a.Kcw : a.K) / 64;
+        if (tile == TILE_128 && g_n96 && amode == A_CONV && epi == EPI_STD && a.N > 64 && a.N <= 96 && (a.act == ACT_NONE || a.act == ACT_RELU) && !a.out2 && !a.o8_off &&
+            k96 <= 128)
             tile = TILE_128x96;
         static int small_tile = -1;
         if (small_tile < 0) { const char *e = getenv("PB_TILE_SMALL"); small_tile = e ? atoi(e) : TILE_128; }

@@ -154,6 +154,15 @@ class _Ctx:
                      launches=arr[i].launches) for i in range(n)]
 
 
+_SPLIT_INFO = ("pw", "pa", "mx3", "mx2", "sa", "sw", "tapin", "K", "cw", "Cseg", "ldo", "lo8", "lo8_pa")
+
+
+def _split_info(info, M: int) -> dict:
+    d = dict(zip(_SPLIT_INFO, list(info)))
+    d["M"] = M
+    return d
+
+
 class Ops(_Ctx):
     """Single-kernel entry points (pb_op_*) used by the parity tests."""
 
@@ -238,6 +247,44 @@ class Ops(_Ctx):
         check(self.lib.pb_op_conv2d(self.ctx, _ptr(x), _ptr(w), _ptr(b), _ptr(out), B, Ci, H, W, Co, ks, stride, pad,
                                     int(relu_in), int(relu_out)))
         return out
+
+    def conv2d_split(self, x, w, bias, skip=None, stride: int = 1, layout: int = 2, sa: int = 1, tapin: int = 0, tile: int = 0,
+                     split_out: bool = True, act: int = 0, pre_relu: bool = False, ci_off: int = 0, guard_rows: int = 64):
+        """one convolution through the engines' split-precision packing and launch code (pb_op_conv2d_split).  x NHWC [B, H, W, Ci]
+        (mx2: [B, H, W, Ctot] of which channels [ci_off, ci_off + Ci) are read); w [Co, Ci, kh, kw].  Returns (raw output buffer as uint8
+        [rows, ldo * 2], info dict, kernel symbol)."""
+        x, w, bias = _f32(x), _f32(w), _f32(bias)
+        B, H, W, Cx = x.shape
+        Co, Ci, kh, kw = w.shape
+        OH, OW = (H + 2 * (kh // 2) - kh) // stride + 1, (W + 2 * (kw // 2) - kw) // stride + 1
+        M = B * OH * OW
+        sk = None if skip is None else _f32(skip)
+        assert sk is None or sk.shape == (M, Co)
+        ldo = (2 if split_out else 1) * (-(-Co // 64) * 64)
+        rows = -(-M // 256) * 256 + guard_rows
+        out = np.empty((rows, ldo * 2), np.uint8)
+        info = (C.c_int * 13)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_conv2d_split(self.ctx, _ptr(x), _ptr(w), _ptr(bias), _ptr(sk), B, H, W, Ci, Cx, ci_off, Co, kh, kw, stride, layout,
+                                          sa, tapin, tile, int(split_out), act, int(pre_relu), rows, _ptr(out), info, kname, 128))
+        return out, _split_info(info, M), kname.value.decode()
+
+    def dense_split(self, A, w, bias, skip=None, layout: int = 2, sa: int = 1, tile: int = 0, split_out: bool = True, act: int = 0,
+                    guard_rows: int = 64):
+        """one dense layer A [M, K] x w [N, K]^T through the same packing and launch code (pb_op_dense_split); returns as conv2d_split"""
+        A, w, bias = _f32(A), _f32(w), _f32(bias)
+        M, K = A.shape
+        N = w.shape[0]
+        sk = None if skip is None else _f32(skip)
+        assert sk is None or sk.shape == (M, N)
+        ldo = (2 if split_out else 1) * (-(-N // 64) * 64)
+        rows = -(-M // 256) * 256 + guard_rows
+        out = np.empty((rows, ldo * 2), np.uint8)
+        info = (C.c_int * 13)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_dense_split(self.ctx, _ptr(A), _ptr(w), _ptr(bias), _ptr(sk), M, K, N, layout, sa, tile, int(split_out), act, rows,
+                                         _ptr(out), info, kname, 128))
+        return out, _split_info(info, M), kname.value.decode()
 
     def bilinear(self, x, OH: int, OW: int, align_corners: bool) -> np.ndarray:
         x = _f32(x)
