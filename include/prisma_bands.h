@@ -345,6 +345,34 @@ int pb_op_conv2d_split(pb_ctx *ctx, const float *x, const float *w, const float 
                        int pre_relu, int rows_out, void *out, int *info, char *kernel, int kernel_cap);
 int pb_op_dense_split(pb_ctx *ctx, const float *A, const float *w, const float *bias, const float *skip, int M, int K, int N, int layout,
                       int sa, int tile, int split_out, int act, int rows_out, void *out, int *info, char *kernel, int kernel_cap);
+/* The flow_raft band's own kernels one by one, through the launchers and arguments RaftEngine::infer uses (tests/test_gpu_raft_ops.py).  Raw
+ * output buffers are preset to 0xFF bytes (NaN as fp16, fp32 and e4m3) and carry guard_rows untouched rows behind the last one.
+ * pb_op_raft_geometry (no GPU needed): geo[l * 5 + {0..4}] = {h, w, padded w, padded h, volume row stride} of pyramid level l over an h8 x w8
+ * grid - the function RaftEngine::prepare plans with.
+ * lookup: avg-pool x3, tile x4, the all-pairs volume x4 per pair, then the 9 x 9 x 4 lookup.  fmap1 [n, h8 w8, 256], fmap2 [n, h8, w8, 256],
+ *   flow [n h8 w8, 2]; out: (rows + guard) x (o8 ? 576 : 384) halfs (o8: the e4m3 copy at byte 768 of a row); levels (or NULL): the four volume
+ *   levels de-tiled, [n h8 w8, h_l, w_l] floats one after the other.
+ * convf1: flow [n, h8, w8, 2], w [128, 2, 7, 7], bias [128]; passes 1 / 2 (w_hi, + w_lo); out: (rows + guard) x (o8 ? 192 : 128) halfs (e4m3
+ *   copy at byte 256); gemm_path: im2col + GEMM (PB_CONVF1_DIRECT=0) instead of the direct kernel.
+ * flow_head2: x [n, H, W, 256], w [2, 256, 3, 3], bias [2]; flow [n H W + guard, 2] is read (rows < n H W) and written in place.
+ * upsample: flow [n, h8 w8, 2], mask [n h8 w8, 576] -> up [n, sh, sw, 2] + guard floats, maxd [n] as the encode kernel decodes it.
+ * instnorm: a (and b) [B, HW, C] -> stats [B, C, 2] = {mean, rstd} of a, out (B HW + guard) x ld halfs; layout 0 [C], 1 [hi | lo], 2 [hi | hi8 |
+ *   lo8] (ld = 2 C); stats_lo: statistics of hi + lo; bmode 0 none / 1 raw / 2 normalised second operand; inplace: out is a's buffer.
+ * state: init_state on ctx_rows [rows, 256] (flow0 = the flow it leaves, rows + guard), then put_flow of `flow` [rows, 2]; ld 384 / 576 (fp8
+ *   copies at byte 768), inp_off 128 / 256; h32 (rows + guard) x 128 floats, hx / hx2 (rows + guard) x ld halfs. */
+int pb_op_raft_geometry(int h8, int w8, int *geo);
+int pb_op_raft_lookup(pb_ctx *ctx, const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows,
+                      void *out, float *levels);
+int pb_op_raft_convf1(pb_ctx *ctx, const float *flow, const float *w, const float *bias, int n, int h8, int w8, int passes, int o8,
+                      int gemm_path, int guard_rows, void *out);
+int pb_op_raft_flow_head2(pb_ctx *ctx, const float *x, const float *w, const float *bias, float *flow, int n, int H, int W, int split,
+                          int guard_rows);
+int pb_op_raft_upsample(pb_ctx *ctx, const float *flow, const float *mask, int n, int h8, int w8, int pad_l, int pad_t, int sh, int sw,
+                        int guard, float *up, float *maxd);
+int pb_op_raft_instnorm(pb_ctx *ctx, const float *a, const float *b, int B, int HW, int C, int layout, int stats_lo, int bmode, int inplace,
+                        int guard_rows, float *stats, void *out);
+int pb_op_raft_state(pb_ctx *ctx, const float *ctx_rows, const float *flow, int rows, int ld, int inp_off, int guard_rows, float *h32, void *hx,
+                     void *hx2, float *flow0);
 /* bilinear resize NCHW float32, align_corners 0/1 (torch F.interpolate semantics). */
 int pb_op_bilinear(pb_ctx *ctx, const float *x, float *y, int B, int C, int H, int W, int OH, int OW,
                    int align_corners);

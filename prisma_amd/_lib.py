@@ -112,6 +112,13 @@ SYMBOLS = {
     "pb_op_conv2d": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 10),
     "pb_op_conv2d_split": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 18 + [_P, _P, _P, C.c_int]),
     "pb_op_dense_split": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P, _P, _P, C.c_int]),
+    "pb_op_raft_geometry": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "pb_op_raft_lookup": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P, _P]),
+    "pb_op_raft_convf1": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 7 + [_P]),
+    "pb_op_raft_flow_head2": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 5),
+    "pb_op_raft_upsample": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),
+    "pb_op_raft_instnorm": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),
+    "pb_op_raft_state": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P, _P, _P, _P]),
     "pb_op_bilinear": (C.c_int, [_P, _P, _P] + [C.c_int] * 7),
     "pb_op_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "pb_op_encode_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -387,6 +387,190 @@ class SplitOpEngine : public EngineBase {
         return 0;
     }
 };
+
+// ---- the flow_raft band's own kernels one by one (pb_op_raft_*) -----------------------------------------------------------------------
+// Every entry point calls the launcher RaftEngine::infer calls, with the engine's arguments; host maps are built by build_map above, weights
+// go through EngineBase::pack / pack_conv / convf1_pack.  Output buffers are preset to 0xFF bytes (an fp16 / fp32 / e4m3 NaN) with guard
+// rows behind the last row, so a test can tell what the kernel did NOT write.
+class RaftOpEngine : public SplitOpEngine {
+  public:
+    explicit RaftOpEngine(int device) : SplitOpEngine(device) {}
+    static int up(DevMem &d, const void *src, size_t bytes) {
+        PB_TRY(d.alloc(bytes));
+        PB_HIP(hipMemcpy(d.p, src, bytes, hipMemcpyHostToDevice));
+        return 0;
+    }
+    static int preset(DevMem &d, size_t bytes) {
+        PB_TRY(d.alloc(bytes));
+        PB_HIP(hipMemset(d.p, 0xFF, bytes));
+        PB_HIP(hipDeviceSynchronize());
+        return 0;
+    }
+    int to_f16(DevMem &d, const float *x, int64_t rows, int C, size_t min_bytes = 0) {
+        std::vector<f16> h((size_t)rows * C);
+        build_map(x, rows, C, C, SL_F16, 0, C, h);
+        PB_TRY(d.alloc(std::max(h.size() * 2, min_bytes)));
+        PB_HIP(hipMemcpy(d.p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
+        return 0;
+    }
+    int finish(void *out, const DevMem &d, size_t bytes) {
+        PB_HIP(hipStreamSynchronize(stream));
+        PB_HIP(hipMemcpy(out, d.p, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+    int lookup(const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows, void *out, float *levels) {
+        PB_CHECK(h8 >= 16 && w8 >= 16, PB_ERR_ARG, "op_raft_lookup: a %d x %d grid is too small (the 4-level pyramid needs >= 16 x 16)", h8, w8);
+        CorrGeo g;
+        corr_pyramid_geometry(h8, w8, g);
+        const int P = h8 * w8;
+        const int64_t rows = (int64_t)n * P;
+        const size_t slack = 1 << 20;                       // what RaftEngine::prepare leaves behind fmap_ and every pyramid buffer
+        const int ldo = o8 ? 576 : 384;
+        DevMem f1, f2, dflow, dout, fpool[4], ftile[4], pyr[4];
+        PB_TRY(to_f16(f1, fmap1, rows, 256, (size_t)round_up(rows, 256) * 256 * 2 + slack));
+        PB_TRY(to_f16(f2, fmap2, rows, 256, (size_t)round_up(rows, 256) * 256 * 2 + slack));
+        PB_TRY(up(dflow, flow, (size_t)rows * 8));
+        PB_TRY(preset(dout, (size_t)(rows + guard_rows) * ldo * 2));
+        const f16 *lv[4];
+        for (int l = 0; l < 4; ++l) {
+            PB_TRY(pyr[l].alloc((size_t)rows * g.ld[l] * 2 + slack));
+            if (l) PB_TRY(fpool[l].alloc((size_t)round_up((int64_t)n * g.h[l] * g.w[l], 256) * 256 * 2 + slack));
+            PB_TRY(ftile[l].alloc((size_t)(n * (int64_t)g.ld[l] + 256) * 256 * 2 + slack));
+            lv[l] = pyr[l].as<f16>();
+        }
+        for (int l = 0; l < 4; ++l) {
+            if (l > 0) PB_TRY(launch_avgpool2_nhwc(stream, l == 1 ? f2.as<f16>() : fpool[l - 1].as<f16>(), fpool[l].as<f16>(), n, g.h[l - 1], g.w[l - 1], 256));
+            PB_TRY(launch_corr_tile(stream, l == 0 ? f2.as<f16>() : fpool[l].as<f16>(), ftile[l].as<f16>(), n, g.h[l], g.w[l], g.wp[l], g.ld[l]));
+        }
+        for (int i = 0; i < n; ++i)
+            for (int l = 0; l < 4; ++l)
+                PB_TRY(launch_corr_volume(stream, f1.as<f16>() + (int64_t)i * P * 256, P, ftile[l].as<f16>() + (int64_t)i * g.ld[l] * 256, g.ld[l], g.ld[l],
+                                          pyr[l].as<f16>() + (int64_t)i * P * g.ld[l], g.ld[l]));
+        PB_TRY(launch_corr_lookup(stream, lv, g.h, g.w, g.wp, g.hp, g.ld, dflow.as<float>(), P, w8, dout.as<f16>(), rows, ldo, o8 ? 768 : 0,
+                                  (float)(1 << kMx2Pa)));
+        PB_TRY(finish(out, dout, (size_t)(rows + guard_rows) * ldo * 2));
+        if (levels) {                                       // the four levels, de-tiled: [n P, h_l, w_l] one after the other
+            float *dst = levels;
+            for (int l = 0; l < 4; ++l) {
+                std::vector<f16> h((size_t)rows * g.ld[l]);
+                PB_HIP(hipMemcpy(h.data(), pyr[l].p, h.size() * 2, hipMemcpyDeviceToHost));
+                const int wt = g.wp[l] >> 3;
+                for (int64_t r = 0; r < rows; ++r)
+                    for (int y = 0; y < g.h[l]; ++y)
+                        for (int x = 0; x < g.w[l]; ++x)
+                            *dst++ = (float)h[(size_t)r * g.ld[l] + ((y >> 3) * wt + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7)];
+            }
+        }
+        return 0;
+    }
+
+    int convf1(const float *flow, const float *wt, const float *bias, int n, int h8, int w8, int passes, int o8, int gemm, int guard_rows, void *out) {
+        const int P = h8 * w8, ldo = o8 ? 192 : 128;
+        const int64_t rows = (int64_t)n * P, rows_buf = round_up(rows + guard_rows, 256);
+        DevMem dflow, dout, dw, db, fa;
+        PB_TRY(up(dflow, flow, (size_t)rows * 8));
+        PB_TRY(preset(dout, (size_t)rows_buf * ldo * 2));
+        if (!gemm) {
+            std::vector<f16> hw((size_t)convf1_packed_halfs(passes));
+            convf1_pack(wt, passes, hw.data());
+            PB_TRY(up(dw, hw.data(), hw.size() * 2));
+            PB_TRY(up(db, bias, 128 * 4));
+            PB_TRY(launch_convf1(stream, dflow.as<float>(), dw.as<f16>(), db.as<float>(), dout.as<f16>(), rows, P, h8, w8, ldo, o8 ? 256 : 0,
+                                 (float)(1 << kMx2Pa), passes));
+        } else {        // PB_CONVF1_DIRECT=0: im2col order k = tap * 2 + c, K 98 -> 128, then the GEMM (RaftEngine::load / infer)
+            PB_CHECK(passes == 2 || !o8, PB_ERR_ARG, "op_raft_convf1: the GEMM path reads fp8 copies only in the split mode");
+            split_w_ = passes == 2; mx_ = o8; pack_mx2_ = o8; pack_tapin_ = 0;
+            std::vector<float> g((size_t)128 * 98);
+            for (int o = 0; o < 128; ++o)
+                for (int c = 0; c < 2; ++c)
+                    for (int tp = 0; tp < 49; ++tp) g[(size_t)o * 98 + tp * 2 + c] = wt[((size_t)o * 2 + c) * 49 + tp];
+            PackedW w;
+            PB_TRY(pack(g.data(), 128, 98, 128, w, bias));
+            PB_TRY(fa.alloc((size_t)round_up(rows, 256) * ldo * 2));
+            PB_TRY(launch_im2col7_flow(stream, dflow.as<float>(), n, h8, w8, fa.as<f16>(), 128, ldo, o8));
+            PB_TRY(dense(fa.as<f16>(), ldo, rows, w, dout.as<f16>(), ldo, ACT_RELU, nullptr, o8 ? 256 : 0, 0));
+        }
+        return finish(out, dout, (size_t)(rows + guard_rows) * ldo * 2);
+    }
+
+    int flow_head2(const float *x, float *flow, int n, int H, int W, int split, int guard_rows) {
+        // as RaftEngine::load packs flow_head.conv2: fp16 residuals (no mx2), tap-major, N = 8
+        split_w_ = split; mx_ = split; pack_mx2_ = 0; pack_tapin_ = 0;
+        PackedW w;
+        PB_TRY(pack_conv("l", true, nullptr, nullptr, w));
+        w.N = 8;
+        const int64_t rows = (int64_t)n * H * W;
+        DevMem dx, dflow;
+        PB_TRY(to_f16(dx, x, rows, 256));
+        PB_TRY(preset(dflow, (size_t)(rows + guard_rows) * 8));
+        PB_HIP(hipMemcpy(dflow.p, flow, (size_t)rows * 8, hipMemcpyHostToDevice));
+        PB_TRY(launch_flow_head2(stream, dx.as<f16>(), w.w, w.bias, dflow.as<float>(), n, H, W, w.sw));
+        return finish(flow, dflow, (size_t)(rows + guard_rows) * 8);
+    }
+
+    int upsample(const float *flow, const float *mask, int n, int h8, int w8, int pad_l, int pad_t, int sh, int sw, int guard, float *upo, float *maxd) {
+        const int64_t rows = (int64_t)n * h8 * w8, px = (int64_t)n * sh * sw;
+        DevMem dflow, dmask, dup, dmax, dmx;
+        PB_TRY(up(dflow, flow, (size_t)rows * 8));
+        PB_TRY(up(dmask, mask, (size_t)rows * 576 * 4));
+        PB_TRY(preset(dup, (size_t)(px * 2 + guard) * 4));
+        PB_TRY(preset(dmax, (size_t)n * 4));
+        PB_TRY(dmx.alloc((size_t)n * 4));
+        PB_TRY(launch_upsample(stream, dflow.as<float>(), dmask.as<float>(), n, h8, w8, pad_l, pad_t, sh, sw, dup.as<float>(), dmax.as<unsigned>()));
+        PB_TRY(launch_flow_encode(stream, dup.as<float>(), n, sh, sw, dmax.as<unsigned>(), nullptr, dmx.as<float>()));     // decodes maxd, no colours
+        PB_TRY(finish(upo, dup, (size_t)(px * 2 + guard) * 4));
+        PB_HIP(hipMemcpy(maxd, dmx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+    // layout 0: [C] fp16, 1: [hi | lo], 2: [hi | hi8 | lo8]; bmode 0: no second operand, 1: raw, 2: normalised with its own statistics
+    int instnorm(const float *a, const float *b, int B, int HW, int C, int layout, int stats_lo, int bmode, int inplace, int guard_rows,
+                 float *stats_out, void *out) {
+        const int ld = layout ? 2 * C : C, lo_off = layout ? C : 0, l8 = layout == 2 ? kLo8Pa : -1;
+        const int sl = layout == 0 ? SL_F16 : (layout == 1 ? SL_SPLIT16 : SL_MX3);
+        const int64_t rows = (int64_t)B * HW;
+        std::vector<f16> ha((size_t)(rows + guard_rows) * ld), hb;
+        memset(ha.data(), 0xFF, ha.size() * 2);
+        build_map(a, rows, C, C, sl, 1, ld, ha);
+        DevMem da, db, dout, part, st, st2;
+        PB_TRY(up(da, ha.data(), ha.size() * 2));
+        if (bmode) {
+            hb.assign((size_t)rows * ld, (f16)0.f);
+            build_map(b, rows, C, C, sl, 1, ld, hb);
+            PB_TRY(up(db, hb.data(), hb.size() * 2));
+        }
+        if (!inplace) PB_TRY(preset(dout, (size_t)(rows + guard_rows) * ld * 2));
+        PB_TRY(part.alloc((size_t)in_stats_chunks(HW) * B * 256 * 2 * 4));
+        PB_TRY(st.alloc((size_t)B * 256 * 2 * 4)); PB_TRY(st2.alloc((size_t)B * 256 * 2 * 4));
+        PB_TRY(launch_in_stats(stream, da.as<f16>(), B, HW, C, ld, part.as<float>(), st.as<float>(), stats_lo ? lo_off : 0, l8));
+        if (bmode == 2) PB_TRY(launch_in_stats(stream, db.as<f16>(), B, HW, C, ld, part.as<float>(), st2.as<float>(), stats_lo ? lo_off : 0, l8));
+        DevMem &o = inplace ? da : dout;
+        PB_TRY(launch_in_apply(stream, da.as<f16>(), st.as<float>(), bmode ? db.as<f16>() : nullptr, bmode == 2 ? st2.as<float>() : nullptr, o.as<f16>(),
+                               B, HW, C, ld, lo_off, l8));
+        PB_TRY(finish(out, o, (size_t)(rows + guard_rows) * ld * 2));
+        PB_HIP(hipMemcpy(stats_out, st.p, (size_t)B * C * 2 * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+    int state(const float *cx, const float *flow, int64_t rows, int ld, int inp_off, int guard_rows, float *h32, void *hx, void *hx2, float *flow0) {
+        const int o8_off = ld == 576 ? 768 : 0, mot = inp_off == 256 ? 128 : 256;      // RaftEngine::infer: hoist_ ? [h | motion | inp] : [h | inp | motion]
+        const float s8 = (float)(1 << kMx2Pa);
+        DevMem dc, dh32, dhx, dhx2, dflow;
+        PB_TRY(to_f16(dc, cx, rows, 256));
+        PB_TRY(preset(dh32, (size_t)(rows + guard_rows) * 128 * 4));
+        PB_TRY(preset(dhx, (size_t)(rows + guard_rows) * ld * 2)); PB_TRY(preset(dhx2, (size_t)(rows + guard_rows) * ld * 2));
+        PB_TRY(preset(dflow, (size_t)(rows + guard_rows) * 8));
+        PB_TRY(launch_init_state(stream, dc.as<f16>(), dh32.as<float>(), dhx.as<f16>(), dhx2.as<f16>(), dflow.as<float>(), rows, ld, o8_off, s8, inp_off));
+        PB_TRY(finish(flow0, dflow, (size_t)(rows + guard_rows) * 8));
+        PB_HIP(hipMemcpy(dflow.p, flow, (size_t)rows * 8, hipMemcpyHostToDevice));
+        PB_TRY(launch_put_flow(stream, dflow.as<float>(), dhx.as<f16>(), dhx2.as<f16>(), rows, ld, o8_off, s8, mot + 126));
+        PB_TRY(finish(h32, dh32, (size_t)(rows + guard_rows) * 128 * 4));
+        PB_HIP(hipMemcpy(hx, dhx.p, (size_t)(rows + guard_rows) * ld * 2, hipMemcpyDeviceToHost));
+        PB_HIP(hipMemcpy(hx2, dhx2.p, (size_t)(rows + guard_rows) * ld * 2, hipMemcpyDeviceToHost));
+        return 0;
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -1412,6 +1596,61 @@ int pb_op_dense_split(pb_ctx *c, const float *A, const float *w, const float *bi
     PB_TRY(e.setup(t, 2, layout, 0));
     return e.run(false, A, skip, M, 1, 1, K, K, 0, N, 1, 1, 1, layout, sa, tile, c->op_splitk, split_out, act, 0, rows_out, out, info, kernel,
                  kernel_cap);
+}
+
+// ---- the flow_raft band's kernels one by one (RaftOpEngine above) ----
+int pb_op_raft_geometry(int h8, int w8, int *geo) {
+    PB_CHECK(geo && h8 >= 1 && w8 >= 1, PB_ERR_ARG, "op_raft_geometry: bad arguments");
+    CorrGeo g;
+    corr_pyramid_geometry(h8, w8, g);
+    for (int l = 0; l < 4; ++l) { geo[l * 5] = g.h[l]; geo[l * 5 + 1] = g.w[l]; geo[l * 5 + 2] = g.wp[l]; geo[l * 5 + 3] = g.hp[l]; geo[l * 5 + 4] = g.ld[l]; }
+    return 0;
+}
+#define RAFT_OP_ENGINE(e) PB_HIP(hipSetDevice(c->device)); RaftOpEngine e(c->device); PB_TRY(e.setup(nullptr, 0, SL_F16, 0))
+int pb_op_raft_lookup(pb_ctx *c, const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows, void *out,
+                      float *levels) {
+    PB_CHECK(c && fmap1 && fmap2 && flow && out && n > 0 && guard_rows >= 0, PB_ERR_ARG, "op_raft_lookup: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.lookup(fmap1, fmap2, flow, n, h8, w8, o8, guard_rows, out, levels);
+}
+int pb_op_raft_convf1(pb_ctx *c, const float *flow, const float *w, const float *bias, int n, int h8, int w8, int passes, int o8, int gemm_path,
+                      int guard_rows, void *out) {
+    PB_CHECK(c && flow && w && bias && out && n > 0 && h8 > 0 && w8 > 0 && (passes == 1 || passes == 2) && guard_rows >= 0, PB_ERR_ARG,
+             "op_raft_convf1: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.convf1(flow, w, bias, n, h8, w8, passes, o8, gemm_path, guard_rows, out);
+}
+int pb_op_raft_flow_head2(pb_ctx *c, const float *x, const float *w, const float *bias, float *flow, int n, int H, int W, int split, int guard_rows) {
+    PB_CHECK(c && x && w && bias && flow && n > 0 && H > 0 && W > 0 && guard_rows >= 0, PB_ERR_ARG, "op_raft_flow_head2: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    pb_tensor t[2] = {};
+    t[0].name = "l.weight"; t[0].dtype = PB_F32; t[0].ndim = 4; t[0].data = (void *)w;
+    t[0].shape[0] = 2; t[0].shape[1] = 256; t[0].shape[2] = 3; t[0].shape[3] = 3;
+    t[1].name = "l.bias"; t[1].dtype = PB_F32; t[1].ndim = 1; t[1].shape[0] = 2; t[1].data = (void *)bias;
+    RaftOpEngine e(c->device);
+    PB_TRY(e.setup(t, 2, SL_F16, 0));
+    return e.flow_head2(x, flow, n, H, W, split, guard_rows);
+}
+int pb_op_raft_upsample(pb_ctx *c, const float *flow, const float *mask, int n, int h8, int w8, int pad_l, int pad_t, int sh, int sw, int guard,
+                        float *up, float *maxd) {
+    PB_CHECK(c && flow && mask && up && maxd && n > 0 && h8 > 0 && w8 > 0 && sh > 0 && sw > 0 && pad_l >= 0 && pad_t >= 0 && guard >= 0 &&
+             pad_t + sh <= 8 * h8 && pad_l + sw <= 8 * w8, PB_ERR_ARG, "op_raft_upsample: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.upsample(flow, mask, n, h8, w8, pad_l, pad_t, sh, sw, guard, up, maxd);
+}
+int pb_op_raft_instnorm(pb_ctx *c, const float *a, const float *b, int B, int HW, int C, int layout, int stats_lo, int bmode, int inplace,
+                        int guard_rows, float *stats, void *out) {
+    PB_CHECK(c && a && stats && out && B > 0 && HW > 0 && C > 0 && layout >= 0 && layout <= 2 && bmode >= 0 && bmode <= 2 && (b || !bmode) &&
+             guard_rows >= 0, PB_ERR_ARG, "op_raft_instnorm: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.instnorm(a, b, B, HW, C, layout, stats_lo, bmode, inplace, guard_rows, stats, out);
+}
+int pb_op_raft_state(pb_ctx *c, const float *ctx_rows, const float *flow, int rows, int ld, int inp_off, int guard_rows, float *h32, void *hx,
+                     void *hx2, float *flow0) {
+    PB_CHECK(c && ctx_rows && flow && h32 && hx && hx2 && flow0 && rows > 0 && (ld == 384 || ld == 576) && (inp_off == 128 || inp_off == 256) &&
+             guard_rows >= 0, PB_ERR_ARG, "op_raft_state: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.state(ctx_rows, flow, rows, ld, inp_off, guard_rows, h32, hx, hx2, flow0);
 }
 
 }  // extern "C"

@@ -243,8 +243,11 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
     geometry(H, W, scale, 8);
     PB_CHECK(h8_ >= 16 && w8_ >= 16, PB_ERR_ARG, "flow_raft: %dx%d is too small (the 4-level pyramid needs >= 128 px)", sh_, sw_);
     P8_ = (P_ + 7) / 8 * 8;       // row stride of the level-0 volume (the GEMM epilogue writes 8-column groups)
-    lh_[0] = h8_; lw_[0] = w8_;
-    for (int l = 1; l < 4; ++l) { lh_[l] = lh_[l - 1] / 2; lw_[l] = lw_[l - 1] / 2; }
+    {
+        CorrGeo g;
+        corr_pyramid_geometry(h8_, w8_, g);
+        for (int l = 0; l < 4; ++l) { lh_[l] = g.h[l]; lw_[l] = g.w[l]; lwp_[l] = g.wp[l]; lhp_[l] = g.hp[l]; pld_[l] = g.ld[l]; }
+    }
     const int64_t ND = (int64_t)(F - 1) * dirs;
     const size_t slack = 1 << 20;
     for (int pass = 0; pass < 2; ++pass) {
@@ -254,12 +257,7 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
         fmap_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2 + slack);
         ctx_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2);
         for (int l = 0; l < 4; ++l) {
-            // level l of the volume: fp16, one row per source pixel, targets in 8 x 8 tiles (raft_kernels.hip corr_tile_kernel)
-            lwp_[l] = (int)round_up(lw_[l], 8);
-            pld_[l] = (int)round_up(lh_[l], 8) * lwp_[l];
-            // a row stride that is a multiple of 256 lets launch_gemm pick the 256 x 256 ping-pong kernel for the level (measured at
-            // 18360 x 19136 x 256: 0.410 -> 0.339 ms, tools/volume_gemm_probe.py); taken when it costs under 2 % of the level's bytes
-            if (round_up(pld_[l], 256) * 50 <= (int64_t)pld_[l] * 51) pld_[l] = (int)round_up(pld_[l], 256);
+            // level l of the volume: fp16, one row per source pixel of pld_[l] entries (raft_kernels.hip corr_pyramid_geometry)
             pyr_[l] = (f16 *)carve((size_t)ND * P_ * pld_[l] * 2 + slack);
             fpool_[l] = l == 0 ? nullptr : (f16 *)carve((size_t)round_up((int64_t)F * lh_[l] * lw_[l], 256) * 256 * 2 + slack);
             ftile_[l] = (f16 *)carve((size_t)(F * (int64_t)pld_[l] + 256) * 256 * 2 + slack);
@@ -516,7 +514,7 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
     // ---- GRU iterations (raft.py:124-144, update.py:122-136) ----
     for (int it = 0; it < iters; ++it) {
         tic(F_ELT, 0, 0);
-        r = launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8);
+        r = launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, lhp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8);
         toc();
         if (r) return r;
         if (debug && it == 0 && (r = snapshot("corr0", corr_, (size_t)ND * P_ * Lhx * 2, Stage{nullptr, 1, ND, 324, h8_, w8_, Lhx, 0}))) return r;

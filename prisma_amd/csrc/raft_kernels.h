@@ -20,7 +20,12 @@ int launch_corr_tile(hipStream_t s, const f16 *x, f16 *y, int F, int h, int w, i
 // volume.hip: out[M, N] fp16 = A[M, 256] . W[N, 256]^T (one pair, one pyramid level); W has w_rows >= N addressable rows; the
 // A-stationary persistent kernel for this K = 256, output-bound shape
 int launch_corr_volume(hipStream_t s, const f16 *A, int M, const f16 *W, int N, int w_rows, f16 *out, int64_t ldo);
-int launch_corr_lookup(hipStream_t s, const f16 *const lv[4], const int h[4], const int w[4], const int wp[4], const int ld[4],
+// Geometry of the 4-level correlation pyramid over an h8 x w8 feature grid, shared by RaftEngine::prepare and the op-level entry points:
+// level sizes (floor halving, corr.py:22-27), the tiled layout's padded width / height (multiples of 8) and the volume's row stride
+struct CorrGeo { int h[4], w[4], wp[4], hp[4], ld[4]; };
+void corr_pyramid_geometry(int h8, int w8, CorrGeo &g);
+// hp: padded target rows of every level (CorrGeo::hp) - NOT ld / wp: the stride may carry more than a tile row of rounding
+int launch_corr_lookup(hipStream_t s, const f16 *const lv[4], const int h[4], const int w[4], const int wp[4], const int hp[4], const int ld[4],
                        const float *flow, int P, int w8, f16 *out, int64_t rows, int ldo = 384, int o8_off = 0, float o8_scale = 16.f);
 // convf1 (7 x 7, 2 -> 128, ReLU) straight from the fp32 flow field (raft_kernels.hip convf1_kernel)
 int convf1_packed_halfs(int passes);

@@ -171,31 +171,54 @@ __device__ __forceinline__ void lo8_load8(const char *p, float inv, float (&l)[8
 }
 
 // lo_off != 0: x is a split-fp16 map [hi | lo] and the statistics are those of hi + lo.
+// The sums are taken of x - pivot, the pivot being the channel's mean over the image's first IN_PIVOT pixels (every thread forms it the same
+// way): var = E[(x - p)^2] - E[x - p]^2 loses 1 + (mean - p)^2 / var of its fp32 digits to cancellation - 1 + 1 / IN_PIVOT on average, about 2
+// when those pixels sit three of their standard deviations off - where the unshifted E[x^2] - mean^2 loses 1 + mean^2 / var (5 for a map
+// with mean / std = 2, ~1000 at 30: the statistics were 10x resp. 400x further from float64 than a float32 two-pass evaluation,
+// tests/test_gpu_raft_ops.py test_instnorm; a single pixel as the pivot still left 1 + 9 on the unluckiest of 64 channels).  Chunk 0's block
+// leaves the pivot in the mean slot of `stats` for in_finalize.
+constexpr int IN_PIVOT = 8;
 __global__ __launch_bounds__(256) void in_stats_kernel(const f16 *__restrict__ x, int HW, int C8, int ldc,
-                                                        float *__restrict__ part, int chunk, int lo_off, int lo8_pa) {
+                                                        float *__restrict__ part, int chunk, int lo_off, int lo8_pa, float *__restrict__ stats) {
     __shared__ float red[256 * 16];
     const int b = blockIdx.y;
     const int c8 = threadIdx.x % C8, pl = threadIdx.x / C8, npl = blockDim.x / C8;
     const int p0 = blockIdx.x * chunk, p1 = min(p0 + chunk, HW);
-    float s[8], q[8];
+    auto load = [&](int64_t pix, float (&f)[8]) {
+        const f16x8 v = *(const f16x8 *)(x + pix * ldc + c8 * 8);
+        if (lo_off && lo8_pa >= 0) {
+            float l[8];
+            lo8_load8((const char *)(x + pix * ldc) + 3 * lo_off + c8 * 8, __builtin_ldexpf(1.f, -(lo8_pa + 12)), l);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
+            for (int j = 0; j < 8; ++j) f[j] = (float)v[j] + l[j];
+        } else if (lo_off) {
+            const f16x8 l = *(const f16x8 *)(x + pix * ldc + c8 * 8 + lo_off);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = (float)v[j] + (float)l[j];
+        } else {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) f[j] = (float)v[j];
+        }
+    };
+    float s[8], q[8], pv[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; pv[j] = 0.f; }
     if (pl < npl) {
+        const int np = min(IN_PIVOT, HW);
+        for (int p = 0; p < np; ++p) {
+            float f[8];
+            load((int64_t)b * HW + p, f);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) pv[j] += f[j];
+        }
+        const float inp = 1.f / (float)np;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) pv[j] *= inp;
         for (int p = p0 + pl; p < p1; p += npl) {
-            const f16x8 v = *(const f16x8 *)(x + ((int64_t)b * HW + p) * ldc + c8 * 8);
-            if (lo_off && lo8_pa >= 0) {
-                float l[8];
-                lo8_load8((const char *)(x + ((int64_t)b * HW + p) * ldc) + 3 * lo_off + c8 * 8, __builtin_ldexpf(1.f, -(lo8_pa + 12)), l);
+            float f[8];
+            load((int64_t)b * HW + p, f);
 #pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)v[j] + l[j]; s[j] += f; q[j] += f * f; }
-            } else if (lo_off) {
-                const f16x8 l = *(const f16x8 *)(x + ((int64_t)b * HW + p) * ldc + c8 * 8 + lo_off);
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)v[j] + (float)l[j]; s[j] += f; q[j] += f * f; }
-            } else {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float f = (float)v[j]; s[j] += f; q[j] += f * f; }
-            }
+            for (int j = 0; j < 8; ++j) { const float d = f[j] - pv[j]; s[j] += d; q[j] += d * d; }
         }
     }
 #pragma unroll
@@ -208,9 +231,14 @@ __global__ __launch_bounds__(256) void in_stats_kernel(const f16 *__restrict__ x
         float *dst = part + (((int64_t)blockIdx.x * gridDim.y + b) * C8 * 8 + c8 * 8) * 2;
 #pragma unroll
         for (int j = 0; j < 8; ++j) { dst[j * 2] = red[c8 * 16 + j]; dst[j * 2 + 1] = red[c8 * 16 + 8 + j]; }
+        if (blockIdx.x == 0) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) stats[((int64_t)b * C8 * 8 + c8 * 8 + j) * 2] = pv[j];
+        }
     }
 }
 
+// stats[i] holds the pivot in its mean slot (in_stats_kernel): mean = pivot + E[x - pivot]
 __global__ __launch_bounds__(256) void in_finalize_kernel(const float *__restrict__ part, int nchunk, int BC, float inv_hw,
                                                            float *__restrict__ stats) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -220,9 +248,9 @@ __global__ __launch_bounds__(256) void in_finalize_kernel(const float *__restric
         const float2 v = *(const float2 *)(part + ((int64_t)k * BC + i) * 2);
         s += v.x; q += v.y;
     }
-    const float mean = s * inv_hw;
-    const float var = fmaxf(q * inv_hw - mean * mean, 0.f);
-    stats[i * 2] = mean;
+    const float ms = s * inv_hw;
+    const float var = fmaxf(q * inv_hw - ms * ms, 0.f);
+    stats[i * 2] = stats[i * 2] + ms;
     stats[i * 2 + 1] = rsqrtf(var + 1e-5f);
 }
 
@@ -386,7 +414,7 @@ __device__ __forceinline__ const f16 *sel4(const f16 *const (&a)[4], int l) {
     const unsigned lo = sel4u((unsigned)p0, (unsigned)p1, (unsigned)p2, (unsigned)p3, l);
     const unsigned hi = sel4u((unsigned)(p0 >> 32), (unsigned)(p1 >> 32), (unsigned)(p2 >> 32), (unsigned)(p3 >> 32), l);
     return (const f16 *)(((unsigned long long)hi << 32) | lo);
-}      // hp8 = ld / wp: padded target rows of the level
+}      // hp8: padded target rows of the level (CorrGeo::hp)
 
 // CorrBlock.__call__ (corr.py:29-50): 9 x 9 bilinear window on each of the 4 levels around coords / 2^l, zero outside.
 // A block covers 7 pixels, i.e. 28 (pixel, level) windows:
@@ -745,7 +773,7 @@ int in_stats_chunks(int HW) { return (HW + 2047) / 2048; }
 int launch_in_stats(hipStream_t s, const f16 *x, int B, int HW, int C, int ldc, float *part, float *stats, int lo_off, int lo8_pa) {
     PB_CHECK(C % 8 == 0 && C <= 256 && 256 % (C / 8) == 0, -1, "instance norm: C=%d unsupported", C);
     const int chunk = 2048, nchunk = in_stats_chunks(HW);
-    hipLaunchKernelGGL(in_stats_kernel, dim3(nchunk, B), dim3(256), 0, s, x, HW, C / 8, ldc, part, chunk, lo_off, lo8_pa);
+    hipLaunchKernelGGL(in_stats_kernel, dim3(nchunk, B), dim3(256), 0, s, x, HW, C / 8, ldc, part, chunk, lo_off, lo8_pa, stats);
     hipLaunchKernelGGL(in_finalize_kernel, dim3((B * C + 255) / 256), dim3(256), 0, s, part, nchunk, B * C, 1.f / (float)HW, stats);
     LAUNCH_CHECK();
 }
@@ -767,10 +795,25 @@ int launch_corr_tile(hipStream_t s, const f16 *x, f16 *y, int F, int h, int w, i
     hipLaunchKernelGGL(corr_tile_kernel, dim3(nblk((int64_t)F * h * w * 32)), dim3(256), 0, s, x, y, F, h, w, wp, npad);
     LAUNCH_CHECK();
 }
-int launch_corr_lookup(hipStream_t s, const f16 *const lv[4], const int h[4], const int w[4], const int wp[4], const int ld[4],
+void corr_pyramid_geometry(int h8, int w8, CorrGeo &g) {
+    g.h[0] = h8; g.w[0] = w8;
+    for (int l = 1; l < 4; ++l) { g.h[l] = g.h[l - 1] / 2; g.w[l] = g.w[l - 1] / 2; }
+    for (int l = 0; l < 4; ++l) {
+        // level l of the volume: fp16, one row per source pixel, targets in 8 x 8 tiles (corr_tile_kernel)
+        g.wp[l] = (int)round_up(g.w[l], 8);
+        g.hp[l] = (int)round_up(g.h[l], 8);
+        g.ld[l] = g.hp[l] * g.wp[l];
+        // a row stride that is a multiple of 256 lets launch_gemm pick the 256 x 256 ping-pong kernel for the level (measured at
+        // 18360 x 19136 x 256: 0.410 -> 0.339 ms, tools/volume_gemm_probe.py); taken when it costs under 2 % of the level's bytes
+        if (round_up(g.ld[l], 256) * 50 <= (int64_t)g.ld[l] * 51) g.ld[l] = (int)round_up(g.ld[l], 256);
+    }
+}
+int launch_corr_lookup(hipStream_t s, const f16 *const lv[4], const int h[4], const int w[4], const int wp[4], const int hp[4], const int ld[4],
                        const float *flow, int P, int w8, f16 *out, int64_t rows, int ldo, int o8_off, float o8_scale) {
     PyrPtrs py;
-    for (int i = 0; i < 4; ++i) { py.lv[i] = lv[i]; py.h[i] = h[i]; py.w[i] = w[i]; py.wp[i] = wp[i]; py.ld[i] = ld[i]; py.hp8[i] = ld[i] / wp[i]; }
+    // hp8 is the level's padded height, not ld / wp: where the stride's rounding to 256 adds a tile row's worth of entries (e.g. a 129 x 17 or a
+    // 56 x 184 grid) rows hp .. ld / wp - 1 would pass the kernel's range test and address the next source pixel's volume row
+    for (int i = 0; i < 4; ++i) { py.lv[i] = lv[i]; py.h[i] = h[i]; py.w[i] = w[i]; py.wp[i] = wp[i]; py.ld[i] = ld[i]; py.hp8[i] = hp[i]; }
     PB_CHECK(rows < (1LL << 31), -1, "corr_lookup: %lld rows", (long long)rows);
     hipLaunchKernelGGL(corr_lookup_kernel, dim3((unsigned)((rows + 6) / 7)), dim3(256), 0, s, py, flow, P, w8, out, rows, ldo, o8_off, o8_scale);
     LAUNCH_CHECK();

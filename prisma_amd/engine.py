@@ -163,6 +163,14 @@ def _split_info(info, M: int) -> dict:
     return d
 
 
+def raft_geometry(h8: int, w8: int) -> List[dict]:
+    """the flow_raft band's pyramid plan over an h8 x w8 feature grid (csrc corr_pyramid_geometry; needs no GPU): per level h, w, the tiled
+    layout's padded wp / hp and the volume's row stride ld"""
+    geo = (C.c_int * 20)()
+    check(_lib.load().pb_op_raft_geometry(h8, w8, geo))
+    return [dict(h=geo[l * 5], w=geo[l * 5 + 1], wp=geo[l * 5 + 2], hp=geo[l * 5 + 3], ld=geo[l * 5 + 4]) for l in range(4)]
+
+
 class Ops(_Ctx):
     """Single-kernel entry points (pb_op_*) used by the parity tests."""
 
@@ -285,6 +293,84 @@ class Ops(_Ctx):
         check(self.lib.pb_op_dense_split(self.ctx, _ptr(A), _ptr(w), _ptr(bias), _ptr(sk), M, K, N, layout, sa, tile, int(split_out), act, rows,
                                          _ptr(out), info, kname, 128))
         return out, _split_info(info, M), kname.value.decode()
+
+    # ---- the flow_raft band's kernels one by one (pb_op_raft_*; tests/test_gpu_raft_ops.py) ----
+    def raft_lookup(self, fmap1, fmap2, flow, o8: bool = False, guard_rows: int = 8, want_levels: bool = False):
+        """pooling, tiling, the all-pairs volumes and the 9 x 9 x 4 lookup as RaftEngine::infer launches them.  fmap1 [n, P, 256], fmap2
+        [n, h8, w8, 256], flow [n P, 2] -> (raw rows as uint8 [n P + guard_rows, ldo * 2], [levels [n P, h_l, w_l]] or None)"""
+        fmap1, fmap2, flow = _f32(fmap1), _f32(fmap2), _f32(flow)
+        n, h8, w8, _ = fmap2.shape
+        rows = n * h8 * w8
+        assert fmap1.shape == (n, h8 * w8, 256) and fmap2.shape[3] == 256 and flow.shape == (rows, 2)
+        ldo = 576 if o8 else 384
+        out = np.empty((rows + guard_rows, ldo * 2), np.uint8)
+        geo = raft_geometry(h8, w8)
+        lv = np.empty(sum(rows * g["h"] * g["w"] for g in geo), np.float32) if want_levels else None
+        check(self.lib.pb_op_raft_lookup(self.ctx, _ptr(fmap1), _ptr(fmap2), _ptr(flow), n, h8, w8, int(o8), guard_rows, _ptr(out), _ptr(lv)))
+        levels = None
+        if want_levels:
+            levels, o = [], 0
+            for g in geo:
+                k = rows * g["h"] * g["w"]
+                levels.append(lv[o:o + k].reshape(rows, g["h"], g["w"]))
+                o += k
+        return out, levels
+
+    def raft_convf1(self, flow, w, bias, passes: int = 2, o8: bool = True, gemm_path: bool = False, guard_rows: int = 8) -> np.ndarray:
+        """flow [n, h8, w8, 2], w [128, 2, 7, 7] -> raw rows uint8 [n h8 w8 + guard_rows, ldo * 2] (ldo 192 with the e4m3 copy at byte 256, else 128)"""
+        flow, w, bias = _f32(flow), _f32(w), _f32(bias)
+        n, h8, w8, _ = flow.shape
+        assert w.shape == (128, 2, 7, 7) and bias.shape == (128,) and flow.shape[3] == 2
+        out = np.empty((n * h8 * w8 + guard_rows, (192 if o8 else 128) * 2), np.uint8)
+        check(self.lib.pb_op_raft_convf1(self.ctx, _ptr(flow), _ptr(w), _ptr(bias), n, h8, w8, passes, int(o8), int(gemm_path), guard_rows, _ptr(out)))
+        return out
+
+    def raft_flow_head2(self, x, w, bias, flow, split: bool = True, guard_rows: int = 8) -> np.ndarray:
+        """x [n, H, W, 256], w [2, 256, 3, 3], flow [n H W, 2] -> flow + conv (float32 [n H W + guard_rows, 2], guard rows NaN)"""
+        x, w, bias, flow = _f32(x), _f32(w), _f32(bias), _f32(flow)
+        n, H, W, _ = x.shape
+        assert x.shape[3] == 256 and w.shape == (2, 256, 3, 3) and flow.shape == (n * H * W, 2)
+        buf = np.empty((n * H * W + guard_rows, 2), np.float32)
+        buf[:n * H * W] = flow
+        check(self.lib.pb_op_raft_flow_head2(self.ctx, _ptr(x), _ptr(w), _ptr(bias), _ptr(buf), n, H, W, int(split), guard_rows))
+        return buf
+
+    def raft_upsample(self, flow, mask, h8: int, w8: int, pad_l: int, pad_t: int, sh: int, sw: int, guard: int = 64):
+        """flow [n, h8 w8, 2], mask [n h8 w8, 576] -> (up [n, sh, sw, 2], guard floats behind it, maxd [n])"""
+        flow, mask = _f32(flow), _f32(mask)
+        n = flow.shape[0]
+        assert flow.shape == (n, h8 * w8, 2) and mask.shape == (n * h8 * w8, 576)
+        buf = np.empty(n * sh * sw * 2 + guard, np.float32)
+        mx = np.empty(n, np.float32)
+        check(self.lib.pb_op_raft_upsample(self.ctx, _ptr(flow), _ptr(mask), n, h8, w8, pad_l, pad_t, sh, sw, guard, _ptr(buf), _ptr(mx)))
+        return buf[:n * sh * sw * 2].reshape(n, sh, sw, 2), buf[n * sh * sw * 2:], mx
+
+    def raft_instnorm(self, a, b=None, layout: int = 0, stats_lo: bool = True, normalise_b: bool = False, inplace: bool = False,
+                      guard_rows: int = 8):
+        """a (and b) [B, HW, C] -> (stats [B, C, 2] = {mean, rstd}, raw out uint8 [B HW + guard_rows, ld * 2]); layout 0 [C], 1 [hi | lo],
+        2 [hi | hi8 | lo8]"""
+        a = _f32(a)
+        B, HW, Cc = a.shape
+        bb = None if b is None else _f32(b)
+        assert bb is None or bb.shape == a.shape
+        ld = 2 * Cc if layout else Cc
+        st = np.empty((B, Cc, 2), np.float32)
+        out = np.empty((B * HW + guard_rows, ld * 2), np.uint8)
+        check(self.lib.pb_op_raft_instnorm(self.ctx, _ptr(a), _ptr(bb), B, HW, Cc, layout, int(stats_lo), 0 if bb is None else (2 if normalise_b else 1),
+                                           int(inplace), guard_rows, _ptr(st), _ptr(out)))
+        return st, out
+
+    def raft_state(self, ctx_rows, flow, ld: int = 576, inp_off: int = 256, guard_rows: int = 8):
+        """init_state + put_flow -> (h32 [rows + guard, 128], hx raw, hx2 raw uint8 [rows + guard, ld * 2], flow after init [rows + guard, 2])"""
+        ctx_rows, flow = _f32(ctx_rows), _f32(flow)
+        rows = ctx_rows.shape[0]
+        assert ctx_rows.shape == (rows, 256) and flow.shape == (rows, 2)
+        h32 = np.empty((rows + guard_rows, 128), np.float32)
+        hx = np.empty((rows + guard_rows, ld * 2), np.uint8)
+        hx2 = np.empty_like(hx)
+        f0 = np.empty((rows + guard_rows, 2), np.float32)
+        check(self.lib.pb_op_raft_state(self.ctx, _ptr(ctx_rows), _ptr(flow), rows, ld, inp_off, guard_rows, _ptr(h32), _ptr(hx), _ptr(hx2), _ptr(f0)))
+        return h32, hx, hx2, f0
 
     def bilinear(self, x, OH: int, OW: int, align_corners: bool) -> np.ndarray:
         x = _f32(x)

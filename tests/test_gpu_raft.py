@@ -177,6 +177,19 @@ def test_scaled_sequence_matches_oracle(net):
         assert relmax(flow[i, 0], fwd) < TOL_RANGE and rell2(flow[i, 0], fwd) < TOL_L2
 
 
+def test_stride_rounded_grid_matches_oracle(net):
+    """448 x 1472 -> a 56 x 184 feature grid: level 0 of the volume has 56 x 184 = 10304 entries per source pixel and its row stride is rounded
+    up to 10496 (a multiple of 256, under 2 % more).  10496 / 184 = 57: a lookup that takes its row bound from the stride accepts target row
+    56, which does not exist - its tile address lies in the NEXT source pixel's row - so the bottom four rows of feature pixels read live
+    correlation values where the reference reads zero padding, already at zero flow (tests/test_gpu_raft_ops.py isolates it on a 129 x 17
+    grid).  No frame size of the golden vectors has such a stride."""
+    fr = synth.frame_pair_sequence(2, 448, 1472, seed=21)
+    flow, _, _ = net.infer_sequence(fr, scale=1.0, iters=3, backward=False)
+    fwd, _ = R.infer_pair(synth.raft_weights(seed=4321), fr[0], fr[1], scale=1.0, iters=3, backward=False)
+    print("\n  448x1472 relmax %.3e relL2 %.3e  %s" % (relmax(flow[0, 0], fwd), rell2(flow[0, 0], fwd), pw(flow[0, 0], fwd)))
+    assert relmax(flow[0, 0], fwd) < TOL_RANGE and rell2(flow[0, 0], fwd) < TOL_L2
+
+
 def test_identical_frames_give_finite_encode(net):
     fr = synth.frame_pair_sequence(1, 128, 160, seed=9)
     flow, rgb, mx = net.infer_sequence(np.concatenate([fr, fr]), scale=1.0, iters=2)
