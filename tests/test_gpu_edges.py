@@ -265,3 +265,65 @@ def test_submit_wait_streams_clips_with_the_bytes_of_the_blocking_calls():
     assert np.array_equal(d, ref[2][0]) and np.array_equal(rgb, ref[2][1]) and np.array_equal(fl, ref[2][4]) and np.array_equal(fmx, ref[2][6])
     check_clip(0)
     dn.close(); fn.close()
+
+
+def test_host_pipelines_with_page_locked_and_pageable_buffers_mixed():
+    """The host-pointer pipelines decide lane by lane (frames in, each result out) whether the copy engines address the caller's array or a
+    pinned staging buffer of the ctx.  One ctx per band, chunks of 2 (three depth chunks / two flow chunks per call, so slots are reused):
+    page-locked frames with pageable results, pageable frames with page-locked results, the same two at a larger size (every lane regrows
+    while staging exists on some lanes and not on others), and depth without the depth map (a lane of zero bytes).  Every result equals the
+    device-pointer entry point's on the same frames, which does not go through the pipeline."""
+    torch = pytest.importorskip("torch")
+    dn = engine.DepthAnything(synth.depth_anything_weights("vits", seed=1234), "vits", max_batch=3)
+    fn = engine.FlowRaft(synth.raft_weights(seed=4321))
+    dn.set_option("host_chunk", 2); fn.set_option("host_chunk", 2)
+    held = []
+
+    def pinned(a):                  # a page-locked copy of `a` as a numpy view
+        t = torch.from_numpy(a).pin_memory()
+        held.append(t)
+        return t.numpy()
+
+    def dev(shape, dt):
+        return torch.zeros(shape, dtype=dt, device="cuda")
+
+    def depth_dev(fr):
+        n, H, W, _ = fr.shape
+        d_fr = torch.from_numpy(fr).cuda()
+        out = (dev((n, H, W), torch.float32), dev((n, H, W, 3), torch.uint8), dev((n,), torch.float32), dev((n,), torch.float32))
+        torch.cuda.synchronize()
+        dn.infer_dev(d_fr.data_ptr(), n, H, W, *(t.data_ptr() for t in out), True)
+        dn.sync()
+        return [t.cpu().numpy() for t in out]
+
+    def flow_dev(fr):
+        F, H, W, _ = fr.shape
+        sh, sw = engine.flow_out_size(H, W, 1.0)
+        d_fr = torch.from_numpy(fr).cuda()
+        out = (dev((F - 1, 1, sh, sw, 2), torch.float32), dev((F - 1, 1, sh, sw, 3), torch.uint8), dev((F - 1, 1), torch.float32))
+        torch.cuda.synchronize()
+        fn.infer_sequence_dev(d_fr.data_ptr(), F, H, W, 1.0, 2, False, *(t.data_ptr() for t in out))
+        fn.sync()
+        return [t.cpu().numpy() for t in out]
+
+    def same(got, want, what):
+        assert len(got) == len(want)
+        for k, (a, b) in enumerate(zip(got, want)):
+            assert np.array_equal(a, b), (what, k)
+
+    for (dh, dw), (fh, fw) in (((90, 120), (136, 168)), ((120, 160), (152, 200))):
+        fr = synth.frames(5, dh, dw, seed=3 + dh)
+        want = depth_dev(fr)
+        same(dn.infer_batch(pinned(fr)), want, ("depth", dh, "page-locked frames"))
+        same(dn.infer_batch(fr, out_depth=pinned(np.zeros_like(want[0])), out_rgb=pinned(np.zeros_like(want[1]))), want,
+             ("depth", dh, "page-locked results"))
+        seq = synth.frame_pair_sequence(5, fh, fw, seed=5 + fh)
+        fwant = flow_dev(seq)
+        same(fn.infer_sequence(pinned(seq), scale=1.0, iters=2), fwant, ("flow", fh, "page-locked frames"))
+        same(fn.infer_sequence(seq, scale=1.0, iters=2, out_flow=pinned(np.zeros_like(fwant[0])), out_rgb=pinned(np.zeros_like(fwant[1]))),
+             fwant, ("flow", fh, "page-locked results"))
+    none, rgb, mn, mx = dn.infer_batch(pinned(fr), want_depth=False)
+    assert none is None
+    same((rgb, mn, mx), want[1:], "depth without the depth map")
+    same(dn.infer_batch(fr, want_depth=False, out_rgb=pinned(np.zeros_like(want[1])))[1:], want[1:], "depth without the depth map, page-locked rgb")
+    dn.close(); fn.close()
