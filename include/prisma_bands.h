@@ -373,6 +373,46 @@ int pb_op_raft_instnorm(pb_ctx *ctx, const float *a, const float *b, int B, int 
                         int guard_rows, float *stats, void *out);
 int pb_op_raft_state(pb_ctx *ctx, const float *ctx_rows, const float *flow, int rows, int ld, int inp_off, int guard_rows, float *h32, void *hx,
                      void *hx2, float *flow0);
+/* The flow_gmflow band's own kernels one by one, through the launchers and arguments GmflowEngine::infer uses (tests/test_gpu_gmflow_ops.py).
+ * (h8, w8) is the 1/8-resolution token grid (both even, >= 4): P = h8 w8 tokens per image, 2 x 2 windows of Lw = P / 4 tokens, V^T row strides
+ * ldv = Lw and ldvP = P rounded up to 32.  Raw buffers are preset to 0xFF bytes and carry guard_rows untouched rows, as above.
+ * pb_op_gm_tables (no GPU needed): the two host tables of the engine's plan - pos [P, 128] (per-window sine embedding, tiled) and the
+ *   shifted-window region ids [4, Lw] in window order.
+ * tokens: feat [NP + 1, P, 128], pos [P, 128] -> X (2 NP P + guard) x 128 floats, Xs the same rows x 256 halfs [hi | lo].
+ * split_rows: src [rows, ld] of which C columns -> (rows + guard) x 2 C halfs.   grid_vt: (64 + guard) x ldvP halfs.
+ * pack: src [images P, ld]; job j takes columns cols[j] .. + 128 as kinds[j] 0: window rows (4 images Lw + guard) x 256 halfs, 1: V^T
+ *   (4 images x 2 x 128 + guard) x ldv halfs; outs[j] receives job j's buffer.
+ * ln: M [rows, 128], X (xrows + guard) x 128 floats read and returned whole; out (xrows + guard) x (mode ? 512 : 256) halfs.
+ * match_flow: O [B, P, 32] -> flow (B P + guard) x 2 floats, vt (64 B + guard) x ldvP halfs, NOT zeroed first (the engine's arena is).
+ * upsampler_in: O [B, P, 32], X [images, P, 128] (batch element b takes image b img_step) -> flow (B P + guard) x 2, map (B P + guard) x 384 halfs.
+ * pb_op_attention128_cfg: attention128.hip's general form.  q, k [B, L, 128] as rows of ldq halfs ([hi] or [hi | lo]); strided 0: packed
+ *   buffers; 1: ONE buffer of B images, Q = K, batch stride one image, kxor 1 (k unused); 2: ONE buffer [q_0, k_0, q_1, ..], stride two images,
+ *   K = Q + one image.  v [v_shared ? 1 : B, L, vcols] as V^T [.., 2, vcols, ldv]; `fill` goes into columns [L, ldv) and into the lo rows
+ *   wherever the kernel must not read them (split = 0 or pv_single).  region [nreg, L] or NULL.  o [B, L, vcols].
+ * window_block: Y [images P, 384] = q | k | v in token order; pack, the window attention (pv_single, the production region table when
+ *   shifted, kxor 4 when cross), then gm_ln (windowed, mode 0, gamma / beta [128]) on the attention output; X [images P, 128] in and out.
+ * match: tokens [2 NP, P, 128]; split_rows, the global matching over the shared coordinate V^T, match_flow -> flow [NP dirs, P, 2].
+ * propagate: q, k, X [2 NP, P, 128], flow_in [NP dirs, P, 2]; match_flow on flow_in + own coordinate (flow_match returns the fp32 flow it made
+ *   of that), the propagation attention, upsampler_in -> flow_prop [NP dirs, P, 2], map (NP dirs P + guard) x 384 halfs.  Both flow chains
+ *   zero the flow V^T first, as the engine's arena is zeroed. */
+int pb_op_gm_tables(int h8, int w8, float *pos, int8_t *region);
+int pb_op_gm_tokens(pb_ctx *ctx, const float *feat, const float *pos, int NP, int P, int guard_rows, float *X, void *Xs);
+int pb_op_gm_split_rows(pb_ctx *ctx, const float *src, int rows, int ld, int C, int guard_rows, void *out);
+int pb_op_gm_grid_vt(pb_ctx *ctx, int h8, int w8, int guard_rows, void *out);
+int pb_op_gm_pack(pb_ctx *ctx, const float *src, int images, int h8, int w8, int ld, int njobs, const int *cols, const int *kinds, int shifted,
+                  int guard_rows, void **outs);
+int pb_op_gm_ln(pb_ctx *ctx, const float *M, const float *gamma, const float *beta, float *X, int rows, int xrows, int h8, int w8, int windowed,
+                int shifted, int mode, int guard_rows, void *out);
+int pb_op_gm_match_flow(pb_ctx *ctx, const float *O, int B, int h8, int w8, int guard_rows, float *flow, void *vt);
+int pb_op_gm_upsampler_in(pb_ctx *ctx, const float *O, const float *X, int B, int images, int P, int img_step, int guard_rows, float *flow,
+                          void *map);
+int pb_op_attention128_cfg(pb_ctx *ctx, const float *q, const float *k, const float *v, const int8_t *region, int nreg, float *o, int B, int L,
+                           int split, int pv_single, int vcols, int v_shared, int kxor, int ldq, int strided, float fill);
+int pb_op_gm_window_block(pb_ctx *ctx, const float *Y, float *X, const float *gamma, const float *beta, int images, int h8, int w8, int shifted,
+                          int cross, int split);
+int pb_op_gm_match(pb_ctx *ctx, const float *tokens, int NP, int h8, int w8, int dirs, int split, float *flow);
+int pb_op_gm_propagate(pb_ctx *ctx, const float *q, const float *k, const float *flow_in, const float *X, int NP, int h8, int w8, int dirs,
+                       int split, int guard_rows, float *flow_match, float *flow_prop, void *map);
 /* bilinear resize NCHW float32, align_corners 0/1 (torch F.interpolate semantics). */
 int pb_op_bilinear(pb_ctx *ctx, const float *x, float *y, int B, int C, int H, int W, int OH, int OW,
                    int align_corners);

@@ -119,6 +119,18 @@ SYMBOLS = {
     "pb_op_raft_upsample": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),
     "pb_op_raft_instnorm": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),
     "pb_op_raft_state": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P, _P, _P, _P]),
+    "pb_op_gm_tables": (C.c_int, [C.c_int, C.c_int, _P, _P]),
+    "pb_op_gm_tokens": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "pb_op_gm_split_rows": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
+    "pb_op_gm_grid_vt": (C.c_int, [_P] + [C.c_int] * 3 + [_P]),
+    "pb_op_gm_pack": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P, _P, C.c_int, C.c_int, _P]),
+    "pb_op_gm_ln": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8 + [_P]),
+    "pb_op_gm_match_flow": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P, _P]),
+    "pb_op_gm_upsampler_in": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P, _P]),
+    "pb_op_attention128_cfg": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P] + [C.c_int] * 9 + [C.c_float]),
+    "pb_op_gm_window_block": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 6),
+    "pb_op_gm_match": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
+    "pb_op_gm_propagate": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P]),
     "pb_op_bilinear": (C.c_int, [_P, _P, _P] + [C.c_int] * 7),
     "pb_op_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "pb_op_encode_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

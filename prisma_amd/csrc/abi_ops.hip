@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "abi_ctx.h"
+#include "gmflow_engine.h"
 
 namespace {
 // ---- one layer through EngineBase's own packing and launch code (pb_op_conv2d_split / pb_op_dense_split) ------------------------------
@@ -315,6 +316,246 @@ class RaftOpEngine : public SplitOpEngine {
         PB_HIP(hipMemcpy(hx, dhx.p, (size_t)(rows + guard_rows) * ld * 2, hipMemcpyDeviceToHost));
         PB_HIP(hipMemcpy(hx2, dhx2.p, (size_t)(rows + guard_rows) * ld * 2, hipMemcpyDeviceToHost));
         return 0;
+    }
+};
+
+// ---- the flow_gmflow band's own kernels one by one (pb_op_gm_*, pb_op_attention128_cfg) ------------------------------------------------
+// Every entry point calls the launcher GmflowEngine::infer calls, with the arguments infer gives it; the window geometry comes from
+// gm_geometry, the function prepare_g plans with.  Raw output buffers are preset to 0xFF bytes and carry guard rows, as the raft ops above.
+class GmOpEngine : public RaftOpEngine {
+  public:
+    explicit GmOpEngine(int device) : RaftOpEngine(device) {}
+    static constexpr size_t kSlack = 1 << 16;               // what prepare_g leaves behind every fp16 buffer
+    GmGeom g{};
+    int ldvP = 0;
+    int geom(int h8, int w8) {
+        PB_CHECK(h8 >= 4 && w8 >= 4 && h8 % 2 == 0 && w8 % 2 == 0, PB_ERR_ARG, "op_gm: a %d x %d token grid (both even, >= 4)", h8, w8);
+        gm_geometry(h8, w8, g, ldvP);
+        return 0;
+    }
+    int down(void *dst, const DevMem &d, size_t bytes) {
+        PB_HIP(hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+    int tokens(const float *feat, const float *pos, int NP, int P, int guard, float *X, void *Xs) {
+        const int64_t R = (int64_t)NP * 2 * P;
+        DevMem df, dp, dX, dXs;
+        PB_TRY(up(df, feat, (size_t)(NP + 1) * P * 128 * 4)); PB_TRY(up(dp, pos, (size_t)P * 128 * 4));
+        PB_TRY(preset(dX, (size_t)(R + guard) * 128 * 4)); PB_TRY(preset(dXs, (size_t)(R + guard) * 256 * 2));
+        PB_TRY(launch_gm_tokens(stream, df.as<float>(), dp.as<float>(), dX.as<float>(), dXs.as<f16>(), NP, P));
+        PB_TRY(finish(X, dX, (size_t)(R + guard) * 128 * 4));
+        return down(Xs, dXs, (size_t)(R + guard) * 256 * 2);
+    }
+
+    int split_rows(const float *src, int64_t rows, int ld, int C, int guard, void *out) {
+        DevMem ds, dd;
+        PB_TRY(up(ds, src, (size_t)rows * ld * 4));
+        PB_TRY(preset(dd, (size_t)(rows + guard) * 2 * C * 2));
+        PB_TRY(launch_gm_split_rows(stream, ds.as<float>(), ld, C, dd.as<f16>(), rows));
+        return finish(out, dd, (size_t)(rows + guard) * 2 * C * 2);
+    }
+
+    int grid_vt(int guard, void *out) {
+        DevMem dv;
+        PB_TRY(preset(dv, (size_t)(64 + guard) * ldvP * 2));
+        PB_TRY(launch_gm_grid_vt(stream, dv.as<f16>(), g.P, g.w8, ldvP));
+        return finish(out, dv, (size_t)(64 + guard) * ldvP * 2);
+    }
+
+    size_t pack_bytes(int Bw, int is_vt, int guard) const {
+        return is_vt ? ((size_t)Bw * 2 * 128 + guard) * g.ldv * 2 : ((size_t)Bw * g.Lw + guard) * 256 * 2;
+    }
+    int pack(const float *src, int images, int ld, int njobs, const int *cols, const int *kinds, int shifted, int guard, void **outs) {
+        const int Bw = images * 4;
+        DevMem ds, dd[5];
+        PB_TRY(up(ds, src, (size_t)images * g.P * ld * 4));
+        GmPackJobs jobs{};
+        jobs.n = njobs;
+        for (int j = 0; j < njobs; ++j) {
+            PB_TRY(preset(dd[j], pack_bytes(Bw, kinds[j], guard)));
+            jobs.j[j] = GmPackJob{ds.as<float>(), ld, cols[j], dd[j].as<f16>(), kinds[j]};
+        }
+        PB_TRY(launch_gm_pack(stream, jobs, g, Bw, shifted));
+        PB_HIP(hipStreamSynchronize(stream));
+        for (int j = 0; j < njobs; ++j) PB_TRY(down(outs[j], dd[j], pack_bytes(Bw, kinds[j], guard)));
+        return 0;
+    }
+
+    // X arrives with its guard rows (the caller presets them) and is returned whole: mode 1 must leave every byte of it alone
+    int ln(const float *M, const float *gamma, const float *beta, float *X, int64_t rows, int64_t xrows, int windowed, int shifted, int mode, int guard,
+           void *out) {
+        const int ldo = mode ? 512 : 256;
+        DevMem dM, dg, db, dX, dout;
+        PB_TRY(up(dM, M, (size_t)rows * 128 * 4)); PB_TRY(up(dg, gamma, 128 * 4)); PB_TRY(up(db, beta, 128 * 4));
+        PB_TRY(up(dX, X, (size_t)(xrows + guard) * 128 * 4));
+        PB_TRY(preset(dout, (size_t)(xrows + guard) * ldo * 2));
+        PB_TRY(launch_gm_ln(stream, dM.as<float>(), dg.as<float>(), db.as<float>(), dX.as<float>(), dout.as<f16>(), rows, g, windowed, shifted, mode));
+        PB_TRY(finish(X, dX, (size_t)(xrows + guard) * 128 * 4));
+        return down(out, dout, (size_t)(xrows + guard) * ldo * 2);
+    }
+
+    // stand-alone: Vt is NOT zeroed first (0xFF preset), so the test sees exactly which halfs the kernel owns; the engine and the two flow
+    // chains below rely on commit_arena's memset for rows 2..31, 34..63 and the pad columns
+    int match_flow(const float *O, int B, int guard, float *flow, void *vt) {
+        const int64_t n = (int64_t)B * g.P;
+        DevMem dO, dflow, dvt;
+        PB_TRY(up(dO, O, (size_t)n * 32 * 4));
+        PB_TRY(preset(dflow, (size_t)(n + guard) * 2 * 4)); PB_TRY(preset(dvt, (size_t)(B * 64 + guard) * ldvP * 2));
+        PB_TRY(launch_gm_match_flow(stream, dO.as<float>(), dflow.as<float>(), dvt.as<f16>(), B, g.P, g.w8, ldvP));
+        PB_TRY(finish(flow, dflow, (size_t)(n + guard) * 2 * 4));
+        return down(vt, dvt, (size_t)(B * 64 + guard) * ldvP * 2);
+    }
+
+    int upsampler_in(const float *O, const float *X, int B, int nimg, int P, int img_step, int guard, float *flow, void *map) {
+        const int64_t n = (int64_t)B * P;
+        DevMem dO, dX, dflow, dmap;
+        PB_TRY(up(dO, O, (size_t)n * 32 * 4)); PB_TRY(up(dX, X, (size_t)nimg * P * 128 * 4));
+        PB_TRY(preset(dflow, (size_t)(n + guard) * 2 * 4)); PB_TRY(preset(dmap, (size_t)(n + guard) * 384 * 2));
+        PB_TRY(launch_gm_upsampler_in(stream, dO.as<float>(), dX.as<float>(), dflow.as<float>(), dmap.as<f16>(), B, P, img_step));
+        PB_TRY(finish(flow, dflow, (size_t)(n + guard) * 2 * 4));
+        return down(map, dmap, (size_t)(n + guard) * 384 * 2);
+    }
+
+    // rows of ldq halfs: [hi (128)] or [hi | lo]
+    static void host_rows(f16 *dst, const float *src, int64_t rows, int ldq) {
+        for (int64_t r = 0; r < rows; ++r)
+            for (int d = 0; d < 128; ++d) {
+                const float x = src[r * 128 + d];
+                const f16 hi = (f16)x;
+                dst[r * ldq + d] = hi;
+                if (ldq == 256) dst[r * ldq + 128 + d] = (f16)(x - (float)hi);
+            }
+    }
+    // strided 0: Q and K packed, one buffer each.  1: ONE buffer of B images, Q = K = its base, batch stride one image (the caller gives kxor = 1:
+    // the matching in both directions; k is not read).  2: ONE buffer of 2 B images [q_0, k_0, q_1, k_1, ..], batch stride two images, K = Q + one
+    // image (the matching in one direction).  Vt is [Bv, 2, vcols, ldv] with the batch stride given explicitly, as the engine does for its window
+    // attention and its propagation: hi rows f16(v); lo rows f16(v - hi) where the kernel reads them (split without pv_single), else `fill`;
+    // columns [L, ldv) of every row `fill`.
+    int attention_cfg(const float *q, const float *k, const float *v, const int8_t *region, int nreg, float *o, int B, int L, int split, int pv_single,
+                      int vcols, int v_shared, int kxor, int ldq, int strided, float fill) {
+        const int64_t img = (int64_t)L * ldq;
+        const int ldv = (int)round_up(L, 32), Bv = v_shared ? 1 : B, spv = split && !pv_single;
+        std::vector<f16> hq, hk;
+        if (strided == 2) {
+            hq.resize((size_t)2 * B * img);
+            for (int b = 0; b < B; ++b) {
+                host_rows(hq.data() + (size_t)2 * b * img, q + (size_t)b * L * 128, L, ldq);
+                host_rows(hq.data() + (size_t)(2 * b + 1) * img, k + (size_t)b * L * 128, L, ldq);
+            }
+        } else {
+            hq.resize((size_t)B * img);
+            host_rows(hq.data(), q, (int64_t)B * L, ldq);
+            if (!strided) { hk.resize((size_t)B * img); host_rows(hk.data(), k, (int64_t)B * L, ldq); }
+        }
+        std::vector<f16> hv((size_t)Bv * 2 * vcols * ldv, (f16)fill);
+        for (int b = 0; b < Bv; ++b)
+            for (int t = 0; t < L; ++t)
+                for (int d = 0; d < vcols; ++d) {
+                    const float x = v[((size_t)b * L + t) * vcols + d];
+                    const f16 hi = (f16)x;
+                    hv[(((size_t)b * 2 + 0) * vcols + d) * ldv + t] = hi;
+                    if (spv) hv[(((size_t)b * 2 + 1) * vcols + d) * ldv + t] = (f16)(x - (float)hi);
+                }
+        DevMem dq, dk, dv, dr, dout;
+        PB_TRY(dq.alloc(hq.size() * 2 + kSlack));
+        PB_HIP(hipMemcpy(dq.p, hq.data(), hq.size() * 2, hipMemcpyHostToDevice));
+        if (!strided) {
+            PB_TRY(dk.alloc(hk.size() * 2 + kSlack));
+            PB_HIP(hipMemcpy(dk.p, hk.data(), hk.size() * 2, hipMemcpyHostToDevice));
+        }
+        PB_TRY(dv.alloc(hv.size() * 2 + kSlack));
+        PB_HIP(hipMemcpy(dv.p, hv.data(), hv.size() * 2, hipMemcpyHostToDevice));
+        if (region) PB_TRY(up(dr, region, (size_t)nreg * L));
+        PB_TRY(preset(dout, (size_t)B * L * vcols * 4));
+        Attn128Args a;
+        a.Q = dq.as<f16>(); a.K = strided == 0 ? dk.as<f16>() : (strided == 1 ? dq.as<f16>() : dq.as<f16>() + img);
+        a.Vt = dv.as<f16>(); a.region = region ? dr.as<int8_t>() : nullptr; a.nreg = nreg; a.O = dout.as<float>();
+        a.B = B; a.L = L; a.ldv = ldv; a.split = split; a.vcols = vcols; a.v_shared = v_shared; a.kxor = kxor; a.pv_single = pv_single; a.ldq = ldq;
+        a.v_bstride = (int64_t)2 * vcols * ldv;
+        if (strided) a.q_bstride = a.k_bstride = strided == 1 ? img : 2 * img;
+        PB_TRY(launch_attention128x(stream, a));
+        return finish(o, dout, (size_t)B * L * vcols * 4);
+    }
+
+    // pack (q, k, v), the window attention as infer configures it, gm_ln (windowed, mode 0) straight on the attention output
+    int window_block(const float *Y, float *X, const float *gamma, const float *beta, int images, int shifted, int cross, int split) {
+        const int64_t R = (int64_t)images * g.P;
+        const int Bw = images * 4;
+        DevMem dY, dX, dg, db, dQ, dK, dVt, dO, dXs, dreg;
+        PB_TRY(up(dY, Y, (size_t)R * 384 * 4)); PB_TRY(up(dX, X, (size_t)R * 128 * 4)); PB_TRY(up(dg, gamma, 128 * 4)); PB_TRY(up(db, beta, 128 * 4));
+        PB_TRY(dQ.alloc((size_t)R * 256 * 2 + kSlack)); PB_TRY(dK.alloc((size_t)R * 256 * 2 + kSlack)); PB_TRY(dXs.alloc((size_t)R * 256 * 2 + kSlack));
+        PB_TRY(dVt.alloc((size_t)Bw * 2 * 128 * g.ldv * 2 + kSlack)); PB_TRY(dO.alloc((size_t)R * 128 * 4));
+        GmPackJobs jobs{};
+        jobs.n = 3;
+        jobs.j[0] = GmPackJob{dY.as<float>(), 384, 0, dQ.as<f16>(), 0};
+        jobs.j[1] = GmPackJob{dY.as<float>(), 384, 128, dK.as<f16>(), 0};
+        jobs.j[2] = GmPackJob{dY.as<float>(), 384, 256, dVt.as<f16>(), 1};
+        PB_TRY(launch_gm_pack(stream, jobs, g, Bw, shifted));
+        if (shifted) {
+            std::vector<int8_t> reg;
+            shift_regions(g.h8, g.w8, reg);
+            PB_TRY(up(dreg, reg.data(), reg.size()));
+        }
+        Attn128Args a;
+        a.Q = dQ.as<f16>(); a.K = dK.as<f16>(); a.Vt = dVt.as<f16>(); a.region = shifted ? dreg.as<int8_t>() : nullptr; a.nreg = 4; a.O = dO.as<float>();
+        a.B = Bw; a.L = g.Lw; a.ldv = g.ldv; a.split = split; a.vcols = 128; a.ldq = 256; a.v_bstride = (int64_t)2 * 128 * g.ldv;
+        a.pv_single = 1;
+        if (cross) a.kxor = 4;
+        PB_TRY(launch_attention128x(stream, a));
+        PB_TRY(launch_gm_ln(stream, dO.as<float>(), dg.as<float>(), db.as<float>(), dX.as<float>(), dXs.as<f16>(), R, g, 1, shifted, 0));
+        return finish(X, dX, (size_t)R * 128 * 4);
+    }
+
+    // split_rows, the global matching with the shared coordinate V^T, match_flow.  DevMem::alloc zeroes Vtf as commit_arena zeroes the arena.
+    int match(const float *tok, int NP, int dirs, int split, float *flow) {
+        const int P = g.P, B = NP * dirs;
+        const int64_t R = (int64_t)NP * 2 * P, img = (int64_t)P * 256;
+        DevMem dT, dXs, dgrid, dOm, dflow, dVtf;
+        PB_TRY(up(dT, tok, (size_t)R * 128 * 4));
+        PB_TRY(dXs.alloc((size_t)R * 256 * 2 + kSlack)); PB_TRY(dgrid.alloc((size_t)64 * ldvP * 2 + kSlack));
+        PB_TRY(dOm.alloc((size_t)B * P * 32 * 4)); PB_TRY(preset(dflow, (size_t)B * P * 2 * 4)); PB_TRY(dVtf.alloc((size_t)B * 64 * ldvP * 2 + kSlack));
+        PB_TRY(launch_gm_split_rows(stream, dT.as<float>(), 128, 128, dXs.as<f16>(), R));
+        PB_TRY(launch_gm_grid_vt(stream, dgrid.as<f16>(), P, g.w8, ldvP));
+        Attn128Args m;
+        m.Q = dXs.as<f16>(); m.O = dOm.as<float>(); m.B = B; m.L = P; m.ldv = ldvP; m.split = split; m.vcols = 32; m.ldq = 256;
+        m.Vt = dgrid.as<f16>(); m.v_shared = 1;
+        if (dirs == 2) { m.K = dXs.as<f16>(); m.q_bstride = m.k_bstride = img; m.kxor = 1; }
+        else { m.K = dXs.as<f16>() + img; m.q_bstride = m.k_bstride = 2 * img; }
+        PB_TRY(launch_attention128x(stream, m));
+        PB_TRY(launch_gm_match_flow(stream, dOm.as<float>(), dflow.as<float>(), dVtf.as<f16>(), B, P, g.w8, ldvP));
+        return finish(flow, dflow, (size_t)B * P * 2 * 4);
+    }
+
+    // match_flow on O = flow_in + own coordinate (fp32: flowm returns the flow the kernel made of it, the V of what follows), the propagation
+    // attention over the zeroed Vtf, upsampler_in
+    int propagate(const float *q, const float *k, const float *flow_in, const float *X, int NP, int dirs, int split, int guard, float *flowm, float *flowp,
+                  void *map) {
+        const int P = g.P, B = NP * dirs;
+        const int64_t R = (int64_t)NP * 2 * P, img = (int64_t)P * 256, n = (int64_t)B * P;
+        std::vector<float> hO((size_t)n * 32, 0.f);
+        for (int64_t i = 0; i < n; ++i) {
+            const int t = (int)(i % P);
+            hO[i * 32] = flow_in[i * 2] + (float)(t % g.w8);
+            hO[i * 32 + 1] = flow_in[i * 2 + 1] + (float)(t / g.w8);
+        }
+        DevMem dOm, dq, dk, dX, dqs, dks, dVtf, dfm, dfp, dmap;
+        PB_TRY(up(dOm, hO.data(), hO.size() * 4)); PB_TRY(up(dq, q, (size_t)R * 128 * 4)); PB_TRY(up(dk, k, (size_t)R * 128 * 4));
+        PB_TRY(up(dX, X, (size_t)R * 128 * 4));
+        PB_TRY(dqs.alloc((size_t)R * 256 * 2 + kSlack)); PB_TRY(dks.alloc((size_t)R * 256 * 2 + kSlack)); PB_TRY(dVtf.alloc((size_t)B * 64 * ldvP * 2 + kSlack));
+        PB_TRY(preset(dfm, (size_t)n * 2 * 4)); PB_TRY(preset(dfp, (size_t)n * 2 * 4)); PB_TRY(preset(dmap, (size_t)(n + guard) * 384 * 2));
+        PB_TRY(launch_gm_match_flow(stream, dOm.as<float>(), dfm.as<float>(), dVtf.as<f16>(), B, P, g.w8, ldvP));
+        PB_TRY(launch_gm_split_rows(stream, dq.as<float>(), 128, 128, dqs.as<f16>(), R));
+        PB_TRY(launch_gm_split_rows(stream, dk.as<float>(), 128, 128, dks.as<f16>(), R));
+        Attn128Args pa;
+        pa.Q = dqs.as<f16>(); pa.K = dks.as<f16>(); pa.O = dOm.as<float>(); pa.B = B; pa.L = P; pa.ldv = ldvP; pa.split = split; pa.vcols = 32; pa.ldq = 256;
+        pa.Vt = dVtf.as<f16>(); pa.v_bstride = (int64_t)64 * ldvP;
+        pa.q_bstride = pa.k_bstride = dirs == 2 ? img : 2 * img;
+        PB_TRY(launch_attention128x(stream, pa));
+        PB_TRY(launch_gm_upsampler_in(stream, dOm.as<float>(), dX.as<float>(), dfp.as<float>(), dmap.as<f16>(), B, P, dirs == 2 ? 1 : 2));
+        PB_TRY(finish(flowm, dfm, (size_t)n * 2 * 4));
+        PB_TRY(down(flowp, dfp, (size_t)n * 2 * 4));
+        return down(map, dmap, (size_t)(n + guard) * 384 * 2);
     }
 };
 
@@ -742,6 +983,95 @@ int pb_op_raft_state(pb_ctx *c, const float *ctx_rows, const float *flow, int ro
              guard_rows >= 0, PB_ERR_ARG, "op_raft_state: bad arguments");
     RAFT_OP_ENGINE(e);
     return e.state(ctx_rows, flow, rows, ld, inp_off, guard_rows, h32, hx, hx2, flow0);
+}
+
+// ---- the flow_gmflow band's kernels one by one (GmOpEngine above) ----
+int pb_op_gm_tables(int h8, int w8, float *pos, int8_t *region) {
+    PB_CHECK(pos && region && h8 >= 4 && w8 >= 4 && h8 % 2 == 0 && w8 % 2 == 0, PB_ERR_ARG, "op_gm_tables: bad arguments");
+    std::vector<float> p;
+    std::vector<int8_t> r;
+    sine_positions(h8, w8, p);
+    shift_regions(h8, w8, r);
+    memcpy(pos, p.data(), p.size() * 4);
+    memcpy(region, r.data(), r.size());
+    return 0;
+}
+#define GM_OP_ENGINE(e) PB_HIP(hipSetDevice(c->device)); GmOpEngine e(c->device); PB_TRY(e.setup(nullptr, 0, SL_F16, 0))
+int pb_op_gm_tokens(pb_ctx *c, const float *feat, const float *pos, int NP, int P, int guard_rows, float *X, void *Xs) {
+    PB_CHECK(c && feat && pos && X && Xs && NP > 0 && P > 0 && guard_rows >= 0, PB_ERR_ARG, "op_gm_tokens: bad arguments");
+    GM_OP_ENGINE(e);
+    return e.tokens(feat, pos, NP, P, guard_rows, X, Xs);
+}
+int pb_op_gm_split_rows(pb_ctx *c, const float *src, int rows, int ld, int C, int guard_rows, void *out) {
+    PB_CHECK(c && src && out && rows > 0 && C > 0 && ld >= C && guard_rows >= 0, PB_ERR_ARG, "op_gm_split_rows: bad arguments");
+    GM_OP_ENGINE(e);
+    return e.split_rows(src, rows, ld, C, guard_rows, out);
+}
+int pb_op_gm_grid_vt(pb_ctx *c, int h8, int w8, int guard_rows, void *out) {
+    PB_CHECK(c && out && guard_rows >= 0, PB_ERR_ARG, "op_gm_grid_vt: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.grid_vt(guard_rows, out);
+}
+int pb_op_gm_pack(pb_ctx *c, const float *src, int images, int h8, int w8, int ld, int njobs, const int *cols, const int *kinds, int shifted,
+                  int guard_rows, void **outs) {
+    PB_CHECK(c && src && cols && kinds && outs && images > 0 && njobs >= 1 && njobs <= 5 && ld % 4 == 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_gm_pack: bad arguments");
+    for (int j = 0; j < njobs; ++j)
+        PB_CHECK(outs[j] && cols[j] >= 0 && cols[j] % 8 == 0 && cols[j] + 128 <= ld, PB_ERR_ARG, "op_gm_pack: job %d takes columns %d.. of %d", j, cols[j], ld);
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.pack(src, images, ld, njobs, cols, kinds, shifted, guard_rows, outs);
+}
+int pb_op_gm_ln(pb_ctx *c, const float *M, const float *gamma, const float *beta, float *X, int rows, int xrows, int h8, int w8, int windowed,
+                int shifted, int mode, int guard_rows, void *out) {
+    PB_CHECK(c && M && gamma && beta && X && out && rows > 0 && rows <= xrows && (mode == 0 || mode == 1) && guard_rows >= 0, PB_ERR_ARG,
+             "op_gm_ln: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    PB_CHECK(!windowed || xrows % e.g.P == 0, PB_ERR_ARG, "op_gm_ln: windowed rows address whole images of %d tokens, X has %d rows", e.g.P, xrows);
+    return e.ln(M, gamma, beta, X, rows, xrows, windowed, shifted, mode, guard_rows, out);
+}
+int pb_op_gm_match_flow(pb_ctx *c, const float *O, int B, int h8, int w8, int guard_rows, float *flow, void *vt) {
+    PB_CHECK(c && O && flow && vt && B > 0 && guard_rows >= 0, PB_ERR_ARG, "op_gm_match_flow: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.match_flow(O, B, guard_rows, flow, vt);
+}
+int pb_op_gm_upsampler_in(pb_ctx *c, const float *O, const float *X, int B, int images, int P, int img_step, int guard_rows, float *flow, void *map) {
+    PB_CHECK(c && O && X && flow && map && B > 0 && P > 0 && (img_step == 1 || img_step == 2) && (B - 1) * img_step < images && guard_rows >= 0,
+             PB_ERR_ARG, "op_gm_upsampler_in: bad arguments");
+    GM_OP_ENGINE(e);
+    return e.upsampler_in(O, X, B, images, P, img_step, guard_rows, flow, map);
+}
+int pb_op_attention128_cfg(pb_ctx *c, const float *q, const float *k, const float *v, const int8_t *region, int nreg, float *o, int B, int L,
+                           int split, int pv_single, int vcols, int v_shared, int kxor, int ldq, int strided, float fill) {
+    PB_CHECK(c && q && v && o && B > 0 && L > 0 && (vcols == 128 || vcols == 32) && (ldq == 256 || (ldq == 128 && !split)) && strided >= 0 &&
+                 strided <= 2 && (k || strided == 1) && (strided != 1 || (kxor == 1 && B % 2 == 0)) && (!region || nreg > 0),
+             PB_ERR_ARG, "op_attention128_cfg: bad arguments");
+    GM_OP_ENGINE(e);
+    return e.attention_cfg(q, k, v, region, nreg, o, B, L, split, pv_single, vcols, v_shared, kxor, ldq, strided, fill);
+}
+int pb_op_gm_window_block(pb_ctx *c, const float *Y, float *X, const float *gamma, const float *beta, int images, int h8, int w8, int shifted,
+                          int cross, int split) {
+    PB_CHECK(c && Y && X && gamma && beta && images > 0 && (!cross || images % 2 == 0), PB_ERR_ARG, "op_gm_window_block: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.window_block(Y, X, gamma, beta, images, shifted, cross, split);
+}
+int pb_op_gm_match(pb_ctx *c, const float *tokens, int NP, int h8, int w8, int dirs, int split, float *flow) {
+    PB_CHECK(c && tokens && flow && NP > 0 && (dirs == 1 || dirs == 2), PB_ERR_ARG, "op_gm_match: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.match(tokens, NP, dirs, split, flow);
+}
+int pb_op_gm_propagate(pb_ctx *c, const float *q, const float *k, const float *flow_in, const float *X, int NP, int h8, int w8, int dirs, int split,
+                       int guard_rows, float *flow_match, float *flow_prop, void *map) {
+    PB_CHECK(c && q && k && flow_in && X && flow_match && flow_prop && map && NP > 0 && (dirs == 1 || dirs == 2) && guard_rows >= 0, PB_ERR_ARG,
+             "op_gm_propagate: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.propagate(q, k, flow_in, X, NP, dirs, split, guard_rows, flow_match, flow_prop, map);
 }
 
 }  // extern "C"

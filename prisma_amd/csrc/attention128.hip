@@ -14,7 +14,8 @@
 //   * scores and the running max live in log2 units (Q . K scaled by log2 e / sqrt(128)); statistics, O and the output are fp32.
 // SPLIT (the flow_gmflow band's precision mode, DESIGN.md section 7: this network's two softmax stages amplify operand rounding): Q, K and
 // V arrive as hi + lo fp16 pairs and P is split in registers, S = q_hi k_hi + q_lo k_hi + q_hi k_lo and O += v_hi p_hi + v_hi p_lo +
-// v_lo p_hi in the same fp32 accumulators - three MFMA passes each, operands good to ~22 bits.
+// v_lo p_hi in the same fp32 accumulators - three MFMA passes each, operands good to ~22 bits (P is carried 2^14 above its softmax scale so
+// that this also holds for the small probabilities: see the loop).
 // (First version, round 3: plain loads + ds_write through registers, two buffers - every tile exposed a global-load latency before its
 // ds_writes; the matrix pipe was busy ~27 % of the time.)
 #include "common.h"
@@ -181,11 +182,16 @@ __global__ __launch_bounds__(256, 2) void attn128_kernel(const f16 *__restrict__
         }
         tmax = fmaxf(tmax, __shfl_xor(tmax, 32));
         const float mn = fmaxf(m, tmax), corr = __builtin_amdgcn_exp2f(m - mn);
+        // SPV: the probabilities are carried 2^14 higher (the row's largest is 16384, exact in fp16; l carries the same factor, so o / l does
+        // not).  Relative to a largest value of 1 the lo half of every p below 2^-3 is an fp16 subnormal - the pair is then good to 2^-25
+        // ABSOLUTE, not to 2^-22 of p - and a softmax with one dominant key puts every other key there (tests/test_gpu_gmflow_ops.py
+        // test_match_chain, test_propagate_chain).
+        const float mb = SPV ? mn - 14.f : mn;
         float psum = 0.f;
         f16x8 pf[NPV][2];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const float p = __builtin_amdgcn_exp2f(st[r] - mn);
+            const float p = __builtin_amdgcn_exp2f(st[r] - mb);
             const f16 ph = (f16)p;
             pf[0][r >> 3][r & 7] = ph;
             if constexpr (SPV) {
@@ -199,20 +205,33 @@ __global__ __launch_bounds__(256, 2) void attn128_kernel(const f16 *__restrict__
         psum += __shfl_xor(psum, 32);
         l = l * corr + psum;
         m = mn;
+        // SPV with one V block (coordinates / flow): the tile's six MFMAs sum into a fresh accumulator that joins o in ONE fma.  Chained
+        // through o itself every MFMA rounds at o's magnitude - a coordinate of tens under flows of about a pixel - six times a tile
+        // (measured on 28 x 38: 6.9e-5 px, 2^-19 of the largest coordinate).
+        constexpr bool LOCAL = SPV && NVB == 1;
 #pragma unroll
         for (int bb = 0; bb < NVB; ++bb) {
+            f32x16 acc;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) o[bb][r] *= corr;
+            for (int r = 0; r < 16; ++r) {
+                if constexpr (LOCAL) acc[r] = 0.f;
+                else acc[r] = o[bb][r] * corr;
+            }
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
                 const int vsw = (li >> 2) & 3;                  // rows bb * 32 + li and (NVB + bb) * 32 + li share (row >> 2) & 3
                 const f16x8 vh = *(const f16x8 *)(sv + (bb * 32 + li) * G::VROW + (((2 * s + lh) ^ vsw) * 16));
-                o[bb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pf[0][s], o[bb], 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pf[0][s], acc, 0, 0, 0);
                 if constexpr (SPV) {
                     const f16x8 vl = *(const f16x8 *)(sv + ((NVB + bb) * 32 + li) * G::VROW + (((2 * s + lh) ^ vsw) * 16));
-                    o[bb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pf[1][s], o[bb], 0, 0, 0);
-                    o[bb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, pf[0][s], o[bb], 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vh, pf[1][s], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(vl, pf[0][s], acc, 0, 0, 0);
                 }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                if constexpr (LOCAL) o[bb][r] = __builtin_fmaf(o[bb][r], corr, acc[r]);
+                else o[bb][r] = acc[r];
             }
         }
     }

@@ -5,6 +5,13 @@
 #include "gmflow_kernels.h"
 #include "raft_engine.h"
 
+// Host tables of prepare_g (gmflow_engine.hip; pb_op_gm_tables hands the same two functions to the tests): the per-window sine position
+// embedding tiled over the 2 x 2 windows, token-major [h8 * w8, 128], and the shifted-window region ids in window order [4][Lw]
+void sine_positions(int h8, int w8, std::vector<float> &pos);
+void shift_regions(int h8, int w8, std::vector<int8_t> &reg);
+// the window geometry of an h8 x w8 token grid (both even, >= 4) and ldvP, the row stride of the matching / propagation V^T (round_up(P, 32))
+void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP);
+
 class GmflowEngine : public RaftEngine {
   public:
     explicit GmflowEngine(int device) : RaftEngine(device) {}

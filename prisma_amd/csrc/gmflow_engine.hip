@@ -82,7 +82,6 @@ int GmflowEngine::load(const pb_tensor *w, int n) {
     return 0;
 }
 
-namespace {
 // PositionEmbeddingSine(num_pos_feats = 64, temperature 10000, normalize, scale 2 pi) of ONE wh x ww window (position.py:26-46), tiled over
 // the 2 x 2 windows (utils.py:61-86), as a token-major table [h8 * w8, 128]: channels 0..63 from y, 64..127 from x, (sin, cos) interleaved
 void sine_positions(int h8, int w8, std::vector<float> &pos) {
@@ -115,7 +114,11 @@ void shift_regions(int h8, int w8, std::vector<int8_t> &reg) {
                 reg[((size_t)win * wh + ly) * ww + lx] = (int8_t)(cy * 3 + cx);
             }
 }
-}  // namespace
+
+void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP) {
+    g.h8 = h8; g.w8 = w8; g.P = h8 * w8; g.wh = h8 / 2; g.ww = w8 / 2; g.Lw = g.wh * g.ww; g.ldv = (int)round_up(g.Lw, 32);
+    ldvP = (int)round_up(g.P, 32);
+}
 
 int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
     if (F <= gF_ && H == gH_ && W == gW_ && scale == gS_ && dirs <= gD_) return 0;
@@ -128,8 +131,7 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
         h8_ = Hp_ / 8; w8_ = Wp_ / 8; P_ = h8_ * w8_;
     }
     PB_CHECK(h8_ >= 4 && w8_ >= 4 && h8_ % 2 == 0 && w8_ % 2 == 0, PB_ERR_ARG, "flow_gmflow: %dx%d is too small", sh_, sw_);
-    g_.h8 = h8_; g_.w8 = w8_; g_.P = P_; g_.wh = h8_ / 2; g_.ww = w8_ / 2; g_.Lw = g_.wh * g_.ww; g_.ldv = (int)round_up(g_.Lw, 32);
-    ldvP_ = (int)round_up(P_, 32);
+    gm_geometry(h8_, w8_, g_, ldvP_);
     const int NP = F - 1;
     const int64_t R = (int64_t)NP * 2 * P_, B = (int64_t)NP * dirs, Bw = (int64_t)NP * 8;
     const size_t slack = 1 << 16;

@@ -171,6 +171,21 @@ def raft_geometry(h8: int, w8: int) -> List[dict]:
     return [dict(h=geo[l * 5], w=geo[l * 5 + 1], wp=geo[l * 5 + 2], hp=geo[l * 5 + 3], ld=geo[l * 5 + 4]) for l in range(4)]
 
 
+def gm_geometry(h8: int, w8: int) -> dict:
+    """the flow_gmflow band's window geometry of an h8 x w8 token grid (csrc gm_geometry): P, window wh x ww = Lw tokens, V^T row strides"""
+    P, wh, ww = h8 * w8, h8 // 2, w8 // 2
+    return dict(h8=h8, w8=w8, P=P, wh=wh, ww=ww, Lw=wh * ww, ldv=-(-(wh * ww) // 32) * 32, ldvP=-(-P // 32) * 32)
+
+
+def gm_tables(h8: int, w8: int):
+    """the two host tables GmflowEngine::prepare_g uploads (csrc sine_positions / shift_regions; needs no GPU): pos [P, 128] float32 and the
+    shifted-window region ids [4, Lw] int8 in window order"""
+    pos = np.empty((h8 * w8, 128), np.float32)
+    reg = np.empty((4, (h8 // 2) * (w8 // 2)), np.int8)
+    check(_lib.load().pb_op_gm_tables(h8, w8, _ptr(pos), _ptr(reg)))
+    return pos, reg
+
+
 class Ops(_Ctx):
     """Single-kernel entry points (pb_op_*) used by the parity tests."""
 
@@ -371,6 +386,122 @@ class Ops(_Ctx):
         f0 = np.empty((rows + guard_rows, 2), np.float32)
         check(self.lib.pb_op_raft_state(self.ctx, _ptr(ctx_rows), _ptr(flow), rows, ld, inp_off, guard_rows, _ptr(h32), _ptr(hx), _ptr(hx2), _ptr(f0)))
         return h32, hx, hx2, f0
+
+    # ---- the flow_gmflow band's kernels one by one (pb_op_gm_*, pb_op_attention128_cfg; tests/test_gpu_gmflow_ops.py) ----
+    # raw buffers come back as uint8 [rows + guard_rows, bytes per row]: 0xFF wherever the kernel did not write
+    def gm_tokens(self, feat, pos, guard_rows: int = 8):
+        """feat [NP + 1, P, 128], pos [P, 128] -> (X float32 [2 NP P + guard, 128], Xs raw [.., 512])"""
+        feat, pos = _f32(feat), _f32(pos)
+        F, P, _ = feat.shape
+        assert feat.shape[2] == 128 and pos.shape == (P, 128) and F >= 2
+        R = (F - 1) * 2 * P
+        X = np.empty((R + guard_rows, 128), np.float32)
+        Xs = np.empty((R + guard_rows, 512), np.uint8)
+        check(self.lib.pb_op_gm_tokens(self.ctx, _ptr(feat), _ptr(pos), F - 1, P, guard_rows, _ptr(X), _ptr(Xs)))
+        return X, Xs
+
+    def gm_split_rows(self, src, Cc: int, guard_rows: int = 8) -> np.ndarray:
+        """src [rows, ld >= Cc] -> raw [rows + guard, 4 Cc] ([hi | lo] halfs)"""
+        src = _f32(src)
+        rows, ld = src.shape
+        out = np.empty((rows + guard_rows, 4 * Cc), np.uint8)
+        check(self.lib.pb_op_gm_split_rows(self.ctx, _ptr(src), rows, ld, Cc, guard_rows, _ptr(out)))
+        return out
+
+    def gm_grid_vt(self, h8: int, w8: int, guard_rows: int = 8) -> np.ndarray:
+        out = np.empty((64 + guard_rows, gm_geometry(h8, w8)["ldvP"] * 2), np.uint8)
+        check(self.lib.pb_op_gm_grid_vt(self.ctx, h8, w8, guard_rows, _ptr(out)))
+        return out
+
+    def gm_pack(self, src, h8: int, w8: int, jobs, shifted: bool, guard_rows: int = 8):
+        """src [images P, ld]; jobs [(first column, is_vt)] (at most 5) -> per job raw [4 images Lw + guard, 512] or [4 images 256 + guard, 2 ldv]"""
+        src = _f32(src)
+        g = gm_geometry(h8, w8)
+        images, ld = src.shape[0] // g["P"], src.shape[1]
+        assert src.shape[0] == images * g["P"] and 1 <= len(jobs) <= 5
+        outs = [np.empty((images * 4 * 256 + guard_rows, g["ldv"] * 2) if vt else (images * 4 * g["Lw"] + guard_rows, 512), np.uint8) for _, vt in jobs]
+        cols = (C.c_int * 5)(*[c for c, _ in jobs])
+        kinds = (C.c_int * 5)(*[int(vt) for _, vt in jobs])
+        ptrs = (C.c_void_p * 5)(*[o.ctypes.data for o in outs])
+        check(self.lib.pb_op_gm_pack(self.ctx, _ptr(src), images, h8, w8, ld, len(jobs), cols, kinds, int(shifted), guard_rows, ptrs))
+        return outs
+
+    def gm_ln(self, M, gamma, beta, X, h8: int, w8: int, windowed: bool, shifted: bool, mode: int, guard_rows: int = 8):
+        """M [rows, 128]; X [xrows, 128] -> (X afterwards float32 [xrows + guard, 128] with the guard rows as preset, raw out [xrows + guard,
+        512 or 1024]); rows <= xrows (windowed: X is whole images)"""
+        M, gamma, beta, X = _f32(M), _f32(gamma), _f32(beta), _f32(X)
+        rows, xrows = M.shape[0], X.shape[0]
+        Xb = np.empty((xrows + guard_rows, 128), np.float32)
+        Xb.view(np.uint8)[...] = 0xFF
+        Xb[:xrows] = X
+        out = np.empty((xrows + guard_rows, 1024 if mode else 512), np.uint8)
+        check(self.lib.pb_op_gm_ln(self.ctx, _ptr(M), _ptr(gamma), _ptr(beta), _ptr(Xb), rows, xrows, h8, w8, int(windowed), int(shifted), mode,
+                                   guard_rows, _ptr(out)))
+        return Xb, out
+
+    def gm_match_flow(self, O, h8: int, w8: int, guard_rows: int = 8):
+        """O [B, P, 32] -> (flow float32 [B P + guard, 2], vt raw [64 B + guard, 2 ldvP])"""
+        O = _f32(O)
+        B, P, _ = O.shape
+        assert O.shape[1:] == (h8 * w8, 32)
+        flow = np.empty((B * P + guard_rows, 2), np.float32)
+        vt = np.empty((64 * B + guard_rows, gm_geometry(h8, w8)["ldvP"] * 2), np.uint8)
+        check(self.lib.pb_op_gm_match_flow(self.ctx, _ptr(O), B, h8, w8, guard_rows, _ptr(flow), _ptr(vt)))
+        return flow, vt
+
+    def gm_upsampler_in(self, O, X, img_step: int, guard_rows: int = 8):
+        """O [B, P, 32], X [images, P, 128] -> (flow float32 [B P + guard, 2], map raw [B P + guard, 768])"""
+        O, X = _f32(O), _f32(X)
+        B, P, _ = O.shape
+        assert X.shape[1:] == (P, 128)
+        flow = np.empty((B * P + guard_rows, 2), np.float32)
+        mp = np.empty((B * P + guard_rows, 768), np.uint8)
+        check(self.lib.pb_op_gm_upsampler_in(self.ctx, _ptr(O), _ptr(X), B, X.shape[0], P, img_step, guard_rows, _ptr(flow), _ptr(mp)))
+        return flow, mp
+
+    def attention128_cfg(self, q, k, v, region=None, split: int = 1, pv_single: int = 0, v_shared: bool = False, kxor: int = 0, ldq: int = 256,
+                         strided: int = 0, fill: float = 0.0) -> np.ndarray:
+        """attention128.hip's general form (pb_op_attention128_cfg): q, k [B, L, 128], v [1 if v_shared else B, L, 32 or 128] -> [B, L, vcols]"""
+        q, v = _f32(q), _f32(v)
+        k = None if k is None else _f32(k)
+        B, L, _ = q.shape
+        vc = v.shape[2]
+        assert q.shape[2] == 128 and (k is None or k.shape == q.shape) and v.shape[:2] == (1 if v_shared else B, L)
+        rg = None if region is None else np.ascontiguousarray(region, np.int8)
+        out = np.empty((B, L, vc), np.float32)
+        check(self.lib.pb_op_attention128_cfg(self.ctx, _ptr(q), _ptr(k), _ptr(v), _ptr(rg), 0 if rg is None else rg.shape[0], _ptr(out), B, L,
+                                              split, pv_single, vc, int(v_shared), kxor, ldq, strided, fill))
+        return out
+
+    def gm_window_block(self, Y, X, gamma, beta, h8: int, w8: int, shifted: bool, cross: bool, split: int = 1) -> np.ndarray:
+        """Y [images P, 384] = q | k | v, X [images P, 128] -> X + LayerNorm(window attention), float32 [images P, 128]"""
+        Y, X, gamma, beta = _f32(Y), _f32(X).copy(), _f32(gamma), _f32(beta)
+        images = X.shape[0] // (h8 * w8)
+        assert X.shape == (images * h8 * w8, 128) and Y.shape == (X.shape[0], 384)
+        check(self.lib.pb_op_gm_window_block(self.ctx, _ptr(Y), _ptr(X), _ptr(gamma), _ptr(beta), images, h8, w8, int(shifted), int(cross), split))
+        return X
+
+    def gm_match(self, tokens, h8: int, w8: int, dirs: int, split: int = 1) -> np.ndarray:
+        """tokens [2 NP, P, 128] -> matched flow [NP dirs, P, 2]"""
+        tokens = _f32(tokens)
+        NP = tokens.shape[0] // 2
+        assert tokens.shape == (2 * NP, h8 * w8, 128)
+        flow = np.empty((NP * dirs, h8 * w8, 2), np.float32)
+        check(self.lib.pb_op_gm_match(self.ctx, _ptr(tokens), NP, h8, w8, dirs, split, _ptr(flow)))
+        return flow
+
+    def gm_propagate(self, q, k, flow_in, X, h8: int, w8: int, dirs: int, split: int = 1, guard_rows: int = 8):
+        """q, k, X [2 NP, P, 128], flow_in [NP dirs, P, 2] -> (the fp32 flow match_flow made of flow_in + coordinate, propagated flow, both
+        [NP dirs, P, 2]; upsampler map raw [NP dirs P + guard, 768])"""
+        q, k, flow_in, X = _f32(q), _f32(k), _f32(flow_in), _f32(X)
+        NP, P = q.shape[0] // 2, h8 * w8
+        B = NP * dirs
+        assert q.shape == (2 * NP, P, 128) and k.shape == q.shape and X.shape == q.shape and flow_in.shape == (B, P, 2)
+        fm, fp = np.empty((B, P, 2), np.float32), np.empty((B, P, 2), np.float32)
+        mp = np.empty((B * P + guard_rows, 768), np.uint8)
+        check(self.lib.pb_op_gm_propagate(self.ctx, _ptr(q), _ptr(k), _ptr(flow_in), _ptr(X), NP, h8, w8, dirs, split, guard_rows, _ptr(fm), _ptr(fp),
+                                          _ptr(mp)))
+        return fm, fp, mp
 
     def bilinear(self, x, OH: int, OW: int, align_corners: bool) -> np.ndarray:
         x = _f32(x)

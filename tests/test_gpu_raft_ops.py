@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import raft_ref as R
+from gm_ref import check, preset          # the assert helpers the op-level GPU tests share
 from prisma_amd import engine
 from split_ref import BUDGET, F16, MX2, SPLIT16, e4m3_bytes, e4m3_decode, e4m3_step
 
@@ -23,25 +24,6 @@ def ops():
     o = engine.Ops(0)
     yield o
     o.close()
-
-
-def check(what, got, ref, tol):
-    """asserts |got - ref| <= tol element-wise; the message names the worst element.  Returns worst error / tolerance."""
-    got, ref, tol = np.asarray(got, np.float64), np.asarray(ref, np.float64), np.broadcast_to(np.asarray(tol, np.float64), np.shape(ref))
-    bad = ~np.isfinite(got)
-    assert not bad.any(), "%s: element %s is %r" % (what, tuple(np.argwhere(bad)[0]), got[tuple(np.argwhere(bad)[0])])
-    r = np.abs(got - ref) / tol
-    i = np.unravel_index(np.argmax(r), r.shape)
-    print("\n  %-58s worst err / tol %.3f at %s" % (what, r[i], i), end="")
-    assert r[i] <= 1, "%s: element %s: kernel %.9g reference %.9g |err| %.3e tolerance %.3e (%d elements outside)" % (
-        what, i, got[i], ref[i], abs(got[i] - ref[i]), tol[i], int((r > 1).sum()))
-    return float(r[i])
-
-
-def preset(what, raw):
-    raw = np.ascontiguousarray(raw).view(np.uint8)
-    bad = raw != 0xFF
-    assert not bad.any(), "%s: %d bytes written outside what the kernel owns, first at %s" % (what, int(bad.sum()), tuple(np.argwhere(bad)[0]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
