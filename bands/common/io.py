@@ -1,7 +1,8 @@
 """Frame sources / sinks of the band scripts (host side, stays Python like the reference).
 
 Re-states the file behaviour of /root/reference/bands/common/io.py: open_rgb (:78-83),
-check_overwrite (:35-41), VideoWriter (:246-305, libx264 crf 15 yuv420p), write_depth (:138-172).
+check_overwrite (:35-41), VideoWriter (:246-305, libx264 crf 15 yuv420p), write_depth (:138-172),
+write_ply (the file half of write_pcl :201-211; its arithmetic runs on the GPU, pb_depth_point_cloud).
 decord / PyAV / OpenCV are optional here (absent in the build image): .mp4 needs them, .npy
 frame stacks ([n,H,W,3] uint8) and .png work everywhere.
 """
@@ -155,6 +156,19 @@ def write_depth(path, depth, heat_rgb_fn, normalize=True, flip=False, heatmap=Tr
         rgb[0, 0] = float_to_rgb(dmin, 0.0, 1000.0)
         rgb[0, 1] = float_to_rgb(dmax, 0.0, 1000.0)
     write_rgb(path, (rgb * 255).astype(np.uint8))
+
+
+def write_ply(path, vertices):
+    """Binary PLY of one `vertex` element (geom.py:27-47 save_point_cloud): the header plyfile writes for the structured dtype
+    (x, y, z '<f4'; red, green, blue 'u1'), then the packed 15-byte records.  PARITY UNPINNED (third-party plyfile absent): the header
+    is restated from the PLY format, not compared with a file the real package wrote."""
+    vertices = np.ascontiguousarray(vertices).reshape(-1)
+    names = {"<f4": "float", "|u1": "uchar"}
+    props = ["property %s %s" % (names[vertices.dtype[n].str], n) for n in vertices.dtype.names]
+    header = ["ply", "format binary_little_endian 1.0", "element vertex %d" % vertices.size] + props + ["end_header"]
+    with open(path, "wb") as f:
+        f.write(("\n".join(header) + "\n").encode("ascii"))
+        f.write(vertices.tobytes())
 
 
 def write_flo(path, flow):

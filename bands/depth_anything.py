@@ -17,7 +17,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_rgb  # noqa: E402
+from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_ply, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.meta import get_target, get_url, is_video, load_metadata, write_metadata  # noqa: E402
 from common.pipe import AsyncSink, prefetch  # noqa: E402
@@ -95,17 +95,27 @@ def infer(img, normalize=False):
 def write_depth_png(path, depth):
     """write_depth(path, depth, normalize=True, flip, heatmap=True, encode_range=True) (reference :176-180, :221-225;
     bands/common/io.py:138-172) with the encode on the GPU (pb_depth_encode_still): bytes equal common.io.write_depth's."""
-    global _still
-    if _still is None:      # its own ctx and stream: the --subpath dumps run on the sink thread while the band's ctx computes the next chunk
-        _still = engine.Ops(device=ranks.device if ranks else 0)
-    rgb, _, _ = _still.encode_still(depth, flip=_flip(), encode_range=True)
+    rgb, _, _ = _still_ctx().encode_still(depth, flip=_flip(), encode_range=True)
     write_rgb(path, rgb)
 
 
+def _still_ctx():
+    global _still
+    if _still is None:      # its own ctx and stream: the --subpath dumps run on the sink thread while the band's ctx computes the next chunk
+        _still = engine.Ops(device=ranks.device if ranks else 0)
+    return _still
+
+
+def write_depth_ply(path, depth, img):
+    """write_pcl(path, depth, img, flip) (reference :170-171; bands/common/io.py:201-211, bands/common/geom.py:5-47: u0 = W / 2, v0 = H / 2,
+    fx = fy = 1000) with the un-flip, the 5 x 5 median and the back-projection on the GPU (pb_depth_point_cloud) and the binary PLY
+    written here (common.io.write_ply).  cv2.medianBlur and plyfile's header are pinned by restatement (tests/pcl_ref.py): neither
+    package is installed where this is tested."""
+    h, w = depth.shape
+    write_ply(path, _still_ctx().point_cloud(depth, img, flip=_flip(), u0=w / 2, v0=h / 2, fx=1000.0, fy=1000.0))
+
+
 def process_image(a):
-    if getattr(a, "ply", False):       # reference :168-174 write_pcl (camera intrinsics + plyfile): geometry export, SURVEY section 2 out of scope
-        print(f"[{BAND}] --ply (point cloud export, reference :168-174) is not built (SURVEY.md section 2.1 geom); writing the depth image only",
-              file=sys.stderr)
     img = open_rgb(a.input)
     out_folder = os.path.dirname(a.output)
     pred = infer(img)
@@ -114,6 +124,8 @@ def process_image(a):
                                          "max": {"value": float(pred.max()), "type": "float"}}
     if a.npy:
         np.save(os.path.join(out_folder, BAND + ".npy"), pred)
+    if getattr(a, "ply", False):
+        write_depth_ply(os.path.join(out_folder, BAND + ".ply"), pred, img)
     write_depth_png(a.output, pred)
 
 

@@ -175,6 +175,23 @@ int pb_gather_scalars(pb_ctx *ctx, const float *local, int n_local, float *globa
 int pb_depth_encode_still(pb_ctx *ctx, const float *depth, int H, int W, int flip, int encode_range, uint8_t *rgb_out,
                           float *min_out, float *max_out);
 
+/* Still-image `--ply` post-process: write_pcl of bands/common/io.py:201-211 as called from bands/depth_anything.py:170-171, with
+ * create_point_cloud / save_point_cloud of bands/common/geom.py:5-47 - with `flip` the relative model's range is turned over in float32
+ * (d = mn + (1 - (d - mn) / (mx - mn)) * (mx - mn) by the frame's own min / max, every operation separately rounded), then
+ * cv2.medianBlur(d, 5), x = (col - u0) / fx, y = (row - v0) / fy, vertex = (m x, m (-y), m (-1)) and the source pixel's colour, one packed
+ * 15-byte record <f4 x, f4 y, f4 z, u1 red, u1 green, u1 blue (little endian) per pixel in row-major order: the body of the binary PLY
+ * the reference writes through plyfile.  cv2 and plyfile are absent where this library is built and tested, so medianBlur (the exact
+ * median of the 5 x 5 window, border replicated, also on maps smaller than 5) and the record layout are pinned by restatement
+ * (tests/pcl_ref.py), not against the real packages.  Contract: finite depth; NaN and -0.0 in the map are outside it.  A constant map
+ * with `flip` gives NaN vertices, as in the reference.  Works on any ctx.
+ *   depth : n x H x W float32     rgb : n x H x W x 3 uint8     vertices_out : n x H x W x 15 bytes (no alignment needed)
+ * pb_depth_point_cloud: host pointers, blocking (its own stream and buffers, shared with pb_depth_encode_still: callable from another
+ * thread while the ctx stream works).  pb_depth_point_cloud_dev: device pointers, asynchronous on the ctx stream; pb_sync() waits. */
+int pb_depth_point_cloud(pb_ctx *ctx, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip,
+                         float u0, float v0, float fx, float fy, uint8_t *vertices_out);
+int pb_depth_point_cloud_dev(pb_ctx *ctx, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip,
+                             float u0, float v0, float fx, float fy, uint8_t *vertices_out);
+
 /* Network input size for an H x W frame: keep-aspect lower-bound resize to 518, each side a
  * multiple of 14 (bands/d_anything/util/transform.py:100-166). */
 int pb_depth_net_size(int H, int W, int *net_h, int *net_w);

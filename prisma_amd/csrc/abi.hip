@@ -332,6 +332,7 @@ void pb_destroy(pb_ctx *c) {
     if (c->comm_buf) hipFree(c->comm_buf);
     if (c->still_stream) { hipStreamSynchronize(c->still_stream); hipStreamDestroy(c->still_stream); }
     if (c->still_buf) hipFree(c->still_buf);
+    if (c->pcl_mm) { hipStreamSynchronize(c->stream); hipFree(c->pcl_mm); }
     for (hipEvent_t e : c->pending) { hipEventSynchronize(e); hipEventDestroy(e); }
     c->pipe.release();
     c->mpipe.release();
@@ -708,6 +709,53 @@ int pb_depth_encode_still(pb_ctx *c, const float *depth, int H, int W, int flip,
     if (min_out) *min_out = mnmx[0];
     if (max_out) *max_out = mnmx[1];
     return 0;
+}
+
+int pb_depth_point_cloud_dev(pb_ctx *c, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip, float u0, float v0, float fx,
+                             float fy, uint8_t *vertices_out) {
+    PB_CHECK(c && depth && rgb && vertices_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "depth_point_cloud: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    if (flip && n > c->pcl_mm_cap) {
+        if (c->pcl_mm) { PB_HIP(hipStreamSynchronize(c->stream)); PB_HIP(hipFree(c->pcl_mm)); c->pcl_mm = nullptr; c->pcl_mm_cap = 0; }
+        PB_HIP(hipMalloc((void **)&c->pcl_mm, (size_t)n * 8));
+        c->pcl_mm_cap = n;
+    }
+    // with a band on the ctx and pb_set_profiling on, the call is one record of pb_get_kernel_stats (22 algorithmic bytes per pixel)
+    KernelTimer *t = c->depth ? &c->depth->timer : (c->raft ? &c->raft->timer : (c->mask ? &c->mask->timer : nullptr));
+    if (t && !t->enabled) t = nullptr;
+    if (t) {
+        t->reset();
+        t->recs.push_back(KernelTimer::Rec{0, t->get(), t->get(), 0.0, 22.0 * n * H * W, 0.0, "depth_point_cloud"});
+        PB_HIP(hipEventRecord(t->recs.back().a, c->stream));
+    }
+    const int r = launch_point_cloud(c->stream, depth, rgb, n, H, W, flip, u0, v0, fx, fy, c->pcl_mm, vertices_out);
+    if (t) PB_HIP(hipEventRecord(t->recs.back().b, c->stream));
+    return r;
+}
+
+int pb_depth_point_cloud(pb_ctx *c, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip, float u0, float v0, float fx,
+                         float fy, uint8_t *vertices_out) {
+    PB_CHECK(c && depth && rgb && vertices_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "depth_point_cloud: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    std::lock_guard<std::mutex> lock(c->still_mu);
+    const size_t px = (size_t)n * H * W;
+    // [depth f32 | rgb u8 x 3 | vertices 15 bytes | min / max words], each part 256-byte aligned
+    const size_t o_rgb = round_up(px * 4, 256), o_v = o_rgb + round_up(px * 3, 256), o_mm = o_v + round_up(px * 15, 256),
+                 need = o_mm + round_up((size_t)n * 8, 256);
+    if (!c->still_stream) PB_HIP(hipStreamCreateWithFlags(&c->still_stream, hipStreamNonBlocking));
+    if (need > c->still_cap) {
+        if (c->still_buf) { PB_HIP(hipStreamSynchronize(c->still_stream)); PB_HIP(hipFree(c->still_buf)); c->still_buf = nullptr; c->still_cap = 0; }
+        PB_HIP(hipMalloc((void **)&c->still_buf, need));
+        c->still_cap = need;
+    }
+    hipStream_t st = c->still_stream;
+    PB_HIP(hipMemcpyAsync(c->still_buf, depth, px * 4, hipMemcpyHostToDevice, st));
+    PB_HIP(hipMemcpyAsync(c->still_buf + o_rgb, rgb, px * 3, hipMemcpyHostToDevice, st));
+    const int r = launch_point_cloud(st, (const float *)c->still_buf, (const uint8_t *)(c->still_buf + o_rgb), n, H, W, flip, u0, v0, fx, fy,
+                                     (unsigned *)(c->still_buf + o_mm), (uint8_t *)(c->still_buf + o_v));
+    if (!r) PB_HIP(hipMemcpyAsync(vertices_out, c->still_buf + o_v, px * 15, hipMemcpyDeviceToHost, st));
+    PB_HIP(hipStreamSynchronize(st));
+    return r;
 }
 
 }  // extern "C"

@@ -156,4 +156,7 @@ struct pb_ctx {
     char *still_buf = nullptr;
     size_t still_cap = 0;
     std::mutex still_mu;
+    // pb_depth_point_cloud_dev: the per-frame min / max words of the un-flip, on the ctx stream (the host variant keeps its own in still_buf)
+    unsigned *pcl_mm = nullptr;
+    int pcl_mm_cap = 0;
 };

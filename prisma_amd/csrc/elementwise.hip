@@ -399,6 +399,126 @@ __global__ __launch_bounds__(256) void still_encode_kernel(const float *__restri
     }
 }
 
+// ---- still-image point cloud: write_pcl ----------------------------------------------------------------------------
+// bands/common/io.py:201-211 + bands/common/geom.py:5-47: un-flip the relative model's range (float32: d = mn + (1 - (d - mn) / (mx - mn))
+// * (mx - mn), the last line a multiply and an add, no FMA), cv2.medianBlur(d, 5) (the exact median of the 5 x 5 window, border replicated),
+// x = (col - u0) / fx, y = (row - v0) / fy, vertex = (m x, m (-y), m (-1)), stored with the source pixel's colour as packed 15-byte records
+// <f4 x, f4 y, f4 z, u1 r, u1 g, u1 b in row-major order.  Every floating operation is separately rounded (common.h ex_*).
+// Contract: finite depth.  NaN and -0.0 in the map are outside it (fminf / fmaxf order neither the way a sort does).
+//
+// One block of 256 lanes owns a PC_TW x PC_TH tile: the tile and its 2-pixel halo are staged in the LDS through clamped coordinates with
+// the un-flip folded into the load; a lane owns four consecutive pixels of one row (60 bytes = fifteen dwords).  A frame's records start
+// at byte 15 H W frame and a row's at 15 W row, so nothing is dword-aligned in general: the lanes of a row lay their records into the
+// LDS as the byte stream of the row's segment shifted to the segment's misalignment (v_alignbyte over neighbouring dwords; the dword two
+// lanes share takes the previous lane's last word by a shuffle), and the row's sixteen lanes then copy that stream out dword by dword,
+// consecutive lanes to consecutive dwords - byte stores only for the partial dwords at the two ends of the segment, which neighbouring
+// tiles share.
+constexpr int PC_TW = 64, PC_TH = 16, PC_LW = PC_TW + 4, PC_LH = PC_TH + 4;
+constexpr int PC_ROW_DW = PC_TW * 15 / 4 + 1;      // a row segment's stream: 960 record bytes + up to 3 bytes of misalignment
+
+__device__ __forceinline__ void pc_ce(float &a, float &b) {
+    const float lo = fminf(a, b), hi = fmaxf(a, b);
+    a = lo; b = hi;
+}
+
+// Median of 25 by forgetful selection, a fixed network of compare-exchanges: stage S holds 14 - S candidates in a[S .. 13], moves their
+// minimum to a[S] and their maximum to a[13] and forgets both - of the 25 - 2 S values still in play the minimum of 14 - S has at least
+// 13 - S above it and so ranks 12 - S at most, below the median's 13 - S (the maximum likewise) - then takes the next input into a[13].
+// Stage 11 is a median of three and leaves it in a[12].
+template <int S> __device__ __forceinline__ void pc_median_stage(float (&a)[25]) {
+    constexpr int LO = S, HI = 13, N = HI - LO + 1;
+#pragma unroll
+    for (int i = 0; i < N / 2; ++i) pc_ce(a[LO + i], a[HI - i]);
+#pragma unroll
+    for (int i = 1; i < (N + 1) / 2; ++i) pc_ce(a[LO], a[LO + i]);
+#pragma unroll
+    for (int i = 1; i < (N + 1) / 2; ++i) pc_ce(a[HI - i], a[HI]);
+    if constexpr (S < 11) {
+        a[HI] = a[14 + S];
+        pc_median_stage<S + 1>(a);
+    }
+}
+
+// `bytes` (1 or 4) of v into the little-endian byte stream w at the compile-time byte offset `at`
+__device__ __forceinline__ void pc_put(unsigned (&w)[15], int at, unsigned v, int bytes) {
+    const int i = at >> 2, sh = (at & 3) * 8;
+    w[i] |= v << sh;
+    if (sh + bytes * 8 > 32) w[i + 1] |= v >> (32 - sh);
+}
+
+__global__ __launch_bounds__(256) void point_cloud_kernel(const float *__restrict__ depth, const uint8_t *__restrict__ rgb, int H, int W,
+                                                          const unsigned *__restrict__ mm, int flip, float u0, float v0, float fx, float fy,
+                                                          uint8_t *__restrict__ out) {
+    __shared__ float tile[PC_LH * PC_LW];
+    __shared__ unsigned stream[PC_TH][PC_ROW_DW];
+    const int f = blockIdx.z, x0 = blockIdx.x * PC_TW, y0 = blockIdx.y * PC_TH;
+    const int64_t per = (int64_t)H * W;
+    const float *src = depth + f * per;
+    float dmin = 0.f, range = 0.f;
+    if (flip) { dmin = ord2f(mm[2 * f]); range = ex_fsub(ord2f(mm[2 * f + 1]), dmin); }
+    for (int i = threadIdx.x; i < PC_LH * PC_LW; i += 256) {
+        const int ly = i / PC_LW, lx = i - ly * PC_LW;
+        const int gy = min(max(y0 + ly - 2, 0), H - 1), gx = min(max(x0 + lx - 2, 0), W - 1);
+        float d = src[(int64_t)gy * W + gx];
+        if (flip) d = ex_fadd(dmin, ex_fmul(ex_fsub(1.0f, ex_fdiv(ex_fsub(d, dmin), range)), range));
+        tile[i] = d;
+    }
+    __syncthreads();
+
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4, row = y0 + ty, col0 = x0 + 4 * tx;
+    float win[5][8];                                    // the 5 x 8 window the four medians share
+#pragma unroll
+    for (int r = 0; r < 5; ++r)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) win[r][c] = tile[(ty + r) * PC_LW + 4 * tx + c];
+    const float ny = -ex_fdiv(ex_fsub((float)row, v0), fy);
+    const int64_t pix0 = f * per + (int64_t)row * W + col0;
+    unsigned w[15] = {};
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        float a[25];
+#pragma unroll
+        for (int r = 0; r < 5; ++r)
+#pragma unroll
+            for (int c = 0; c < 5; ++c) a[r * 5 + c] = win[r][p + c];
+        pc_median_stage<0>(a);
+        const float m = a[12];
+        const float x = ex_fdiv(ex_fsub((float)(col0 + p), u0), fx);
+        pc_put(w, 15 * p, __float_as_uint(ex_fmul(m, x)), 4);
+        pc_put(w, 15 * p + 4, __float_as_uint(ex_fmul(m, ny)), 4);
+        pc_put(w, 15 * p + 8, __float_as_uint(ex_fmul(m, -1.0f)), 4);
+        if (row < H && col0 + p < W) {
+            const uint8_t *c = rgb + (pix0 + p) * 3;
+            pc_put(w, 15 * p + 12, c[0], 1);
+            pc_put(w, 15 * p + 13, c[1], 1);
+            pc_put(w, 15 * p + 14, c[2], 1);
+        }
+    }
+
+    // the row segment's first record byte goes to out + seg; s = that address mod 4; stream byte k is the byte for address out + seg - s + k
+    const int64_t seg = 15 * (f * per + (int64_t)row * W + x0);
+    const int s = (int)(((uintptr_t)out + (uint64_t)seg) & 3);
+    const unsigned prev = __shfl_up(w[14], 1);          // lane 0 of a row reads another row's word into bytes [0, s): never stored
+#pragma unroll
+    for (int j = 0; j < 15; ++j)
+        stream[ty][15 * tx + j] = s ? __builtin_amdgcn_alignbyte(w[j], j ? w[j - 1] : prev, 4 - s) : w[j];
+    if (tx == 15) stream[ty][PC_ROW_DW - 1] = s ? w[14] >> (8 * (4 - s)) : 0u;
+    __syncthreads();
+
+    const int ncols = row < H ? min(PC_TW, W - x0) : 0, end = s + 15 * ncols;       // the segment is stream bytes [s, end)
+    uint8_t *ga = out + seg - s;
+    for (int q = tx; 4 * q < end; q += 16) {
+        const unsigned v = stream[ty][q];
+        if (4 * q >= s && 4 * q + 4 <= end) {
+            *(unsigned *)(ga + 4 * q) = v;
+        } else {
+#pragma unroll
+            for (int b = 0; b < 4; ++b)
+                if (4 * q + b >= s && 4 * q + b < end) ga[4 * q + b] = (uint8_t)(v >> (8 * b));
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // layout converters (tests / stage dumps)
 // ------------------------------------------------------------------------------------------------
@@ -629,6 +749,19 @@ int launch_still_encode(hipStream_t s, const float *depth, int H, int W, unsigne
     hipLaunchKernelGGL(still_quant_kernel, dim3(gx), dim3(256), 0, s, depth, per, mm, flip, q);
     hipLaunchKernelGGL(still_gradmax_kernel, dim3(gx), dim3(256), 0, s, q, H, W, g2max);
     hipLaunchKernelGGL(still_encode_kernel, dim3(gx), dim3(256), 0, s, depth, q, H, W, mm, g2max, flip, encode_range, rgb, mnmx);
+    PB_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_point_cloud(hipStream_t s, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip, float u0, float v0, float fx,
+                       float fy, unsigned *mm, uint8_t *out) {
+    const unsigned gx = (W + PC_TW - 1) / PC_TW, gy = (H + PC_TH - 1) / PC_TH;
+    PB_CHECK(n <= 65535 && gy <= 65535, -1, "point cloud: %d frames of %d rows exceed the launch grid", n, H);
+    if (flip) {
+        if (int r = launch_init_minmax(s, mm, n)) return r;
+        if (int r = launch_minmax_only(s, depth, n, (int64_t)H * W, mm)) return r;
+    }
+    hipLaunchKernelGGL(point_cloud_kernel, dim3(gx, gy, n), dim3(256), 0, s, depth, rgb, H, W, mm, flip, u0, v0, fx, fy, out);
     PB_HIP(hipGetLastError());
     return 0;
 }

@@ -43,6 +43,11 @@ int launch_init_minmax(hipStream_t s, unsigned *mm, int B);
 // pixels (0, 0), (0, 1).  Scratch: mm [2] ordered-uint min / max, g2max [1], q [H * W] bytes; mnmx [2] floats out (optional).
 int launch_still_encode(hipStream_t s, const float *depth, int H, int W, unsigned *mm, unsigned *g2max, uint8_t *q, int flip, int encode_range,
                         uint8_t *rgb, float *mnmx);
+// write_pcl of n depth maps (bands/common/io.py:201-211, bands/common/geom.py:5-47): un-flip by the frame's own min / max (flip), 5 x 5 median with a
+// replicated border, pinhole back-projection, packed 15-byte vertex records <f4 x, y, z, u1 r, g, b> in out [n, H, W, 15].  Scratch: mm [2 n]
+// ordered-uint min / max (written only with flip).  `out` needs no alignment.
+int launch_point_cloud(hipStream_t s, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip, float u0, float v0, float fx,
+                       float fy, unsigned *mm, uint8_t *out);
 
 // layout converters used by the op-level tests and the stage dumps
 int launch_nchw_f32_to_nhwc_f16(hipStream_t s, const float *x, f16 *y, int B, int C, int H, int W, int ldc, int relu);

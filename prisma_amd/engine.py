@@ -23,6 +23,10 @@ def _f32(a) -> np.ndarray:
     return np.ascontiguousarray(a, dtype=np.float32)
 
 
+# one vertex of the reference's point cloud (bands/common/geom.py:32-33 npy_types): 15 packed bytes
+VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+
 def device_count() -> int:
     return _lib.load().pb_device_count()
 
@@ -137,6 +141,28 @@ class _Ctx:
         lo, hi = C.c_float(), C.c_float()
         check(self.lib.pb_depth_encode_still(self.ctx, _ptr(depth), H, W, int(flip), int(encode_range), _ptr(rgb), C.byref(lo), C.byref(hi)))
         return rgb, lo.value, hi.value
+
+    def point_cloud(self, depth: np.ndarray, rgb: np.ndarray, flip: bool = True, u0: Optional[float] = None, v0: Optional[float] = None,
+                    fx: float = 1000.0, fy: float = 1000.0) -> np.ndarray:
+        """write_pcl's vertices on the GPU (bands/common/io.py:201-211, bands/common/geom.py:5-47; pb_depth_point_cloud): depth [H, W] or
+        [n, H, W] float32 and rgb [..., H, W, 3] uint8 -> the PLY's vertex records, a structured array of depth's shape viewed over the
+        returned bytes.  u0 / v0 default to the reference's W / 2 and H / 2."""
+        depth = _f32(depth)
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert depth.ndim in (2, 3) and rgb.shape == depth.shape + (3,), (depth.shape, rgb.shape)
+        H, W = depth.shape[-2:]
+        n = depth.shape[0] if depth.ndim == 3 else 1
+        raw = np.empty(depth.shape + (VERTEX_DTYPE.itemsize,), np.uint8)
+        check(self.lib.pb_depth_point_cloud(self.ctx, _ptr(depth), _ptr(rgb), n, H, W, int(flip), W / 2 if u0 is None else u0,
+                                            H / 2 if v0 is None else v0, fx, fy, _ptr(raw)))
+        return raw.view(VERTEX_DTYPE).reshape(depth.shape)
+
+    def point_cloud_dev(self, depth_ptr: int, rgb_ptr: int, n: int, H: int, W: int, out_ptr: int, flip: bool = True,
+                        u0: Optional[float] = None, v0: Optional[float] = None, fx: float = 1000.0, fy: float = 1000.0):
+        """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_depth_point_cloud_dev): sync() waits; out_ptr takes
+        n * H * W * 15 bytes"""
+        check(self.lib.pb_depth_point_cloud_dev(self.ctx, C.c_void_p(depth_ptr), C.c_void_p(rgb_ptr), n, H, W, int(flip),
+                                                W / 2 if u0 is None else u0, H / 2 if v0 is None else v0, fx, fy, C.c_void_p(out_ptr)))
 
     def set_option(self, key: str, value: int):
         check(self.lib.pb_set_option(self.ctx, key.encode(), int(value)))
