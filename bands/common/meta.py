@@ -2,8 +2,8 @@
 
 Re-statement of the behaviour of /root/reference/bands/common/meta.py (load_metadata :27-32,
 create_metadata :35-58, is_video :65-67, get_target :70-93, get_url :96-104, add_band :109-121,
-write_metadata :124-134, set_default_band :137-146) - same function names, arguments and JSON
-layout, so files written by either implementation are interchangeable.
+write_metadata :124-134, set_default_band :137-146, get_record3d_data :148-156) - same function names,
+arguments and JSON layout, so files written by either implementation are interchangeable.
 """
 import json
 import os
@@ -85,3 +85,24 @@ def set_default_band(path, band, band_default):
     if data and band_default in data.get("bands", {}):
         data["bands"][band] = data["bands"][band_default]
         write_metadata(path, data)
+
+
+def get_record3d_data(path):
+    """Record3D's capture data of a video, {"intrinsicMatrix": [9 numbers, column major], "rangeOfEncodedDepth": [min, max]} (:148-156).
+    The reference reads the container's `movie_more` tag through pymediainfo.  Looked up here in this order: a sidecar
+    `<path without extension>.record3d.json` holding that tag's JSON (the offline stand-in, as .npy stacks are for .mp4), then pymediainfo
+    when it imports; otherwise an error that names both."""
+    sidecar = path.rsplit(".", 1)[0] + ".record3d.json"
+    if os.path.exists(sidecar):
+        with open(sidecar) as f:
+            info = json.load(f)
+    else:
+        try:
+            from pymediainfo import MediaInfo
+        except ImportError as e:
+            raise RuntimeError("Record3D data of %s: no sidecar %s and pymediainfo (the reference's reader of the video's `movie_more` tag) is "
+                               "not installed" % (path, sidecar)) from e
+        info = json.loads(json.loads(MediaInfo.parse(path).to_json())["tracks"][0]["movie_more"])
+    if len(info.get("intrinsicMatrix", ())) != 9 or len(info.get("rangeOfEncodedDepth", ())) != 2:
+        raise RuntimeError("Record3D data of %s: needs intrinsicMatrix (9 numbers) and rangeOfEncodedDepth (min, max)" % path)
+    return info

@@ -192,6 +192,27 @@ int pb_depth_point_cloud(pb_ctx *ctx, const float *depth, const uint8_t *rgb, in
 int pb_depth_point_cloud_dev(pb_ctx *ctx, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip,
                              float u0, float v0, float fx, float fy, uint8_t *vertices_out);
 
+/* rgba band, side-by-side RGB-D captures (`--rgbd left|right|top|bottom`, Record3D): split() of bands/rgba.py:24-75.
+ * pb_rgbd_boxes (no GPU needed): the two halves of an H x W frame as half-open boxes {y0, y1, x0, x1}.  `side` is where the DEPTH is:
+ * 0 left, 1 right, 2 top, 3 bottom.  The reference slices with int() of width / 2 and height / 2 (rgba.py:29-40, 58-59), so with
+ * k = W / 2 (integer division) left gives depth columns [0, k) and rgb [k, W), right rgb [0, k) and depth [k, W); top and bottom the same
+ * on rows with H / 2: of an odd size the half that starts at the middle is one wider.  PB_ERR_ARG when a half is empty (W < 2 for left /
+ * right, H < 2 for top / bottom) or `side` is unknown.  The colour half is a crop without arithmetic and stays with the caller.
+ * pb_rgbd_depth: `--encoding_depth hue` of the depth half (rgba.py:61-63 with rgb_to_hsv / heat_to_rgb / hue_to_rgb of
+ * bands/common/encode.py:13-58): d = clip(hue / 360, 0, 1) of every pixel, then heat_to_rgb(d) * 255 truncated to uint8 - float64 with
+ * numpy's operation order, every operation separately rounded; the bytes equal the reference's on all 2^24 colours
+ * (tests/golden/rgbd_hue.npz).  With `--encoding_depth none` the half is a crop too and needs no call.
+ *   frames    : n x H x W x 3 uint8, the whole side-by-side frames
+ *   depth_out : n x Hd x Wd x 3 uint8, the heat-encoded half (Hd x Wd = pb_rgbd_boxes' depth box), or NULL
+ *   heat_out  : n x Hd x Wd float32, d itself rounded to float32 - what a viewer recovers from the video as min + heat (max - min),
+ *               without the 8-bit round trip - or NULL (not both)
+ * pb_rgbd_depth: host pointers, blocking, in chunks of "host_chunk" frames (pb_set_option; default 8) whose copies overlap the kernel;
+ * page-locked caller arrays are addressed directly.  pb_rgbd_depth_dev: device pointers, asynchronous on the ctx stream; pb_sync() waits.
+ * Works on any ctx: the rgba band has no model. */
+int pb_rgbd_boxes(int H, int W, int side, int rgb_box[4], int depth_box[4]);
+int pb_rgbd_depth(pb_ctx *ctx, const uint8_t *frames, int n, int H, int W, int side, uint8_t *depth_out, float *heat_out);
+int pb_rgbd_depth_dev(pb_ctx *ctx, const uint8_t *frames, int n, int H, int W, int side, uint8_t *depth_out, float *heat_out);
+
 /* Network input size for an H x W frame: keep-aspect lower-bound resize to 518, each side a
  * multiple of 14 (bands/d_anything/util/transform.py:100-166). */
 int pb_depth_net_size(int H, int W, int *net_h, int *net_w);

@@ -758,4 +758,49 @@ int pb_depth_point_cloud(pb_ctx *c, const float *depth, const uint8_t *rgb, int 
     return r;
 }
 
+// ---- rgba band: side-by-side RGB-D captures (bands/rgba.py:24-75) ------------------------------------------------------------
+int pb_rgbd_boxes(int H, int W, int side, int rgb_box[4], int depth_box[4]) {
+    PB_CHECK(rgb_box && depth_box, PB_ERR_ARG, "rgbd_boxes: null box");
+    PB_CHECK(side >= 0 && side <= 3, PB_ERR_ARG, "rgbd_boxes: side %d unknown (0 left, 1 right, 2 top, 3 bottom: where the depth is)", side);
+    PB_CHECK(H > 0 && W > 0 && (side < 2 ? W : H) >= 2, PB_ERR_ARG, "rgbd_boxes: a %d x %d frame has no %s half", H, W,
+             side == 0 ? "left" : (side == 1 ? "right" : (side == 2 ? "top" : "bottom")));
+    // int(width / 2), int(height / 2) of rgba.py:29-40 as the slice bounds of :58-59: the half that starts at the middle takes the odd column / row
+    const int k = (side < 2 ? W : H) / 2;
+    int first[4] = {0, H, 0, W}, second[4] = {0, H, 0, W};
+    if (side < 2) { first[3] = k; second[2] = k; } else { first[1] = k; second[0] = k; }
+    const bool depth_first = side == 0 || side == 2;
+    for (int i = 0; i < 4; ++i) {
+        depth_box[i] = depth_first ? first[i] : second[i];
+        rgb_box[i] = depth_first ? second[i] : first[i];
+    }
+    return 0;
+}
+
+int pb_rgbd_depth_dev(pb_ctx *c, const uint8_t *frames, int n, int H, int W, int side, uint8_t *depth_out, float *heat_out) {
+    PB_CHECK(c && frames && (depth_out || heat_out) && n > 0, PB_ERR_ARG, "rgbd_depth: bad arguments");
+    int rb[4], db[4];
+    PB_TRY(pb_rgbd_boxes(H, W, side, rb, db));
+    PB_HIP(hipSetDevice(c->device));
+    return launch_hue_heat(c->stream, frames, n, H, W, db[0], db[2], db[1] - db[0], db[3] - db[2], depth_out, heat_out);
+}
+
+// Host-pointer variant: run_chunks over chunks of "host_chunk" (default 8) frames; lanes: the frames in, the two results out.
+int pb_rgbd_depth(pb_ctx *c, const uint8_t *frames, int n, int H, int W, int side, uint8_t *depth_out, float *heat_out) {
+    PB_CHECK(c && frames && (depth_out || heat_out) && n > 0, PB_ERR_ARG, "rgbd_depth: bad arguments");
+    int rb[4], db[4];
+    PB_TRY(pb_rgbd_boxes(H, W, side, rb, db));
+    PB_HIP(hipSetDevice(c->device));
+    const int Hd = db[1] - db[0], Wd = db[3] - db[2];
+    const size_t px = (size_t)H * W, pd = (size_t)Hd * Wd;
+    const int cap = std::min(n, c->host_chunk > 0 ? c->host_chunk : 8);
+    const ChunkLane lanes[3] = {{(void *)frames, px * 3, false, pb_is_pinned(frames, (size_t)n * px * 3)},
+                                {depth_out, depth_out ? pd * 3 : 0, true, pb_is_pinned(depth_out, (size_t)n * pd * 3)},
+                                {heat_out, heat_out ? pd * 4 : 0, true, pb_is_pinned(heat_out, (size_t)n * pd * 4)}};
+    const ChunkPipe::Lane *l = c->pipe.lane;
+    return run_chunks(c, n, cap, 0, lanes, 3, false, [&](int slot, int, int m) {
+        return launch_hue_heat(c->stream, (const uint8_t *)l[0].d[slot], m, H, W, db[0], db[2], Hd, Wd,
+                               (uint8_t *)(depth_out ? l[1].d[slot] : nullptr), (float *)(heat_out ? l[2].d[slot] : nullptr));
+    });
+}
+
 }  // extern "C"

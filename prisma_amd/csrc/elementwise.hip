@@ -280,6 +280,22 @@ __global__ void init_minmax_kernel(unsigned *mm, int B) {
     if (i < B) { mm[2 * i] = 0xFFFFFFFFu; mm[2 * i + 1] = 0u; }
 }
 
+// hue_to_rgb(hue) * 255 -> uint8 (truncation) from h6 = hue * 6 (bands/common/encode.py:13-28): the tail heat_encode_kernel and
+// hue_heat_kernel share.  float64 with numpy's operation order, every operation separately rounded.
+__device__ __forceinline__ void hue6_to_u8(double h6, uint8_t (&o)[3]) {
+    const double off[3] = {0.0, 4.0, 2.0};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        double v = ex_dadd(h6, off[c]);
+        v = fmod(v, 6.0);
+        if (v < 0.0) v = ex_dadd(v, 6.0);
+        v = ex_dsub(fabs(ex_dsub(v, 3.0)), 1.0);
+        v = fmin(fmax(v, 0.0), 1.0);
+        v = ex_dmul(v, 255.0);
+        o[c] = (v == v) ? (uint8_t)(int)v : (uint8_t)0;      // NaN (max == min) -> 0 like numpy on x86
+    }
+}
+
 // heat_to_rgb(1 - (p - min) / (max - min)) * 255 -> uint8 (truncation).
 // bands/depth_anything.py:215-220 + bands/common/encode.py:13-33: normalise / flip in float32,
 // colour ramp in float64 with numpy's operation order; explicit _rn intrinsics keep the compiler
@@ -299,19 +315,8 @@ __global__ __launch_bounds__(256) void heat_encode_kernel(const float *__restric
         float d = ex_fdiv(ex_fsub(depth[(int64_t)b * per + i], dmin), range);
         if (flip) d = ex_fsub(1.0f, d);
         const double hue = ex_dmul(ex_dsub(1.0, (double)d), 0.65);
-        const double h6 = ex_dmul(hue, 6.0);
-        const double off[3] = {0.0, 4.0, 2.0};
         uint8_t o[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            double v = ex_dadd(h6, off[c]);
-            v = fmod(v, 6.0);
-            if (v < 0.0) v = ex_dadd(v, 6.0);
-            v = ex_dsub(fabs(ex_dsub(v, 3.0)), 1.0);
-            v = fmin(fmax(v, 0.0), 1.0);
-            v = ex_dmul(v, 255.0);
-            o[c] = (v == v) ? (uint8_t)(int)v : (uint8_t)0;      // NaN (max == min) -> 0 like numpy on x86
-        }
+        hue6_to_u8(ex_dmul(hue, 6.0), o);
         uint8_t *dst = rgb + ((int64_t)b * per + i) * 3;
         dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
     }
@@ -515,6 +520,116 @@ __global__ __launch_bounds__(256) void point_cloud_kernel(const float *__restric
 #pragma unroll
             for (int b = 0; b < 4; ++b)
                 if (4 * q + b >= s && 4 * q + b < end) ga[4 * q + b] = (uint8_t)(v >> (8 * b));
+        }
+    }
+}
+
+// ---- rgba band, RGB-D split: hue-coded depth half -> heat ramp ------------------------------------------------------
+// bands/rgba.py:58-63 with rgb_to_hsv / heat_to_rgb of bands/common/encode.py:13-58, per pixel of the depth box, float64, every operation
+// separately rounded (common.h ex_*):  den = (max - min) + 2^-52;  the FIRST maximum channel picks the branch like np.argmax -
+// r: h = ((g - b) * 60 / den) % 360, g: (b - r) * 60 / den + 120, b: (r - g) * 60 / den + 240;  d = clip(h / 360, 0, 1) (a true division);
+// bytes = hue6_to_u8(((1 - d) * 0.65) * 6).  Greys give h = 0 (g - b = 0 over den = 2^-52): no NaN arises.
+//
+// Both outputs are packed, so over all frames they are ONE stream of n Hd Wd pixels: a lane owns HH_PX = 4 consecutive pixels of it - twelve
+// bytes = three dwords of depth_out at a dword-aligned offset, four floats of heat_out.  The input is strided (a box row starts at byte
+// (y W + x0) 3 of its frame: no alignment at all): where a lane's four pixels lie in one row their twelve bytes are contiguous, and the lane
+// reads the three or four ALIGNED dwords that cover them - each holds at least one byte of the box, so no read leaves a page the frames
+// do not own - and shifts the stream down to its misalignment (v_alignbyte).  A group that straddles a row end (Wd % 4 != 0) or the end
+// of the stream reads byte by byte; the partial group at the end of the stream, and every group of a depth_out that is not dword-aligned
+// itself, stores byte by byte.
+constexpr int HH_PX = 4;
+
+__device__ __forceinline__ double hue_decode(unsigned r8, unsigned g8, unsigned b8) {
+    const double r = (double)r8, g = (double)g8, b = (double)b8;
+    const double mx = fmax(fmax(r, g), b), mn = fmin(fmin(r, g), b);
+    const double den = ex_dadd(ex_dsub(mx, mn), 0x1p-52);
+    double h;
+    if (r >= fmax(g, b)) {
+        h = fmod(ex_ddiv(ex_dmul(ex_dsub(g, b), 60.0), den), 360.0);        // np's %: fmod, then + 360 where the sign is the wrong one
+        if (h < 0.0) h = ex_dadd(h, 360.0);
+    } else if (g >= b) {
+        h = ex_dadd(ex_ddiv(ex_dmul(ex_dsub(b, r), 60.0), den), 120.0);
+    } else {
+        h = ex_dadd(ex_ddiv(ex_dmul(ex_dsub(r, g), 60.0), den), 240.0);
+    }
+    return fmin(fmax(ex_ddiv(h, 360.0), 0.0), 1.0);
+}
+
+__global__ __launch_bounds__(256) void hue_heat_kernel(const uint8_t *__restrict__ frames, int H, int W, int y0, int x0, int Hd, int Wd,
+                                                       int64_t total, uint8_t *__restrict__ depth_out, float *__restrict__ heat_out) {
+    const int64_t p0 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * HH_PX;
+    if (p0 >= total) return;
+    const int cnt = total - p0 < HH_PX ? (int)(total - p0) : HH_PX;
+    const int64_t row = p0 / Wd;                        // row of the stream: frame * Hd + y
+    const int x = (int)(p0 - row * Wd);
+    unsigned w[3] = {0u, 0u, 0u};                       // the group's twelve input bytes, little endian
+    if (cnt == HH_PX && x + HH_PX <= Wd) {
+        const int64_t f = row / Hd;
+        const int y = (int)(row - f * Hd);
+        const uint8_t *a = frames + ((f * H + y0 + y) * W + x0 + x) * 3;
+        const int s = (int)((uintptr_t)a & 3);
+        const unsigned *q = (const unsigned *)(a - s);
+        const unsigned q0 = q[0], q1 = q[1], q2 = q[2];
+        if (s) {
+            const unsigned q3 = q[3];
+            w[0] = __builtin_amdgcn_alignbyte(q1, q0, s);
+            w[1] = __builtin_amdgcn_alignbyte(q2, q1, s);
+            w[2] = __builtin_amdgcn_alignbyte(q3, q2, s);
+        } else {
+            w[0] = q0; w[1] = q1; w[2] = q2;
+        }
+    } else {
+        int64_t r = row;
+        int xx = x;
+        for (int p = 0; p < cnt; ++p) {
+            const int64_t f = r / Hd;
+            const int y = (int)(r - f * Hd);
+            const uint8_t *a = frames + ((f * H + y0 + y) * W + x0 + xx) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int at = 3 * p + k;
+                w[at >> 2] |= (unsigned)a[k] << (8 * (at & 3));
+            }
+            if (++xx == Wd) { xx = 0; ++r; }
+        }
+    }
+    unsigned o[3] = {0u, 0u, 0u};
+    float heat[HH_PX];
+#pragma unroll
+    for (int p = 0; p < HH_PX; ++p) {
+        unsigned c[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int at = 3 * p + k;
+            c[k] = (w[at >> 2] >> (8 * (at & 3))) & 255u;
+        }
+        const double d = hue_decode(c[0], c[1], c[2]);
+        heat[p] = (float)d;
+        if (depth_out) {
+            uint8_t e[3];
+            hue6_to_u8(ex_dmul(ex_dmul(ex_dsub(1.0, d), 0.65), 6.0), e);
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                const int at = 3 * p + k;
+                o[at >> 2] |= (unsigned)e[k] << (8 * (at & 3));
+            }
+        }
+    }
+    if (depth_out) {
+        uint8_t *dst = depth_out + p0 * 3;
+        if (cnt == HH_PX && ((uintptr_t)depth_out & 3) == 0) {
+            unsigned *dw = (unsigned *)dst;
+            dw[0] = o[0]; dw[1] = o[1]; dw[2] = o[2];
+        } else {
+            for (int i = 0; i < 3 * cnt; ++i) dst[i] = (uint8_t)(o[i >> 2] >> (8 * (i & 3)));
+        }
+    }
+    if (heat_out) {
+        float *dst = heat_out + p0;
+        if (cnt == HH_PX && ((uintptr_t)heat_out & 15) == 0) {
+            *(f32x4 *)dst = f32x4{heat[0], heat[1], heat[2], heat[3]};
+        } else {
+            for (int i = 0; i < cnt; ++i) dst[i] = heat[i];
         }
     }
 }
@@ -762,6 +877,16 @@ int launch_point_cloud(hipStream_t s, const float *depth, const uint8_t *rgb, in
         if (int r = launch_minmax_only(s, depth, n, (int64_t)H * W, mm)) return r;
     }
     hipLaunchKernelGGL(point_cloud_kernel, dim3(gx, gy, n), dim3(256), 0, s, depth, rgb, H, W, mm, flip, u0, v0, fx, fy, out);
+    PB_HIP(hipGetLastError());
+    return 0;
+}
+
+int launch_hue_heat(hipStream_t s, const uint8_t *frames, int n, int H, int W, int y0, int x0, int Hd, int Wd, uint8_t *depth_out, float *heat_out) {
+    PB_CHECK(n > 0 && Hd > 0 && Wd > 0 && y0 >= 0 && x0 >= 0 && y0 + Hd <= H && x0 + Wd <= W, -1, "hue_heat: box %d x %d at (%d, %d) outside the %d x %d frame",
+             Hd, Wd, y0, x0, H, W);
+    const int64_t total = (int64_t)n * Hd * Wd, blocks = (total + 256 * HH_PX - 1) / (256 * HH_PX);
+    PB_CHECK(blocks <= 0x7fffffff, -1, "hue_heat: %lld pixels exceed the launch grid", (long long)total);
+    hipLaunchKernelGGL(hue_heat_kernel, dim3((unsigned)blocks), dim3(256), 0, s, frames, H, W, y0, x0, Hd, Wd, total, depth_out, heat_out);
     PB_HIP(hipGetLastError());
     return 0;
 }

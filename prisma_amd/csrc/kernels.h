@@ -48,6 +48,11 @@ int launch_still_encode(hipStream_t s, const float *depth, int H, int W, unsigne
 // ordered-uint min / max (written only with flip).  `out` needs no alignment.
 int launch_point_cloud(hipStream_t s, const float *depth, const uint8_t *rgb, int n, int H, int W, int flip, float u0, float v0, float fx,
                        float fy, unsigned *mm, uint8_t *out);
+// rgba band, RGB-D split (bands/rgba.py:58-63, bands/common/encode.py:13-58): the hue-encoded depth half of n side-by-side frames [n, H, W, 3]
+// - the box of Hd x Wd pixels at (y0, x0) of every frame - decoded (rgb_to_hsv(...)[..., 0] / 360, clipped) and re-encoded in the heat ramp.
+// depth_out [n, Hd, Wd, 3] uint8 and heat_out [n, Hd, Wd] float32 (the decoded value) are packed; either may be null.  depth_out needs no
+// alignment (a dword-aligned one takes dword stores), heat_out a float's.
+int launch_hue_heat(hipStream_t s, const uint8_t *frames, int n, int H, int W, int y0, int x0, int Hd, int Wd, uint8_t *depth_out, float *heat_out);
 
 // layout converters used by the op-level tests and the stage dumps
 int launch_nchw_f32_to_nhwc_f16(hipStream_t s, const float *x, f16 *y, int B, int C, int H, int W, int ldc, int relu);

@@ -38,6 +38,25 @@ def net_size(H: int, W: int) -> Tuple[int, int]:
     return nh.value, nw.value
 
 
+RGBD_SIDES = ("left", "right", "top", "bottom")      # where the depth is: pb_rgbd_boxes' side 0 .. 3
+
+
+def _rgbd_side(side) -> int:
+    if isinstance(side, str):
+        if side not in RGBD_SIDES:
+            raise ValueError("side %r: one of %s" % (side, ", ".join(RGBD_SIDES)))
+        return RGBD_SIDES.index(side)
+    return int(side)
+
+
+def rgbd_boxes(H: int, W: int, side) -> Tuple[Tuple[int, int, int, int], Tuple[int, int, int, int]]:
+    """(rgb_box, depth_box) of an H x W side-by-side RGB-D frame as half-open (y0, y1, x0, x1); `side` (a name of RGBD_SIDES or its index)
+    is where the depth is (bands/rgba.py:29-40, 58-59; pb_rgbd_boxes, needs no GPU)"""
+    rb, db = (C.c_int * 4)(), (C.c_int * 4)()
+    check(_lib.load().pb_rgbd_boxes(H, W, _rgbd_side(side), rb, db))
+    return tuple(rb), tuple(db)
+
+
 def run_concurrently(jobs):
     """Drive several band contexts at once: jobs = [(ctx, enqueue), ...] where `enqueue()` calls one of ctx's asynchronous device-pointer
     entry points (`infer_dev`, `infer_sequence_dev`, `infer_batch_dev`).  Every job is enqueued on its own ctx stream from this thread
@@ -163,6 +182,29 @@ class _Ctx:
         n * H * W * 15 bytes"""
         check(self.lib.pb_depth_point_cloud_dev(self.ctx, C.c_void_p(depth_ptr), C.c_void_p(rgb_ptr), n, H, W, int(flip),
                                                 W / 2 if u0 is None else u0, H / 2 if v0 is None else v0, fx, fy, C.c_void_p(out_ptr)))
+
+    def rgbd_depth(self, frames: np.ndarray, side, want_heat: bool = False, want_rgb: bool = True, out_rgb: Optional[np.ndarray] = None,
+                   out_heat: Optional[np.ndarray] = None):
+        """`--encoding_depth hue` of the depth half of side-by-side RGB-D frames [n, H, W, 3] uint8 (bands/rgba.py:58-63; pb_rgbd_depth):
+        -> the heat-encoded half [n, Hd, Wd, 3] uint8, or with want_heat (that, heat [n, Hd, Wd] float32: the decoded value in [0, 1]);
+        want_rgb=False: heat alone.  out_rgb / out_heat: the caller's own (page-locked) arrays."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        assert frames.ndim == 4 and frames.shape[-1] == 3, frames.shape
+        n, H, W = frames.shape[:3]
+        _, db = rgbd_boxes(H, W, side)
+        shape = (n, db[1] - db[0], db[3] - db[2])
+        rgb = (np.empty(shape + (3,), np.uint8) if out_rgb is None else out_rgb) if want_rgb else None
+        heat = (np.empty(shape, np.float32) if out_heat is None else out_heat) if want_heat else None
+        assert rgb is None or (rgb.shape == shape + (3,) and rgb.dtype == np.uint8 and rgb.flags.c_contiguous)
+        assert heat is None or (heat.shape == shape and heat.dtype == np.float32 and heat.flags.c_contiguous)
+        check(self.lib.pb_rgbd_depth(self.ctx, _ptr(frames), n, H, W, _rgbd_side(side), _ptr(rgb), _ptr(heat)))
+        return (rgb, heat) if want_heat and want_rgb else (heat if want_heat else rgb)
+
+    def rgbd_depth_dev(self, frames_ptr: int, n: int, H: int, W: int, side, depth_ptr: int = 0, heat_ptr: int = 0):
+        """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_rgbd_depth_dev): sync() waits; depth_ptr takes
+        n * Hd * Wd * 3 bytes (no alignment needed), heat_ptr n * Hd * Wd floats; 0 = not wanted"""
+        check(self.lib.pb_rgbd_depth_dev(self.ctx, C.c_void_p(frames_ptr), n, H, W, _rgbd_side(side), C.c_void_p(depth_ptr or None),
+                                         C.c_void_p(heat_ptr or None)))
 
     def set_option(self, key: str, value: int):
         check(self.lib.pb_set_option(self.ctx, key.encode(), int(value)))

@@ -8,6 +8,13 @@ field_of_view), same band order (mask -> depth -> flow -> camera, :205-290), sam
 default-band aliases (`depth`, `flow`, `flow_bwd`, `flow_mask`, `flow_mask_bwd`, :243-287).  It shells out to
 `bands/<band>.py` exactly like the reference's run() (:60-73), with `sys.executable` instead of a bare `python3`.
 
+Side-by-side RGB-D captures (:124-166, 243): `--rgbd left|right|top|bottom` (where the depth is) is handed to the rgba band, which
+writes the colour half as rgba.<ext> and the other half as band `depth`; every other band then runs on the colour half, and the
+`depth` alias is NOT pointed at the estimated depth band.  `--record3d` is `--rgbd right` with `--encoding_depth hue`, plus the
+capture's own camera: focal_length = max(fx, fy), principal_point = [cx, cy], field_of_view from the input's full height, and the
+metric range of the `depth` band (values.min / max) from Record3D's tag - read from `<input>.record3d.json` beside the input, or
+through pymediainfo where it is installed (bands/common/meta.py get_record3d_data).
+
 Bands this repo builds: rgba, depth_anything, flow_raft, flow_gmflow (the reference's default flow band, :23 -
 and this script's), mask_mmdet.  The reference's default for still images (depth_patchfusion) and camera_colmap are out of scope
 (SURVEY section 2): a request for a band that is not built is reported and skipped; a default that is not built falls back to the
@@ -24,8 +31,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 from bands.common.io import get_image_size, get_video_data  # noqa: E402
-from bands.common.meta import (add_band, create_metadata, is_video, load_metadata, set_default_band,  # noqa: E402
-                               write_metadata)
+from bands.common.meta import (add_band, create_metadata, get_record3d_data, is_video, load_metadata,  # noqa: E402
+                               set_default_band, write_metadata)
 
 # Default BANDS & MODELS (reference :17-30; defaults narrowed to what is built here)
 BUILT = ("rgba", "depth_anything", "flow_raft", "flow_gmflow", "mask_mmdet")
@@ -89,8 +96,6 @@ def main(argv=None):
     parser.add_argument("--flow_backwards", "-b", help="Save backwards video", action="store_true")
     parser.add_argument("--flow_mask", "-m", help="Save mask of videos", action="store_true")
     args = parser.parse_args(argv)
-    if args.record3d or args.rgbd:
-        raise SystemExit("process.py: --record3d / --rgbd (side-by-side RGB-D captures) are not built in this repo")
     del COMMANDS[:]
     del RESULTS[:]
 
@@ -105,9 +110,31 @@ def main(argv=None):
     name_rgba = "rgba." + extension
     path_rgba = os.path.join(folder_name, name_rgba)
 
+    # Record3D capture (reference :124-160): depth on the right, hue-coded; intrinsics and the depth range from the video's own tag
+    extra_rgba_args = EXTRA_ARGS["rgba"]
+    if args.record3d:
+        args.rgbd = "right"
+        height = get_video_data(input_path)[1] if video else get_image_size(input_path)[1]       # the INPUT's full height (:128-131)
+        try:
+            record3d_info = get_record3d_data(input_path)
+        except RuntimeError as e:
+            raise SystemExit("process.py: --record3d: %s" % e)
+        print(record3d_info)
+        camera = record3d_info["intrinsicMatrix"]
+        fx, fy, cx, cy = camera[0], camera[4], camera[6], camera[7]
+        depth_range = record3d_info["rangeOfEncodedDepth"]
+        data["focal_length"] = max(fx, fy)
+        data["principal_point"] = [cx, cy]
+        data["field_of_view"] = float(2 * np.arctan(0.5 * height / data["focal_length"]) * 180 / np.pi)
+        extra_rgba_args += "--encoding_depth hue "
+        add_band(data, "depth", url="depth." + extension)
+        data["bands"]["depth"]["values"] = {"min": {"type": "float", "value": depth_range[0]},
+                                            "max": {"type": "float", "value": depth_range[1]}}
+
     # 3. extract RGBA (reference :160-171)
     add_band(data, "rgba", url=name_rgba)
-    extra_rgba_args = EXTRA_ARGS["rgba"]
+    if args.rgbd:
+        extra_rgba_args += "--rgbd " + args.rgbd
     if video:
         extra_rgba_args += " --fps " + str(args.fps)
     write_metadata(folder_name, data)
@@ -150,7 +177,8 @@ def main(argv=None):
         if band == "depth_patchfusion" and video:
             extra_args += "--mode=p49 "
         run(band, folder_name, subpath=args.extra, extra_args=extra_args)
-    set_default_band(folder_name, "depth", (DEPTH_VIDEO_DEFAULT if video else DEPTH_IMAGE_DEFAULT) if args.depth == "all" else args.depth)
+    if args.rgbd is None:           # reference :243: a measured depth half keeps the `depth` name; the estimated band stays under its own
+        set_default_band(folder_name, "depth", (DEPTH_VIDEO_DEFAULT if video else DEPTH_IMAGE_DEFAULT) if args.depth == "all" else args.depth)
 
     if video:
         if args.flow is None:
