@@ -2,10 +2,17 @@
 """flow_gmflow band - drop-in for /root/reference/bands/flow_gmflow.py on MI355X (prisma's DEFAULT flow band, process.py:23).
 
 Same CLI (reference :223-255; the GMFlow architecture flags are accepted and must equal the band's defaults, which is the model the
-engine builds), same outputs (<BAND>.mp4, <BAND>.csv with the per-frame max displacement, optional <BAND>_bwd / _mask / _mask_bwd
+engine builds; the two inference-time radii are honoured: --corr_radius_list R, 1 .. 4, selects local matching over (2 R + 1)^2 target
+tokens and --prop_radius_list r, 1 .. 2, local-window flow propagation, -1 = global, reference bands/gmflow/gmflow.py:128-157), same outputs
+(<BAND>.mp4, <BAND>.csv with the per-frame max displacement, optional <BAND>_bwd / _mask / _mask_bwd
 videos, .flo / 16-bit PNG dumps, metadata entries :195-218), same module API (BAND, init_model(), infer()).  The frame loop, the file
 writers and the multi-rank relay are flow_raft's (bands/flow_raft.py process_video: the two reference scripts share them line for line,
 flow_gmflow.py:121-218 vs flow_raft.py:69-166); the model is libprisma_bands.so's GmflowEngine through prisma_amd.engine.FlowGMFlow.
+
+--backwards / --mask with a matching radius: the reference raises there (pred_bidir_flow: local_correlation_softmax returns B flows while
+the features were concatenated to 2 B, gmflow.py:142,153-157).  This band computes the backward direction as the forward direction of the
+swapped pair, which is what pred_bidir_flow equals wherever the reference can run it (global matching, either propagation).
+--num_scales 2 and --attn_splits_list other than 2 stay refused.
 """
 import argparse
 import os
@@ -26,9 +33,12 @@ from prisma_amd import engine, shard, synth  # noqa: E402
 
 BAND = "flow_gmflow"
 MODEL = "models/gmflow_sintel-0c07dcb3.pth"      # reference :35
-# the model flags of reference :239-249 and the only values the engine implements (the band's defaults)
+# the model flags of reference :239-249 and the only values the engine implements (the band's defaults); corr_radius_list and
+# prop_radius_list are also taken as one radius each (RADII: the largest the engine's kernels are built for)
 ARCH = {"feature_channels": 128, "num_scales": 1, "upsample_factor": 8, "num_head": 1, "attention_type": "swin", "ffn_dim_expansion": 4,
         "num_transformer_layers": 6, "attn_splits_list": [2], "corr_radius_list": [-1], "prop_radius_list": [-1], "padding_factor": 16}
+
+RADII = {"corr_radius_list": 4, "prop_radius_list": 2}
 
 model = None
 data = None
@@ -46,8 +56,18 @@ def load_weights(path):
     return synth.gmflow_weights(seed=2468)
 
 
+def radius(args, key):
+    """the one radius of a --corr_radius_list / --prop_radius_list (-1 = global)"""
+    v = getattr(args, key, None) if args is not None else None
+    return int(v[0]) if v else -1
+
+
 def check_arch(args):
-    bad = {k: getattr(args, k) for k, v in ARCH.items() if hasattr(args, k) and getattr(args, k) != v}
+    bad = {k: getattr(args, k) for k, v in ARCH.items() if hasattr(args, k) and getattr(args, k) != v and k not in RADII}
+    for k, top in RADII.items():
+        v = getattr(args, k, None)
+        if v is not None and (len(v) != 1 or not (v[0] == -1 or 1 <= v[0] <= top)):
+            raise SystemExit(f"[{BAND}] --{k} takes one radius (one scale): -1 (global) or 1 .. {top}; got {v}")
     if bad:
         raise SystemExit(f"[{BAND}] only the band's default GMFlow is built ({ARCH}); got {bad}")
     isz = getattr(args, "inference_size", None)
@@ -62,6 +82,7 @@ def init_model(args=None, device=0):
         _SYNTH[0] = bool(getattr(args, "synthetic", False))
     model = engine.FlowGMFlow(load_weights(getattr(args, "model", MODEL) if args else MODEL), device=device)
     model.set_inference_size(getattr(args, "inference_size", None) if args is not None else None)      # reference :76-100
+    model.set_matching(radius(args, "corr_radius_list"), radius(args, "prop_radius_list"))              # reference :84-89
     return model
 
 

@@ -255,7 +255,8 @@ int pb_flow_fwdbwd_mask(pb_ctx *ctx, const float *flows, int n, int sh, int sw, 
  * GMFlow(attn_splits_list=[2], corr_radius_list=[-1], prop_radius_list=[-1], pred_bidir_flow per `backward`)) ->
  * bands/gmflow/gmflow.py:12-170 (shared instance-norm encoder, position encoding, 6 transformer blocks with 2 x 2 shifted windows,
  * global matching, self-attention propagation, convex upsampling) and the same write_flow / process_flow encode.  Only the band's
- * default configuration is built (1 scale, 128 channels, 6 layers, 1 head, ffn x 4); the band script rejects other GMFlow flags. */
+ * default architecture is built (1 scale, 128 channels, 6 layers, 1 head, ffn x 4, attn_splits 2); the band script rejects other GMFlow
+ * flags - in particular --num_scales 2 and --attn_splits_list other than 2 - except the two inference-time radii below. */
 /* Stages of the last flow call: "fmap" [F,256,h/8,w/8], "flow_lo" [pairs*dirs, h/8*w/8, 2]; flow_gmflow (token-major fp32, shape
  * [n, tokens, channels, 1]): "feat" [F, h/8*w/8, 128] (encoder output), "block0" / "tfeat" [2 pairs, tokens, 128] (after the first / last
  * transformer block; both images of every pair), "flow_match" / "flow_prop" [pairs*dirs, tokens, 2]. */
@@ -264,6 +265,15 @@ int64_t pb_flow_get_stage(pb_ctx *ctx, const char *name, float *out, int64_t cap
  * F.interpolate(bilinear, align_corners = True) of the (scaled) frame to h x w instead of on the frame padded to /16, and the flow is
  * resized back the same way with u * W' / w, v * H' / h.  (0, 0) turns it off.  flow_gmflow contexts only. */
 int pb_flow_set_inference_size(pb_ctx *ctx, int h, int w);
+/* flow_gmflow --corr_radius_list R / --prop_radius_list r (reference bands/gmflow/gmflow.py:128-157, same checkpoint): -1 = global (the
+ * default: nothing of the default path changes).  corr_radius 1 .. 4: local matching - the softmax runs over the (2 R + 1)^2 target tokens
+ * around the source token, those outside the grid masked (matching.py:39-83).  prop_radius 1 .. 2: local-window propagation over
+ * (2 r + 1)^2 zero-padded neighbours, pads counted in the softmax (transformer.py:376-409; its key is k_proj of the feature, where the
+ * global form takes k_proj of the projected query).  Backward direction (`backward`, masks): with global matching it is the reference's
+ * pred_bidir_flow; with a matching radius the reference's pred_bidir_flow raises (local_correlation_softmax returns B flows for 2 B
+ * features), and the band defines it as the forward direction of the swapped pair - what pred_bidir_flow equals wherever the reference
+ * can run it.  Other values are an error and leave the context as it was.  flow_gmflow contexts only. */
+int pb_flow_set_matching(pb_ctx *ctx, int corr_radius, int prop_radius);
 
 /* mask_mmdet band (band = "mask_mmdet", cfg = pb_mask_cfg; weights: backbone.*, neck.*, mask_head.* in mmdet's
  * state_dict naming).  Replaces the per-frame body of bands/mask_mmdet.py:131-154: inference_detector
@@ -432,7 +442,11 @@ int pb_op_raft_state(pb_ctx *ctx, const float *ctx_rows, const float *flow, int 
  * match: tokens [2 NP, P, 128]; split_rows, the global matching over the shared coordinate V^T, match_flow -> flow [NP dirs, P, 2].
  * propagate: q, k, X [2 NP, P, 128], flow_in [NP dirs, P, 2]; match_flow on flow_in + own coordinate (flow_match returns the fp32 flow it made
  *   of that), the propagation attention, upsampler_in -> flow_prop [NP dirs, P, 2], map (NP dirs P + guard) x 384 halfs.  Both flow chains
- *   zero the flow V^T first, as the engine's arena is zeroed. */
+ *   zero the flow V^T first, as the engine's arena is zeroed.
+ * local_match (gmflow_local.hip): tokens [2 NP, P, 128]; batch element (pair, direction) reads source image 2 pair + dir and the other image
+ *   of the pair as target (dirs 1: the even images only) -> flow (NP dirs P + guard) x 2 floats; 1 <= radius <= 4.
+ * local_propagate: q, k [B img_step, P, 128] (batch element b takes image b img_step), flow_in [B, P, 2] -> flow_out (B P + guard) x 32
+ *   floats, the propagation output's layout: the kernel owns columns 0, 1 (where upsampler_in reads the flow); 1 <= radius <= 2. */
 int pb_op_gm_tables(int h8, int w8, float *pos, int8_t *region);
 int pb_op_gm_tokens(pb_ctx *ctx, const float *feat, const float *pos, int NP, int P, int guard_rows, float *X, void *Xs);
 int pb_op_gm_split_rows(pb_ctx *ctx, const float *src, int rows, int ld, int C, int guard_rows, void *out);
@@ -451,6 +465,9 @@ int pb_op_gm_window_block(pb_ctx *ctx, const float *Y, float *X, const float *ga
 int pb_op_gm_match(pb_ctx *ctx, const float *tokens, int NP, int h8, int w8, int dirs, int split, float *flow);
 int pb_op_gm_propagate(pb_ctx *ctx, const float *q, const float *k, const float *flow_in, const float *X, int NP, int h8, int w8, int dirs,
                        int split, int guard_rows, float *flow_match, float *flow_prop, void *map);
+int pb_op_gm_local_match(pb_ctx *ctx, const float *tokens, int NP, int h8, int w8, int dirs, int radius, int guard_rows, float *flow);
+int pb_op_gm_local_propagate(pb_ctx *ctx, const float *q, const float *k, const float *flow_in, int B, int h8, int w8, int img_step, int radius,
+                             int guard_rows, float *flow_out);
 /* bilinear resize NCHW float32, align_corners 0/1 (torch F.interpolate semantics). */
 int pb_op_bilinear(pb_ctx *ctx, const float *x, float *y, int B, int C, int H, int W, int OH, int OW,
                    int align_corners);

@@ -87,6 +87,7 @@ SYMBOLS = {
                                    C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pb_mask_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "pb_flow_set_inference_size": (C.c_int, [_P, C.c_int, C.c_int]),
+    "pb_flow_set_matching": (C.c_int, [_P, C.c_int, C.c_int]),
     "pb_mask_set_sdf": (C.c_int, [_P, _P, _P, C.c_int]),
     "pb_mask_sdf_green": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
     "pb_mask_sdf_green_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
@@ -136,6 +137,8 @@ SYMBOLS = {
     "pb_op_gm_window_block": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 6),
     "pb_op_gm_match": (C.c_int, [_P, _P] + [C.c_int] * 5 + [_P]),
     "pb_op_gm_propagate": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P]),
+    "pb_op_gm_local_match": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
+    "pb_op_gm_local_propagate": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [_P]),
     "pb_op_bilinear": (C.c_int, [_P, _P, _P] + [C.c_int] * 7),
     "pb_op_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "pb_op_encode_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

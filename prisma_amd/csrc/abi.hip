@@ -631,6 +631,13 @@ int pb_flow_set_inference_size(pb_ctx *c, int h, int w) {
     return g->set_inference_size(h, w);
 }
 
+int pb_flow_set_matching(pb_ctx *c, int corr_radius, int prop_radius) {
+    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow band");
+    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->raft);
+    PB_CHECK(g, PB_ERR_STATE, "--corr_radius_list / --prop_radius_list are flow_gmflow options");
+    return g->set_matching(corr_radius, prop_radius);
+}
+
 int64_t pb_flow_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {
     PB_CHECK(c && c->raft && name && out && shape_out, PB_ERR_ARG, "flow get_stage: bad arguments");
     PB_HIP(hipSetDevice(c->device));

@@ -557,6 +557,26 @@ class GmOpEngine : public RaftOpEngine {
         PB_TRY(down(flowp, dfp, (size_t)n * 2 * 4));
         return down(map, dmap, (size_t)(n + guard) * 384 * 2);
     }
+
+    // the local matching alone, as infer launches it before a local propagation (no flow V^T)
+    int local_match(const float *tok, int NP, int dirs, int radius, int guard, float *flow) {
+        const int B = NP * dirs;
+        const int64_t n = (int64_t)B * g.P;
+        DevMem dT, dflow;
+        PB_TRY(up(dT, tok, (size_t)NP * 2 * g.P * 128 * 4));
+        PB_TRY(preset(dflow, (size_t)(n + guard) * 2 * 4));
+        PB_TRY(launch_gm_local_match(stream, dT.as<float>(), dflow.as<float>(), nullptr, B, g.h8, g.w8, dirs == 2 ? 1 : 2, radius, ldvP));
+        return finish(flow, dflow, (size_t)(n + guard) * 2 * 4);
+    }
+
+    int local_propagate(const float *q, const float *k, const float *flow_in, int B, int img_step, int radius, int guard, float *out) {
+        const int64_t n = (int64_t)B * g.P;
+        DevMem dq, dk, dfi, dO;
+        PB_TRY(up(dq, q, (size_t)n * img_step * 128 * 4)); PB_TRY(up(dk, k, (size_t)n * img_step * 128 * 4)); PB_TRY(up(dfi, flow_in, (size_t)n * 2 * 4));
+        PB_TRY(preset(dO, (size_t)(n + guard) * 32 * 4));
+        PB_TRY(launch_gm_local_prop(stream, dq.as<float>(), dk.as<float>(), dfi.as<float>(), dO.as<float>(), B, g.h8, g.w8, img_step, radius));
+        return finish(out, dO, (size_t)(n + guard) * 32 * 4);
+    }
 };
 
 // the "l.weight" [n, k] or [n, k, kh, kw] / "l.bias" [n] pair of one layer, as begin_load() takes it
@@ -1072,6 +1092,20 @@ int pb_op_gm_propagate(pb_ctx *c, const float *q, const float *k, const float *f
     GM_OP_ENGINE(e);
     PB_TRY(e.geom(h8, w8));
     return e.propagate(q, k, flow_in, X, NP, dirs, split, guard_rows, flow_match, flow_prop, map);
+}
+int pb_op_gm_local_match(pb_ctx *c, const float *tokens, int NP, int h8, int w8, int dirs, int radius, int guard_rows, float *flow) {
+    PB_CHECK(c && tokens && flow && NP > 0 && (dirs == 1 || dirs == 2) && guard_rows >= 0, PB_ERR_ARG, "op_gm_local_match: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.local_match(tokens, NP, dirs, radius, guard_rows, flow);
+}
+int pb_op_gm_local_propagate(pb_ctx *c, const float *q, const float *k, const float *flow_in, int B, int h8, int w8, int img_step, int radius,
+                             int guard_rows, float *flow_out) {
+    PB_CHECK(c && q && k && flow_in && flow_out && B > 0 && (img_step == 1 || img_step == 2) && guard_rows >= 0, PB_ERR_ARG,
+             "op_gm_local_propagate: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h8, w8));
+    return e.local_propagate(q, k, flow_in, B, img_step, radius, guard_rows, flow_out);
 }
 
 }  // extern "C"

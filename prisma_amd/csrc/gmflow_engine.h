@@ -1,5 +1,6 @@
 // flow_gmflow band engine: GMFlow at the band's defaults (bands/flow_gmflow.py:223-255: feature_channels 128, 1 scale,
-// 1 head, swin attention with 2 x 2 windows, global matching, global propagation, 6 transformer blocks, ffn x 4, padding_factor 16).
+// 1 head, swin attention with 2 x 2 windows, global matching, global propagation, 6 transformer blocks, ffn x 4, padding_factor 16), and
+// with set_matching the two inference-time radii of the same checkpoint (local matching, local-window propagation: gmflow_local.hip).
 // Shares RaftEngine's frame prep, instance-norm encoder, convex upsampling, flow encode and consistency-mask kernels.
 #pragma once
 #include "gmflow_kernels.h"
@@ -25,6 +26,11 @@ class GmflowEngine : public RaftEngine {
     // --inference_size of the band (reference flow_gmflow.py:76-100): the network runs on a bilinear (align_corners) resize of the scaled frame to
     // (h, w) - multiples of 16, no padding - and the flow is resized back and rescaled; (0, 0) = off (InputPadder(16), the default)
     int set_inference_size(int h, int w);
+    // --corr_radius_list / --prop_radius_list of the band (reference gmflow.py:128-157): -1 = global (the default), else local matching
+    // over (2 R + 1)^2 target tokens, 1 <= R <= 4, and local-window propagation, 1 <= r <= 2.  With local matching the backward direction
+    // is the forward direction of the swapped pair - what pred_bidir_flow equals wherever the reference can run it (with a matching
+    // radius its pred_bidir_flow raises: local_correlation_softmax returns B flows for 2 B features).
+    int set_matching(int corr_radius, int prop_radius);
 
   private:
     struct Layer {
@@ -44,6 +50,7 @@ class GmflowEngine : public RaftEngine {
     GmGeom g_{};
     int gF_ = 0, gH_ = 0, gW_ = 0, gD_ = 0;
     int isz_h_ = 0, isz_w_ = 0;
+    int corr_r_ = -1, prop_r_ = -1;
     float *gupi_ = nullptr;           // flow at the inference size, before the resize back
     float gS_ = 0.f;
     int ldvP_ = 0;

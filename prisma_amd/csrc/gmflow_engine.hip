@@ -218,6 +218,15 @@ int GmflowEngine::set_inference_size(int h, int w) {
     return 0;
 }
 
+int GmflowEngine::set_matching(int corr_radius, int prop_radius) {
+    PB_CHECK(corr_radius == -1 || (corr_radius >= 1 && corr_radius <= 4), PB_ERR_ARG,
+             "flow_gmflow: --corr_radius_list %d must be -1 (global matching) or 1 .. 4", corr_radius);
+    PB_CHECK(prop_radius == -1 || (prop_radius >= 1 && prop_radius <= 2), PB_ERR_ARG,
+             "flow_gmflow: --prop_radius_list %d must be -1 (global propagation) or 1 .. 2", prop_radius);
+    if (corr_radius != corr_r_ || prop_radius != prop_r_) { corr_r_ = corr_radius; prop_r_ = prop_radius; gF_ = 0; }      // re-plan on the next call
+    return 0;
+}
+
 int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, int /*iters*/, int backward, float *flow_out,
                         uint8_t *rgb_out, float *maxdisp, uint8_t *mask_out, float alpha1, float alpha2) {
     PB_CHECK(frames && F >= 2 && H > 0 && W > 0 && scale > 0.f, PB_ERR_ARG, "flow_gmflow infer: bad arguments");
@@ -311,40 +320,62 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     }
     fstages_["tfeat"] = FStage{X_, (int64_t)NP * 2, P, 128};
 
-    // ---- global matching (matching.py:7-42): softmax over ALL target tokens of the dot products, expectation of their coordinates ----
+    // ---- matching: global (matching.py:7-42: softmax over ALL target tokens of the dot products, expectation of their coordinates) or, with a
+    // radius, local (matching.py:39-83: over the (2R + 1)^2 target tokens around the source token; both directions = source and target swapped) ----
     const int64_t img = (int64_t)P * 256;                    // one frame's rows of a split token matrix
-    Attn128Args m;
-    m.Q = Xs_; m.O = Om_; m.B = B; m.L = P; m.ldv = ldvP_; m.split = split; m.vcols = 32; m.ldq = 256;
-    m.Vt = gridvt_; m.v_shared = 1;
-    if (dirs == 2) { m.K = Xs_; m.q_bstride = m.k_bstride = img; m.kxor = 1; }
-    else { m.K = Xs_ + img; m.q_bstride = m.k_bstride = 2 * img; }
-    if ((r = attention(m, P))) return r;
-    tic(F_ELT, 0, 0);
-    r = launch_gm_match_flow(stream, Om_, flowm_, Vtf_, B, P, w8_, ldvP_);
-    toc();
-    if (r) return r;
+    const int img_step = dirs == 2 ? 1 : 2;
+    if (corr_r_ < 0) {
+        Attn128Args m;
+        m.Q = Xs_; m.O = Om_; m.B = B; m.L = P; m.ldv = ldvP_; m.split = split; m.vcols = 32; m.ldq = 256;
+        m.Vt = gridvt_; m.v_shared = 1;
+        if (dirs == 2) { m.K = Xs_; m.q_bstride = m.k_bstride = img; m.kxor = 1; }
+        else { m.K = Xs_ + img; m.q_bstride = m.k_bstride = 2 * img; }
+        if ((r = attention(m, P))) return r;
+        tic(F_ELT, 0, 0);
+        r = launch_gm_match_flow(stream, Om_, flowm_, Vtf_, B, P, w8_, ldvP_);
+        toc();
+        if (r) return r;
+    } else {
+        const double nc = (2.0 * corr_r_ + 1) * (2.0 * corr_r_ + 1);
+        tic(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4);
+        r = launch_gm_local_match(stream, X_, flowm_, prop_r_ < 0 ? Vtf_ : nullptr, B, h8_, w8_, img_step, corr_r_, ldvP_);
+        if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_match_kernel";
+        toc();
+        if (r) return r;
+    }
     fstages_["flow_match"] = FStage{flowm_, B, P, 2};
 
-    // ---- flow propagation (transformer.py:316-337): self-similarity of the source frame's features spreads the matched flow ----
+    // ---- flow propagation (transformer.py:316-337 global, :376-409 local window): self-similarity of the source frame's features spreads the
+    // matched flow ----
     if ((r = gemm32(Xs_, 256, R, ffq_, Yq_, 128))) return r;
-    tic(F_ELT, 0, 0);
-    r = launch_gm_split_rows(stream, Yq_, 128, 128, qs_, R);
-    toc();
-    if (r) return r;
-    if ((r = gemm32(qs_, 256, R, ffk_, M_, 128))) return r;         // the key is k_proj of the PROJECTED query, as in the reference (:326-327)
-    tic(F_ELT, 0, 0);
-    r = launch_gm_split_rows(stream, M_, 128, 128, ks_, R);
-    toc();
-    if (r) return r;
-    Attn128Args pa;
-    pa.Q = qs_; pa.K = ks_; pa.O = Om_; pa.B = B; pa.L = P; pa.ldv = ldvP_; pa.split = split; pa.vcols = 32; pa.ldq = 256;
-    pa.Vt = Vtf_; pa.v_bstride = (int64_t)64 * ldvP_;
-    pa.q_bstride = pa.k_bstride = dirs == 2 ? img : 2 * img;
-    if ((r = attention(pa, P))) return r;
+    if (prop_r_ < 0) {
+        tic(F_ELT, 0, 0);
+        r = launch_gm_split_rows(stream, Yq_, 128, 128, qs_, R);
+        toc();
+        if (r) return r;
+        if ((r = gemm32(qs_, 256, R, ffk_, M_, 128))) return r;         // the key is k_proj of the PROJECTED query, as in the reference (:363-364)
+        tic(F_ELT, 0, 0);
+        r = launch_gm_split_rows(stream, M_, 128, 128, ks_, R);
+        toc();
+        if (r) return r;
+        Attn128Args pa;
+        pa.Q = qs_; pa.K = ks_; pa.O = Om_; pa.B = B; pa.L = P; pa.ldv = ldvP_; pa.split = split; pa.vcols = 32; pa.ldq = 256;
+        pa.Vt = Vtf_; pa.v_bstride = (int64_t)64 * ldvP_;
+        pa.q_bstride = pa.k_bstride = dirs == 2 ? img : 2 * img;
+        if ((r = attention(pa, P))) return r;
+    } else {
+        if ((r = gemm32(Xs_, 256, R, ffk_, M_, 128))) return r;         // the local form projects the key from the feature itself (:389), not from the query
+        const double nc = (2.0 * prop_r_ + 1) * (2.0 * prop_r_ + 1);
+        tic(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4);
+        r = launch_gm_local_prop(stream, Yq_, M_, flowm_, Om_, B, h8_, w8_, img_step, prop_r_);
+        if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_prop_kernel";
+        toc();
+        if (r) return r;
+    }
 
     // ---- convex upsampling (gmflow.py:74-92), unpad, encode ----
     tic(F_ELT, 0, 0);
-    r = launch_gm_upsampler_in(stream, Om_, X_, flowp_, umap_, B, P, dirs == 2 ? 1 : 2);
+    r = launch_gm_upsampler_in(stream, Om_, X_, flowp_, umap_, B, P, img_step);
     toc();
     if (r) return r;
     fstages_["flow_prop"] = FStage{flowp_, B, P, 2};

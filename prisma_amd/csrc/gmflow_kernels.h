@@ -25,3 +25,10 @@ int launch_gm_ln(hipStream_t s, const float *M, const float *gamma, const float 
 int launch_gm_grid_vt(hipStream_t s, f16 *vt, int P, int w8, int ldv);
 int launch_gm_match_flow(hipStream_t s, const float *O, float *flow, f16 *vt, int B, int P, int w8, int ldv);
 int launch_gm_upsampler_in(hipStream_t s, const float *O, const float *X, float *flow, f16 *map, int B, int P, int img_step);
+
+// gmflow_local.hip: the local forms of matching and propagation over fp32 token maps [images, P, 128]; batch element b reads image b * img_step.
+// Matching (radius 1 .. 4): the target is the other image of the pair (index ^ 1); flow [B, P, 2], and with vt != nullptr the global
+// propagation's V^T as launch_gm_match_flow writes it.  Propagation (radius 1 .. 2): writes columns 0, 1 of O [B, P, 32] (launch_gm_upsampler_in's input).
+int launch_gm_local_match(hipStream_t s, const float *X, float *flow, f16 *vt, int B, int h8, int w8, int img_step, int radius, int ldv);
+int launch_gm_local_prop(hipStream_t s, const float *q, const float *k, const float *flow_in, float *O, int B, int h8, int w8, int img_step,
+                         int radius);

@@ -571,6 +571,24 @@ class Ops(_Ctx):
                                           _ptr(mp)))
         return fm, fp, mp
 
+    def gm_local_match(self, tokens, h8: int, w8: int, dirs: int, radius: int, guard_rows: int = 8) -> np.ndarray:
+        """tokens [2 NP, P, 128] -> raw flow [NP dirs P + guard, 2] of the local matching over (2 radius + 1)^2 target tokens"""
+        tokens = _f32(tokens)
+        NP = tokens.shape[0] // 2
+        assert tokens.shape == (2 * NP, h8 * w8, 128)
+        flow = np.empty((NP * dirs * h8 * w8 + guard_rows, 2), np.float32)
+        check(self.lib.pb_op_gm_local_match(self.ctx, _ptr(tokens), NP, h8, w8, dirs, radius, guard_rows, _ptr(flow)))
+        return flow
+
+    def gm_local_propagate(self, q, k, flow_in, h8: int, w8: int, img_step: int, radius: int, guard_rows: int = 8) -> np.ndarray:
+        """q, k [B img_step, P, 128], flow_in [B, P, 2] -> raw [B P + guard, 32]: the local-window propagation owns columns 0, 1"""
+        q, k, flow_in = _f32(q), _f32(k), _f32(flow_in)
+        B, P = flow_in.shape[0], h8 * w8
+        assert q.shape == (B * img_step, P, 128) and k.shape == q.shape and flow_in.shape == (B, P, 2)
+        out = np.empty((B * P + guard_rows, 32), np.float32)
+        check(self.lib.pb_op_gm_local_propagate(self.ctx, _ptr(q), _ptr(k), _ptr(flow_in), B, h8, w8, img_step, radius, guard_rows, _ptr(out)))
+        return out
+
     def bilinear(self, x, OH: int, OW: int, align_corners: bool) -> np.ndarray:
         x = _f32(x)
         B, Cc, H, W = x.shape
@@ -805,6 +823,12 @@ class FlowGMFlow(FlowRaft):
         scaled frame to (H, W), multiples of 16, and resize the flow back; None / (0, 0) = off (pad to /16, the default)."""
         h, w = (0, 0) if not size else (int(size[0]), int(size[1]))
         check(self.lib.pb_flow_set_inference_size(self.ctx, h, w))
+
+    def set_matching(self, corr_radius: int = -1, prop_radius: int = -1):
+        """--corr_radius_list R / --prop_radius_list r of the band (reference gmflow.py:128-157): -1 = global (the default); R in 1 .. 4 =
+        local matching over (2 R + 1)^2 target tokens; r in 1 .. 2 = local-window propagation.  With a matching radius the backward flow is
+        the forward flow of the swapped pair (the reference's pred_bidir_flow raises there)."""
+        check(self.lib.pb_flow_set_matching(self.ctx, int(corr_radius), int(prop_radius)))
 
 
 def _mask_cfg(cfg: MaskCfg, max_batch: int, precision: int = 0) -> "_lib.pb_mask_cfg":
