@@ -52,14 +52,16 @@ def init_model(args=None, device=0):
         # BasicUpdateBlock (hidden 128, corr radius 4, 5.26 M parameters) whatever the flag says, and loads args.model into it.  Drop-in
         # behaviour is therefore: accept the flag, run the basic model (round 4 refused it as "another network"; it never was one here)
         print(f"[{BAND}] --small: the reference builds the basic RAFT regardless (bands/raft/raft.py:28-53, the small branches are commented out); flag ignored", file=sys.stderr)
-    if args is not None and getattr(args, "alternate_corr", False):
-        # reference raft.py:103-106: AlternateCorrBlock computes the same correlations on the fly (memory saving, needs the alt_cuda_corr
-        # extension); results are those of CorrBlock, and the volume is no memory problem in 288 GB - run the normal path
-        print(f"[{BAND}] --alternate_corr: same result as the default correlation block (reference raft.py:103-106); flag ignored", file=sys.stderr)
     if args is not None and getattr(args, "mixed_precision", False):
         print(f"[{BAND}] --mixed_precision: the engine's precision is set by PRISMA_PRECISION (split-fp16 by default); flag ignored", file=sys.stderr)
     _SYNTH[0] = bool(getattr(args, "synthetic", False))
     model = engine.FlowRaft(load_weights(getattr(args, "model", MODEL) if args else MODEL), device=device)
+    if args is not None and getattr(args, "alternate_corr", False):
+        # reference raft.py:103-106, corr.py:63-91 (AlternateCorrBlock): the correlations of every lookup window are computed from the feature
+        # maps when they are needed, and the all-pairs volume - 4 P^2 / 3 fp16 entries per pair and direction, 45 GB for a 2160p frame - is
+        # never built.  Same flows within the band's tolerance (a window entry is not rounded to fp16 on the way)
+        model.set_alternate_corr(True)
+        print(f"[{BAND}] --alternate_corr: correlation windows computed on the fly, no all-pairs volume in memory", file=sys.stderr)
     return model
 
 

@@ -274,6 +274,16 @@ int pb_flow_set_inference_size(pb_ctx *ctx, int h, int w);
  * features), and the band defines it as the forward direction of the swapped pair - what pred_bidir_flow equals wherever the reference
  * can run it.  Other values are an error and leave the context as it was.  flow_gmflow contexts only. */
 int pb_flow_set_matching(pb_ctx *ctx, int corr_radius, int prop_radius);
+/* flow_raft --alternate_corr (reference bands/raft/raft.py:103-106 selects AlternateCorrBlock, bands/raft/corr.py:63-91, same checkpoint):
+ * on != 0 - the 9 x 9 x 4 lookup of every GRU iteration computes its window entries from the feature maps (fp16 operands, fp32
+ * accumulation, no fp16 rounding of an entry) instead of reading them from the all-pairs correlation volume, which is then neither
+ * allocated nor computed: the arena loses pairs * dirs * P * sum_l ld_l * 2 bytes (P = 1/8-grid pixels).  0 (the default): nothing of the
+ * default path changes.  Takes effect with the next call, which re-plans the arena.  flow_raft contexts only: on a flow_gmflow (or any
+ * other) context it returns PB_ERR_ARG and leaves the context as it was. */
+int pb_flow_set_alternate_corr(pb_ctx *ctx, int on);
+/* Bytes of the arena the context's current plan committed (the last call's frame size, pair count and mode); 0 before the first call.
+ * Flow contexts only. */
+int64_t pb_flow_arena_bytes(pb_ctx *ctx);
 
 /* mask_mmdet band (band = "mask_mmdet", cfg = pb_mask_cfg; weights: backbone.*, neck.*, mask_head.* in mmdet's
  * state_dict naming).  Replaces the per-frame body of bands/mask_mmdet.py:131-154: inference_detector
@@ -411,6 +421,9 @@ int pb_op_dense_split(pb_ctx *ctx, const float *A, const float *w, const float *
 int pb_op_raft_geometry(int h8, int w8, int *geo);
 int pb_op_raft_lookup(pb_ctx *ctx, const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows,
                       void *out, float *levels);
+/* lookup_otf (--alternate_corr): the inputs, output convention and refusals of pb_op_raft_lookup; avg-pool x3, then corr_lookup_otf_kernel. */
+int pb_op_raft_lookup_otf(pb_ctx *ctx, const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8,
+                          int guard_rows, void *out);
 int pb_op_raft_convf1(pb_ctx *ctx, const float *flow, const float *w, const float *bias, int n, int h8, int w8, int passes, int o8,
                       int gemm_path, int guard_rows, void *out);
 int pb_op_raft_flow_head2(pb_ctx *ctx, const float *x, const float *w, const float *bias, float *flow, int n, int H, int W, int split,

@@ -88,6 +88,8 @@ SYMBOLS = {
     "pb_mask_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "pb_flow_set_inference_size": (C.c_int, [_P, C.c_int, C.c_int]),
     "pb_flow_set_matching": (C.c_int, [_P, C.c_int, C.c_int]),
+    "pb_flow_set_alternate_corr": (C.c_int, [_P, C.c_int]),
+    "pb_flow_arena_bytes": (C.c_int64, [_P]),
     "pb_mask_set_sdf": (C.c_int, [_P, _P, _P, C.c_int]),
     "pb_mask_sdf_green": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
     "pb_mask_sdf_green_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int]),
@@ -120,6 +122,7 @@ SYMBOLS = {
     "pb_op_dense_split": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P, _P, _P, C.c_int]),
     "pb_op_raft_geometry": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pb_op_raft_lookup": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P, _P]),
+    "pb_op_raft_lookup_otf": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P]),
     "pb_op_raft_convf1": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 7 + [_P]),
     "pb_op_raft_flow_head2": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 5),
     "pb_op_raft_upsample": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),

@@ -458,6 +458,9 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     static const int env_cp = pb_env_int("PB_FLOW_HOST_PAIRS", 32);
     int cp = c->host_chunk > 0 ? c->host_chunk : (env_cp > 0 ? env_cp : 32);
     if (pairs <= cp + cp / 4) cp = pairs;                       // a short tail is not worth a chunk of its own
+    // ... and no chunk larger than one infer() call accepts at this size (flow_chunk.h: 4K frames); a single pair that does not fit goes
+    // through as it is and the engine refuses it
+    cp = std::max(1, c->raft->chunk_pairs(cp, H, W, scale, dirs));
     const size_t fpx = (size_t)H * W * 3, px = (size_t)sh * sw * dirs, np = (size_t)pairs;      // px: result pixels of a pair, all directions
     const bool pin_in = pb_is_pinned(frames, (size_t)F * fpx), pin_f = pb_is_pinned(flow_out, np * px * 8), pin_r = pb_is_pinned(rgb_out, np * px * 3),
                pin_k = pb_is_pinned(mask_out, np * px), pin_m = !maxdisp_out || pb_is_pinned(maxdisp_out, np * dirs * 4);
@@ -636,6 +639,18 @@ int pb_flow_set_matching(pb_ctx *c, int corr_radius, int prop_radius) {
     GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->raft);
     PB_CHECK(g, PB_ERR_STATE, "--corr_radius_list / --prop_radius_list are flow_gmflow options");
     return g->set_matching(corr_radius, prop_radius);
+}
+
+int pb_flow_set_alternate_corr(pb_ctx *c, int on) {
+    PB_CHECK(c && c->raft, PB_ERR_ARG, "ctx has no flow band");
+    PB_CHECK(!dynamic_cast<GmflowEngine *>(c->raft), PB_ERR_ARG, "--alternate_corr is a flow_raft option");
+    c->raft->set_alternate_corr(on);
+    return 0;
+}
+
+int64_t pb_flow_arena_bytes(pb_ctx *c) {
+    PB_CHECK(c && c->raft, PB_ERR_ARG, "ctx has no flow band");
+    return c->raft->plan_bytes();
 }
 
 int64_t pb_flow_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {

@@ -212,6 +212,30 @@ class RaftOpEngine : public SplitOpEngine {
         return 0;
     }
 
+    // --alternate_corr: RaftEngine::infer's sequence with alt_corr_ - three pooling passes, then the lookup straight from the feature maps
+    int lookup_otf(const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows, void *out) {
+        PB_CHECK(h8 >= 16 && w8 >= 16, PB_ERR_ARG, "op_raft_lookup_otf: a %d x %d grid is too small (the 4-level pyramid needs >= 16 x 16)", h8, w8);
+        CorrGeo g;
+        corr_pyramid_geometry(h8, w8, g);
+        const int P = h8 * w8;
+        const int64_t rows = (int64_t)n * P;
+        const size_t slack = 1 << 20;
+        const int ldo = o8 ? 576 : 384;
+        DevMem f1, f2, dflow, dout, fpool[4];
+        PB_TRY(to_f16(f1, fmap1, rows, 256, (size_t)round_up(rows, 256) * 256 * 2 + slack));
+        PB_TRY(to_f16(f2, fmap2, rows, 256, (size_t)round_up(rows, 256) * 256 * 2 + slack));
+        PB_TRY(up(dflow, flow, (size_t)rows * 8));
+        PB_TRY(preset(dout, (size_t)(rows + guard_rows) * ldo * 2));
+        for (int l = 1; l < 4; ++l) {
+            PB_TRY(fpool[l].alloc((size_t)round_up((int64_t)n * g.h[l] * g.w[l], 256) * 256 * 2 + slack));
+            PB_TRY(launch_avgpool2_nhwc(stream, l == 1 ? f2.as<f16>() : fpool[l - 1].as<f16>(), fpool[l].as<f16>(), n, g.h[l - 1], g.w[l - 1], 256));
+        }
+        const f16 *const tg[4] = {f2.as<f16>(), fpool[1].as<f16>(), fpool[2].as<f16>(), fpool[3].as<f16>()};
+        PB_TRY(launch_corr_lookup_otf(stream, f1.as<f16>(), tg, g.h, g.w, dflow.as<float>(), P, w8, dout.as<f16>(), rows, ldo, o8 ? 768 : 0,
+                                      (float)(1 << kMx2Pa), 0));
+        return finish(out, dout, (size_t)(rows + guard_rows) * ldo * 2);
+    }
+
     int convf1(const float *flow, const float *wt, const float *bias, int n, int h8, int w8, int passes, int o8, int gemm, int guard_rows, void *out) {
         const int P = h8 * w8, ldo = o8 ? 192 : 128;
         const int64_t rows = (int64_t)n * P, rows_buf = round_up(rows + guard_rows, 256);
@@ -967,6 +991,11 @@ int pb_op_raft_lookup(pb_ctx *c, const float *fmap1, const float *fmap2, const f
     PB_CHECK(c && fmap1 && fmap2 && flow && out && n > 0 && guard_rows >= 0, PB_ERR_ARG, "op_raft_lookup: bad arguments");
     RAFT_OP_ENGINE(e);
     return e.lookup(fmap1, fmap2, flow, n, h8, w8, o8, guard_rows, out, levels);
+}
+int pb_op_raft_lookup_otf(pb_ctx *c, const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows, void *out) {
+    PB_CHECK(c && fmap1 && fmap2 && flow && out && n > 0 && guard_rows >= 0, PB_ERR_ARG, "op_raft_lookup_otf: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.lookup_otf(fmap1, fmap2, flow, n, h8, w8, o8, guard_rows, out);
 }
 int pb_op_raft_convf1(pb_ctx *c, const float *flow, const float *w, const float *bias, int n, int h8, int w8, int passes, int o8, int gemm_path,
                       int guard_rows, void *out) {

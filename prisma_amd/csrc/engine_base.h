@@ -80,6 +80,7 @@ class EngineBase {
     f16 *zero_ = nullptr;
     char *arena_ = nullptr;
     size_t arena_bytes_ = 0, arena_off_ = 0;
+    size_t plan_bytes_ = 0;                     // what the last commit_arena's plan carved (arena_bytes_ never shrinks)
     bool planning_ = false;
     hipStream_t cur_ = nullptr;
     std::vector<size_t> open_;                  // tic / toc nesting across streams

@@ -269,6 +269,7 @@ void *EngineBase::carve(size_t bytes) {
 }
 
 int EngineBase::commit_arena(const char *what) {
+    plan_bytes_ = arena_off_;
     if (arena_off_ > arena_bytes_) {
         if (arena_) PB_HIP(hipFree(arena_));
         arena_ = nullptr; arena_bytes_ = 0;

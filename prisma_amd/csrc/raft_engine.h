@@ -19,6 +19,12 @@ class RaftEngine : public EngineBase {
                       float alpha2 = 0.5f);
     virtual int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]);
     static void out_size(int H, int W, float scale, int *sh, int *sw);
+    // --alternate_corr (raft.py:103-106): the lookup computes its window entries from the feature maps (corr_otf.hip) and prepare() carves no
+    // correlation volume.  Part of the plan key: the next call re-plans.
+    void set_alternate_corr(int on) { alt_corr_ = on ? 1 : 0; }
+    int64_t plan_bytes() const { return (int64_t)plan_bytes_; }
+    // largest chunk of pairs <= wanted that one infer() call accepts at this frame size (flow_chunk.h); 0: not even one pair
+    virtual int chunk_pairs(int wanted, int H, int W, float scale, int dirs) const;
 
   protected:            // shared with GmflowEngine (gmflow_engine.h): GMFlow's CNNEncoder is this encoder without conv biases
     struct Enc {                    // BasicEncoder weights (BN folded for cnet)
@@ -42,7 +48,8 @@ class RaftEngine : public EngineBase {
     f16 *gz_[2] = {}, *gq_[2] = {};             // hoisted shares: [hi plane | lo plane], rows x 256 (z | r) and rows x Lhx (q)
 
     // plan
-    int pF_ = 0, pH_ = 0, pW_ = 0, pD_ = 0;
+    int pF_ = 0, pH_ = 0, pW_ = 0, pD_ = 0, pA_ = 0;
+    int alt_corr_ = 0;
     float pS_ = 0.f;
     int sh_ = 0, sw_ = 0, Hp_ = 0, Wp_ = 0, padl_ = 0, padt_ = 0, h8_ = 0, w8_ = 0, P_ = 0, P8_ = 0;
     int lh_[4] = {0, 0, 0, 0}, lw_[4] = {0, 0, 0, 0};

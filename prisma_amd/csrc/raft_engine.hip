@@ -11,6 +11,7 @@
 //   * cnet's eval-mode BatchNorm is folded into its convolutions at pack time; fnet's InstanceNorm uses
 //     run-time statistics and stays a separate pass.
 #include "raft_engine.h"
+#include "flow_chunk.h"
 
 #include <math.h>
 #include <string.h>
@@ -42,6 +43,14 @@ void cubic_taps_u8(int src, int dst, double scale, std::vector<int> &idx, std::v
     }
 }
 }  // namespace
+
+int RaftEngine::chunk_pairs(int wanted, int H, int W, float scale, int dirs) const {
+    if (!hoist_) return wanted;
+    int sh, sw;
+    out_size(H, W, scale, &sh, &sw);
+    const int64_t P = (int64_t)((sh + 7) / 8) * ((sw + 7) / 8);       // geometry(): the scaled frame padded to multiples of 8
+    return flow_chunk_pairs(wanted, dirs, P, upd8_ ? 576 : 384);
+}
 
 void RaftEngine::out_size(int H, int W, float scale, int *sh, int *sw) {
     *sh = (int)nearbyint((double)H * scale);
@@ -234,7 +243,7 @@ int RaftEngine::load(const pb_tensor *w, int n) {
 }
 
 int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
-    if (F <= pF_ && H == pH_ && W == pW_ && scale == pS_ && dirs <= pD_) return 0;
+    if (F <= pF_ && H == pH_ && W == pW_ && scale == pS_ && dirs <= pD_ && alt_corr_ == pA_) return 0;
     PB_HIP(hipStreamSynchronize(stream));
     // from here on the plan's members are being rewritten: a failure below (a frame too small, an allocation) must not leave the OLD plan's key
     // behind, or the next call with the old size would skip this function and run on the half-written geometry (round 6: found by
@@ -257,10 +266,11 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
         fmap_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2 + slack);
         ctx_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2);
         for (int l = 0; l < 4; ++l) {
-            // level l of the volume: fp16, one row per source pixel of pld_[l] entries (raft_kernels.hip corr_pyramid_geometry)
-            pyr_[l] = (f16 *)carve((size_t)ND * P_ * pld_[l] * 2 + slack);
+            // level l of the volume: fp16, one row per source pixel of pld_[l] entries (raft_kernels.hip corr_pyramid_geometry).  alt_corr_:
+            // no volume and no tiled B operand - corr_otf.hip reads fmap_ and the pooled maps
+            pyr_[l] = alt_corr_ ? nullptr : (f16 *)carve((size_t)ND * P_ * pld_[l] * 2 + slack);
             fpool_[l] = l == 0 ? nullptr : (f16 *)carve((size_t)round_up((int64_t)F * lh_[l] * lw_[l], 256) * 256 * 2 + slack);
-            ftile_[l] = (f16 *)carve((size_t)(F * (int64_t)pld_[l] + 256) * 256 * 2 + slack);
+            ftile_[l] = alt_corr_ ? nullptr : (f16 *)carve((size_t)(F * (int64_t)pld_[l] + 256) * 256 * 2 + slack);
         }
         const int64_t rows = round_up(ND * P_, 256);
         h32_ = (float *)carve((size_t)rows * 128 * 4); flow_ = (float *)carve((size_t)rows * 2 * 4);
@@ -286,7 +296,7 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
     }
     int rt = upload_resize_tables(H, W, scale);
     if (rt) return rt;
-    pF_ = F; pH_ = H; pW_ = W; pS_ = scale; pD_ = dirs;
+    pF_ = F; pH_ = H; pW_ = W; pS_ = scale; pD_ = dirs; pA_ = alt_corr_;
     return 0;
 }
 
@@ -460,14 +470,14 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
     for (int l = 0; l < 4; ++l) {
         tic(F_ELT, 0, 0);
         if (l > 0) r = launch_avgpool2_nhwc(stream, l == 1 ? fmap_ : fpool_[l - 1], fpool_[l], F, lh_[l - 1], lw_[l - 1], 256);
-        if (!r) r = launch_corr_tile(stream, l == 0 ? fmap_ : fpool_[l], ftile_[l], F, lh_[l], lw_[l], lwp_[l], pld_[l]);
+        if (!r && !alt_corr_) r = launch_corr_tile(stream, l == 0 ? fmap_ : fpool_[l], ftile_[l], F, lh_[l], lw_[l], lwp_[l], pld_[l]);
         toc();
         if (r) return r;
     }
     for (int i = 0; i < F - 1; ++i)
         for (int d = 0; d < dirs; ++d) {
             const int n = i * dirs + d;
-            for (int l = 0; l < 4; ++l) {
+            for (int l = 0; l < 4 && !alt_corr_; ++l) {
                 GemmArgs a;
                 a.A = fmap_ + (int64_t)(i + d) * P_ * 256; a.lda = 256; a.M = P_;
                 a.W = ftile_[l] + (int64_t)(i + 1 - d) * pld_[l] * 256;
@@ -513,8 +523,15 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
 
     // ---- GRU iterations (raft.py:124-144, update.py:122-136) ----
     for (int it = 0; it < iters; ++it) {
-        tic(F_ELT, 0, 0);
-        r = launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, lhp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8);
+        if (alt_corr_) {       // --alternate_corr (corr.py:63-91): the window entries are computed from fmap_ and the pooled maps, 100 per row and level
+            const f16 *const tg[4] = {fmap_, fpool_[1], fpool_[2], fpool_[3]};
+            tic(F_GEMM, 2.0 * rows * 4.0 * 100.0 * 256.0, 0);
+            r = launch_corr_lookup_otf(stream, fmap_, tg, lh_, lw_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8, dirs);
+            if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = "corr_lookup_otf_kernel";
+        } else {
+            tic(F_ELT, 0, 0);
+            r = launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, lhp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8);
+        }
         toc();
         if (r) return r;
         if (debug && it == 0 && (r = snapshot("corr0", corr_, (size_t)ND * P_ * Lhx * 2, Stage{nullptr, 1, ND, 324, h8_, w8_, Lhx, 0}))) return r;

@@ -27,6 +27,11 @@ void corr_pyramid_geometry(int h8, int w8, CorrGeo &g);
 // hp: padded target rows of every level (CorrGeo::hp) - NOT ld / wp: the stride may carry more than a tile row of rounding
 int launch_corr_lookup(hipStream_t s, const f16 *const lv[4], const int h[4], const int w[4], const int wp[4], const int hp[4], const int ld[4],
                        const float *flow, int P, int w8, f16 *out, int64_t rows, int ldo = 384, int o8_off = 0, float o8_scale = 16.f);
+// corr_otf.hip (--alternate_corr): the same rows as launch_corr_lookup, computed from the feature maps without a volume.  fmap_tgt[0] is the
+// feature map itself, [1..3] its avg-pooled levels; h / w the level sizes (CorrGeo).  dirs 1 / 2: pair-direction n = i * dirs + d reads source
+// frame i + d and target frame i + 1 - d of the maps (RaftEngine::infer's order); dirs 0: row block n reads frame n of both maps
+int launch_corr_lookup_otf(hipStream_t s, const f16 *fmap_src, const f16 *const fmap_tgt[4], const int h[4], const int w[4], const float *flow, int P,
+                           int w8, f16 *out, int64_t rows, int ldo = 384, int o8_off = 0, float o8_scale = 16.f, int dirs = 0);
 // convf1 (7 x 7, 2 -> 128, ReLU) straight from the fp32 flow field (raft_kernels.hip convf1_kernel)
 int convf1_packed_halfs(int passes);
 void convf1_pack(const float *w, int passes, f16 *dst);

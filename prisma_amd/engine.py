@@ -399,6 +399,17 @@ class Ops(_Ctx):
                 o += k
         return out, levels
 
+    def raft_lookup_otf(self, fmap1, fmap2, flow, o8: bool = False, guard_rows: int = 8) -> np.ndarray:
+        """--alternate_corr: pooling and the 9 x 9 x 4 lookup straight from the feature maps (corr_otf.hip) as RaftEngine::infer launches them
+        with set_alternate_corr(True).  Arguments and raw rows as raft_lookup; there is no volume, so no levels."""
+        fmap1, fmap2, flow = _f32(fmap1), _f32(fmap2), _f32(flow)
+        n, h8, w8, _ = fmap2.shape
+        rows = n * h8 * w8
+        assert fmap1.shape == (n, h8 * w8, 256) and fmap2.shape[3] == 256 and flow.shape == (rows, 2)
+        out = np.empty((rows + guard_rows, (576 if o8 else 384) * 2), np.uint8)
+        check(self.lib.pb_op_raft_lookup_otf(self.ctx, _ptr(fmap1), _ptr(fmap2), _ptr(flow), n, h8, w8, int(o8), guard_rows, _ptr(out)))
+        return out
+
     def raft_convf1(self, flow, w, bias, passes: int = 2, o8: bool = True, gemm_path: bool = False, guard_rows: int = 8) -> np.ndarray:
         """flow [n, h8, w8, 2], w [128, 2, 7, 7] -> raw rows uint8 [n h8 w8 + guard_rows, ldo * 2] (ldo 192 with the e4m3 copy at byte 256, else 128)"""
         flow, w, bias = _f32(flow), _f32(w), _f32(bias)
@@ -799,6 +810,15 @@ class FlowRaft(_Ctx):
         v = lambda p: C.c_void_p(p) if p else None
         check(self.lib.pb_flow_infer_sequence_dev(self.ctx, v(frames_ptr), F, H, W, C.c_float(scale), iters, int(backward),
                                                   v(flow_ptr), v(rgb_ptr), v(max_ptr)))
+
+    def set_alternate_corr(self, on: bool = True):
+        """--alternate_corr of the band (reference raft.py:103-106, corr.py:63-91): every lookup computes its window entries from the feature
+        maps and no all-pairs correlation volume is allocated or computed.  Takes effect with the next call.  flow_raft only."""
+        check(self.lib.pb_flow_set_alternate_corr(self.ctx, int(bool(on))))
+
+    def arena_bytes(self) -> int:
+        """bytes of the arena the current plan (the last call's size, pair count and mode) committed; 0 before the first call"""
+        return int(check(self.lib.pb_flow_arena_bytes(self.ctx)))
 
     def stage(self, name: str, cap: int = 1 << 26) -> np.ndarray:
         out = np.empty(cap, np.float32)
