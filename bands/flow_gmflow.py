@@ -2,7 +2,7 @@
 """flow_gmflow band - drop-in for /root/reference/bands/flow_gmflow.py on MI355X (prisma's DEFAULT flow band, process.py:23).
 
 Same CLI (reference :223-255; the GMFlow architecture flags are accepted and must equal the band's defaults, which is the model the
-engine builds; the two inference-time radii are honoured: --corr_radius_list R, 1 .. 4, selects local matching over (2 R + 1)^2 target
+engine builds, or the one flag set of GMFlow's refinement model, REFINE below; the two inference-time radii are honoured: --corr_radius_list R, 1 .. 4, selects local matching over (2 R + 1)^2 target
 tokens and --prop_radius_list r, 1 .. 2, local-window flow propagation, -1 = global, reference bands/gmflow/gmflow.py:128-157), same outputs
 (<BAND>.mp4, <BAND>.csv with the per-frame max displacement, optional <BAND>_bwd / _mask / _mask_bwd
 videos, .flo / 16-bit PNG dumps, metadata entries :195-218), same module API (BAND, init_model(), infer()).  The frame loop, the file
@@ -12,7 +12,12 @@ flow_gmflow.py:121-218 vs flow_raft.py:69-166); the model is libprisma_bands.so'
 --backwards / --mask with a matching radius: the reference raises there (pred_bidir_flow: local_correlation_softmax returns B flows while
 the features were concatenated to 2 B, gmflow.py:142,153-157).  This band computes the backward direction as the forward direction of the
 swapped pair, which is what pred_bidir_flow equals wherever the reference can run it (global matching, either propagation).
---num_scales 2 and --attn_splits_list other than 2 stay refused.
+
+--num_scales 2 is GMFlow's two-scale refinement model (gmflow_with_refine_*), with exactly the reference's flag set for it:
+  --num_scales 2 --upsample_factor 4 --padding_factor 32 --attn_splits_list 2 8 --corr_radius_list -1 R --prop_radius_list -1 r
+(R in 1 .. 4, r in 1 .. 2: the fine scale's radii; the coarse scale is global) and a checkpoint - or --synthetic weights - that is two-scale.
+The engine reads the architecture from the weights; a mismatch between the flags and the checkpoint is refused before anything runs.
+--num_scales 2 on its own, other split counts and other flag mixes stay refused.
 """
 import argparse
 import os
@@ -39,11 +44,15 @@ ARCH = {"feature_channels": 128, "num_scales": 1, "upsample_factor": 8, "num_hea
         "num_transformer_layers": 6, "attn_splits_list": [2], "corr_radius_list": [-1], "prop_radius_list": [-1], "padding_factor": 16}
 
 RADII = {"corr_radius_list": 4, "prop_radius_list": 2}
+# the refinement model's flag set (reference :46-53, 84-89 with gmflow_with_refine_*): the second entry of the two radius lists is the fine
+# scale's radius, 1 .. RADII
+REFINE = {"num_scales": 2, "upsample_factor": 4, "padding_factor": 32, "attn_splits_list": [2, 8]}
 
 model = None
 data = None
 ranks = None
 _SYNTH = [False]
+_SCALES = [1]               # what the flags ask for: the synthetic weights are made to match
 
 
 def load_weights(path):
@@ -53,16 +62,41 @@ def load_weights(path):
     if not shard.synthetic_allowed(_SYNTH[0]):
         raise SystemExit(f"[{BAND}] checkpoint {path!r} not found; pass --model, or --synthetic / PRISMA_SYNTH=1 for seeded synthetic weights")
     print(f"[{BAND}] checkpoint {path!r} not found; using seeded synthetic weights (--synthetic)", file=sys.stderr)
-    return synth.gmflow_weights(seed=2468)
+    return synth.gmflow_weights(seed=2468, num_scales=_SCALES[0])
 
 
 def radius(args, key):
-    """the one radius of a --corr_radius_list / --prop_radius_list (-1 = global)"""
+    """the one radius of a --corr_radius_list / --prop_radius_list (-1 = global); with two scales the fine scale's (the list's second entry)"""
     v = getattr(args, key, None) if args is not None else None
-    return int(v[0]) if v else -1
+    return int(v[-1]) if v else -1
+
+
+def two_scale(args):
+    """the flags are the refinement model's set (REFINE and two radius lists [-1, radius])"""
+    if args is None or any(getattr(args, k, None) != v for k, v in REFINE.items()):
+        return False
+    return all((lambda v: v is not None and len(v) == 2 and v[0] == -1 and 1 <= v[1] <= top)(getattr(args, k, None)) for k, top in RADII.items())
+
+
+def weights_scales(w):
+    """1 or 2: what the engine will read from these weights (upsampler.2 of 4 * 4 * 9 rows and the backbone's trident convolution)"""
+    return 2 if "backbone.trident_conv.weight" in w and np.asarray(w["upsampler.2.weight"]).shape[0] == 144 else 1
 
 
 def check_arch(args):
+    isz = getattr(args, "inference_size", None)
+    if two_scale(args):
+        bad = {k: getattr(args, k) for k, v in ARCH.items() if hasattr(args, k) and getattr(args, k) != v and k not in RADII and k not in REFINE}
+        if bad:                                          # the refinement model shares every other architecture flag with the default one
+            raise SystemExit(f"[{BAND}] only the band's default GMFlow is built ({ARCH}), or its refinement flag set ({REFINE}); got {bad}")
+        if isz and (len(isz) != 2 or any(v < 64 or v % 32 for v in isz)):
+            raise SystemExit(f"[{BAND}] --inference_size takes H W, multiples of 32 with --num_scales 2 (4 x the fine scale's 8 x 8 window split); got {isz}")
+        return
+    if getattr(args, "num_scales", 1) == 2:              # the refinement model's flag set, or nothing of it
+        raise SystemExit(f"[{BAND}] --num_scales 2 takes exactly --upsample_factor 4 --padding_factor 32 --attn_splits_list 2 8 --corr_radius_list -1 R "
+                         f"(R in 1 .. {RADII['corr_radius_list']}) --prop_radius_list -1 r (r in 1 .. {RADII['prop_radius_list']}); besides it "
+                         f"only the band's default GMFlow is built ({ARCH}); got "
+                         f"{ {k: getattr(args, k) for k in list(REFINE) + list(RADII) if hasattr(args, k)} }")
     bad = {k: getattr(args, k) for k, v in ARCH.items() if hasattr(args, k) and getattr(args, k) != v and k not in RADII}
     for k, top in RADII.items():
         v = getattr(args, k, None)
@@ -70,7 +104,6 @@ def check_arch(args):
             raise SystemExit(f"[{BAND}] --{k} takes one radius (one scale): -1 (global) or 1 .. {top}; got {v}")
     if bad:
         raise SystemExit(f"[{BAND}] only the band's default GMFlow is built ({ARCH}); got {bad}")
-    isz = getattr(args, "inference_size", None)
     if isz and (len(isz) != 2 or any(v < 32 or v % 16 for v in isz)):
         raise SystemExit(f"[{BAND}] --inference_size takes H W, multiples of 16 (the reference's 2 x 2 window split of the 1/8 grid fails otherwise); got {isz}")
 
@@ -80,7 +113,14 @@ def init_model(args=None, device=0):
     if args is not None:
         check_arch(args)
         _SYNTH[0] = bool(getattr(args, "synthetic", False))
-    model = engine.FlowGMFlow(load_weights(getattr(args, "model", MODEL) if args else MODEL), device=device)
+    _SCALES[0] = 2 if two_scale(args) else 1
+    weights = load_weights(getattr(args, "model", MODEL) if args else MODEL)
+    if weights_scales(weights) != _SCALES[0]:             # before anything runs: the engine would build what the weights say, not what the flags say
+        raise SystemExit(f"[{BAND}] the flags ask for the {_SCALES[0]}-scale model but the checkpoint is a {weights_scales(weights)}-scale one "
+                         f"(backbone.trident_conv.weight and an upsampler.2.weight of 144 rows make a two-scale checkpoint; --num_scales 2 takes "
+                         f"--upsample_factor 4 --padding_factor 32 --attn_splits_list 2 8 --corr_radius_list -1 R --prop_radius_list -1 r)")
+    model = engine.FlowGMFlow(weights, device=device)
+    assert model.num_scales == _SCALES[0]
     model.set_inference_size(getattr(args, "inference_size", None) if args is not None else None)      # reference :76-100
     model.set_matching(radius(args, "corr_radius_list"), radius(args, "prop_radius_list"))              # reference :84-89
     return model

@@ -254,16 +254,33 @@ int pb_flow_fwdbwd_mask(pb_ctx *ctx, const float *flows, int n, int sh, int sw, 
  * pb_flow_out_size; `iters` is ignored): replaces bands/flow_gmflow.py:60-118 infer (cv2.resize by --scale, InputPadder(16),
  * GMFlow(attn_splits_list=[2], corr_radius_list=[-1], prop_radius_list=[-1], pred_bidir_flow per `backward`)) ->
  * bands/gmflow/gmflow.py:12-170 (shared instance-norm encoder, position encoding, 6 transformer blocks with 2 x 2 shifted windows,
- * global matching, self-attention propagation, convex upsampling) and the same write_flow / process_flow encode.  Only the band's
- * default architecture is built (1 scale, 128 channels, 6 layers, 1 head, ffn x 4, attn_splits 2); the band script rejects other GMFlow
- * flags - in particular --num_scales 2 and --attn_splits_list other than 2 - except the two inference-time radii below. */
+ * global matching, self-attention propagation, convex upsampling) and the same write_flow / process_flow encode.
+ * Two architectures are built (128 channels, 6 layers, 1 head, ffn x 4), and the WEIGHTS say which: the band's default (1 scale, attn_splits
+ * 2, upsample_factor 8, InputPadder(16)), and GMFlow's refinement model (gmflow_with_refine: num_scales 2, upsample_factor 4,
+ * padding_factor 32, attn_splits_list 2 8, corr_radius_list -1 R, prop_radius_list -1 r) when the state dict carries
+ * backbone.trident_conv.weight [128, 128, 3, 3] and an upsampler.2.weight of 4 * 4 * 9 = 144 rows (576 rows and no trident weight: one
+ * scale; anything else: PB_ERR_ARG naming the tensor).  The two-scale model runs the coarse scale at 1/8 exactly as the default model runs
+ * (2 x 2 windows, global matching and propagation), enlarges its flow x 2, warps the target's 1/4 features by it, and runs the six blocks
+ * again at 1/4 with 8 x 8 windows, local matching and local-window propagation, then convex upsampling by 4 (gmflow.py:112-165); frames are
+ * padded to multiples of 32 and must reach 64 x 64.  Its backward direction is the forward direction of the swapped pair - what
+ * pred_bidir_flow computes, every batch element of it being its own sample.  The band script rejects every other GMFlow flag set. */
+/* 1 or 2: the architecture a flow_gmflow context was built with (see above); PB_ERR_ARG on other contexts. */
+int pb_flow_num_scales(pb_ctx *ctx);
 /* Stages of the last flow call: "fmap" [F,256,h/8,w/8], "flow_lo" [pairs*dirs, h/8*w/8, 2]; flow_gmflow (token-major fp32, shape
  * [n, tokens, channels, 1]): "feat" [F, h/8*w/8, 128] (encoder output), "block0" / "tfeat" [2 pairs, tokens, 128] (after the first / last
- * transformer block; both images of every pair), "flow_match" / "flow_prop" [pairs*dirs, tokens, 2]. */
+ * transformer block; both images of every pair), "flow_match" / "flow_prop" [pairs*dirs, tokens, 2].  On a two-scale context these names
+ * mean the coarse scale, and the fine scale adds (B = pairs*dirs, P4 = h/4*w/4): "feat4" [F, P4, 128], "flow_up" [B, P4, 2] (the coarse flow
+ * enlarged and doubled), "warp" [B, P4, 128] (the target's features warped by it), "block0_4" / "tfeat4" [2 B, P4, 128] (source and warped
+ * target of every batch element), "flow_match4" [B, P4, 2] (flow_up + the matched residual), "flow_prop4" [B, P4, 2].  The fine scale re-uses
+ * the token stream, so on a two-scale context the coarse "tfeat" and "block0" (like "block0" / "block0_4" everywhere) are copies made only
+ * with pb_set_profiling's debug bit and are unknown stages without it.
+ * One call on a two-scale context takes at most 511 (pair, direction) elements and 2^20 token rows (elements x 2 x P4): the host entry points
+ * split a sequence into such chunks, the *_dev entry points refuse a larger F with PB_ERR_ARG. */
 int64_t pb_flow_get_stage(pb_ctx *ctx, const char *name, float *out, int64_t cap, int64_t shape_out[4]);
 /* flow_gmflow --inference_size (reference bands/flow_gmflow.py:76-100): with (h, w) > 0 - multiples of 16 - the network runs on
  * F.interpolate(bilinear, align_corners = True) of the (scaled) frame to h x w instead of on the frame padded to /16, and the flow is
- * resized back the same way with u * W' / w, v * H' / h.  (0, 0) turns it off.  flow_gmflow contexts only. */
+ * resized back the same way with u * W' / w, v * H' / h.  (0, 0) turns it off.  flow_gmflow contexts only.  A two-scale context takes
+ * multiples of 32, at least 64; a refused size leaves the context as it was. */
 int pb_flow_set_inference_size(pb_ctx *ctx, int h, int w);
 /* flow_gmflow --corr_radius_list R / --prop_radius_list r (reference bands/gmflow/gmflow.py:128-157, same checkpoint): -1 = global (the
  * default: nothing of the default path changes).  corr_radius 1 .. 4: local matching - the softmax runs over the (2 R + 1)^2 target tokens
@@ -272,7 +289,9 @@ int pb_flow_set_inference_size(pb_ctx *ctx, int h, int w);
  * global form takes k_proj of the projected query).  Backward direction (`backward`, masks): with global matching it is the reference's
  * pred_bidir_flow; with a matching radius the reference's pred_bidir_flow raises (local_correlation_softmax returns B flows for 2 B
  * features), and the band defines it as the forward direction of the swapped pair - what pred_bidir_flow equals wherever the reference
- * can run it.  Other values are an error and leave the context as it was.  flow_gmflow contexts only. */
+ * can run it.  Other values are an error and leave the context as it was.  flow_gmflow contexts only.
+ * On a two-scale context the two radii are the FINE scale's (the reference's -1 R / -1 r): R in 1 .. 4, r in 1 .. 2, default (4, 1); -1 is
+ * refused there (global matching or propagation over the 1/4 grid is not built) and the coarse scale is always global. */
 int pb_flow_set_matching(pb_ctx *ctx, int corr_radius, int prop_radius);
 /* flow_raft --alternate_corr (reference bands/raft/raft.py:103-106 selects AlternateCorrBlock, bands/raft/corr.py:63-91, same checkpoint):
  * on != 0 - the 9 x 9 x 4 lookup of every GRU iteration computes its window entries from the feature maps (fp16 operands, fp32
@@ -459,8 +478,33 @@ int pb_op_raft_state(pb_ctx *ctx, const float *ctx_rows, const float *flow, int 
  * local_match (gmflow_local.hip): tokens [2 NP, P, 128]; batch element (pair, direction) reads source image 2 pair + dir and the other image
  *   of the pair as target (dirs 1: the even images only) -> flow (NP dirs P + guard) x 2 floats; 1 <= radius <= 4.
  * local_propagate: q, k [B img_step, P, 128] (batch element b takes image b img_step), flow_in [B, P, 2] -> flow_out (B P + guard) x 32
- *   floats, the propagation output's layout: the kernel owns columns 0, 1 (where upsampler_in reads the flow); 1 <= radius <= 2. */
+ *   floats, the propagation output's layout: the kernel owns columns 0, 1 (where upsampler_in reads the flow); 1 <= radius <= 2.
+ * The two-scale model's forms (tests/test_gpu_gmflow_scale2_ops.py).  `splits` is 2 (as above) or 8: the (h, w) grid - multiples of splits, at
+ *   least two tokens per window and axis - is cut into splits x splits windows, window index wy splits + wx, region table [splits^2, Lw],
+ *   and the cross attention pairs a window with the other image's same window.  tables_n / pack_n / ln_n / window_block_n are tables / pack /
+ *   ln / window_block with that argument (pack: splits^2 images Lw window rows).  window_block_n also takes pv_single: 1 is window_block's
+ *   attention (P and V single fp16, the one-scale model's), 0 the attention a two-scale context launches on both of its scales (P and V
+ *   split into hi + lo, nreg = splits^2, kxor = splits^2 when cross).
+ * tokens_warped: feat [B / dirs + 1, P, 128], warped [B, P, 128], pos [P, 128]: batch element b = pair dirs + d takes frame pair + d plus pos
+ *   as image 2 b and warped[b] plus pos as image 2 b + 1 -> X (2 B P + guard) x 128 floats, Xs the same rows x 256 halfs.
+ * warp: flow8 [B, h8 w8, 2], feat4 [B / dirs + 1, 4 h8 w8, 128] -> flow_up (4 B h8 w8 + guard) x 2 floats = 2 x the bilinear (align_corners)
+ *   enlargement to (2 h8) x (2 w8), warped (4 B h8 w8 + guard) x 128 floats = the features of frame pair + 1 - d sampled at token + flow_up
+ *   (bilinear, align_corners, zeros outside the grid).
+ * upsample: pb_op_raft_upsample with the factor: 8, or 4 with mask rows of 4 * 4 * 9 = 144 floats on the (h, w) = 1/4 grid. */
 int pb_op_gm_tables(int h8, int w8, float *pos, int8_t *region);
+int pb_op_gm_tables_n(int h, int w, int splits, float *pos, int8_t *region);
+int pb_op_gm_tokens_warped(pb_ctx *ctx, const float *feat, const float *warped, const float *pos, int B, int dirs, int P, int guard_rows, float *X,
+                           void *Xs);
+int pb_op_gm_warp(pb_ctx *ctx, const float *flow8, const float *feat4, int B, int dirs, int h8, int w8, int guard_rows, float *flow_up,
+                  float *warped);
+int pb_op_gm_upsample(pb_ctx *ctx, const float *flow, const float *mask, int n, int h, int w, int factor, int pad_l, int pad_t, int sh, int sw,
+                      int guard, float *up, float *maxd);
+int pb_op_gm_pack_n(pb_ctx *ctx, const float *src, int images, int h, int w, int splits, int ld, int njobs, const int *cols, const int *kinds,
+                    int shifted, int guard_rows, void **outs);
+int pb_op_gm_ln_n(pb_ctx *ctx, const float *M, const float *gamma, const float *beta, float *X, int rows, int xrows, int h, int w, int splits,
+                  int windowed, int shifted, int mode, int guard_rows, void *out);
+int pb_op_gm_window_block_n(pb_ctx *ctx, const float *Y, float *X, const float *gamma, const float *beta, int images, int h, int w, int splits,
+                            int shifted, int cross, int split, int pv_single);
 int pb_op_gm_tokens(pb_ctx *ctx, const float *feat, const float *pos, int NP, int P, int guard_rows, float *X, void *Xs);
 int pb_op_gm_split_rows(pb_ctx *ctx, const float *src, int rows, int ld, int C, int guard_rows, void *out);
 int pb_op_gm_grid_vt(pb_ctx *ctx, int h8, int w8, int guard_rows, void *out);

@@ -88,6 +88,7 @@ SYMBOLS = {
     "pb_mask_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "pb_flow_set_inference_size": (C.c_int, [_P, C.c_int, C.c_int]),
     "pb_flow_set_matching": (C.c_int, [_P, C.c_int, C.c_int]),
+    "pb_flow_num_scales": (C.c_int, [_P]),
     "pb_flow_set_alternate_corr": (C.c_int, [_P, C.c_int]),
     "pb_flow_arena_bytes": (C.c_int64, [_P]),
     "pb_mask_set_sdf": (C.c_int, [_P, _P, _P, C.c_int]),
@@ -129,6 +130,13 @@ SYMBOLS = {
     "pb_op_raft_instnorm": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),
     "pb_op_raft_state": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P, _P, _P, _P]),
     "pb_op_gm_tables": (C.c_int, [C.c_int, C.c_int, _P, _P]),
+    "pb_op_gm_tables_n": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
+    "pb_op_gm_tokens_warped": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 4 + [_P, _P]),
+    "pb_op_gm_warp": (C.c_int, [_P, _P, _P] + [C.c_int] * 5 + [_P, _P]),
+    "pb_op_gm_upsample": (C.c_int, [_P, _P, _P] + [C.c_int] * 9 + [_P, _P]),
+    "pb_op_gm_pack_n": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P, C.c_int, C.c_int, _P]),
+    "pb_op_gm_ln_n": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P]),
+    "pb_op_gm_window_block_n": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 8),
     "pb_op_gm_tokens": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "pb_op_gm_split_rows": (C.c_int, [_P, _P] + [C.c_int] * 4 + [_P]),
     "pb_op_gm_grid_vt": (C.c_int, [_P] + [C.c_int] * 3 + [_P]),

@@ -641,6 +641,13 @@ int pb_flow_set_matching(pb_ctx *c, int corr_radius, int prop_radius) {
     return g->set_matching(corr_radius, prop_radius);
 }
 
+int pb_flow_num_scales(pb_ctx *c) {
+    PB_CHECK(c && c->raft, PB_ERR_ARG, "ctx has no flow band");
+    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->raft);
+    PB_CHECK(g, PB_ERR_ARG, "num_scales is a flow_gmflow property");
+    return g->num_scales();
+}
+
 int pb_flow_set_alternate_corr(pb_ctx *c, int on) {
     PB_CHECK(c && c->raft, PB_ERR_ARG, "ctx has no flow band");
     PB_CHECK(!dynamic_cast<GmflowEngine *>(c->raft), PB_ERR_ARG, "--alternate_corr is a flow_raft option");

@@ -280,15 +280,17 @@ class RaftOpEngine : public SplitOpEngine {
         return finish(flow, dflow, (size_t)(rows + guard_rows) * 8);
     }
 
-    int upsample(const float *flow, const float *mask, int n, int h8, int w8, int pad_l, int pad_t, int sh, int sw, int guard, float *upo, float *maxd) {
+    int upsample(const float *flow, const float *mask, int n, int h8, int w8, int pad_l, int pad_t, int sh, int sw, int guard, float *upo, float *maxd,
+                 int factor = 8) {
         const int64_t rows = (int64_t)n * h8 * w8, px = (int64_t)n * sh * sw;
         DevMem dflow, dmask, dup, dmax, dmx;
         PB_TRY(up(dflow, flow, (size_t)rows * 8));
-        PB_TRY(up(dmask, mask, (size_t)rows * 576 * 4));
+        PB_TRY(up(dmask, mask, (size_t)rows * 9 * factor * factor * 4));
         PB_TRY(preset(dup, (size_t)(px * 2 + guard) * 4));
         PB_TRY(preset(dmax, (size_t)n * 4));
         PB_TRY(dmx.alloc((size_t)n * 4));
-        PB_TRY(launch_upsample(stream, dflow.as<float>(), dmask.as<float>(), n, h8, w8, pad_l, pad_t, sh, sw, dup.as<float>(), dmax.as<unsigned>()));
+        PB_TRY(launch_upsample(stream, dflow.as<float>(), dmask.as<float>(), n, h8, w8, pad_l, pad_t, sh, sw, dup.as<float>(), dmax.as<unsigned>(),
+                               factor));
         PB_TRY(launch_flow_encode(stream, dup.as<float>(), n, sh, sw, dmax.as<unsigned>(), nullptr, dmx.as<float>()));     // decodes maxd, no colours
         PB_TRY(finish(upo, dup, (size_t)(px * 2 + guard) * 4));
         PB_HIP(hipMemcpy(maxd, dmx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
@@ -352,9 +354,11 @@ class GmOpEngine : public RaftOpEngine {
     static constexpr size_t kSlack = 1 << 16;               // what prepare_g leaves behind every fp16 buffer
     GmGeom g{};
     int ldvP = 0;
-    int geom(int h8, int w8) {
-        PB_CHECK(h8 >= 4 && w8 >= 4 && h8 % 2 == 0 && w8 % 2 == 0, PB_ERR_ARG, "op_gm: a %d x %d token grid (both even, >= 4)", h8, w8);
-        gm_geometry(h8, w8, g, ldvP);
+    // splits 2: the 1/8 grid and its 2 x 2 windows; 8: the two-scale model's 1/4 grid and its 8 x 8 windows
+    int geom(int h8, int w8, int splits = 2) {
+        PB_CHECK((splits == 2 || splits == 8) && h8 >= 2 * splits && w8 >= 2 * splits && h8 % splits == 0 && w8 % splits == 0, PB_ERR_ARG,
+                 "op_gm: a %d x %d token grid (multiples of the %d splits, at least two tokens per window and axis)", h8, w8, splits);
+        gm_geometry(h8, w8, g, ldvP, splits);
         return 0;
     }
     int down(void *dst, const DevMem &d, size_t bytes) {
@@ -370,6 +374,28 @@ class GmOpEngine : public RaftOpEngine {
         PB_TRY(launch_gm_tokens(stream, df.as<float>(), dp.as<float>(), dX.as<float>(), dXs.as<f16>(), NP, P));
         PB_TRY(finish(X, dX, (size_t)(R + guard) * 128 * 4));
         return down(Xs, dXs, (size_t)(R + guard) * 256 * 2);
+    }
+
+    // the fine scale's tokens: feat [frames, P, 128], warped [B, P, 128], batch element b = pair * dirs + d takes frame pair + d as its source
+    int tokens_warped(const float *feat, const float *warped, const float *pos, int B, int dirs, int P, int guard, float *X, void *Xs) {
+        const int64_t R = (int64_t)B * 2 * P;
+        DevMem df, dw, dp, dX, dXs;
+        PB_TRY(up(df, feat, (size_t)(B / dirs + 1) * P * 128 * 4)); PB_TRY(up(dw, warped, (size_t)B * P * 128 * 4)); PB_TRY(up(dp, pos, (size_t)P * 128 * 4));
+        PB_TRY(preset(dX, (size_t)(R + guard) * 128 * 4)); PB_TRY(preset(dXs, (size_t)(R + guard) * 256 * 2));
+        PB_TRY(launch_gm_tokens(stream, df.as<float>(), dp.as<float>(), dX.as<float>(), dXs.as<f16>(), B, P, dw.as<float>(), dirs));
+        PB_TRY(finish(X, dX, (size_t)(R + guard) * 128 * 4));
+        return down(Xs, dXs, (size_t)(R + guard) * 256 * 2);
+    }
+
+    // flow8 [B, h8 w8, 2], feat4 [B / dirs + 1, 4 h8 w8, 128] -> flow_up (4 B h8 w8 + guard) x 2, warped (4 B h8 w8 + guard) x 128 floats
+    int warp(const float *flow8, const float *feat4, int B, int dirs, int h8, int w8, int guard, float *flow_up, float *warped) {
+        const int64_t P8 = (int64_t)h8 * w8, n4 = (int64_t)B * 4 * P8;
+        DevMem df, dx, du, dw;
+        PB_TRY(up(df, flow8, (size_t)B * P8 * 2 * 4)); PB_TRY(up(dx, feat4, (size_t)(B / dirs + 1) * 4 * P8 * 128 * 4));
+        PB_TRY(preset(du, (size_t)(n4 + guard) * 2 * 4)); PB_TRY(preset(dw, (size_t)(n4 + guard) * 128 * 4));
+        PB_TRY(launch_gm_warp(stream, df.as<float>(), dx.as<float>(), du.as<float>(), dw.as<float>(), B, dirs, h8, w8));
+        PB_TRY(finish(flow_up, du, (size_t)(n4 + guard) * 2 * 4));
+        return down(warped, dw, (size_t)(n4 + guard) * 128 * 4);
     }
 
     int split_rows(const float *src, int64_t rows, int ld, int C, int guard, void *out) {
@@ -391,7 +417,7 @@ class GmOpEngine : public RaftOpEngine {
         return is_vt ? ((size_t)Bw * 2 * 128 + guard) * g.ldv * 2 : ((size_t)Bw * g.Lw + guard) * 256 * 2;
     }
     int pack(const float *src, int images, int ld, int njobs, const int *cols, const int *kinds, int shifted, int guard, void **outs) {
-        const int Bw = images * 4;
+        const int Bw = images * g.ns * g.ns;
         DevMem ds, dd[5];
         PB_TRY(up(ds, src, (size_t)images * g.P * ld * 4));
         GmPackJobs jobs{};
@@ -502,10 +528,11 @@ class GmOpEngine : public RaftOpEngine {
         return finish(o, dout, (size_t)B * L * vcols * 4);
     }
 
-    // pack (q, k, v), the window attention as infer configures it, gm_ln (windowed, mode 0) straight on the attention output
-    int window_block(const float *Y, float *X, const float *gamma, const float *beta, int images, int shifted, int cross, int split) {
+    // pack (q, k, v), the window attention as blocks() configures it - pv_single 1: the one-scale model's (P and V single fp16), 0: the
+    // two-scale model's on both of its scales (P and V split) -, gm_ln (windowed, mode 0) straight on the attention output
+    int window_block(const float *Y, float *X, const float *gamma, const float *beta, int images, int shifted, int cross, int split, int pv_single = 1) {
         const int64_t R = (int64_t)images * g.P;
-        const int Bw = images * 4;
+        const int nw = g.ns * g.ns, Bw = images * nw;
         DevMem dY, dX, dg, db, dQ, dK, dVt, dO, dXs, dreg;
         PB_TRY(up(dY, Y, (size_t)R * 384 * 4)); PB_TRY(up(dX, X, (size_t)R * 128 * 4)); PB_TRY(up(dg, gamma, 128 * 4)); PB_TRY(up(db, beta, 128 * 4));
         PB_TRY(dQ.alloc((size_t)R * 256 * 2 + kSlack)); PB_TRY(dK.alloc((size_t)R * 256 * 2 + kSlack)); PB_TRY(dXs.alloc((size_t)R * 256 * 2 + kSlack));
@@ -518,14 +545,14 @@ class GmOpEngine : public RaftOpEngine {
         PB_TRY(launch_gm_pack(stream, jobs, g, Bw, shifted));
         if (shifted) {
             std::vector<int8_t> reg;
-            shift_regions(g.h8, g.w8, reg);
+            shift_regions(g.h8, g.w8, reg, g.ns);
             PB_TRY(up(dreg, reg.data(), reg.size()));
         }
         Attn128Args a;
-        a.Q = dQ.as<f16>(); a.K = dK.as<f16>(); a.Vt = dVt.as<f16>(); a.region = shifted ? dreg.as<int8_t>() : nullptr; a.nreg = 4; a.O = dO.as<float>();
+        a.Q = dQ.as<f16>(); a.K = dK.as<f16>(); a.Vt = dVt.as<f16>(); a.region = shifted ? dreg.as<int8_t>() : nullptr; a.nreg = nw; a.O = dO.as<float>();
         a.B = Bw; a.L = g.Lw; a.ldv = g.ldv; a.split = split; a.vcols = 128; a.ldq = 256; a.v_bstride = (int64_t)2 * 128 * g.ldv;
-        a.pv_single = 1;
-        if (cross) a.kxor = 4;
+        a.pv_single = pv_single;
+        if (cross) a.kxor = nw;
         PB_TRY(launch_attention128x(stream, a));
         PB_TRY(launch_gm_ln(stream, dO.as<float>(), dg.as<float>(), db.as<float>(), dX.as<float>(), dXs.as<f16>(), R, g, 1, shifted, 0));
         return finish(X, dX, (size_t)R * 128 * 4);
@@ -1045,7 +1072,65 @@ int pb_op_gm_tables(int h8, int w8, float *pos, int8_t *region) {
     memcpy(region, r.data(), r.size());
     return 0;
 }
+int pb_op_gm_tables_n(int h, int w, int splits, float *pos, int8_t *region) {
+    PB_CHECK(pos && region && (splits == 2 || splits == 8) && h >= 2 * splits && w >= 2 * splits && h % splits == 0 && w % splits == 0, PB_ERR_ARG,
+             "op_gm_tables_n: bad arguments");
+    std::vector<float> p;
+    std::vector<int8_t> r;
+    sine_positions(h, w, p, splits);
+    shift_regions(h, w, r, splits);
+    memcpy(pos, p.data(), p.size() * 4);
+    memcpy(region, r.data(), r.size());
+    return 0;
+}
 #define GM_OP_ENGINE(e) PB_HIP(hipSetDevice(c->device)); GmOpEngine e(c->device); PB_TRY(e.setup(nullptr, 0, SL_F16, 0))
+int pb_op_gm_tokens_warped(pb_ctx *c, const float *feat, const float *warped, const float *pos, int B, int dirs, int P, int guard_rows, float *X,
+                           void *Xs) {
+    PB_CHECK(c && feat && warped && pos && X && Xs && B > 0 && (dirs == 1 || dirs == 2) && B % dirs == 0 && P > 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_gm_tokens_warped: bad arguments");
+    GM_OP_ENGINE(e);
+    return e.tokens_warped(feat, warped, pos, B, dirs, P, guard_rows, X, Xs);
+}
+int pb_op_gm_warp(pb_ctx *c, const float *flow8, const float *feat4, int B, int dirs, int h8, int w8, int guard_rows, float *flow_up, float *warped) {
+    PB_CHECK(c && flow8 && feat4 && flow_up && warped && B > 0 && (dirs == 1 || dirs == 2) && B % dirs == 0 && h8 >= 2 && w8 >= 2 && guard_rows >= 0,
+             PB_ERR_ARG, "op_gm_warp: bad arguments");
+    GM_OP_ENGINE(e);
+    return e.warp(flow8, feat4, B, dirs, h8, w8, guard_rows, flow_up, warped);
+}
+int pb_op_gm_upsample(pb_ctx *c, const float *flow, const float *mask, int n, int h, int w, int factor, int pad_l, int pad_t, int sh, int sw, int guard,
+                      float *up, float *maxd) {
+    PB_CHECK(c && flow && mask && up && maxd && n > 0 && h > 0 && w > 0 && (factor == 4 || factor == 8) && sh > 0 && sw > 0 && pad_l >= 0 &&
+             pad_t >= 0 && guard >= 0 && pad_t + sh <= factor * h && pad_l + sw <= factor * w, PB_ERR_ARG, "op_gm_upsample: bad arguments");
+    GM_OP_ENGINE(e);
+    return e.upsample(flow, mask, n, h, w, pad_l, pad_t, sh, sw, guard, up, maxd, factor);
+}
+int pb_op_gm_pack_n(pb_ctx *c, const float *src, int images, int h, int w, int splits, int ld, int njobs, const int *cols, const int *kinds, int shifted,
+                    int guard_rows, void **outs) {
+    PB_CHECK(c && src && cols && kinds && outs && images > 0 && njobs >= 1 && njobs <= 5 && ld % 4 == 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_gm_pack_n: bad arguments");
+    for (int j = 0; j < njobs; ++j)
+        PB_CHECK(outs[j] && cols[j] >= 0 && cols[j] % 8 == 0 && cols[j] + 128 <= ld, PB_ERR_ARG, "op_gm_pack_n: job %d takes columns %d.. of %d", j, cols[j], ld);
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h, w, splits));
+    return e.pack(src, images, ld, njobs, cols, kinds, shifted, guard_rows, outs);
+}
+int pb_op_gm_ln_n(pb_ctx *c, const float *M, const float *gamma, const float *beta, float *X, int rows, int xrows, int h, int w, int splits, int windowed,
+                  int shifted, int mode, int guard_rows, void *out) {
+    PB_CHECK(c && M && gamma && beta && X && out && rows > 0 && rows <= xrows && (mode == 0 || mode == 1) && guard_rows >= 0, PB_ERR_ARG,
+             "op_gm_ln_n: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h, w, splits));
+    PB_CHECK(!windowed || xrows % e.g.P == 0, PB_ERR_ARG, "op_gm_ln_n: windowed rows address whole images of %d tokens, X has %d rows", e.g.P, xrows);
+    return e.ln(M, gamma, beta, X, rows, xrows, windowed, shifted, mode, guard_rows, out);
+}
+int pb_op_gm_window_block_n(pb_ctx *c, const float *Y, float *X, const float *gamma, const float *beta, int images, int h, int w, int splits,
+                            int shifted, int cross, int split, int pv_single) {
+    PB_CHECK(c && Y && X && gamma && beta && images > 0 && (!cross || images % 2 == 0) && (pv_single == 0 || pv_single == 1), PB_ERR_ARG,
+             "op_gm_window_block_n: bad arguments");
+    GM_OP_ENGINE(e);
+    PB_TRY(e.geom(h, w, splits));
+    return e.window_block(Y, X, gamma, beta, images, shifted, cross, split, pv_single);
+}
 int pb_op_gm_tokens(pb_ctx *c, const float *feat, const float *pos, int NP, int P, int guard_rows, float *X, void *Xs) {
     PB_CHECK(c && feat && pos && X && Xs && NP > 0 && P > 0 && guard_rows >= 0, PB_ERR_ARG, "op_gm_tokens: bad arguments");
     GM_OP_ENGINE(e);

@@ -8,10 +8,12 @@
 
 // Host tables of prepare_g (gmflow_engine.hip; pb_op_gm_tables hands the same two functions to the tests): the per-window sine position
 // embedding tiled over the 2 x 2 windows, token-major [h8 * w8, 128], and the shifted-window region ids in window order [4][Lw]
-void sine_positions(int h8, int w8, std::vector<float> &pos);
-void shift_regions(int h8, int w8, std::vector<int8_t> &reg);
-// the window geometry of an h8 x w8 token grid (both even, >= 4) and ldvP, the row stride of the matching / propagation V^T (round_up(P, 32))
-void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP);
+// (splits = 8 on the 1/4 grid: the two-scale model's fine scale, [64][Lw] regions)
+void sine_positions(int h8, int w8, std::vector<float> &pos, int splits = 2);
+void shift_regions(int h8, int w8, std::vector<int8_t> &reg, int splits = 2);
+// the window geometry of an h8 x w8 token grid (multiples of splits, at least 2 x splits) and ldvP, the row stride of the matching /
+// propagation V^T (round_up(P, 32))
+void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP, int splits = 2);
 
 class GmflowEngine : public RaftEngine {
   public:
@@ -21,7 +23,9 @@ class GmflowEngine : public RaftEngine {
     int infer(const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward, float *flow_out, uint8_t *rgb_out,
               float *maxdisp, uint8_t *mask_out = nullptr, float alpha1 = 0.05f, float alpha2 = 0.5f) override;
     // fp32 stages of the last call as [n, rows, cols]: "feat" [F, P, 128], "block0" / "tfeat" [2 pairs, P, 128] (token stream after the
-    // first / last transformer block), "flow_match" / "flow_prop" [pairs * dirs, P, 2]
+    // first / last transformer block), "flow_match" / "flow_prop" [pairs * dirs, P, 2] - with two scales these are the coarse scale's, and
+    // the fine scale adds (B = pairs * dirs, P4 = 4 P): "feat4" [F, P4, 128], "flow_up" [B, P4, 2], "warp" [B, P4, 128], "block0_4" / "tfeat4"
+    // [2 B, P4, 128], "flow_match4" (enlarged flow + matched residual) / "flow_prop4" [B, P4, 2]
     int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) override;
     // --inference_size of the band (reference flow_gmflow.py:76-100): the network runs on a bilinear (align_corners) resize of the scaled frame to
     // (h, w) - multiples of 16, no padding - and the flow is resized back and rescaled; (0, 0) = off (InputPadder(16), the default)
@@ -30,7 +34,13 @@ class GmflowEngine : public RaftEngine {
     // over (2 R + 1)^2 target tokens, 1 <= R <= 4, and local-window propagation, 1 <= r <= 2.  With local matching the backward direction
     // is the forward direction of the swapped pair - what pred_bidir_flow equals wherever the reference can run it (with a matching
     // radius its pred_bidir_flow raises: local_correlation_softmax returns B flows for 2 B features).
+    // On a two-scale context these are the FINE scale's radii (reference flags -1 R / -1 r): 1 <= R <= 4, 1 <= r <= 2, default (4, 1); -1 is
+    // refused (global matching over the 1/4 grid is not built) and the coarse scale is always global.
     int set_matching(int corr_radius, int prop_radius);
+    // 1, or 2 for the refinement model (gmflow_with_refine: num_scales 2, upsample_factor 4, padding_factor 32, attn_splits_list 2 8) - decided
+    // by the weights in load(): 'backbone.trident_conv.weight' and an 'upsampler.2.weight' of 144 rows
+    int num_scales() const { return scales_; }
+    int chunk_pairs(int wanted, int H, int W, float scale, int dirs) const override;
 
   private:
     struct Layer {
@@ -43,11 +53,24 @@ class GmflowEngine : public RaftEngine {
     int gemm32(const f16 *A, int lda, int64_t M, const PackedW &w, float *out, int ldo);
     int gemm16(const f16 *A, int lda, int64_t M, const PackedW &w, f16 *out, int ldo, int act, int lo_off);
     int attention(const Attn128Args &a, double keys_per_query);
+    int conv32(const f16 *in, int n, int H, int W, int stride, const PackedW &w, float *out);
+    int blocks(const GmGeom &g, int NPs, const int8_t *region, const char *blk0);
+    int fine_scale(int B, int dirs);
     struct FStage { const float *ptr; int64_t n, rows, cols; };
 
     Layer layers_[6];
     PackedW ffq_, ffk_, up0_, up2_;
     GmGeom g_{};
+    // two scales: the trident convolution, the 1/4 grid and its 8 x 8 windows, the fine scale's radii and buffers (stages of the same names)
+    int scales_ = 1;
+    PackedW trident_;
+    GmGeom g4_{};
+    int h4_ = 0, w4_ = 0, P4_ = 0;
+    int corr_r4_ = 4, prop_r4_ = 1;
+    f16 *c2_ = nullptr;               // conv2's output at 1/4 as a split map, the trident convolution's input
+    float *feat4_ = nullptr, *pos4_ = nullptr, *warp_ = nullptr, *flowu_ = nullptr, *flowm4_ = nullptr, *flowf_ = nullptr, *flowp4_ = nullptr,
+          *tfeat8_ = nullptr, *blk08_ = nullptr;
+    int8_t *region4_ = nullptr;
     int gF_ = 0, gH_ = 0, gW_ = 0, gD_ = 0;
     int isz_h_ = 0, isz_w_ = 0;
     int corr_r_ = -1, prop_r_ = -1;

@@ -39,8 +39,24 @@ int GmflowEngine::load(const pb_tensor *w, int n) {
     if (r) return r;
     mx_ = 0;                                    // fp16 residual parts everywhere: activations AND weights split, three K segments
     pack_tapin_ = 0;
+    {   // the architecture comes from the weights: the two-scale model (gmflow_with_refine: num_scales 2, upsample_factor 4) carries the
+        // backbone's trident convolution and an upsampler of 4 * 4 * 9 logits, the one-scale model neither
+        const pb_tensor *tri = find("backbone.trident_conv.weight"), *u2 = find("upsampler.2.weight");
+        PB_CHECK(u2 && u2->ndim == 4, PB_ERR_ARG, "missing conv 'upsampler.2'");
+        const int rows = (int)u2->shape[0];
+        if (tri) {
+            PB_CHECK(tri->ndim == 4 && tri->shape[0] == 128 && tri->shape[1] == 128 && tri->shape[2] == 3 && tri->shape[3] == 3, PB_ERR_ARG,
+                     "flow_gmflow: 'backbone.trident_conv.weight' must be [128, 128, 3, 3] (the two-scale model's shared 3 x 3 convolution)");
+            PB_CHECK(rows == 144, PB_ERR_ARG, "flow_gmflow: 'upsampler.2.weight' has %d rows; with 'backbone.trident_conv.weight' (two scales) it has 4 * 4 * 9 = 144", rows);
+        } else {
+            PB_CHECK(rows == 576, PB_ERR_ARG, "flow_gmflow: 'upsampler.2.weight' has %d rows; without 'backbone.trident_conv.weight' (one scale) it has 8 * 8 * 9 = 576", rows);
+        }
+        scales_ = tri ? 2 : 1;
+        enc_s3_ = tri ? 1 : 2;
+    }
     if ((r = pack_encoder("backbone", false, false, fnet_))) return r;
     if ((r = pack_conv("backbone.conv2", true, nullptr, nullptr, fnet_.out, 1))) return r;
+    if (scales_ == 2 && (r = pack_conv("backbone.trident_conv", false, nullptr, nullptr, trident_, 1))) return r;
     auto lin = [&](const std::string &name, int N, int K, PackedW &out, bool bias) -> int {
         const pb_tensor *t = find(name + ".weight");
         PB_CHECK(t && t->ndim == 2 && t->shape[0] == N && t->shape[1] == K, PB_ERR_ARG, "missing linear '%s' [%d, %d]", name.c_str(), N, K);
@@ -83,9 +99,9 @@ int GmflowEngine::load(const pb_tensor *w, int n) {
 }
 
 // PositionEmbeddingSine(num_pos_feats = 64, temperature 10000, normalize, scale 2 pi) of ONE wh x ww window (position.py:26-46), tiled over
-// the 2 x 2 windows (utils.py:61-86), as a token-major table [h8 * w8, 128]: channels 0..63 from y, 64..127 from x, (sin, cos) interleaved
-void sine_positions(int h8, int w8, std::vector<float> &pos) {
-    const int wh = h8 / 2, ww = w8 / 2;
+// the splits x splits windows (utils.py:61-86), as a token-major table [h8 * w8, 128]: channels 0..63 from y, 64..127 from x, (sin, cos) interleaved
+void sine_positions(int h8, int w8, std::vector<float> &pos, int splits) {
+    const int wh = h8 / splits, ww = w8 / splits;
     const float eps = 1e-6f, scale = 6.283185307179586f;
     pos.assign((size_t)h8 * w8 * 128, 0.f);
     float dim_t[64];
@@ -102,21 +118,21 @@ void sine_positions(int h8, int w8, std::vector<float> &pos) {
         }
 }
 
-// region ids of generate_shift_window_attn_mask (transformer.py:18-44) in window order: [4 windows][Lw]
-void shift_regions(int h8, int w8, std::vector<int8_t> &reg) {
-    const int wh = h8 / 2, ww = w8 / 2;
-    reg.assign((size_t)4 * wh * ww, 0);
-    for (int win = 0; win < 4; ++win)
+// region ids of generate_shift_window_attn_mask (transformer.py:18-44) in window order: [splits * splits windows][Lw]
+void shift_regions(int h8, int w8, std::vector<int8_t> &reg, int splits) {
+    const int wh = h8 / splits, ww = w8 / splits;
+    reg.assign((size_t)splits * splits * wh * ww, 0);
+    for (int win = 0; win < splits * splits; ++win)
         for (int ly = 0; ly < wh; ++ly)
             for (int lx = 0; lx < ww; ++lx) {
-                const int ry = (win >> 1) * wh + ly, rx = (win & 1) * ww + lx;
+                const int ry = (win / splits) * wh + ly, rx = (win % splits) * ww + lx;
                 const int cy = ry < h8 - wh ? 0 : (ry < h8 - wh / 2 ? 1 : 2), cx = rx < w8 - ww ? 0 : (rx < w8 - ww / 2 ? 1 : 2);
                 reg[((size_t)win * wh + ly) * ww + lx] = (int8_t)(cy * 3 + cx);
             }
 }
 
-void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP) {
-    g.h8 = h8; g.w8 = w8; g.P = h8 * w8; g.wh = h8 / 2; g.ww = w8 / 2; g.Lw = g.wh * g.ww; g.ldv = (int)round_up(g.Lw, 32);
+void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP, int splits) {
+    g.h8 = h8; g.w8 = w8; g.P = h8 * w8; g.wh = h8 / splits; g.ww = w8 / splits; g.Lw = g.wh * g.ww; g.ldv = (int)round_up(g.Lw, 32); g.ns = splits;
     ldvP = (int)round_up(g.P, 32);
 }
 
@@ -124,7 +140,7 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
     if (F <= gF_ && H == gH_ && W == gW_ && scale == gS_ && dirs <= gD_) return 0;
     PB_HIP(hipStreamSynchronize(stream));
     gF_ = 0; gH_ = 0; gW_ = 0; gD_ = 0;       // (a failure below must not leave the old plan's key on a half-written geometry: raft_engine.hip prepare)
-    geometry(H, W, scale, 16);
+    geometry(H, W, scale, scales_ == 2 ? 32 : 16);        // InputPadder(padding_factor): 16 = 8 x the 2 x 2 split, 32 = 4 x the fine scale's 8 x 8 split
     if (isz_h_ > 0) {                 // --inference_size: the network's size is given, nothing is padded (sh_, sw_ stay the output size)
         padl_ = padt_ = 0;
         Hp_ = isz_h_; Wp_ = isz_w_;
@@ -133,7 +149,20 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
     PB_CHECK(h8_ >= 4 && w8_ >= 4 && h8_ % 2 == 0 && w8_ % 2 == 0, PB_ERR_ARG, "flow_gmflow: %dx%d is too small", sh_, sw_);
     gm_geometry(h8_, w8_, g_, ldvP_);
     const int NP = F - 1;
-    const int64_t R = (int64_t)NP * 2 * P_, B = (int64_t)NP * dirs, Bw = (int64_t)NP * 8;
+    const int64_t B = (int64_t)NP * dirs;
+    int64_t R = (int64_t)NP * 2 * P_, VtW = (int64_t)NP * 8 * g_.ldv, Pm = P_;       // token rows, window V^T rows of 2 x 128 halfs, tokens of an image
+    h4_ = w4_ = P4_ = 0;
+    if (scales_ == 2) {               // the fine scale: both frames of every (pair, direction) on the 1/4 grid, 8 x 8 windows; shares the coarse scale's buffers
+        PB_CHECK(Hp_ >= 64 && Wp_ >= 64 && Hp_ % 32 == 0 && Wp_ % 32 == 0, PB_ERR_ARG, "flow_gmflow (two scales): %dx%d is too small (64 x 64 after padding to /32)", sh_, sw_);
+        h4_ = Hp_ / 4; w4_ = Wp_ / 4; P4_ = h4_ * w4_;
+        int ldvP4;
+        gm_geometry(h4_, w4_, g4_, ldvP4, 8);
+        // what chunk_pairs keeps the host pipeline inside; the device entry points (pb_flow_infer_sequence*_dev) come here with the caller's F
+        PB_CHECK(B <= 511 && B * 2 * P4_ <= (INT64_C(1) << 20), PB_ERR_ARG,
+                 "flow_gmflow (two scales): %lld (pair, direction) elements of 2 x %d tokens in one call; one call takes 511 elements and 2^20 token rows "
+                 "(the host entry points split a sequence into such chunks; a device entry point takes one chunk)", (long long)B, P4_);
+        R = std::max(R, B * 2 * P4_); VtW = std::max(VtW, B * 2 * 64 * g4_.ldv); Pm = P4_;
+    }
     const size_t slack = 1 << 16;
     for (int pass = 0; pass < 2; ++pass) {
         planning_ = pass == 0;
@@ -142,21 +171,32 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
         feat_ = (float *)carve((size_t)F * P_ * 128 * 4);
         pos_ = (float *)carve((size_t)P_ * 128 * 4);
         region_ = (int8_t *)carve((size_t)4 * g_.Lw);
+        if (scales_ == 2) {
+            c2_ = (f16 *)carve((size_t)round_up((int64_t)F * P4_, 256) * 256 * 2 + slack);
+            feat4_ = (float *)carve((size_t)F * P4_ * 128 * 4);
+            pos4_ = (float *)carve((size_t)P4_ * 128 * 4);
+            region4_ = (int8_t *)carve((size_t)64 * g4_.Lw);
+            warp_ = (float *)carve((size_t)B * P4_ * 128 * 4);
+            flowu_ = (float *)carve((size_t)B * P4_ * 2 * 4); flowm4_ = (float *)carve((size_t)B * P4_ * 2 * 4);
+            flowf_ = (float *)carve((size_t)B * P4_ * 2 * 4); flowp4_ = (float *)carve((size_t)B * P4_ * 2 * 4);
+            // the fine scale re-uses the token stream's buffers: the coarse scale's "tfeat" / "block0" stages are kept as copies
+            tfeat8_ = (float *)carve((size_t)NP * 2 * P_ * 128 * 4); blk08_ = (float *)carve((size_t)NP * 2 * P_ * 128 * 4);
+        }
         X_ = (float *)carve((size_t)R * 128 * 4); blk0_ = (float *)carve((size_t)R * 128 * 4);
         Xs_ = (f16 *)carve((size_t)R * 256 * 2 + slack);
         Y1_ = (float *)carve((size_t)R * 640 * 4); Yq_ = (float *)carve((size_t)R * 128 * 4);
         Qw_ = (f16 *)carve((size_t)R * 256 * 2 + slack); Kw_ = (f16 *)carve((size_t)R * 256 * 2 + slack); Kcw_ = (f16 *)carve((size_t)R * 256 * 2 + slack);
-        Vtw_ = (f16 *)carve((size_t)Bw * 2 * 128 * g_.ldv * 2 + slack); Vtcw_ = (f16 *)carve((size_t)Bw * 2 * 128 * g_.ldv * 2 + slack);
+        Vtw_ = (f16 *)carve((size_t)VtW * 2 * 128 * 2 + slack); Vtcw_ = (f16 *)carve((size_t)VtW * 2 * 128 * 2 + slack);
         Ow_ = (float *)carve((size_t)R * 128 * 4); Os_ = (f16 *)carve((size_t)R * 256 * 2 + slack);
         M_ = (float *)carve((size_t)R * 128 * 4);
         cat_ = (f16 *)carve((size_t)R * 512 * 2 + slack); Hs_ = (f16 *)carve((size_t)R * 2048 * 2 + slack);
         gridvt_ = (f16 *)carve((size_t)64 * ldvP_ * 2 + slack);
-        Om_ = (float *)carve((size_t)B * P_ * 32 * 4);
+        Om_ = (float *)carve((size_t)B * Pm * 32 * 4);
         flowm_ = (float *)carve((size_t)B * P_ * 2 * 4); flowp_ = (float *)carve((size_t)B * P_ * 2 * 4);
         Vtf_ = (f16 *)carve((size_t)B * 64 * ldvP_ * 2 + slack);
         qs_ = (f16 *)carve((size_t)R * 256 * 2 + slack); ks_ = (f16 *)carve((size_t)R * 256 * 2 + slack);
-        umap_ = (f16 *)carve((size_t)B * P_ * 384 * 2 + slack); u1_ = (f16 *)carve((size_t)round_up(B * P_, 256) * 512 * 2 + slack);
-        gmask_ = (float *)carve((size_t)B * P_ * 576 * 4);
+        umap_ = (f16 *)carve((size_t)B * Pm * 384 * 2 + slack); u1_ = (f16 *)carve((size_t)round_up(B * Pm, 256) * 512 * 2 + slack);
+        gmask_ = (float *)carve((size_t)B * P_ * 576 * 4);                // (two scales: P4 x 144 logits, the same bytes)
         gup_ = (float *)carve((size_t)B * sh_ * sw_ * 2 * 4);
         gupi_ = isz_h_ > 0 ? (float *)carve((size_t)B * Hp_ * Wp_ * 2 * 4) : nullptr;
         gmaxd_ = (unsigned *)carve((size_t)B * 4);
@@ -171,6 +211,14 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
     shift_regions(h8_, w8_, reg);
     PB_HIP(hipMemcpyAsync(pos_, pos.data(), pos.size() * 4, hipMemcpyHostToDevice, stream));
     PB_HIP(hipMemcpyAsync(region_, reg.data(), reg.size(), hipMemcpyHostToDevice, stream));
+    std::vector<float> pos4;
+    std::vector<int8_t> reg4;
+    if (scales_ == 2) {
+        sine_positions(h4_, w4_, pos4, 8);
+        shift_regions(h4_, w4_, reg4, 8);
+        PB_HIP(hipMemcpyAsync(pos4_, pos4.data(), pos4.size() * 4, hipMemcpyHostToDevice, stream));
+        PB_HIP(hipMemcpyAsync(region4_, reg4.data(), reg4.size(), hipMemcpyHostToDevice, stream));
+    }
     int r = launch_gm_grid_vt(stream, gridvt_, P_, w8_, ldvP_);
     if (r) return r;
     if ((r = upload_resize_tables(H, W, scale))) return r;         // synchronises: the host vectors above stay alive until then
@@ -202,6 +250,24 @@ int GmflowEngine::gemm16(const f16 *A, int lda, int64_t M, const PackedW &w, f16
     return r;
 }
 
+// 3 x 3 convolution of a split map [n, H, W, 256] (128 channels) with fp32 output [n * OH * OW, 128]: the implicit GEMM with the fp32 epilogue
+int GmflowEngine::conv32(const f16 *in, int n, int H, int W, int stride, const PackedW &w, float *out) {
+    GemmArgs a;
+    a.A = in; a.N = w.N;
+    a.cH = H; a.cW = W; a.cC = 128; a.cLd = 256; a.cKW = 3; a.cStride = stride; a.cPad = 1; a.cPadX = 1;
+    a.cOH = (H - 1) / stride + 1; a.cOW = (W - 1) / stride + 1;
+    a.M = n * a.cOH * a.cOW;
+    a.out32 = out; a.ldo = 128; a.scale = 1.f;
+    PB_CHECK(!w.sw || w.Cseg == 128, PB_ERR_STATE, "conv32: weights packed for %d channels", w.Cseg);
+    set_weights(a, w, true);
+    PB_CHECK(w.K == 9 * a.cC, PB_ERR_STATE, "conv32: packed K %d != 9*%d", w.K, a.cC);
+    tic(F_CONV128, 2.0 * a.M * (double)a.N * w.Kreal, 2.0 * ((double)n * H * W * 128 + (double)a.N * w.Kreal) + 4.0 * a.M * a.N, 1.0 + w.sa + w.sw);
+    int r = launch_gemm(cur_, A_CONV, EPI_F32, TILE_128, a);
+    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
+    toc();
+    return r;
+}
+
 int GmflowEngine::attention(const Attn128Args &a, double keys_per_query) {
     // S and P V: 2 x 2 x (128 + vcols) flops per (query, key); three MFMA passes each in split mode
     const double qk = 2.0 * a.B * (double)a.L * keys_per_query * 128.0, pv = 2.0 * a.B * (double)a.L * keys_per_query * a.vcols;
@@ -212,6 +278,9 @@ int GmflowEngine::attention(const Attn128Args &a, double keys_per_query) {
 }
 
 int GmflowEngine::set_inference_size(int h, int w) {
+    if (scales_ == 2)
+        PB_CHECK((h == 0 && w == 0) || (h >= 64 && w >= 64 && h % 32 == 0 && w % 32 == 0), PB_ERR_ARG,
+                 "flow_gmflow (two scales): --inference_size %d %d must be multiples of 32, at least 64 (4 x the fine scale's 8 x 8 window split)", h, w);
     PB_CHECK((h == 0 && w == 0) || (h >= 32 && w >= 32 && h % 16 == 0 && w % 16 == 0), PB_ERR_ARG,
              "flow_gmflow: --inference_size %d %d must be multiples of 16 (8 x the 2 x 2 window split; the reference fails in its window split otherwise)", h, w);
     if (h != isz_h_ || w != isz_w_) { isz_h_ = h; isz_w_ = w; gF_ = 0; }      // re-plan on the next call
@@ -219,11 +288,101 @@ int GmflowEngine::set_inference_size(int h, int w) {
 }
 
 int GmflowEngine::set_matching(int corr_radius, int prop_radius) {
+    if (scales_ == 2) {               // the fine scale's radii; the coarse scale is always global
+        PB_CHECK(corr_radius >= 1 && corr_radius <= 4, PB_ERR_ARG,
+                 "flow_gmflow (two scales): --corr_radius_list -1 %d: the fine scale's matching radius must be 1 .. 4 (global matching over the 1/4 grid is not built)", corr_radius);
+        PB_CHECK(prop_radius >= 1 && prop_radius <= 2, PB_ERR_ARG,
+                 "flow_gmflow (two scales): --prop_radius_list -1 %d: the fine scale's propagation radius must be 1 .. 2 (global propagation over the 1/4 grid is not built)", prop_radius);
+        corr_r4_ = corr_radius; prop_r4_ = prop_radius;          // kernel template arguments only: the plan does not depend on them
+        return 0;
+    }
     PB_CHECK(corr_radius == -1 || (corr_radius >= 1 && corr_radius <= 4), PB_ERR_ARG,
              "flow_gmflow: --corr_radius_list %d must be -1 (global matching) or 1 .. 4", corr_radius);
     PB_CHECK(prop_radius == -1 || (prop_radius >= 1 && prop_radius <= 2), PB_ERR_ARG,
              "flow_gmflow: --prop_radius_list %d must be -1 (global propagation) or 1 .. 2", prop_radius);
     if (corr_radius != corr_r_ || prop_radius != prop_r_) { corr_r_ = corr_radius; prop_r_ = prop_radius; gF_ = 0; }      // re-plan on the next call
+    return 0;
+}
+
+// two scales: a (pair, direction) carries 2 x P4 token rows of ~14 KB through the fine scale's blocks - chunks of at most 2^20 rows (~14 GB)
+int GmflowEngine::chunk_pairs(int wanted, int H, int W, float scale, int dirs) const {
+    if (scales_ != 2) return RaftEngine::chunk_pairs(wanted, H, W, scale, dirs);
+    int sh, sw;
+    out_size(H, W, scale, &sh, &sw);
+    const int64_t P4 = isz_h_ > 0 ? (int64_t)(isz_h_ / 4) * (isz_w_ / 4) : (int64_t)((sh + 31) / 32 * 8) * ((sw + 31) / 32 * 8);
+    const int64_t fit = std::min<int64_t>((INT64_C(1) << 20) / ((int64_t)dirs * 2 * P4), 511 / dirs);       // ... and of 511 batch elements (fine_scale)
+    return (int)std::max<int64_t>(1, std::min<int64_t>(wanted, fit));
+}
+
+// The six transformer blocks (transformer.py:108-290) on the token stream X_ / Xs_ of NPs pairs over the grid and windows of g; `region`
+// is g's shifted-window region table, blk0 the stage name of the stream after the first block (debug)
+int GmflowEngine::blocks(const GmGeom &g, int NPs, const int8_t *region, const char *blk0) {
+    int r;
+    const int nw = g.ns * g.ns, Bw = NPs * 2 * nw, split = split_w_ ? 1 : 0;
+    const int64_t R = (int64_t)NPs * 2 * g.P;
+    for (int li = 0; li < 6; ++li) {
+        const Layer &L = layers_[li];
+        const int shifted = li & 1;
+        if ((r = gemm32(Xs_, 256, R, L.w1, Y1_, 640))) return r;
+        GmPackJobs jobs{};
+        jobs.n = 5;
+        jobs.j[0] = GmPackJob{Y1_, 640, 0, Qw_, 0};
+        jobs.j[1] = GmPackJob{Y1_, 640, 128, Kw_, 0};
+        jobs.j[2] = GmPackJob{Y1_, 640, 256, Vtw_, 1};
+        jobs.j[3] = GmPackJob{Y1_, 640, 384, Kcw_, 0};
+        jobs.j[4] = GmPackJob{Y1_, 640, 512, Vtcw_, 1};
+        tic(F_ELT, 0, 0);
+        r = launch_gm_pack(stream, jobs, g, Bw, shifted);
+        toc();
+        if (r) return r;
+        Attn128Args a;
+        a.Q = Qw_; a.K = Kw_; a.Vt = Vtw_; a.region = shifted ? region : nullptr; a.nreg = nw; a.O = Ow_;
+        a.B = Bw; a.L = g.Lw; a.ldv = g.ldv; a.split = split; a.vcols = 128; a.ldq = 256; a.v_bstride = (int64_t)2 * 128 * g.ldv;
+        // window attention: q / k split; P and V as single fp16 in the one-scale model (2.6e-4 of its budget, attention128.hip).  The two-scale
+        // model runs both scales with P and V split as well: its warp samples the target's 1/4 features at the coarse flow, and features that
+        // change by their whole range from one token to the next turn a coarse-flow error of 3e-4 of range into 1e-3 .. 3e-3 of the warped
+        // features (EXPERIMENTS.md 6.12), so the coarse scale has to be several times closer than the one-scale model needs to be.
+        a.pv_single = scales_ == 2 ? 0 : 1;
+        if ((r = attention(a, g.Lw))) return r;
+        tic(F_ELT, 0, 0);
+        r = launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R);
+        toc();
+        if (r) return r;
+        if ((r = gemm32(Os_, 256, R, L.merge_s, M_, 128))) return r;
+        tic(F_LN, 0, 0);
+        r = launch_gm_ln(stream, M_, L.ln1s_g, L.ln1s_b, X_, Xs_, R, g, 1, shifted, 0);
+        toc();
+        if (r) return r;
+        // cross attention + FFN: queries from the updated stream, keys / values from the partner frame's ENTERING stream (Kcw_, Vtcw_)
+        if ((r = gemm32(Xs_, 256, R, L.q_c, Yq_, 128))) return r;
+        jobs.n = 1;
+        jobs.j[0] = GmPackJob{Yq_, 128, 0, Qw_, 0};
+        tic(F_ELT, 0, 0);
+        r = launch_gm_pack(stream, jobs, g, Bw, shifted);
+        toc();
+        if (r) return r;
+        a.K = Kcw_; a.Vt = Vtcw_; a.kxor = nw;            // the same window of the pair's other frame
+        if ((r = attention(a, g.Lw))) return r;
+        tic(F_ELT, 0, 0);
+        r = launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R);
+        toc();
+        if (r) return r;
+        if ((r = gemm32(Os_, 256, R, L.merge_c, M_, 128))) return r;
+        tic(F_LN, 0, 0);
+        r = launch_gm_ln(stream, M_, L.ln1c_g, L.ln1c_b, X_, cat_, R, g, 1, shifted, 1);
+        toc();
+        if (r) return r;
+        if ((r = gemm16(cat_, 512, R, L.mlp0, Hs_, 2048, ACT_GELU, 1024))) return r;
+        if ((r = gemm32(Hs_, 2048, R, L.mlp2, M_, 128))) return r;
+        tic(F_LN, 0, 0);
+        r = launch_gm_ln(stream, M_, L.ln2c_g, L.ln2c_b, X_, Xs_, R, g, 0, 0, 0);
+        toc();
+        if (r) return r;
+        if (debug && li == 0) {
+            PB_HIP(hipMemcpyAsync(blk0_, X_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
+            fstages_[blk0] = FStage{blk0_, (int64_t)NPs * 2, g.P, 128};
+        }
+    }
     return 0;
 }
 
@@ -237,13 +396,15 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     if (r) return r;
     timer.reset();
     fstages_.clear();
-    const int NP = F - 1, B = NP * dirs, Bw = NP * 8, P = P_;
+    const int NP = F - 1, B = NP * dirs, P = P_;
     const int64_t R = (int64_t)NP * 2 * P;
     const int split = split_w_ ? 1 : 0;
     const int es = split_w_ ? 2 : 1;
+    const bool fine = scales_ == 2;
+    const int corr_r = fine ? -1 : corr_r_, prop_r = fine ? -1 : prop_r_;       // two scales: the coarse scale is always global
     last_nd_ = B;
 
-    // ---- frame prep (resize, replicate pad to /16, ImageNet normalisation) and the backbone, once per frame ----
+    // ---- frame prep (resize, replicate pad to /16 - two scales: /32 -, ImageNet normalisation) and the backbone, once per frame ----
     tic(F_PP, 0, (double)F * H * W * 3);
     r = launch_raft_prep(stream, frames, F, H, W, sh_, sw_, Hp_, Wp_, padl_, padt_, scale != 1.f, xi_, xc_, yi_, yc_, img_, nullptr, 1,
                          split_w_ ? 64 : 0, -1, 1, isz_h_ > 0);
@@ -251,7 +412,16 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     if (r) return r;
     const f16 *x = nullptr;
     if ((r = run_encoder(fnet_, true, F, &x))) return r;
-    if ((r = gemm32(x, es * 128, (int64_t)F * P, fnet_.out, feat_, 128))) return r;
+    if (!fine) {
+        if ((r = gemm32(x, es * 128, (int64_t)F * P, fnet_.out, feat_, 128))) return r;
+    } else {
+        // the backbone ends at 1/4 (layer3 at stride 1, conv2 1 x 1) and ONE 3 x 3 weight gives both scales (trident_conv.py:64-72): stride 1
+        // the 1/4 features, stride 2 the 1/8 features
+        if ((r = gemm16(x, es * 128, (int64_t)F * P4_, fnet_.out, c2_, 256, ACT_NONE, split_w_ ? 128 : 0))) return r;
+        if ((r = conv32(c2_, F, h4_, w4_, 1, trident_, feat4_))) return r;
+        if ((r = conv32(c2_, F, h4_, w4_, 2, trident_, feat_))) return r;
+        fstages_["feat4"] = FStage{feat4_, F, P4_, 128};
+    }
     fstages_["feat"] = FStage{feat_, F, P, 128};
 
     // ---- tokens + per-window sine positions; the six transformer blocks ----
@@ -259,72 +429,23 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     r = launch_gm_tokens(stream, feat_, pos_, X_, Xs_, NP, P);
     toc();
     if (r) return r;
-    for (int li = 0; li < 6; ++li) {
-        const Layer &L = layers_[li];
-        const int shifted = li & 1;
-        if ((r = gemm32(Xs_, 256, R, L.w1, Y1_, 640))) return r;
-        GmPackJobs jobs{};
-        jobs.n = 5;
-        jobs.j[0] = GmPackJob{Y1_, 640, 0, Qw_, 0};
-        jobs.j[1] = GmPackJob{Y1_, 640, 128, Kw_, 0};
-        jobs.j[2] = GmPackJob{Y1_, 640, 256, Vtw_, 1};
-        jobs.j[3] = GmPackJob{Y1_, 640, 384, Kcw_, 0};
-        jobs.j[4] = GmPackJob{Y1_, 640, 512, Vtcw_, 1};
-        tic(F_ELT, 0, 0);
-        r = launch_gm_pack(stream, jobs, g_, Bw, shifted);
-        toc();
-        if (r) return r;
-        Attn128Args a;
-        a.Q = Qw_; a.K = Kw_; a.Vt = Vtw_; a.region = shifted ? region_ : nullptr; a.nreg = 4; a.O = Ow_;
-        a.B = Bw; a.L = g_.Lw; a.ldv = g_.ldv; a.split = split; a.vcols = 128; a.ldq = 256; a.v_bstride = (int64_t)2 * 128 * g_.ldv;
-        a.pv_single = 1;                  // window attention: P and V as single fp16 (2.6e-4 of the budget), q / k split (attention128.hip)
-        if ((r = attention(a, g_.Lw))) return r;
-        tic(F_ELT, 0, 0);
-        r = launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R);
-        toc();
-        if (r) return r;
-        if ((r = gemm32(Os_, 256, R, L.merge_s, M_, 128))) return r;
-        tic(F_LN, 0, 0);
-        r = launch_gm_ln(stream, M_, L.ln1s_g, L.ln1s_b, X_, Xs_, R, g_, 1, shifted, 0);
-        toc();
-        if (r) return r;
-        // cross attention + FFN: queries from the updated stream, keys / values from the partner frame's ENTERING stream (Kcw_, Vtcw_)
-        if ((r = gemm32(Xs_, 256, R, L.q_c, Yq_, 128))) return r;
-        jobs.n = 1;
-        jobs.j[0] = GmPackJob{Yq_, 128, 0, Qw_, 0};
-        tic(F_ELT, 0, 0);
-        r = launch_gm_pack(stream, jobs, g_, Bw, shifted);
-        toc();
-        if (r) return r;
-        a.K = Kcw_; a.Vt = Vtcw_; a.kxor = 4;
-        if ((r = attention(a, g_.Lw))) return r;
-        tic(F_ELT, 0, 0);
-        r = launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R);
-        toc();
-        if (r) return r;
-        if ((r = gemm32(Os_, 256, R, L.merge_c, M_, 128))) return r;
-        tic(F_LN, 0, 0);
-        r = launch_gm_ln(stream, M_, L.ln1c_g, L.ln1c_b, X_, cat_, R, g_, 1, shifted, 1);
-        toc();
-        if (r) return r;
-        if ((r = gemm16(cat_, 512, R, L.mlp0, Hs_, 2048, ACT_GELU, 1024))) return r;
-        if ((r = gemm32(Hs_, 2048, R, L.mlp2, M_, 128))) return r;
-        tic(F_LN, 0, 0);
-        r = launch_gm_ln(stream, M_, L.ln2c_g, L.ln2c_b, X_, Xs_, R, g_, 0, 0, 0);
-        toc();
-        if (r) return r;
-        if (debug && li == 0) {
-            PB_HIP(hipMemcpyAsync(blk0_, X_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
-            fstages_["block0"] = FStage{blk0_, (int64_t)NP * 2, P, 128};
+    if ((r = blocks(g_, NP, region_, "block0"))) return r;
+    fstages_["tfeat"] = FStage{X_, (int64_t)NP * 2, P, 128};
+    if (fine) {                       // X_ and blk0_ are the fine scale's next: the coarse "tfeat" / "block0" stages exist as debug copies only
+        fstages_.erase("tfeat");
+        if (debug) {
+            PB_HIP(hipMemcpyAsync(tfeat8_, X_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
+            fstages_["tfeat"] = FStage{tfeat8_, (int64_t)NP * 2, P, 128};
+            PB_HIP(hipMemcpyAsync(blk08_, blk0_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
+            fstages_["block0"] = FStage{blk08_, (int64_t)NP * 2, P, 128};
         }
     }
-    fstages_["tfeat"] = FStage{X_, (int64_t)NP * 2, P, 128};
 
     // ---- matching: global (matching.py:7-42: softmax over ALL target tokens of the dot products, expectation of their coordinates) or, with a
     // radius, local (matching.py:39-83: over the (2R + 1)^2 target tokens around the source token; both directions = source and target swapped) ----
     const int64_t img = (int64_t)P * 256;                    // one frame's rows of a split token matrix
     const int img_step = dirs == 2 ? 1 : 2;
-    if (corr_r_ < 0) {
+    if (corr_r < 0) {
         Attn128Args m;
         m.Q = Xs_; m.O = Om_; m.B = B; m.L = P; m.ldv = ldvP_; m.split = split; m.vcols = 32; m.ldq = 256;
         m.Vt = gridvt_; m.v_shared = 1;
@@ -336,9 +457,9 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
         toc();
         if (r) return r;
     } else {
-        const double nc = (2.0 * corr_r_ + 1) * (2.0 * corr_r_ + 1);
+        const double nc = (2.0 * corr_r + 1) * (2.0 * corr_r + 1);
         tic(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4);
-        r = launch_gm_local_match(stream, X_, flowm_, prop_r_ < 0 ? Vtf_ : nullptr, B, h8_, w8_, img_step, corr_r_, ldvP_);
+        r = launch_gm_local_match(stream, X_, flowm_, prop_r < 0 ? Vtf_ : nullptr, B, h8_, w8_, img_step, corr_r, ldvP_);
         if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_match_kernel";
         toc();
         if (r) return r;
@@ -348,7 +469,7 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     // ---- flow propagation (transformer.py:316-337 global, :376-409 local window): self-similarity of the source frame's features spreads the
     // matched flow ----
     if ((r = gemm32(Xs_, 256, R, ffq_, Yq_, 128))) return r;
-    if (prop_r_ < 0) {
+    if (prop_r < 0) {
         tic(F_ELT, 0, 0);
         r = launch_gm_split_rows(stream, Yq_, 128, 128, qs_, R);
         toc();
@@ -365,9 +486,9 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
         if ((r = attention(pa, P))) return r;
     } else {
         if ((r = gemm32(Xs_, 256, R, ffk_, M_, 128))) return r;         // the local form projects the key from the feature itself (:389), not from the query
-        const double nc = (2.0 * prop_r_ + 1) * (2.0 * prop_r_ + 1);
+        const double nc = (2.0 * prop_r + 1) * (2.0 * prop_r + 1);
         tic(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4);
-        r = launch_gm_local_prop(stream, Yq_, M_, flowm_, Om_, B, h8_, w8_, img_step, prop_r_);
+        r = launch_gm_local_prop(stream, Yq_, M_, flowm_, Om_, B, h8_, w8_, img_step, prop_r);
         if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_prop_kernel";
         toc();
         if (r) return r;
@@ -375,19 +496,27 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
 
     // ---- convex upsampling (gmflow.py:74-92), unpad, encode ----
     tic(F_ELT, 0, 0);
+    // (two scales: launched for the coarse flow it leaves in flowp_; the B P x 768 bytes of umap_ it also writes - 29 MB at 1080p x 0.75 with
+    // both directions, microseconds - are overwritten by the fine scale's launch.  The kernel is the one-scale model's, left as it is.)
     r = launch_gm_upsampler_in(stream, Om_, X_, flowp_, umap_, B, P, img_step);
     toc();
     if (r) return r;
     fstages_["flow_prop"] = FStage{flowp_, B, P, 2};
-    if ((r = conv(umap_, 192, 384, B, h8_, w8_, 3, 3, 1, up0_, u1_, 512, ACT_RELU, 0, nullptr, nullptr, split_w_ ? 256 : 0))) return r;
-    if ((r = gemm32(u1_, 512, (int64_t)B * P, up2_, gmask_, 576))) return r;
+    int hu = h8_, wu = w8_, Pu = P, factor = 8;            // the grid the upsampler runs on
+    const float *flow_lo = flowp_;
+    if (fine) {
+        if ((r = fine_scale(B, dirs))) return r;
+        hu = h4_; wu = w4_; Pu = P4_; factor = 4; flow_lo = flowp4_;
+    }
+    if ((r = conv(umap_, 192, 384, B, hu, wu, 3, 3, 1, up0_, u1_, 512, ACT_RELU, 0, nullptr, nullptr, split_w_ ? 256 : 0))) return r;
+    if ((r = gemm32(u1_, 512, (int64_t)B * Pu, up2_, gmask_, 9 * factor * factor))) return r;
     float *up = flow_out ? flow_out : gup_;
     tic(F_PP, 0, (double)B * sh_ * sw_ * 8);
     if (isz_h_ > 0) {                 // convex upsampling at the inference size, then the bilinear resize back to the scaled frame
-        r = launch_upsample(stream, flowp_, gmask_, B, h8_, w8_, 0, 0, Hp_, Wp_, gupi_, gmaxd_);
+        r = launch_upsample(stream, flow_lo, gmask_, B, hu, wu, 0, 0, Hp_, Wp_, gupi_, gmaxd_, factor);
         if (!r) r = launch_flow_resize_back(stream, gupi_, B, Hp_, Wp_, sh_, sw_, up, gmaxd_);
     } else {
-        r = launch_upsample(stream, flowp_, gmask_, B, h8_, w8_, padl_, padt_, sh_, sw_, up, gmaxd_);
+        r = launch_upsample(stream, flow_lo, gmask_, B, hu, wu, padl_, padt_, sh_, sw_, up, gmaxd_, factor);
     }
     toc();
     if (r) return r;
@@ -399,6 +528,58 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     r = launch_fwdbwd_mask(stream, up, NP, sh_, sw_, alpha1, alpha2, mask_out);
     toc();
     return r;
+}
+
+// The fine scale of the two-scale model (gmflow.py:112-165, scale_idx = 1) from the coarse flow in flowp_ [B, P, 2] and the 1/4 features in
+// feat4_: batch element b = (pair, direction) is its own sample - source frame pair + d, target frame pair + 1 - d - because instance norm and
+// every attention are per sample, which is what pred_bidir_flow's concatenation computes.  Leaves the propagated flow in flowp4_ and the
+// upsampler's input map in umap_.
+int GmflowEngine::fine_scale(int B, int dirs) {
+    int r;
+    const int64_t R4 = (int64_t)B * 2 * P4_;
+    PB_CHECK(B * 128 <= 65535, PB_ERR_ARG, "flow_gmflow (two scales): %d (pair, direction) elements in one call; the window kernels take 511 (128 windows each)", B);
+    tic(F_ELT, 0, (double)B * P4_ * 128 * 8);
+    r = launch_gm_warp(stream, flowp_, feat4_, flowu_, warp_, B, dirs, h8_, w8_);
+    if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_warp_kernel";
+    toc();
+    if (r) return r;
+    fstages_["flow_up"] = FStage{flowu_, B, P4_, 2};
+    fstages_["warp"] = FStage{warp_, B, P4_, 128};
+    tic(F_ELT, 0, 0);
+    r = launch_gm_tokens(stream, feat4_, pos4_, X_, Xs_, B, P4_, warp_, dirs);
+    toc();
+    if (r) return r;
+    if ((r = blocks(g4_, B, region4_, "block0_4"))) return r;
+    fstages_["tfeat4"] = FStage{X_, (int64_t)B * 2, P4_, 128};
+    // local matching of (source, warped target): images 2 b and 2 b + 1 of the stream; the residual adds to the enlarged flow (:145)
+    const double nc = (2.0 * corr_r4_ + 1) * (2.0 * corr_r4_ + 1);
+    tic(F_ATTN, 2.0 * B * (double)P4_ * nc * 128.0, 2.0 * (double)B * P4_ * 128 * 4);
+    r = launch_gm_local_match(stream, X_, flowm4_, nullptr, B, h4_, w4_, 2, corr_r4_, 0);
+    if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_match_kernel";
+    toc();
+    if (r) return r;
+    tic(F_ELT, 0, 0);
+    r = launch_gm_flow_add(stream, flowu_, flowm4_, flowf_, (int64_t)B * P4_);
+    toc();
+    if (r) return r;
+    fstages_["flow_match4"] = FStage{flowf_, B, P4_, 2};
+    // the two projections run over the whole stream in one launch each, as at the coarse scale; gm_local_prop reads the source images only
+    // (every other block of P4 rows, which one GEMM launch cannot address), so half of these 2 x 128 x 128 products per row - 0.5 % of the
+    // six blocks' GEMM work on the same rows - go unread
+    if ((r = gemm32(Xs_, 256, R4, ffq_, Yq_, 128))) return r;
+    if ((r = gemm32(Xs_, 256, R4, ffk_, M_, 128))) return r;
+    const double np = (2.0 * prop_r4_ + 1) * (2.0 * prop_r4_ + 1);
+    tic(F_ATTN, 2.0 * B * (double)P4_ * np * 128.0, 2.0 * (double)B * P4_ * 128 * 4);
+    r = launch_gm_local_prop(stream, Yq_, M_, flowf_, Om_, B, h4_, w4_, 2, prop_r4_);
+    if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_prop_kernel";
+    toc();
+    if (r) return r;
+    tic(F_ELT, 0, 0);
+    r = launch_gm_upsampler_in(stream, Om_, X_, flowp4_, umap_, B, P4_, 2);
+    toc();
+    if (r) return r;
+    fstages_["flow_prop4"] = FStage{flowp4_, B, P4_, 2};
+    return 0;
 }
 
 int64_t GmflowEngine::get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) {

@@ -13,10 +13,10 @@ __device__ __forceinline__ void split8(const float (&v)[8], f16x8 &hi, f16x8 &lo
     for (int j = 0; j < 8; ++j) { hi[j] = (f16)v[j]; lo[j] = (f16)(v[j] - (float)hi[j]); }
 }
 
-// window-order row (bw = image * 4 + wy * 2 + wx, pos = ly * ww + lx) -> row of the [images, P] token matrix; the 2 x 2 windows are cut
+// window-order row (bw = (image * ns + wy) * ns + wx, pos = ly * ww + lx) -> row of the [images, P] token matrix; the ns x ns windows are cut
 // from the map rolled by (-shift_y, -shift_x) (torch.roll(x, (-sy, -sx)): rolled[i] = x[(i + s) mod n])
 __device__ __forceinline__ int64_t win_row(int bw, int pos, const GmGeom &g, int shifted) {
-    const int img = bw >> 2, wy = (bw >> 1) & 1, wx = bw & 1;
+    const int iy = bw / g.ns, wx = bw - iy * g.ns, img = iy / g.ns, wy = iy - img * g.ns;
     const int ly = pos / g.ww, lx = pos - ly * g.ww;
     int gy = wy * g.wh + ly + (shifted ? g.wh / 2 : 0), gx = wx * g.ww + lx + (shifted ? g.ww / 2 : 0);
     gy = gy >= g.h8 ? gy - g.h8 : gy;
@@ -24,16 +24,19 @@ __device__ __forceinline__ int64_t win_row(int bw, int pos, const GmGeom &g, int
     return (int64_t)img * g.P + gy * g.w8 + gx;
 }
 
-// X[(n, e), t] = feat[n + e, t] + pos[t]  (both frames of pair n; feature_add_position tiles ONE window's sine embedding over the 2 x 2
-// windows - the table arrives tiled), and its split copy
+// X[(n, e), t] = feat[n + e, t] + pos[t]  (both frames of pair n; feature_add_position tiles ONE window's sine embedding over the
+// windows - the table arrives tiled), and its split copy.  With `warped` (the fine scale of the two-scale model) n is (pair, direction): the
+// source is frame n / dirs + n % dirs and the target's features arrive warped, one map per n.
 __global__ __launch_bounds__(256) void gm_tokens_kernel(const float *__restrict__ feat, const float *__restrict__ pos, float *__restrict__ X,
-                                                        f16 *__restrict__ Xs, int NP, int P) {
+                                                        f16 *__restrict__ Xs, int NP, int P, const float *__restrict__ warped, int dirs) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;         // (row, 8-channel chunk)
     if (i >= (int64_t)NP * 2 * P * 16) return;
     const int ch = (int)(i & 15);
     const int64_t row = i >> 4;
     const int t = (int)(row % P), img = (int)(row / P), n = img >> 1, e = img & 1;
-    const float *f = feat + ((int64_t)(n + e) * P + t) * 128 + ch * 8, *p = pos + (int64_t)t * 128 + ch * 8;
+    const float *f = (warped ? (e ? warped + (int64_t)n * P * 128 : feat + (int64_t)(n / dirs + n % dirs) * P * 128) : feat + (int64_t)(n + e) * P * 128) +
+                     (int64_t)t * 128 + ch * 8;
+    const float *p = pos + (int64_t)t * 128 + ch * 8;
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = f[j] + p[j];
@@ -193,10 +196,68 @@ __global__ __launch_bounds__(256) void gm_upsampler_in_kernel(const float *__res
     *(f16x8 *)(map + px * 384 + 192 + ch * 8) = lo;
 }
 
+// The step between the two scales (gmflow.py:121-126; geometry.py:41-72 flow_warp): one wave per 1/4-resolution token, lane = channel pair.
+//   flow_up = 2 * F.interpolate(flow8, scale_factor = 2, bilinear, align_corners = True): source coordinate y (h8 - 1) / (2 h8 - 1), as
+//   ATen's area_pixel_compute_scale gives it, taps clamped at the last row / column;
+//   warped = grid_sample(feature of the target frame, token + flow_up; bilinear, zeros, align_corners = True).  The reference normalises the
+//   coordinate to [-1, 1] and grid_sample maps it back - an identity up to a few fp32 ulps of the coordinate, restated as the identity here.
+// A tap outside the grid contributes zero; a tap inside reads its token's whole 512-byte row (64 lanes x 8 bytes).  Every lane of a wave
+// computes the same flow and the same four weights from the same operands; lane 0 writes the flow.
+__global__ __launch_bounds__(256) void gm_warp_kernel(const float *__restrict__ flow8, const float *__restrict__ feat4, float *__restrict__ flow_up,
+                                                      float *__restrict__ warped, int B, int dirs, int h8, int w8) {
+    const int h4 = 2 * h8, w4 = 2 * w8;
+    const int64_t P4 = (int64_t)h4 * w4, tok = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tok >= (int64_t)B * P4) return;
+    const int lane = threadIdx.x & 63;
+    const int b = (int)(tok / P4), t = (int)(tok - (int64_t)b * P4), y = t / w4, x = t - y * w4;
+    const float sy = (float)(h8 - 1) / (float)(h4 - 1), sx = (float)(w8 - 1) / (float)(w4 - 1);
+    const float fy = sy * (float)y, fx = sx * (float)x;
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < h8 - 1 ? 1 : 0), x1 = x0 + (x0 < w8 - 1 ? 1 : 0);
+    const float ly = fy - (float)y0, lx = fx - (float)x0;
+    const float *f8 = flow8 + (int64_t)b * h8 * w8 * 2;
+    const f32x2 p00 = *(const f32x2 *)(f8 + ((int64_t)y0 * w8 + x0) * 2), p01 = *(const f32x2 *)(f8 + ((int64_t)y0 * w8 + x1) * 2);
+    const f32x2 p10 = *(const f32x2 *)(f8 + ((int64_t)y1 * w8 + x0) * 2), p11 = *(const f32x2 *)(f8 + ((int64_t)y1 * w8 + x1) * 2);
+    float uv[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+        uv[c] = 2.f * ((1.f - ly) * ((1.f - lx) * p00[c] + lx * p01[c]) + ly * ((1.f - lx) * p10[c] + lx * p11[c]));
+    if (lane == 0) *(f32x2 *)(flow_up + tok * 2) = f32x2{uv[0], uv[1]};
+    // sample position and its four taps
+    const float gx = (float)x + uv[0], gy = (float)y + uv[1];
+    const float flx = floorf(gx), fly = floorf(gy);
+    const float ax = gx - flx, ay = gy - fly;
+    // (a position far outside, NaN included, keeps every tap outside: the casts below are of values clamped to the grid's neighbourhood)
+    const float cx = fminf(fmaxf(flx, -2.f), (float)w4), cy = fminf(fmaxf(fly, -2.f), (float)h4);
+    const int ix = (int)cx, iy = (int)cy;
+    const int pair = b / dirs, d = b - pair * dirs;
+    const float *src = feat4 + (int64_t)(pair + 1 - d) * P4 * 128 + lane * 2;
+    const float wgt[4] = {(1.f - ay) * (1.f - ax), (1.f - ay) * ax, ay * (1.f - ax), ay * ax};
+    f32x2 acc = {0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int yy = iy + (k >> 1), xx = ix + (k & 1);
+        if ((unsigned)yy < (unsigned)h4 && (unsigned)xx < (unsigned)w4) {
+            const f32x2 v = *(const f32x2 *)(src + ((int64_t)yy * w4 + xx) * 128);
+            acc[0] += wgt[k] * v[0]; acc[1] += wgt[k] * v[1];
+        }
+    }
+    *(f32x2 *)(warped + tok * 128 + lane * 2) = acc;
+}
+
+// gmflow.py:145 at the fine scale: flow = enlarged flow + matched residual, n flows of 2
+__global__ void gm_flow_add_kernel(const float *__restrict__ a, const float *__restrict__ b, float *__restrict__ out, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const f32x2 x = *(const f32x2 *)(a + i * 2), y = *(const f32x2 *)(b + i * 2);
+    *(f32x2 *)(out + i * 2) = f32x2{x[0] + y[0], x[1] + y[1]};
+}
+
 }  // namespace
 
-int launch_gm_tokens(hipStream_t s, const float *feat, const float *pos, float *X, f16 *Xs, int NP, int P) {
-    hipLaunchKernelGGL(gm_tokens_kernel, dim3(nblk((int64_t)NP * 2 * P * 16)), dim3(256), 0, s, feat, pos, X, Xs, NP, P);
+int launch_gm_tokens(hipStream_t s, const float *feat, const float *pos, float *X, f16 *Xs, int NP, int P, const float *warped, int dirs) {
+    PB_CHECK(dirs == 1 || (dirs == 2 && warped), PB_ERR_ARG, "gm_tokens: dirs = %d", dirs);
+    hipLaunchKernelGGL(gm_tokens_kernel, dim3(nblk((int64_t)NP * 2 * P * 16)), dim3(256), 0, s, feat, pos, X, Xs, NP, P, warped, dirs);
     PB_HIP(hipGetLastError());
     return 0;
 }
@@ -225,6 +286,17 @@ int launch_gm_grid_vt(hipStream_t s, f16 *vt, int P, int w8, int ldv) {
 }
 int launch_gm_match_flow(hipStream_t s, const float *O, float *flow, f16 *vt, int B, int P, int w8, int ldv) {
     hipLaunchKernelGGL(gm_match_flow_kernel, dim3(nblk((int64_t)B * P)), dim3(256), 0, s, O, flow, vt, B, P, w8, ldv);
+    PB_HIP(hipGetLastError());
+    return 0;
+}
+int launch_gm_warp(hipStream_t s, const float *flow8, const float *feat4, float *flow_up, float *warped, int B, int dirs, int h8, int w8) {
+    PB_CHECK(B > 0 && (dirs == 1 || dirs == 2) && B % dirs == 0 && h8 >= 2 && w8 >= 2, PB_ERR_ARG, "gm_warp: B = %d, dirs = %d, grid %d x %d", B, dirs, h8, w8);
+    hipLaunchKernelGGL(gm_warp_kernel, dim3(nblk((int64_t)B * 4 * h8 * w8, 4)), dim3(256), 0, s, flow8, feat4, flow_up, warped, B, dirs, h8, w8);
+    PB_HIP(hipGetLastError());
+    return 0;
+}
+int launch_gm_flow_add(hipStream_t s, const float *a, const float *b, float *out, int64_t n) {
+    hipLaunchKernelGGL(gm_flow_add_kernel, dim3(nblk(n)), dim3(256), 0, s, a, b, out, n);
     PB_HIP(hipGetLastError());
     return 0;
 }

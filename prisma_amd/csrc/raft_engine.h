@@ -37,6 +37,7 @@ class RaftEngine : public EngineBase {
     int upload_resize_tables(int H, int W, float scale);
     int prepare(int F, int H, int W, float scale, int dirs);
     Enc fnet_, cnet_;
+    int enc_s3_ = 2;            // stride of the encoder's third stage: 1 = its output stays at 1/4 (the two-scale GMFlow backbone, backbone.py:58-62)
     PackedW convc1_, convc2_, convf1_, convf2_, convm_, zr_[2], q_[2], fh1_, fh2_, mk0_, mk2_;
     // convf1 as a direct kernel on the fp32 flow field (raft_kernels.hip convf1_kernel; PB_CONVF1_DIRECT=0: im2col + GEMM as in rounds 1-3)
     f16 *f1w_ = nullptr;

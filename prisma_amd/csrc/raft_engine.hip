@@ -319,7 +319,7 @@ void RaftEngine::carve_encoder(int F) {
     img_ = (f16 *)carve((size_t)F * Hp_ * Wp_ * 8 * es);
     for (auto &b : r1_) b = (f16 *)carve((size_t)round_up((int64_t)F * h2 * w2, 256) * 64 * 2 * es);
     for (auto &b : r2_) b = (f16 *)carve((size_t)round_up((int64_t)F * h4 * w4, 256) * 128 * 2 * es);
-    for (auto &b : r3_) b = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 128 * 2 * es);
+    for (auto &b : r3_) b = (f16 *)carve((size_t)round_up((int64_t)F * (enc_s3_ == 1 ? h4 * w4 : P_), 256) * 128 * 2 * es);
     for (auto &b : st_) b = (float *)carve((size_t)F * 256 * 2 * 4);
     stp_ = (float *)carve((size_t)in_stats_chunks(h2 * w2) * F * 256 * 2 * 4);     // per-chunk partial sums of the largest map
 }
@@ -340,7 +340,7 @@ int RaftEngine::upload_resize_tables(int H, int W, float scale) {
 
 // BasicEncoder.forward (extractor.py:171-192) without its last 1x1 convolution, on the F prepared frames in img_: stem, three stages of two
 // residual blocks.  inorm: InstanceNorm with run-time statistics (fnet; GMFlow's backbone) - otherwise the folded BatchNorm path (cnet).
-// *x_out = the last block's output map [F, h8, w8, 128] (split-fp16 layout in PB_PREC_SPLIT).
+// *x_out = the last block's output map [F, h8, w8, 128] (split-fp16 layout in PB_PREC_SPLIT); with enc_s3_ = 1 [F, Hp / 4, Wp / 4, 128].
 int RaftEngine::run_encoder(const Enc &E, bool inorm, int F, const f16 **x_out) {
     int r = 0;
     const int h2 = Hp_ / 2, w2 = Wp_ / 2;
@@ -390,11 +390,12 @@ int RaftEngine::run_encoder(const Enc &E, bool inorm, int F, const f16 **x_out) 
     }
     int H_ = h2, W_ = w2, C_ = 64;
     for (int li = 0; li < 3; ++li) {
-        const int stride = li == 0 ? 1 : 2;
+        const int stride = li == 0 ? 1 : (li == 2 ? enc_s3_ : 2);
         const int Cn = li == 0 ? 64 : 128;               // 96 is carried as 128 (zero padded channels)
         f16 **R = li == 0 ? r1_ : (li == 1 ? r2_ : r3_);
         for (int bi = 0; bi < 2; ++bi) {                  // ResidualBlock.forward (extractor.py:46-56)
             const int s = bi == 0 ? stride : 1;
+            const bool ds = bi == 0 && li > 0;            // the block changes stride or channel count: 1 x 1 convolution + norm on the skip path
             const int OH = (H_ - 1) / s + 1, OW = (W_ - 1) / s + 1;
             const int Cin = bi == 0 ? C_ : Cn;
             f16 *t1 = R[0], *t2 = R[1], *t3 = R[2], *outb = R[3 + bi];
@@ -404,7 +405,7 @@ int RaftEngine::run_encoder(const Enc &E, bool inorm, int F, const f16 **x_out) 
                 if ((r = norm_relu(t1, st_[0], t1, OH * OW, Cn, nullptr, nullptr))) return r;
                 if ((r = conv(t1, Cn, es * Cn, F, OH, OW, 3, 3, 1, E.l[li][bi][1], t2, es * Cn, ACT_NONE, 0, nullptr, nullptr, lo(Cn)))) return r;
                 if ((r = stats(t2, st_[1], OH * OW, Cn))) return r;
-                if (s != 1) {
+                if (ds) {
                     if ((r = conv(x, Cin, es * Cin, F, H_, W_, 1, 1, s, E.ds[li], t3, es * Cn, ACT_NONE, 0, nullptr, nullptr, lo(Cn)))) return r;
                     if ((r = stats(t3, st_[2], OH * OW, Cn))) return r;
                     if ((r = norm_relu(t2, st_[1], outb, OH * OW, Cn, t3, st_[2]))) return r;
@@ -414,7 +415,7 @@ int RaftEngine::run_encoder(const Enc &E, bool inorm, int F, const f16 **x_out) 
             } else {
                 if ((r = conv(x, Cin, es * Cin, F, H_, W_, 3, 3, s, E.l[li][bi][0], t1, es * Cn, ACT_RELU, 0, nullptr, nullptr, lo(Cn)))) return r;
                 const f16 *xs = x;
-                if (s != 1) {
+                if (ds) {
                     if ((r = conv(x, Cin, es * Cin, F, H_, W_, 1, 1, s, E.ds[li], t3, es * Cn, ACT_NONE, 0, nullptr, nullptr, lo(Cn)))) return r;
                     xs = t3;
                 }

@@ -42,8 +42,9 @@ int launch_put_flow(hipStream_t s, const float *flow, f16 *hx, f16 *hx2, int64_t
                     int flow_off = 382);       // flow_off: channel offset of the two flow channels inside hx / hx2
 // flow_gmflow --inference_size: flow [N, ih, iw, 2] -> [N, sh, sw, 2], bilinear (align_corners), u * sw / iw, v * sh / ih; maxd as launch_upsample
 int launch_flow_resize_back(hipStream_t s, const float *in, int N, int ih, int iw, int sh, int sw, float *out, unsigned *maxd);
+// factor 8: mask rows of 576; factor 4 (two-scale GMFlow, flow and mask on the 1/4 grid h8 x w8): mask rows of 144
 int launch_upsample(hipStream_t s, const float *flow, const float *mask, int N, int h8, int w8, int pad_l, int pad_t, int sh,
-                    int sw, float *out, unsigned *maxd);
+                    int sw, float *out, unsigned *maxd, int factor = 8);
 int launch_flow_encode(hipStream_t s, const float *flow, int N, int sh, int sw, const unsigned *maxd, uint8_t *rgb,
                        float *max_out);
 int launch_fwdbwd_mask(hipStream_t s, const float *flow, int n, int h, int w, float a1, float a2, uint8_t *mask);

@@ -638,21 +638,25 @@ __device__ __forceinline__ unsigned f2ord_(float f) {
     return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
-// one wave per 1/8-resolution pixel, lane = sub-pixel (sy * 8 + sx): the nine 64-wide mask groups are coalesced reads
+// one wave per 64 / (K * K) low-resolution pixels, lane = (pixel of the wave, sub-pixel sy * K + sx): the nine K * K-wide mask groups are
+// coalesced reads.  K = 8: RAFT and one-scale GMFlow (one pixel per wave); K = 4: the two-scale GMFlow's 1/4 grid (gmflow.py:74-90 with
+// upsample_factor 4: four pixels per wave, mask rows of 144)
+template <int K>
 __global__ __launch_bounds__(256) void upsample_kernel(const float *__restrict__ flow, const float *__restrict__ mask, int h8,
                                                         int w8, int pad_l, int pad_t, int sh, int sw,
                                                         float *__restrict__ out, unsigned *__restrict__ maxd) {
+    constexpr int KK = K * K, PW = 64 / KK;          // sub-pixels of a pixel, pixels of a wave
     const int n = blockIdx.y;
     const int P = h8 * w8;
     float dmax = 0.f;
-    const int sub = threadIdx.x & 63;
+    const int sub = threadIdx.x & (KK - 1), pw = (threadIdx.x & 63) / KK;
     // grid-stride over the low-res pixels so that a wave issues ONE atomicMax at the end (same-address atomics serialise)
-    for (int p = blockIdx.x * 4 + (threadIdx.x >> 6); p < P; p += gridDim.x * 4) {
+    for (int p = (blockIdx.x * 4 + (threadIdx.x >> 6)) * PW + pw; p < P; p += gridDim.x * 4 * PW) {
         const int py = p / w8, px = p - py * w8;
-        const float *m = mask + ((int64_t)n * P + p) * 576 + sub;
+        const float *m = mask + ((int64_t)n * P + p) * (9 * KK) + sub;
         float e[9], mx = -INFINITY;
 #pragma unroll
-        for (int k = 0; k < 9; ++k) { e[k] = m[k * 64]; mx = fmaxf(mx, e[k]); }
+        for (int k = 0; k < 9; ++k) { e[k] = m[k * KK]; mx = fmaxf(mx, e[k]); }
         float den = 0.f;
 #pragma unroll
         for (int k = 0; k < 9; ++k) { e[k] = __expf(e[k] - mx); den += e[k]; }
@@ -663,11 +667,11 @@ __global__ __launch_bounds__(256) void upsample_kernel(const float *__restrict__
             if ((unsigned)yy < (unsigned)h8 && (unsigned)xx < (unsigned)w8) {
                 const float *f = flow + ((int64_t)n * P + yy * w8 + xx) * 2;
                 const float wgt = e[k] / den;
-                u += wgt * (8.f * f[0]);
-                v += wgt * (8.f * f[1]);
+                u += wgt * ((float)K * f[0]);
+                v += wgt * ((float)K * f[1]);
             }
         }
-        const int oy = py * 8 + (sub >> 3) - pad_t, ox = px * 8 + (sub & 7) - pad_l;
+        const int oy = py * K + sub / K - pad_t, ox = px * K + (sub & (K - 1)) - pad_l;
         if ((unsigned)oy < (unsigned)sh && (unsigned)ox < (unsigned)sw) {
             float *o = out + (((int64_t)n * sh + oy) * sw + ox) * 2;
             o[0] = u; o[1] = v;
@@ -930,10 +934,15 @@ int launch_flow_head2(hipStream_t s, const f16 *x, const f16 *w, const float *bi
     LAUNCH_CHECK();
 }
 int launch_upsample(hipStream_t s, const float *flow, const float *mask, int N, int h8, int w8, int pad_l, int pad_t, int sh,
-                    int sw, float *out, unsigned *maxd) {
+                    int sw, float *out, unsigned *maxd, int factor) {
+    PB_CHECK(factor == 8 || factor == 4, -1, "upsample: factor %d (8 or 4)", factor);
     hipLaunchKernelGGL(fill_u32_kernel, dim3(nblk(N)), dim3(256), 0, s, maxd, 0u, N);
-    hipLaunchKernelGGL(upsample_kernel, dim3(std::min(nblk((int64_t)h8 * w8, 4), 256u), N), dim3(256), 0, s, flow, mask, h8, w8, pad_l, pad_t, sh,
-                       sw, out, maxd);
+    if (factor == 8)
+        hipLaunchKernelGGL(upsample_kernel<8>, dim3(std::min(nblk((int64_t)h8 * w8, 4), 256u), N), dim3(256), 0, s, flow, mask, h8, w8, pad_l, pad_t, sh,
+                           sw, out, maxd);
+    else
+        hipLaunchKernelGGL(upsample_kernel<4>, dim3(std::min(nblk((int64_t)h8 * w8, 16), 256u), N), dim3(256), 0, s, flow, mask, h8, w8, pad_l, pad_t,
+                           sh, sw, out, maxd);
     LAUNCH_CHECK();
 }
 // flow_gmflow --inference_size, the way back (reference flow_gmflow.py:92-97): F.interpolate(bilinear, align_corners = True) of the flow from the

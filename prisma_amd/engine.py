@@ -239,10 +239,11 @@ def raft_geometry(h8: int, w8: int) -> List[dict]:
     return [dict(h=geo[l * 5], w=geo[l * 5 + 1], wp=geo[l * 5 + 2], hp=geo[l * 5 + 3], ld=geo[l * 5 + 4]) for l in range(4)]
 
 
-def gm_geometry(h8: int, w8: int) -> dict:
-    """the flow_gmflow band's window geometry of an h8 x w8 token grid (csrc gm_geometry): P, window wh x ww = Lw tokens, V^T row strides"""
-    P, wh, ww = h8 * w8, h8 // 2, w8 // 2
-    return dict(h8=h8, w8=w8, P=P, wh=wh, ww=ww, Lw=wh * ww, ldv=-(-(wh * ww) // 32) * 32, ldvP=-(-P // 32) * 32)
+def gm_geometry(h8: int, w8: int, splits: int = 2) -> dict:
+    """the flow_gmflow band's window geometry of an h8 x w8 token grid (csrc gm_geometry): P, window wh x ww = Lw tokens, V^T row strides;
+    splits = 8: the two-scale model's 1/4 grid"""
+    P, wh, ww = h8 * w8, h8 // splits, w8 // splits
+    return dict(h8=h8, w8=w8, P=P, wh=wh, ww=ww, Lw=wh * ww, ldv=-(-(wh * ww) // 32) * 32, ldvP=-(-P // 32) * 32, ns=splits)
 
 
 def gm_tables(h8: int, w8: int):
@@ -251,6 +252,14 @@ def gm_tables(h8: int, w8: int):
     pos = np.empty((h8 * w8, 128), np.float32)
     reg = np.empty((4, (h8 // 2) * (w8 // 2)), np.int8)
     check(_lib.load().pb_op_gm_tables(h8, w8, _ptr(pos), _ptr(reg)))
+    return pos, reg
+
+
+def gm_tables_n(h: int, w: int, splits: int):
+    """gm_tables for a grid cut into splits x splits windows (2 or 8; pb_op_gm_tables_n): pos [P, 128], region ids [splits^2, Lw]"""
+    pos = np.empty((h * w, 128), np.float32)
+    reg = np.empty((splits * splits, (h // splits) * (w // splits)), np.int8)
+    check(_lib.load().pb_op_gm_tables_n(h, w, splits, _ptr(pos), _ptr(reg)))
     return pos, reg
 
 
@@ -478,6 +487,74 @@ class Ops(_Ctx):
         Xs = np.empty((R + guard_rows, 512), np.uint8)
         check(self.lib.pb_op_gm_tokens(self.ctx, _ptr(feat), _ptr(pos), F - 1, P, guard_rows, _ptr(X), _ptr(Xs)))
         return X, Xs
+
+    # ---- the two-scale model's forms (tests/test_gpu_gmflow_scale2_ops.py) ----
+    def gm_tokens_warped(self, feat, warped, pos, dirs: int, guard_rows: int = 8):
+        """feat [B / dirs + 1, P, 128], warped [B, P, 128], pos [P, 128] -> (X float32 [2 B P + guard, 128], Xs raw [.., 512]): image 2 b is
+        frame b // dirs + b % dirs plus pos, image 2 b + 1 is warped[b] plus pos"""
+        feat, warped, pos = _f32(feat), _f32(warped), _f32(pos)
+        B, P, _ = warped.shape
+        assert feat.shape == (B // dirs + 1, P, 128) and pos.shape == (P, 128) and B % dirs == 0
+        X = np.empty((2 * B * P + guard_rows, 128), np.float32)
+        Xs = np.empty((2 * B * P + guard_rows, 512), np.uint8)
+        check(self.lib.pb_op_gm_tokens_warped(self.ctx, _ptr(feat), _ptr(warped), _ptr(pos), B, dirs, P, guard_rows, _ptr(X), _ptr(Xs)))
+        return X, Xs
+
+    def gm_warp(self, flow8, feat4, h8: int, w8: int, dirs: int, guard_rows: int = 8):
+        """flow8 [B, h8 w8, 2], feat4 [B / dirs + 1, 4 h8 w8, 128] -> raw (flow_up [4 B h8 w8 + guard, 2], warped [4 B h8 w8 + guard, 128])"""
+        flow8, feat4 = _f32(flow8), _f32(feat4)
+        B, P8 = flow8.shape[0], h8 * w8
+        assert flow8.shape == (B, P8, 2) and feat4.shape == (B // dirs + 1, 4 * P8, 128) and B % dirs == 0
+        up = np.empty((4 * B * P8 + guard_rows, 2), np.float32)
+        wp = np.empty((4 * B * P8 + guard_rows, 128), np.float32)
+        check(self.lib.pb_op_gm_warp(self.ctx, _ptr(flow8), _ptr(feat4), B, dirs, h8, w8, guard_rows, _ptr(up), _ptr(wp)))
+        return up, wp
+
+    def gm_upsample(self, flow, mask, h: int, w: int, factor: int, pad_l: int, pad_t: int, sh: int, sw: int, guard: int = 16):
+        """flow [n, h w, 2], mask [n, h w, 9 factor^2] -> (raw up float32 [n sh sw 2 + guard], max displacement [n]); factor 8 or 4"""
+        flow, mask = _f32(flow), _f32(mask)
+        n = flow.shape[0]
+        assert flow.shape == (n, h * w, 2) and mask.shape == (n, h * w, 9 * factor * factor)
+        up = np.empty(n * sh * sw * 2 + guard, np.float32)
+        mx = np.empty(n, np.float32)
+        check(self.lib.pb_op_gm_upsample(self.ctx, _ptr(flow), _ptr(mask), n, h, w, factor, pad_l, pad_t, sh, sw, guard, _ptr(up), _ptr(mx)))
+        return up, mx
+
+    def gm_pack_n(self, src, h: int, w: int, splits: int, jobs, shifted: bool, guard_rows: int = 8):
+        """gm_pack over splits x splits windows: per job raw [splits^2 images Lw + guard, 512] or [splits^2 images 256 + guard, 2 ldv]"""
+        src = _f32(src)
+        g = gm_geometry(h, w, splits)
+        images, ld, nw = src.shape[0] // g["P"], src.shape[1], splits * splits
+        assert src.shape[0] == images * g["P"] and 1 <= len(jobs) <= 5
+        outs = [np.empty((images * nw * 256 + guard_rows, g["ldv"] * 2) if vt else (images * nw * g["Lw"] + guard_rows, 512), np.uint8) for _, vt in jobs]
+        cols = (C.c_int * 5)(*[c for c, _ in jobs])
+        kinds = (C.c_int * 5)(*[int(vt) for _, vt in jobs])
+        ptrs = (C.c_void_p * 5)(*[o.ctypes.data for o in outs])
+        check(self.lib.pb_op_gm_pack_n(self.ctx, _ptr(src), images, h, w, splits, ld, len(jobs), cols, kinds, int(shifted), guard_rows, ptrs))
+        return outs
+
+    def gm_ln_n(self, M, gamma, beta, X, h: int, w: int, splits: int, windowed: bool, shifted: bool, mode: int, guard_rows: int = 8):
+        """gm_ln over splits x splits windows"""
+        M, gamma, beta, X = _f32(M), _f32(gamma), _f32(beta), _f32(X)
+        rows, xrows = M.shape[0], X.shape[0]
+        Xb = np.empty((xrows + guard_rows, 128), np.float32)
+        Xb.view(np.uint8)[...] = 0xFF
+        Xb[:xrows] = X
+        out = np.empty((xrows + guard_rows, 1024 if mode else 512), np.uint8)
+        check(self.lib.pb_op_gm_ln_n(self.ctx, _ptr(M), _ptr(gamma), _ptr(beta), _ptr(Xb), rows, xrows, h, w, splits, int(windowed), int(shifted), mode,
+                                     guard_rows, _ptr(out)))
+        return Xb, out
+
+    def gm_window_block_n(self, Y, X, gamma, beta, h: int, w: int, splits: int, shifted: bool, cross: bool, split: int = 1,
+                          pv_single: bool = False) -> np.ndarray:
+        """gm_window_block over splits x splits windows; pv_single False: P and V split, the attention a two-scale context launches (True: the
+        one-scale model's, gm_window_block's)"""
+        Y, X, gamma, beta = _f32(Y), _f32(X).copy(), _f32(gamma), _f32(beta)
+        images = X.shape[0] // (h * w)
+        assert X.shape == (images * h * w, 128) and Y.shape == (X.shape[0], 384)
+        check(self.lib.pb_op_gm_window_block_n(self.ctx, _ptr(Y), _ptr(X), _ptr(gamma), _ptr(beta), images, h, w, splits, int(shifted), int(cross), split,
+                                               int(pv_single)))
+        return X
 
     def gm_split_rows(self, src, Cc: int, guard_rows: int = 8) -> np.ndarray:
         """src [rows, ld >= Cc] -> raw [rows + guard, 4 Cc] ([hi | lo] halfs)"""
@@ -831,12 +908,21 @@ class FlowRaft(_Ctx):
 
 
 class FlowGMFlow(FlowRaft):
-    """GMFlow optical-flow band on one GPU (bands/flow_gmflow.py:42-118 init_model / infer; the model at the band's default flags).
+    """GMFlow optical-flow band on one GPU (bands/flow_gmflow.py:42-118 init_model / infer; the model at the band's default flags, or - when
+    the weights are a two-scale state dict - GMFlow's refinement model, see num_scales).
 
     weights: reference checkpoint naming (backbone.*, transformer.layers.N.*, feature_flow_attn.*, upsampler.*).  Same calls as FlowRaft
-    (`iters` is ignored: GMFlow is not iterative; frames are padded to multiples of 16).  stage(): "feat", "block0", "tfeat" as
-    [frames, tokens, 128], "flow_match", "flow_prop" as [pairs * dirs, tokens, 2]."""
+    (`iters` is ignored: GMFlow is not iterative; frames are padded to multiples of 16, of 32 with two scales).  stage(): "feat", "block0",
+    "tfeat" as [frames, tokens, 128], "flow_match", "flow_prop" as [pairs * dirs, tokens, 2] (with two scales: the coarse scale's; the fine
+    scale's are "feat4", "flow_up", "warp", "block0_4", "tfeat4", "flow_match4", "flow_prop4" on the 1/4 grid; there the coarse "tfeat" and
+    "block0" exist only after a call under set_profiling(debug_stages=True))."""
     BAND = b"flow_gmflow"
+
+    @property
+    def num_scales(self) -> int:
+        """1: the band's default model; 2: the refinement model (num_scales 2, upsample_factor 4, padding_factor 32, attn_splits_list 2 8) -
+        decided by the weights (backbone.trident_conv.weight and an upsampler.2.weight of 144 rows)"""
+        return int(check(self.lib.pb_flow_num_scales(self.ctx)))
 
     def set_inference_size(self, size=None):
         """--inference_size H W of the band (reference flow_gmflow.py:76-100): run the network on a bilinear (align_corners) resize of the
@@ -847,7 +933,10 @@ class FlowGMFlow(FlowRaft):
     def set_matching(self, corr_radius: int = -1, prop_radius: int = -1):
         """--corr_radius_list R / --prop_radius_list r of the band (reference gmflow.py:128-157): -1 = global (the default); R in 1 .. 4 =
         local matching over (2 R + 1)^2 target tokens; r in 1 .. 2 = local-window propagation.  With a matching radius the backward flow is
-        the forward flow of the swapped pair (the reference's pred_bidir_flow raises there)."""
+        the forward flow of the swapped pair (the reference's pred_bidir_flow raises there).
+        With two scales (num_scales == 2) these are the FINE scale's radii, the reference's --corr_radius_list -1 R --prop_radius_list -1 r:
+        R in 1 .. 4, r in 1 .. 2, default (4, 1); -1 is refused (nothing global is built on the 1/4 grid) and the context stays as it was.
+        The coarse scale is always global."""
         check(self.lib.pb_flow_set_matching(self.ctx, int(corr_radius), int(prop_radius)))
 
 

@@ -511,9 +511,14 @@ def zoe_weights(seed: int = 2468) -> Dict[str, np.ndarray]:
 # ---------------------------------------------------------------------------
 # GMFlow (bands/flow_gmflow.py defaults: feature_channels 128, 1 scale, 1 head, swin attention with 2 x 2 splits, 6 blocks, ffn x 4)
 # ---------------------------------------------------------------------------
-def gmflow_param_shapes(channels: int = 128, layers: int = 6, ffn: int = 4, upsample: int = 8):
+def gmflow_param_shapes(channels: int = 128, layers: int = 6, ffn: int = 4, upsample: int = None, num_scales: int = 1):
     """(name, shape) of every tensor of the reference's GMFlow state_dict at the band's defaults (bands/gmflow/gmflow.py:12-47,
-    backbone.py:5-117, transformer.py:104-139, 284-298).  InstanceNorm2d layers are affine-free: no entries."""
+    backbone.py:5-117, transformer.py:104-139, 284-298).  InstanceNorm2d layers are affine-free: no entries.  num_scales = 2: the refinement
+    model (GMFlow(num_scales=2, upsample_factor=4)) - the backbone's one bias-free trident convolution (trident_conv.py:30-40) and an
+    upsampler of 4 * 4 * 9 logits; every other tensor has the one-scale model's name and shape."""
+    assert num_scales in (1, 2)
+    if upsample is None:
+        upsample = 8 if num_scales == 1 else 4
     C = channels
     out = [("backbone.conv1.weight", (64, 3, 7, 7))]
     cin = 64
@@ -525,6 +530,8 @@ def gmflow_param_shapes(channels: int = 128, layers: int = 6, ffn: int = 4, upsa
                 out += [(p + "downsample.0.weight", (dim, cin, 1, 1)), (p + "downsample.0.bias", (dim,))]
         cin = dim
     out += [("backbone.conv2.weight", (C, 128, 1, 1)), ("backbone.conv2.bias", (C,))]
+    if num_scales == 2:
+        out += [("backbone.trident_conv.weight", (C, C, 3, 3))]
     for i in range(layers):
         for part, has_ffn in (("self_attn", False), ("cross_attn_ffn", True)):
             p = f"transformer.layers.{i}.{part}."
@@ -540,12 +547,13 @@ def gmflow_param_shapes(channels: int = 128, layers: int = 6, ffn: int = 4, upsa
     return out
 
 
-def gmflow_weights(seed: int = 2468) -> Dict[str, np.ndarray]:
+def gmflow_weights(seed: int = 2468, num_scales: int = 1) -> Dict[str, np.ndarray]:
     """Seeded float32 tensors under the reference's state_dict names.  Scales keep the network in the regime of a trained one: unit-scale
     features out of the backbone, LayerNorm'd messages at ~0.3 of the stream they are added to, so the matching softmax is sharply peaked on
-    the true correspondence of the translated synthetic texture without being a hard argmax."""
+    the true correspondence of the translated synthetic texture without being a hard argmax.  Every tensor is seeded by its name, so the
+    tensors the one- and two-scale models share are bit-identical; the two-scale upsampler.2 is its own draw (another shape)."""
     w: Dict[str, np.ndarray] = {}
-    for name, shape in gmflow_param_shapes():
+    for name, shape in gmflow_param_shapes(num_scales=num_scales):
         g = _rng(seed, name)
         if ".norm" in name:
             w[name] = ((0.3 + 0.03 * g.standard_normal(shape, dtype=np.float32)) if name.endswith("weight")
