@@ -525,6 +525,48 @@ int pb_op_gm_propagate(pb_ctx *ctx, const float *q, const float *k, const float 
 int pb_op_gm_local_match(pb_ctx *ctx, const float *tokens, int NP, int h8, int w8, int dirs, int radius, int guard_rows, float *flow);
 int pb_op_gm_local_propagate(pb_ctx *ctx, const float *q, const float *k, const float *flow_in, int B, int h8, int w8, int img_step, int radius,
                              int guard_rows, float *flow_out);
+/* The mask_mmdet band's own kernels one by one, through the launchers of mask_kernels.h with MaskEngine's arguments (tests/test_gpu_mask_ops.py).
+ * Maps are rows of fp16: C halfs, or [hi (C) | lo (C)] with split; row strides L(C) = C (1 + split) unless ldi / ldo say otherwise (then the
+ * halfs a row does not define are NaNs on the way in).  Inputs are fp32 and are rounded to the layout on the host (hi = fp16(v),
+ * lo = fp16(v - hi)).  Raw outputs are preset to 0xFF bytes and carry guard_rows untouched rows (guard: elements).
+ * prep: frames uint8 [n, H, W, 3], xt [nw, 4] / yt [nh, 4] = {i0, i1, c0, c1} -> out (n Hp/4 Wp/4 + guard) x 64 (1 + split) halfs, chw 3 n Hp Wp + guard floats.
+ * maxpool / subsample2 / nearest_add / coord_concat / bilinear: x [rows, C] NHWC.  nearest_add returns dst += src; bilinear accumulates into y0
+ *   when it is given.  coord_concat writes C + 64 channels per part.
+ * gn_relu: layout 0 fp16 -> fp16, 1 split -> split, 2 split -> [hi | hi | lo] rows of 3 C halfs; aff [n, C, 2] = the per-channel (rstd gamma, group mean).
+ * cls_points_nms: logit [n, g g, C] -> score (n pts_total + guard) x C floats, this level's cells from row `off` of every frame.
+ * gather_rows: src [src_rows, cols], idx [count] -> (rows_pad + guard) x cols (1 + split) halfs.
+ * stats: logit [rows, ld] -> (rows + guard) x {area, soft sum}.
+ * intersections: bitpack_rows of rows idx[0 .. n) of logit [src_rows, ld], then mask_intersections with ld 512: bits (n + guard) x HW / 64 words,
+ *   inter [inter_rows, 512] floats returned whole.
+ * matrix_nms: inter [n, 512], area / label / score [n] -> comp, out (n + guard) floats.
+ * sigmoid_rows: -> (count + guard) x HW floats.
+ * dynconv: post_chunk's dynamic convolution.  gather_rows builds A from kernels [src_rows, 256] and idx [row_off + M]; the launch reads its rows
+ *   from row_off (a multiple of 8); feat [HW4, 256] is laid out as gn_relu's layout 0 / 2 output; out (M + guard) x HW4 floats.
+ * band_accumulate: sig [k, fh, fw], use [k] -> out 3 H W + guard bytes, inst k H W + guard bytes (NULL: not computed). */
+int pb_op_mask_prep(pb_ctx *ctx, const uint8_t *frames, int n, int H, int W, int nh, int nw, int Hp, int Wp, const int *xt, const int *yt, int split,
+                    int guard_rows, void *out, float *chw);
+int pb_op_mask_maxpool(pb_ctx *ctx, const float *x, int n, int H, int W, int C, int split, int guard_rows, void *out);
+int pb_op_mask_nearest_add(pb_ctx *ctx, const float *dst, const float *src, int n, int h, int w, int sh, int sw, int C, int split, int guard_rows,
+                           void *out);
+int pb_op_mask_subsample2(pb_ctx *ctx, const float *x, int n, int H, int W, int C, int split, int guard_rows, void *out);
+int pb_op_mask_coord_concat(pb_ctx *ctx, const float *x, int n, int h, int w, int C, int ldi, int split, int guard_rows, void *out);
+int pb_op_mask_bilinear(pb_ctx *ctx, const float *x, const float *y0, int n, int H, int W, int OH, int OW, int C, int ldi, int ldo, int split,
+                        int guard_rows, void *out);
+int pb_op_mask_gn_relu(pb_ctx *ctx, const float *x, const float *gamma, const float *beta, int n, int HW, int C, int layout, int guard_rows, void *out,
+                       float *aff);
+int pb_op_mask_cls_points_nms(pb_ctx *ctx, const float *logit, int n, int pts_total, int off, int g, int C, int guard_rows, float *score);
+int pb_op_mask_gather_rows(pb_ctx *ctx, const float *src, int src_rows, const int *idx, int count, int rows_pad, int cols, int split, int guard_rows,
+                           void *out);
+int pb_op_mask_stats(pb_ctx *ctx, const float *logit, int rows, int HW, int ld, float thr, int guard_rows, float *out);
+int pb_op_mask_intersections(pb_ctx *ctx, const float *logit, int src_rows, int ld, const int *idx, int n, int HW, float thr, int guard_rows,
+                             void *bits, int inter_rows, float *inter);
+int pb_op_mask_matrix_nms(pb_ctx *ctx, const float *inter, const float *area, const int *label, const float *score, int n, float sigma, int guard,
+                          float *comp, float *out);
+int pb_op_mask_sigmoid_rows(pb_ctx *ctx, const float *logit, int src_rows, int ld, const int *idx, int count, int HW, int guard_rows, float *sig);
+int pb_op_mask_dynconv(pb_ctx *ctx, const float *kernels, int src_rows, const int *idx, int row_off, int M, const float *feat, int HW4, int split,
+                       int guard_rows, float *out);
+int pb_op_mask_band_accumulate(pb_ctx *ctx, const float *sig, const uint8_t *use, int k, int fh, int fw, int h, int w, int H, int W, float thr,
+                               int guard, uint8_t *out, uint8_t *inst);
 /* bilinear resize NCHW float32, align_corners 0/1 (torch F.interpolate semantics). */
 int pb_op_bilinear(pb_ctx *ctx, const float *x, float *y, int B, int C, int H, int W, int OH, int OW,
                    int align_corners);

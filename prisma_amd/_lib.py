@@ -150,6 +150,21 @@ SYMBOLS = {
     "pb_op_gm_propagate": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P]),
     "pb_op_gm_local_match": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
     "pb_op_gm_local_propagate": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [_P]),
+    "pb_op_mask_prep": (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "pb_op_mask_maxpool": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
+    "pb_op_mask_nearest_add": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P]),
+    "pb_op_mask_subsample2": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
+    "pb_op_mask_coord_concat": (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P]),
+    "pb_op_mask_bilinear": (C.c_int, [_P, _P, _P] + [C.c_int] * 10 + [_P]),
+    "pb_op_mask_gn_relu": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P, _P]),
+    "pb_op_mask_cls_points_nms": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
+    "pb_op_mask_gather_rows": (C.c_int, [_P, _P, C.c_int, _P] + [C.c_int] * 5 + [_P]),
+    "pb_op_mask_stats": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P]),
+    "pb_op_mask_intersections": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_float, C.c_int, _P, C.c_int, _P]),
+    "pb_op_mask_matrix_nms": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_float, C.c_int, _P, _P]),
+    "pb_op_mask_sigmoid_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_op_mask_dynconv": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_op_mask_band_accumulate": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [C.c_float, C.c_int, _P, _P]),
     "pb_op_bilinear": (C.c_int, [_P, _P, _P] + [C.c_int] * 7),
     "pb_op_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "pb_op_encode_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -7,6 +7,7 @@
 
 #include "abi_ctx.h"
 #include "gmflow_engine.h"
+#include "mask_kernels.h"
 
 namespace {
 // ---- one layer through EngineBase's own packing and launch code (pb_op_conv2d_split / pb_op_dense_split) ------------------------------
@@ -630,6 +631,188 @@ class GmOpEngine : public RaftOpEngine {
     }
 };
 
+// ---- the mask_mmdet band's own kernels one by one (pb_op_mask_*) -----------------------------------------------------------------------
+// Every entry point calls the launcher of mask_kernels.h with the arguments MaskEngine gives it: row strides L(C) = C (1 + split), residual
+// offsets lo(C) = split ? C : 0, ld = 512 for the NMS matrices.  Input maps are rows of `ld` halfs, [hi (C) | lo (C)] when split, every half
+// the map does not define 0xFFFF (a NaN: a kernel that reads a row tail shows it); outputs are preset to 0xFF bytes and carry guard rows.
+class MaskOpEngine : public RaftOpEngine {
+  public:
+    explicit MaskOpEngine(int device) : RaftOpEngine(device) {}
+    // x [rows, C] fp32 -> rows of ld halfs: hi at 0, the residual at lo_off (0 = none); `extra` more rows of 0xFF behind them
+    int to_map(DevMem &d, const float *x, int64_t rows, int C, int ld, int lo_off, int64_t extra = 0) {
+        std::vector<f16> h((size_t)(rows + extra) * ld);
+        memset(h.data(), 0xFF, h.size() * 2);
+        for (int64_t r = 0; r < rows; ++r)
+            for (int c = 0; c < C; ++c) {
+                const float v = x[r * C + c];
+                const f16 hi = (f16)v;
+                h[(size_t)r * ld + c] = hi;
+                if (lo_off) h[(size_t)r * ld + lo_off + c] = (f16)(v - (float)hi);
+            }
+        return up(d, h.data(), h.size() * 2);
+    }
+    int down(void *dst, const DevMem &d, size_t bytes) {
+        PB_HIP(hipMemcpy(dst, d.p, bytes, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+    int prep(const uint8_t *frames, int n, int H, int W, int nh, int nw, int Hp, int Wp, const int *xt, const int *yt, int split, int guard, void *out,
+             float *chw) {
+        const int64_t blocks = (int64_t)n * (Hp / 4) * (Wp / 4), px = (int64_t)n * 3 * Hp * Wp;
+        const int ld = split ? 128 : 64;
+        DevMem df, dx, dy, dout, dchw;
+        PB_TRY(up(df, frames, (size_t)n * H * W * 3)); PB_TRY(up(dx, xt, (size_t)nw * 16)); PB_TRY(up(dy, yt, (size_t)nh * 16));
+        PB_TRY(preset(dout, (size_t)(blocks + guard) * ld * 2)); PB_TRY(preset(dchw, (size_t)(px + guard) * 4));
+        PB_TRY(launch_mask_prep(stream, df.as<uint8_t>(), n, H, W, nh, nw, Hp, Wp, dx.as<int>(), dy.as<int>(), dout.as<f16>(), dchw.as<float>(), split));
+        PB_TRY(finish(out, dout, (size_t)(blocks + guard) * ld * 2));
+        return down(chw, dchw, (size_t)(px + guard) * 4);
+    }
+    int maxpool(const float *x, int n, int H, int W, int C, int split, int guard, void *out) {
+        const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, ld = C * (1 + split);
+        const int64_t orows = (int64_t)n * OH * OW;
+        DevMem dx, dout;
+        PB_TRY(to_map(dx, x, (int64_t)n * H * W, C, ld, split ? C : 0));
+        PB_TRY(preset(dout, (size_t)(orows + guard) * ld * 2));
+        PB_TRY(launch_maxpool3x3s2(stream, dx.as<f16>(), dout.as<f16>(), n, H, W, C, split));
+        return finish(out, dout, (size_t)(orows + guard) * ld * 2);
+    }
+    int nearest_add(const float *dst, const float *src, int n, int h, int w, int sh, int sw, int C, int split, int guard, void *out) {
+        const int ld = C * (1 + split);
+        const int64_t rows = (int64_t)n * h * w;
+        DevMem dd, ds;
+        PB_TRY(to_map(dd, dst, rows, C, ld, split ? C : 0, guard)); PB_TRY(to_map(ds, src, (int64_t)n * sh * sw, C, ld, split ? C : 0));
+        PB_TRY(launch_nearest_add(stream, dd.as<f16>(), ds.as<f16>(), n, h, w, sh, sw, C, split));
+        return finish(out, dd, (size_t)(rows + guard) * ld * 2);
+    }
+    int subsample2(const float *x, int n, int H, int W, int C, int split, int guard, void *out) {
+        const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1, ld = C * (1 + split);
+        const int64_t orows = (int64_t)n * OH * OW;
+        DevMem dx, dout;
+        PB_TRY(to_map(dx, x, (int64_t)n * H * W, C, ld, split ? C : 0));
+        PB_TRY(preset(dout, (size_t)(orows + guard) * ld * 2));
+        PB_TRY(launch_subsample2(stream, dx.as<f16>(), dout.as<f16>(), n, H, W, ld));         // whole rows: both parts of a split map
+        return finish(out, dout, (size_t)(orows + guard) * ld * 2);
+    }
+    int coord_concat(const float *x, int n, int h, int w, int C, int ldi, int split, int guard, void *out) {
+        const int64_t rows = (int64_t)n * h * w;
+        const int ldo = (C + 64) * (1 + split);
+        DevMem dx, dout;
+        PB_TRY(to_map(dx, x, rows, C, ldi, split ? C : 0));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * ldo * 2));
+        PB_TRY(launch_coord_concat(stream, dx.as<f16>(), dout.as<f16>(), n, h, w, C, ldi, split ? C : 0));
+        return finish(out, dout, (size_t)(rows + guard) * ldo * 2);
+    }
+    int bilinear(const float *x, const float *y0, int n, int H, int W, int OH, int OW, int C, int ldi, int ldo, int split, int guard, void *out) {
+        const int64_t orows = (int64_t)n * OH * OW;
+        const int lo = split ? C : 0;
+        DevMem dx, dout;
+        PB_TRY(to_map(dx, x, (int64_t)n * H * W, C, ldi, lo));
+        if (y0) PB_TRY(to_map(dout, y0, orows, C, ldo, lo, guard));
+        else PB_TRY(preset(dout, (size_t)(orows + guard) * ldo * 2));
+        PB_TRY(launch_bilinear(stream, dx.as<f16>(), dout.as<f16>(), n, H, W, OH, OW, C, ldi, ldo, y0 ? 1 : 0, lo, lo));
+        return finish(out, dout, (size_t)(orows + guard) * ldo * 2);
+    }
+    // layout 0: fp16 -> fp16, 1: split -> split, 2: split -> [hi | hi | lo] (the B operand of the dynamic convolution)
+    int gn_relu(const float *x, const float *gamma, const float *beta, int n, int HW, int C, int layout, int guard, void *out, float *aff) {
+        const int sa = layout ? 1 : 0, ldc = C * (1 + sa), ldo = layout == 2 ? 3 * C : ldc;
+        const int64_t rows = (int64_t)n * HW;
+        DevMem dx, dg, db, dout, dst, daff;
+        PB_TRY(to_map(dx, x, rows, C, ldc, sa ? C : 0));
+        PB_TRY(up(dg, gamma, (size_t)C * 4)); PB_TRY(up(db, beta, (size_t)C * 4));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * ldo * 2));
+        PB_TRY(preset(dst, (size_t)n * gn_chunks(HW) * C * 2 * 4)); PB_TRY(preset(daff, (size_t)n * C * 2 * 4));
+        PB_TRY(launch_gn_relu(stream, dx.as<f16>(), dout.as<f16>(), n, HW, C, ldc, ldo, 32, dg.as<float>(), db.as<float>(), dst.as<float>(), daff.as<float>(),
+                              sa ? C : 0, layout == 2 ? 2 * C : (sa ? C : 0), layout == 2 ? C : 0));
+        PB_TRY(finish(out, dout, (size_t)(rows + guard) * ldo * 2));
+        return down(aff, daff, (size_t)n * C * 2 * 4);
+    }
+    int cls_points_nms(const float *logit, int n, int pts_total, int off, int g, int C, int guard, float *score) {
+        DevMem dl, ds;
+        PB_TRY(up(dl, logit, (size_t)n * g * g * C * 4));
+        PB_TRY(preset(ds, ((size_t)n * pts_total + guard) * C * 4));
+        PB_TRY(launch_cls_points_nms(stream, dl.as<float>(), ds.as<float>(), n, pts_total, off, g, C));
+        return finish(score, ds, ((size_t)n * pts_total + guard) * C * 4);
+    }
+    int gather_rows(const float *src, int src_rows, const int *idx, int count, int rows_pad, int cols, int split, int guard, void *out) {
+        const int ld = cols * (1 + split);
+        DevMem ds, di, dout;
+        PB_TRY(up(ds, src, (size_t)src_rows * cols * 4)); PB_TRY(up(di, idx, (size_t)std::max(count, 1) * 4));
+        PB_TRY(preset(dout, (size_t)(rows_pad + guard) * ld * 2));
+        PB_TRY(launch_gather_rows_f16(stream, ds.as<float>(), di.as<int>(), dout.as<f16>(), count, rows_pad, cols, split));
+        return finish(out, dout, (size_t)(rows_pad + guard) * ld * 2);
+    }
+    int mask_stats(const float *logit, int rows, int HW, int ld, float thr, int guard, float *out) {
+        DevMem dl, dout;
+        PB_TRY(up(dl, logit, (size_t)rows * ld * 4));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * 2 * 4));
+        PB_TRY(launch_mask_stats(stream, dl.as<float>(), rows, HW, ld, thr, dout.as<float>()));
+        return finish(out, dout, (size_t)(rows + guard) * 2 * 4);
+    }
+    // bitpack_rows then mask_intersections on its output; inter is [irows, 512] floats, returned whole
+    int intersections(const float *logit, int src_rows, int ld, const int *idx, int n, int HW, float thr, int guard, void *bits, int irows, float *inter) {
+        const int words = HW / 64;
+        DevMem dl, di, dbits, dint;
+        PB_TRY(up(dl, logit, (size_t)src_rows * ld * 4)); PB_TRY(up(di, idx, (size_t)n * 4));
+        PB_TRY(preset(dbits, (size_t)(n + guard) * words * 8)); PB_TRY(preset(dint, (size_t)irows * 512 * 4));
+        PB_TRY(launch_bitpack_rows(stream, dl.as<float>(), ld, di.as<int>(), n, HW, thr, dbits.as<unsigned long long>()));
+        PB_TRY(launch_mask_intersections(stream, dbits.as<unsigned long long>(), n, words, dint.as<float>(), 512));
+        PB_TRY(finish(bits, dbits, (size_t)(n + guard) * words * 8));
+        return down(inter, dint, (size_t)irows * 512 * 4);
+    }
+    int matrix_nms(const float *inter, const float *area, const int *label, const float *score, int n, float sigma, int guard, float *comp, float *out) {
+        DevMem di, da, dl, ds, dc, dout;
+        PB_TRY(up(di, inter, (size_t)n * 512 * 4)); PB_TRY(up(da, area, (size_t)n * 4)); PB_TRY(up(dl, label, (size_t)n * 4)); PB_TRY(up(ds, score, (size_t)n * 4));
+        PB_TRY(preset(dc, (size_t)(n + guard) * 4)); PB_TRY(preset(dout, (size_t)(n + guard) * 4));
+        PB_TRY(launch_matrix_nms(stream, di.as<float>(), 512, da.as<float>(), dl.as<int>(), ds.as<float>(), n, sigma, dc.as<float>(), dout.as<float>()));
+        PB_TRY(finish(comp, dc, (size_t)(n + guard) * 4));
+        return down(out, dout, (size_t)(n + guard) * 4);
+    }
+    int sigmoid_rows(const float *logit, int src_rows, int ld, const int *idx, int count, int HW, int guard, float *sig) {
+        DevMem dl, di, ds;
+        PB_TRY(up(dl, logit, (size_t)src_rows * ld * 4)); PB_TRY(up(di, idx, (size_t)count * 4));
+        PB_TRY(preset(ds, (size_t)(count + guard) * HW * 4));
+        PB_TRY(launch_sigmoid_rows(stream, dl.as<float>(), ld, di.as<int>(), count, HW, ds.as<float>()));
+        return finish(sig, ds, (size_t)(count + guard) * HW * 4);
+    }
+    // post_chunk's dynamic convolution: gather_rows_f16 builds A (row_off + M kernels, the launch reads rows [row_off, row_off + M)), B is the
+    // mask-feature map in the layout gn_relu's dup output has ([hi | hi | lo] when split), EPI_F32 into [M, HW4]
+    int dynconv(const float *kern, int src_rows, const int *idx, int row_off, int M, const float *feat, int HW4, int split, int guard, float *out) {
+        const int total = row_off + M, lda = 256 * (1 + split), ldb = split ? 768 : 256;
+        const int64_t arows = round_up(total, 256) + 256, brows = round_up(HW4, 256);
+        std::vector<f16> hb((size_t)brows * ldb, (f16)0.f);
+        for (int64_t p = 0; p < HW4; ++p)
+            for (int c = 0; c < 256; ++c) {
+                const float v = feat[p * 256 + c];
+                const f16 hi = (f16)v;
+                hb[(size_t)p * ldb + c] = hi;
+                if (split) { hb[(size_t)p * ldb + 256 + c] = hi; hb[(size_t)p * ldb + 512 + c] = (f16)(v - (float)hi); }
+            }
+        DevMem dk, di, da, dB, dout;
+        PB_TRY(up(dk, kern, (size_t)src_rows * 256 * 4)); PB_TRY(up(di, idx, (size_t)total * 4)); PB_TRY(up(dB, hb.data(), hb.size() * 2));
+        PB_TRY(da.alloc((size_t)arows * lda * 2));
+        PB_TRY(preset(dout, (size_t)(M + guard) * HW4 * 4));
+        PB_TRY(launch_gather_rows_f16(stream, dk.as<float>(), di.as<int>(), da.as<f16>(), total, total, 256, split));
+        GemmArgs a;
+        a.A = da.as<f16>() + (int64_t)row_off * lda; a.lda = lda; a.M = M; a.W = dB.as<f16>(); a.K = ldb; a.N = HW4;
+        if (split) a.kwrap = 8;
+        a.out32 = dout.as<float>(); a.ldo = HW4; a.scale = 1.f; a.zero = zero_;
+        PB_TRY(launch_gemm(stream, A_DENSE, EPI_F32, TILE_AUTO, a));
+        return finish(out, dout, (size_t)(M + guard) * HW4 * 4);
+    }
+    int band_accumulate(const float *sig, const uint8_t *use, int k, int fh, int fw, int h, int w, int H, int W, float thr, int guard, uint8_t *out,
+                        uint8_t *inst) {
+        const int64_t px = (int64_t)H * W;
+        DevMem ds, du, dout, dinst;
+        PB_TRY(up(ds, sig, (size_t)k * fh * fw * 4)); PB_TRY(up(du, use, (size_t)k));
+        PB_TRY(preset(dout, (size_t)px * 3 + guard));
+        if (inst) PB_TRY(preset(dinst, (size_t)k * px + guard));
+        PB_TRY(launch_band_accumulate(stream, ds.as<float>(), k, fh, fw, h, w, H, W, thr, du.as<uint8_t>(), dout.as<uint8_t>(),
+                                      inst ? dinst.as<uint8_t>() : nullptr));
+        PB_TRY(finish(out, dout, (size_t)px * 3 + guard));
+        return inst ? down(inst, dinst, (size_t)k * px + guard) : 0;
+    }
+};
+
 // the "l.weight" [n, k] or [n, k, kh, kw] / "l.bias" [n] pair of one layer, as begin_load() takes it
 struct LayerTensors {
     pb_tensor t[2] = {};
@@ -1220,6 +1403,109 @@ int pb_op_gm_local_propagate(pb_ctx *c, const float *q, const float *k, const fl
     GM_OP_ENGINE(e);
     PB_TRY(e.geom(h8, w8));
     return e.local_propagate(q, k, flow_in, B, img_step, radius, guard_rows, flow_out);
+}
+
+// ---- the mask_mmdet band's kernels one by one (MaskOpEngine above) ----
+#define MASK_OP_ENGINE(e) PB_HIP(hipSetDevice(c->device)); MaskOpEngine e(c->device); PB_TRY(e.setup(nullptr, 0, SL_F16, 0))
+int pb_op_mask_prep(pb_ctx *c, const uint8_t *frames, int n, int H, int W, int nh, int nw, int Hp, int Wp, const int *xt, const int *yt, int split,
+                    int guard_rows, void *out, float *chw) {
+    PB_CHECK(c && frames && xt && yt && out && chw && n > 0 && H > 0 && W > 0 && nh > 0 && nw > 0 && nh <= Hp && nw <= Wp && Hp % 4 == 0 && Wp % 4 == 0 &&
+                 guard_rows >= 0, PB_ERR_ARG, "op_mask_prep: bad arguments");
+    for (int i = 0; i < nw; ++i) PB_CHECK(xt[i * 4] >= 0 && xt[i * 4] < W && xt[i * 4 + 1] >= 0 && xt[i * 4 + 1] < W, PB_ERR_ARG, "op_mask_prep: column table entry %d outside the frame", i);
+    for (int i = 0; i < nh; ++i) PB_CHECK(yt[i * 4] >= 0 && yt[i * 4] < H && yt[i * 4 + 1] >= 0 && yt[i * 4 + 1] < H, PB_ERR_ARG, "op_mask_prep: row table entry %d outside the frame", i);
+    MASK_OP_ENGINE(e);
+    return e.prep(frames, n, H, W, nh, nw, Hp, Wp, xt, yt, split, guard_rows, out, chw);
+}
+int pb_op_mask_maxpool(pb_ctx *c, const float *x, int n, int H, int W, int C, int split, int guard_rows, void *out) {
+    PB_CHECK(c && x && out && n > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && guard_rows >= 0, PB_ERR_ARG, "op_mask_maxpool: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.maxpool(x, n, H, W, C, split, guard_rows, out);
+}
+int pb_op_mask_nearest_add(pb_ctx *c, const float *dst, const float *src, int n, int h, int w, int sh, int sw, int C, int split, int guard_rows, void *out) {
+    PB_CHECK(c && dst && src && out && n > 0 && h > 0 && w > 0 && sh > 0 && sw > 0 && C > 0 && C % 8 == 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_mask_nearest_add: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.nearest_add(dst, src, n, h, w, sh, sw, C, split, guard_rows, out);
+}
+int pb_op_mask_subsample2(pb_ctx *c, const float *x, int n, int H, int W, int C, int split, int guard_rows, void *out) {
+    PB_CHECK(c && x && out && n > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && guard_rows >= 0, PB_ERR_ARG, "op_mask_subsample2: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.subsample2(x, n, H, W, C, split, guard_rows, out);
+}
+int pb_op_mask_coord_concat(pb_ctx *c, const float *x, int n, int h, int w, int C, int ldi, int split, int guard_rows, void *out) {
+    PB_CHECK(c && x && out && n > 0 && h > 0 && w > 0 && C > 0 && C % 8 == 0 && ldi % 8 == 0 && ldi >= C * (1 + (split ? 1 : 0)) && guard_rows >= 0, PB_ERR_ARG,
+             "op_mask_coord_concat: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.coord_concat(x, n, h, w, C, ldi, split, guard_rows, out);
+}
+int pb_op_mask_bilinear(pb_ctx *c, const float *x, const float *y0, int n, int H, int W, int OH, int OW, int C, int ldi, int ldo, int split, int guard_rows,
+                        void *out) {
+    PB_CHECK(c && x && out && n > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && C > 0 && C % 8 == 0 && ldi % 8 == 0 && ldo % 8 == 0 &&
+                 ldi >= C * (1 + (split ? 1 : 0)) && ldo >= C * (1 + (split ? 1 : 0)) && guard_rows >= 0, PB_ERR_ARG, "op_mask_bilinear: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.bilinear(x, y0, n, H, W, OH, OW, C, ldi, ldo, split, guard_rows, out);
+}
+int pb_op_mask_gn_relu(pb_ctx *c, const float *x, const float *gamma, const float *beta, int n, int HW, int C, int layout, int guard_rows, void *out,
+                       float *aff) {
+    PB_CHECK(c && x && gamma && beta && out && aff && n > 0 && HW > 0 && C > 0 && C % 32 == 0 && layout >= 0 && layout <= 2 && guard_rows >= 0, PB_ERR_ARG,
+             "op_mask_gn_relu: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.gn_relu(x, gamma, beta, n, HW, C, layout, guard_rows, out, aff);
+}
+int pb_op_mask_cls_points_nms(pb_ctx *c, const float *logit, int n, int pts_total, int off, int g, int C, int guard_rows, float *score) {
+    PB_CHECK(c && logit && score && n > 0 && g > 0 && C > 0 && off >= 0 && off + g * g <= pts_total && guard_rows >= 0, PB_ERR_ARG,
+             "op_mask_cls_points_nms: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.cls_points_nms(logit, n, pts_total, off, g, C, guard_rows, score);
+}
+int pb_op_mask_gather_rows(pb_ctx *c, const float *src, int src_rows, const int *idx, int count, int rows_pad, int cols, int split, int guard_rows,
+                           void *out) {
+    PB_CHECK(c && src && idx && out && src_rows > 0 && count >= 0 && count <= rows_pad && cols > 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_mask_gather_rows: bad arguments");
+    for (int i = 0; i < count; ++i) PB_CHECK(idx[i] >= 0 && idx[i] < src_rows, PB_ERR_ARG, "op_mask_gather_rows: idx[%d] = %d of %d rows", i, idx[i], src_rows);
+    MASK_OP_ENGINE(e);
+    return e.gather_rows(src, src_rows, idx, count, rows_pad, cols, split, guard_rows, out);
+}
+int pb_op_mask_stats(pb_ctx *c, const float *logit, int rows, int HW, int ld, float thr, int guard_rows, float *out) {
+    PB_CHECK(c && logit && out && rows > 0 && HW > 0 && ld >= HW && guard_rows >= 0, PB_ERR_ARG, "op_mask_stats: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.mask_stats(logit, rows, HW, ld, thr, guard_rows, out);
+}
+int pb_op_mask_intersections(pb_ctx *c, const float *logit, int src_rows, int ld, const int *idx, int n, int HW, float thr, int guard_rows, void *bits,
+                             int inter_rows, float *inter) {
+    PB_CHECK(c && logit && idx && bits && inter && src_rows > 0 && n > 0 && n <= 512 && HW > 0 && HW % 64 == 0 && ld >= HW && inter_rows >= n &&
+                 guard_rows >= 0, PB_ERR_ARG, "op_mask_intersections: bad arguments");
+    for (int i = 0; i < n; ++i) PB_CHECK(idx[i] >= 0 && idx[i] < src_rows, PB_ERR_ARG, "op_mask_intersections: idx[%d] = %d of %d rows", i, idx[i], src_rows);
+    MASK_OP_ENGINE(e);
+    return e.intersections(logit, src_rows, ld, idx, n, HW, thr, guard_rows, bits, inter_rows, inter);
+}
+int pb_op_mask_matrix_nms(pb_ctx *c, const float *inter, const float *area, const int *label, const float *score, int n, float sigma, int guard,
+                          float *comp, float *out) {
+    PB_CHECK(c && inter && area && label && score && comp && out && n > 0 && n <= 512 && guard >= 0, PB_ERR_ARG, "op_mask_matrix_nms: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.matrix_nms(inter, area, label, score, n, sigma, guard, comp, out);
+}
+int pb_op_mask_sigmoid_rows(pb_ctx *c, const float *logit, int src_rows, int ld, const int *idx, int count, int HW, int guard_rows, float *sig) {
+    PB_CHECK(c && logit && idx && sig && src_rows > 0 && count > 0 && HW > 0 && HW % 4 == 0 && ld % 4 == 0 && ld >= HW && guard_rows >= 0, PB_ERR_ARG,
+             "op_mask_sigmoid_rows: bad arguments");
+    for (int i = 0; i < count; ++i) PB_CHECK(idx[i] >= 0 && idx[i] < src_rows, PB_ERR_ARG, "op_mask_sigmoid_rows: idx[%d] = %d of %d rows", i, idx[i], src_rows);
+    MASK_OP_ENGINE(e);
+    return e.sigmoid_rows(logit, src_rows, ld, idx, count, HW, guard_rows, sig);
+}
+int pb_op_mask_dynconv(pb_ctx *c, const float *kernels, int src_rows, const int *idx, int row_off, int M, const float *feat, int HW4, int split,
+                       int guard_rows, float *out) {
+    PB_CHECK(c && kernels && idx && feat && out && src_rows > 0 && row_off >= 0 && row_off % 8 == 0 && M > 0 && HW4 > 0 && HW4 % 8 == 0 && guard_rows >= 0,
+             PB_ERR_ARG, "op_mask_dynconv: bad arguments");
+    for (int i = 0; i < row_off + M; ++i) PB_CHECK(idx[i] >= 0 && idx[i] < src_rows, PB_ERR_ARG, "op_mask_dynconv: idx[%d] = %d of %d rows", i, idx[i], src_rows);
+    MASK_OP_ENGINE(e);
+    return e.dynconv(kernels, src_rows, idx, row_off, M, feat, HW4, split, guard_rows, out);
+}
+int pb_op_mask_band_accumulate(pb_ctx *c, const float *sig, const uint8_t *use, int k, int fh, int fw, int h, int w, int H, int W, float thr, int guard,
+                               uint8_t *out, uint8_t *inst) {
+    PB_CHECK(c && sig && use && out && k > 0 && fh > 0 && fw > 0 && h > 0 && w > 0 && h <= 4 * fh && w <= 4 * fw && H > 0 && W > 0 && guard >= 0, PB_ERR_ARG,
+             "op_mask_band_accumulate: bad arguments");
+    MASK_OP_ENGINE(e);
+    return e.band_accumulate(sig, use, k, fh, fw, h, w, H, W, thr, guard, out, inst);
 }
 
 }  // extern "C"

@@ -215,75 +215,115 @@ __global__ __launch_bounds__(256) void bilinear_kernel(const f16 *__restrict__ x
 }
 
 // ------------------------------------------------------------------------------------------------
-// GroupNorm(32 groups, eps 1e-5) + ReLU: per-(sample, chunk of 256 pixels, channel) partial sums -> one wave per
-// (sample, group) adds them in a fixed order -> per-(sample, channel) affine -> one fused apply pass.  No atomics, and the
+// GroupNorm(32 groups, eps 1e-5) + ReLU: per-(sample, chunk of 256 pixels, channel) mean and centred sum of squares -> one wave per
+// (sample, group) combines them in a fixed order -> per-(sample, channel) affine -> one fused apply pass.  No atomics, and the
 // chunking depends on the map size only, so a frame's statistics (hence its mask image) do not depend on which other frames
-// share the launch or on block scheduling.  x: [n][HW][ldc] fp16; part: [n][nchunk][C][2].
+// share the launch or on block scheduling.  x: [n][HW][ldc] fp16; part: [n][nchunk][C][2] = (mean, M2).
+// The variance is never formed as E[x^2] - mean^2: with a group mean of 10 sigma that loses four digits in fp32.  A chunk sums v - k
+// (k = its first pixel, so the sum stays at the scale of the spread), then re-reads its 256 pixels - still in cache - for
+// M2 = sum (v - mean)^2; gn_finalize_kernel combines the chunks with the parallel-variance formula.  Both pixel loops are unrolled by 4 so that
+// four pixels' loads are in flight (a 512-channel map leaves a thread 64 pixels of a chunk); the sums keep their order.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void gn_stats_kernel(const f16 *__restrict__ x, int HW, int C8, int ldc, float *__restrict__ part,
                                                        int chunk, int lo) {
-    __shared__ float red[256 * 16];
+    __shared__ float red[256 * 8];
+    __shared__ float ctr[256 * 8];           // the chunk's mean per channel (C <= 2048)
     const int b = blockIdx.y;
     const int c8 = threadIdx.x % C8, pl = threadIdx.x / C8, npl = blockDim.x / C8;
     const int p0 = blockIdx.x * chunk, p1 = min(p0 + chunk, HW);
-    float s[8], q[8];
+    const f16 *base = x + (int64_t)b * HW * ldc + c8 * 8;
+    const float inv_n = 1.f / (float)(p1 - p0);
+    float k[8], s[8];
+    ld8(base + (int64_t)p0 * ldc, lo, k);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { s[j] = 0.f; q[j] = 0.f; }
-    if (pl < npl) {
-        for (int p = p0 + pl; p < p1; p += npl) {
-            float v[8];
-            ld8(x + ((int64_t)b * HW + p) * ldc + c8 * 8, lo, v);
+    for (int j = 0; j < 8; ++j) s[j] = 0.f;
+#pragma unroll 4
+    for (int p = p0 + pl; p < p1; p += npl) {
+        float v[8];
+        ld8(base + (int64_t)p * ldc, lo, v);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) { const float f = v[j]; s[j] += f; q[j] += f * f; }
-        }
+        for (int j = 0; j < 8; ++j) s[j] += v[j] - k[j];
     }
 #pragma unroll
-    for (int j = 0; j < 8; ++j) { red[threadIdx.x * 16 + j] = s[j]; red[threadIdx.x * 16 + 8 + j] = q[j]; }
+    for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = s[j];
     __syncthreads();
     if (pl == 0) {
         for (int o = 1; o < npl; ++o)
 #pragma unroll
-            for (int j = 0; j < 16; ++j) red[c8 * 16 + j] += red[(o * C8 + c8) * 16 + j];
+            for (int j = 0; j < 8; ++j) red[c8 * 8 + j] += red[(o * C8 + c8) * 8 + j];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) ctr[c8 * 8 + j] = k[j] + red[c8 * 8 + j] * inv_n;
+    }
+    __syncthreads();
+    float m[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { m[j] = ctr[c8 * 8 + j]; s[j] = 0.f; }
+#pragma unroll 4
+    for (int p = p0 + pl; p < p1; p += npl) {
+        float v[8];
+        ld8(base + (int64_t)p * ldc, lo, v);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float d = v[j] - m[j]; s[j] += d * d; }
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) red[threadIdx.x * 8 + j] = s[j];
+    __syncthreads();
+    if (pl == 0) {
+        for (int o = 1; o < npl; ++o)
+#pragma unroll
+            for (int j = 0; j < 8; ++j) red[c8 * 8 + j] += red[(o * C8 + c8) * 8 + j];
         float *dst = part + (((int64_t)b * gridDim.x + blockIdx.x) * C8 * 8 + c8 * 8) * 2;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            dst[j * 2 + 0] = red[c8 * 16 + j];
-            dst[j * 2 + 1] = red[c8 * 16 + 8 + j];
+            dst[j * 2 + 0] = m[j];
+            dst[j * 2 + 1] = red[c8 * 8 + j];
         }
     }
 }
 
-// part [n][nchunk][C][2] -> affine [n][C][2] = (rstd_g * gamma_c, beta_c - mean_g * rstd_g * gamma_c); one wave per (sample, group):
-// lane l adds the (chunk, channel) items l, l + 64, ... in that order, then a fixed butterfly
+// part [n][nchunk][C][2] -> aff [n][C][2] = (rstd_g * gamma_c, mean_g); one wave per (sample, group):
+// lane l adds the (chunk, channel) items l, l + 64, ... in that order, then a fixed butterfly.  Item i holds n_i pixels with mean m_i and
+// M2_i: mean = k + sum n_i (m_i - k) / N with k = the first item's mean, var = sum (M2_i + n_i (m_i - mean)^2) / N
 __global__ __launch_bounds__(256) void gn_finalize_kernel(const float *__restrict__ part, const float *__restrict__ gamma,
-                                                          const float *__restrict__ beta, float *__restrict__ aff, int n, int C,
-                                                          int cpg, int nchunk, float inv_cnt) {
+                                                          float *__restrict__ aff, int n, int C, int cpg, int nchunk, int HW, int chunk,
+                                                          float inv_cnt) {
     const int lane = threadIdx.x & 63;
     const int wg = blockIdx.x * 4 + (threadIdx.x >> 6);          // (sample, group)
     const int groups = C / cpg;
     if (wg >= n * groups) return;
     const int b = wg / groups, g0 = (wg - b * groups) * cpg;
-    float s = 0.f, q = 0.f;
+    const float *pb = part + ((int64_t)b * nchunk * C + g0) * 2;
+    const float k = pb[0];
+    float s = 0.f;
     for (int it = lane; it < nchunk * cpg; it += 64) {
-        const int ch = it / cpg, k = it - ch * cpg;
-        const float *p = part + (((int64_t)b * nchunk + ch) * C + g0 + k) * 2;
-        s += p[0]; q += p[1];
+        const int ch = it / cpg, c = it - ch * cpg;
+        const float cnt = (float)min(chunk, HW - ch * chunk);
+        s += cnt * (pb[((int64_t)ch * C + c) * 2] - k);
     }
-    s = wave_sum(s); q = wave_sum(q);
-    const float mean = s * inv_cnt;
-    const float var = fmaxf(q * inv_cnt - mean * mean, 0.f);
-    const float rs = rsqrtf(var + 1e-5f);
-    for (int k = lane; k < cpg; k += 64) {
-        const int c = g0 + k;
-        const float r = rs * gamma[c];
-        aff[((int64_t)b * C + c) * 2] = r;
-        aff[((int64_t)b * C + c) * 2 + 1] = beta[c] - mean * r;
+    s = wave_sum(s);
+    const float mean = k + s * inv_cnt;
+    float q = 0.f;
+    for (int it = lane; it < nchunk * cpg; it += 64) {
+        const int ch = it / cpg, c = it - ch * cpg;
+        const float cnt = (float)min(chunk, HW - ch * chunk);
+        const float *p = pb + ((int64_t)ch * C + c) * 2;
+        const float d = p[0] - mean;
+        q += p[1] + cnt * (d * d);
+    }
+    q = wave_sum(q);
+    const float rs = rsqrtf(q * inv_cnt + 1e-5f);
+    for (int c = lane; c < cpg; c += 64) {
+        const int ci = g0 + c;
+        aff[((int64_t)b * C + ci) * 2] = rs * gamma[ci];
+        aff[((int64_t)b * C + ci) * 2 + 1] = mean;
     }
 }
 
+// y = max((v - mean) r + beta, 0): the mean comes off first, so a map far from zero (or a group without spread, r ~ 316) does not round at
+// the magnitude of mean * r
 __global__ __launch_bounds__(256) void gn_apply_relu_kernel(const f16 *__restrict__ x, const float *__restrict__ aff,
-                                                            f16 *__restrict__ y, int n, int HW, int C8, int ldc, int ldo, int lo_in,
-                                                            int lo_out, int dup) {
+                                                            const float *__restrict__ beta, f16 *__restrict__ y, int n, int HW, int C8,
+                                                            int ldc, int ldo, int lo_in, int lo_out, int dup) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (int64_t)n * HW * C8) return;
     const int c8 = (int)(i % C8);
@@ -291,9 +331,9 @@ __global__ __launch_bounds__(256) void gn_apply_relu_kernel(const f16 *__restric
     const int b = (int)(pix / HW);
     float v[8];
     ld8(x + pix * ldc + c8 * 8, lo_in, v);
-    const float *a = aff + ((int64_t)b * C8 * 8 + c8 * 8) * 2;
+    const float *a = aff + ((int64_t)b * C8 * 8 + c8 * 8) * 2, *bt = beta + c8 * 8;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = fmaxf(v[j] * a[j * 2] + a[j * 2 + 1], 0.f);
+    for (int j = 0; j < 8; ++j) v[j] = fmaxf((v[j] - a[j * 2 + 1]) * a[j * 2] + bt[j], 0.f);
     f16 *dst = y + pix * ldo + c8 * 8;
     st8(dst, lo_out, v);
     if (dup) *(f16x8 *)(dst + dup) = *(const f16x8 *)dst;       // [hi | hi | lo] rows: the map is the B operand of a split GEMM (dynamic convolution)
@@ -529,9 +569,9 @@ int launch_gn_relu(hipStream_t s, const f16 *x, f16 *y, int n, int HW, int C, in
     const int chunk = GN_CHUNK, nchunk = gn_chunks(HW);           // fixed: the partition must not depend on the batch
     hipLaunchKernelGGL(gn_stats_kernel, dim3(nchunk, n), dim3(256), 0, s, x, HW, C8, ldc, stats, chunk, lo_in);
     const int cpg = C / groups;
-    hipLaunchKernelGGL(gn_finalize_kernel, dim3((n * groups + 3) / 4), dim3(256), 0, s, stats, gamma, beta, aff, n, C, cpg, nchunk,
-                       1.f / ((float)HW * (float)cpg));
-    hipLaunchKernelGGL(gn_apply_relu_kernel, dim3(nblk((int64_t)n * HW * C8)), dim3(256), 0, s, x, aff, y, n, HW, C8, ldc, ldo, lo_in,
+    hipLaunchKernelGGL(gn_finalize_kernel, dim3((n * groups + 3) / 4), dim3(256), 0, s, stats, gamma, aff, n, C, cpg, nchunk,
+                       HW, chunk, 1.f / ((float)HW * (float)cpg));
+    hipLaunchKernelGGL(gn_apply_relu_kernel, dim3(nblk((int64_t)n * HW * C8)), dim3(256), 0, s, x, aff, beta, y, n, HW, C8, ldc, ldo, lo_in,
                        lo_out, dup);
     LAUNCH_CHECK();
 }

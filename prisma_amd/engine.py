@@ -677,6 +677,138 @@ class Ops(_Ctx):
         check(self.lib.pb_op_gm_local_propagate(self.ctx, _ptr(q), _ptr(k), _ptr(flow_in), B, h8, w8, img_step, radius, guard_rows, _ptr(out)))
         return out
 
+    # ---- the mask_mmdet band's kernels one by one (pb_op_mask_*; tests/test_gpu_mask_ops.py) ----
+    # maps come back raw: uint8 [rows + guard_rows, bytes per row], 0xFF wherever the kernel did not write.  split: [hi | lo] rows
+    @staticmethod
+    def _i32(a) -> np.ndarray:
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def mask_prep(self, frames, nh: int, nw: int, Hp: int, Wp: int, xt, yt, split: bool, guard_rows: int = 8):
+        """frames uint8 [n, H, W, 3], xt [nw, 4], yt [nh, 4] -> (raw [n Hp/4 Wp/4 + guard, 128 (1 + split)], chw float32 [3 n Hp Wp + guard])"""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, H, W, _ = frames.shape
+        xt, yt = self._i32(xt), self._i32(yt)
+        assert xt.shape == (nw, 4) and yt.shape == (nh, 4) and frames.shape[3] == 3
+        out = np.empty((n * (Hp // 4) * (Wp // 4) + guard_rows, 128 * (1 + int(split))), np.uint8)
+        chw = np.empty(3 * n * Hp * Wp + guard_rows, np.float32)
+        check(self.lib.pb_op_mask_prep(self.ctx, _ptr(frames), n, H, W, nh, nw, Hp, Wp, _ptr(xt), _ptr(yt), int(split), guard_rows, _ptr(out), _ptr(chw)))
+        return out, chw
+
+    def mask_maxpool(self, x, split: bool, guard_rows: int = 8) -> np.ndarray:
+        """x [n, H, W, C] -> raw [n OH OW + guard, 2 C (1 + split)]"""
+        x = _f32(x)
+        n, H, W, Cc = x.shape
+        out = np.empty((n * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) + guard_rows, 2 * Cc * (1 + int(split))), np.uint8)
+        check(self.lib.pb_op_mask_maxpool(self.ctx, _ptr(x), n, H, W, Cc, int(split), guard_rows, _ptr(out)))
+        return out
+
+    def mask_nearest_add(self, dst, src, split: bool, guard_rows: int = 8) -> np.ndarray:
+        """dst [n, h, w, C] += src [n, sh, sw, C] -> raw [n h w + guard, 2 C (1 + split)]"""
+        dst, src = _f32(dst), _f32(src)
+        n, h, w, Cc = dst.shape
+        assert src.shape[0] == n and src.shape[3] == Cc
+        out = np.empty((n * h * w + guard_rows, 2 * Cc * (1 + int(split))), np.uint8)
+        check(self.lib.pb_op_mask_nearest_add(self.ctx, _ptr(dst), _ptr(src), n, h, w, src.shape[1], src.shape[2], Cc, int(split), guard_rows, _ptr(out)))
+        return out
+
+    def mask_subsample2(self, x, split: bool, guard_rows: int = 8) -> np.ndarray:
+        x = _f32(x)
+        n, H, W, Cc = x.shape
+        out = np.empty((n * ((H - 1) // 2 + 1) * ((W - 1) // 2 + 1) + guard_rows, 2 * Cc * (1 + int(split))), np.uint8)
+        check(self.lib.pb_op_mask_subsample2(self.ctx, _ptr(x), n, H, W, Cc, int(split), guard_rows, _ptr(out)))
+        return out
+
+    def mask_coord_concat(self, x, ldi: int, split: bool, guard_rows: int = 8) -> np.ndarray:
+        """x [n, h, w, C] in rows of ldi halfs -> raw [n h w + guard, 2 (C + 64) (1 + split)]"""
+        x = _f32(x)
+        n, h, w, Cc = x.shape
+        out = np.empty((n * h * w + guard_rows, 2 * (Cc + 64) * (1 + int(split))), np.uint8)
+        check(self.lib.pb_op_mask_coord_concat(self.ctx, _ptr(x), n, h, w, Cc, ldi, int(split), guard_rows, _ptr(out)))
+        return out
+
+    def mask_bilinear(self, x, OH: int, OW: int, ldi: int, ldo: int, split: bool, y0=None, guard_rows: int = 8) -> np.ndarray:
+        """x [n, H, W, C] (rows of ldi halfs) -> raw [n OH OW + guard, 2 ldo]; y0 [n, OH, OW, C]: accumulate into it"""
+        x = _f32(x)
+        n, H, W, Cc = x.shape
+        y0 = None if y0 is None else _f32(y0)
+        assert y0 is None or y0.shape == (n, OH, OW, Cc)
+        out = np.empty((n * OH * OW + guard_rows, 2 * ldo), np.uint8)
+        check(self.lib.pb_op_mask_bilinear(self.ctx, _ptr(x), _ptr(y0), n, H, W, OH, OW, Cc, ldi, ldo, int(split), guard_rows, _ptr(out)))
+        return out
+
+    def mask_gn_relu(self, x, gamma, beta, layout: int, guard_rows: int = 8):
+        """x [n, HW, C]; layout 0 fp16 -> fp16, 1 split -> split, 2 split -> [hi | hi | lo] -> (raw [n HW + guard, 2 ldo], aff [n, C, 2])"""
+        x, gamma, beta = _f32(x), _f32(gamma), _f32(beta)
+        n, HW, Cc = x.shape
+        assert gamma.shape == (Cc,) and beta.shape == (Cc,)
+        out = np.empty((n * HW + guard_rows, 2 * Cc * (1, 2, 3)[layout]), np.uint8)
+        aff = np.empty((n, Cc, 2), np.float32)
+        check(self.lib.pb_op_mask_gn_relu(self.ctx, _ptr(x), _ptr(gamma), _ptr(beta), n, HW, Cc, layout, guard_rows, _ptr(out), _ptr(aff)))
+        return out, aff
+
+    def mask_cls_points_nms(self, logit, pts_total: int, off: int, guard_rows: int = 8) -> np.ndarray:
+        """logit [n, g, g, C] -> raw float32 [n pts_total + guard, C] (0xFF bytes = NaN outside this level's rows)"""
+        logit = _f32(logit)
+        n, g, _, Cc = logit.shape
+        out = np.empty((n * pts_total + guard_rows, Cc), np.float32)
+        check(self.lib.pb_op_mask_cls_points_nms(self.ctx, _ptr(logit), n, pts_total, off, g, Cc, guard_rows, _ptr(out)))
+        return out
+
+    def mask_gather_rows(self, src, idx, rows_pad: int, split: bool, guard_rows: int = 8) -> np.ndarray:
+        src, idx = _f32(src), self._i32(idx)
+        out = np.empty((rows_pad + guard_rows, 2 * src.shape[1] * (1 + int(split))), np.uint8)
+        check(self.lib.pb_op_mask_gather_rows(self.ctx, _ptr(src), src.shape[0], _ptr(idx), len(idx), rows_pad, src.shape[1], int(split), guard_rows, _ptr(out)))
+        return out
+
+    def mask_stats(self, logit, HW: int, thr: float, guard_rows: int = 1) -> np.ndarray:
+        """logit [rows, ld] -> raw float32 [rows + guard, 2] = (area, soft sum)"""
+        logit = _f32(logit)
+        out = np.empty((logit.shape[0] + guard_rows, 2), np.float32)
+        check(self.lib.pb_op_mask_stats(self.ctx, _ptr(logit), logit.shape[0], HW, logit.shape[1], thr, guard_rows, _ptr(out)))
+        return out
+
+    def mask_intersections(self, logit, idx, HW: int, thr: float, inter_rows: int, guard_rows: int = 2):
+        """-> (bits uint64 [n + guard, HW / 64], inter raw float32 [inter_rows, 512])"""
+        logit, idx = _f32(logit), self._i32(idx)
+        bits = np.empty((len(idx) + guard_rows, HW // 64), np.uint64)
+        inter = np.empty((inter_rows, 512), np.float32)
+        check(self.lib.pb_op_mask_intersections(self.ctx, _ptr(logit), logit.shape[0], logit.shape[1], _ptr(idx), len(idx), HW, thr, guard_rows, _ptr(bits),
+                                                inter_rows, _ptr(inter)))
+        return bits, inter
+
+    def mask_matrix_nms(self, inter, area, label, score, sigma: float, guard: int = 4):
+        """inter [n, 512] (upper triangle read) -> (comp, decayed scores), raw float32 [n + guard] each"""
+        inter, area, score, label = _f32(inter), _f32(area), _f32(score), self._i32(label)
+        n = len(area)
+        assert inter.shape == (n, 512)
+        comp, out = np.empty(n + guard, np.float32), np.empty(n + guard, np.float32)
+        check(self.lib.pb_op_mask_matrix_nms(self.ctx, _ptr(inter), _ptr(area), _ptr(label), _ptr(score), n, sigma, guard, _ptr(comp), _ptr(out)))
+        return comp, out
+
+    def mask_sigmoid_rows(self, logit, idx, HW: int, guard_rows: int = 1) -> np.ndarray:
+        logit, idx = _f32(logit), self._i32(idx)
+        out = np.empty((len(idx) + guard_rows, HW), np.float32)
+        check(self.lib.pb_op_mask_sigmoid_rows(self.ctx, _ptr(logit), logit.shape[0], logit.shape[1], _ptr(idx), len(idx), HW, guard_rows, _ptr(out)))
+        return out
+
+    def mask_dynconv(self, kernels, idx, row_off: int, feat, split: bool, guard_rows: int = 2) -> np.ndarray:
+        """kernels [rows, 256], idx [row_off + M], feat [HW4, 256] -> raw float32 [M + guard, HW4]: row m = <kernels[idx[row_off + m]], feat>"""
+        kernels, feat, idx = _f32(kernels), _f32(feat), self._i32(idx)
+        M = len(idx) - row_off
+        out = np.empty((M + guard_rows, feat.shape[0]), np.float32)
+        check(self.lib.pb_op_mask_dynconv(self.ctx, _ptr(kernels), kernels.shape[0], _ptr(idx), row_off, M, _ptr(feat), feat.shape[0], int(split),
+                                          guard_rows, _ptr(out)))
+        return out
+
+    def mask_band_accumulate(self, sig, use, h: int, w: int, H: int, W: int, thr: float, guard: int = 64):
+        """sig [k, fh, fw], use [k] -> (out raw uint8 [3 H W + guard], inst raw uint8 [k H W + guard])"""
+        sig, use = _f32(sig), np.ascontiguousarray(use, np.uint8)
+        k, fh, fw = sig.shape
+        out = np.empty(3 * H * W + guard, np.uint8)
+        inst = np.empty(k * H * W + guard, np.uint8)
+        check(self.lib.pb_op_mask_band_accumulate(self.ctx, _ptr(sig), _ptr(use), k, fh, fw, h, w, H, W, thr, guard, _ptr(out), _ptr(inst)))
+        return out, inst
+
     def bilinear(self, x, OH: int, OW: int, align_corners: bool) -> np.ndarray:
         x = _f32(x)
         B, Cc, H, W = x.shape
