@@ -5,10 +5,15 @@ create_metadata :35-58, is_video :65-67, get_target :70-93, get_url :96-104, add
 write_metadata :124-134, set_default_band :137-146, get_record3d_data :148-156) - same function names,
 arguments and JSON layout, so files written by either implementation are interchangeable.
 """
+import copy
+import fcntl
 import json
 import os
+import stat
+import tempfile
 
 META_FILE = "metadata.json"
+LOCK_SUFFIX = ".lock"     # <folder>/metadata.json.lock: flock()ed by update_metadata, never deleted (unlinking a lock file races)
 
 
 def get_metadata_path(path):
@@ -80,11 +85,74 @@ def write_metadata(path, metadata):
             f.write(json.dumps(metadata, indent=4))
 
 
+def update_metadata(path, fn):
+    """Read-modify-write of metadata.json that is safe against other processes doing the same: an exclusive flock on
+    `metadata.json.lock`, the file re-read under it, `fn(data)` applied (it changes `data` in place or returns the new dict; False means
+    "nothing to write"), the result written to a temporary name in the same folder and renamed over metadata.json - a reader never sees a torn file.
+    Returns what was written; None (and nothing written) where there is no metadata.json, as write_metadata."""
+    mp = get_metadata_path(path)
+    if not (mp and os.path.exists(mp)):
+        return None
+    with open(mp + LOCK_SUFFIX, "a") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            with open(mp) as f:
+                data = json.load(f)
+            out = fn(data)
+            if out is False:
+                return data
+            if out is None:
+                out = data
+            fd, tmp = tempfile.mkstemp(prefix=META_FILE + ".", suffix=".tmp", dir=os.path.dirname(mp))
+            try:
+                with os.fdopen(fd, "w") as f:
+                    f.write(json.dumps(out, indent=4))
+                os.chmod(tmp, stat.S_IMODE(os.stat(mp).st_mode))      # mkstemp's 0600 would change who can read the folder's metadata
+                os.replace(tmp, mp)
+            except BaseException:
+                if os.path.exists(tmp):
+                    os.unlink(tmp)
+                raise
+            return out
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+
+
+def merge_metadata(path, data, loaded):
+    """A band's last metadata write when other bands may be writing the same folder.  `loaded` is a deep copy of what the band read
+    at start, `data` its copy now; under the lock only what the band changed goes into the current file: every top-level key that
+    differs, and every key of `bands` that was added or changed - a changed entry replaces the file's as a whole (mask_mmdet
+    relies on that to drop its `folder` key).  A key the band did not touch keeps the file's current value.  A band running alone
+    writes the bytes write_metadata(path, data) would."""
+    if data is None:
+        return
+    loaded = loaded or {}
+    missing = object()
+
+    def apply(cur):
+        for k, v in data.items():
+            if k == "bands" and isinstance(v, dict) and isinstance(cur.get("bands"), dict):
+                old = loaded.get("bands") if isinstance(loaded.get("bands"), dict) else {}
+                for b, entry in v.items():
+                    if old.get(b, missing) != entry:
+                        cur["bands"][b] = copy.deepcopy(entry)
+                for b in old:
+                    if b not in v:
+                        cur["bands"].pop(b, None)
+            elif loaded.get(k, missing) != v:
+                cur[k] = copy.deepcopy(v)
+        for k in loaded:
+            if k not in data:
+                cur.pop(k, None)
+    update_metadata(path, apply)
+
+
 def set_default_band(path, band, band_default):
-    data = load_metadata(path)
-    if data and band_default in data.get("bands", {}):
+    def alias(data):
+        if band_default not in data.get("bands", {}):
+            return False
         data["bands"][band] = data["bands"][band_default]
-        write_metadata(path, data)
+    update_metadata(path, alias)
 
 
 def get_record3d_data(path):

@@ -7,6 +7,7 @@ The PyTorch model and the numpy post-process are replaced by libprisma_bands.so 
 prisma_amd.engine (C ABI, include/prisma_bands.h); frames are pushed in batches instead of one by one.
 """
 import argparse
+import copy
 import os
 import sys
 
@@ -19,7 +20,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_ply, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, write_metadata  # noqa: E402
+from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
 from common.pipe import AsyncSink, prefetch  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
@@ -211,6 +212,7 @@ def main(argv=None):
     ap.add_argument("--synthetic", help="seeded synthetic weights when no checkpoint is found (tests / benchmarks)", action="store_true")
     args = ap.parse_args(argv)
     data = load_metadata(args.input)
+    loaded = copy.deepcopy(data)
     if data:
         print("PRISMA metadata found and loaded")
         folder = args.input
@@ -231,7 +233,7 @@ def main(argv=None):
     elif ranks.main:
         process_image(args)
     if ranks.main:
-        write_metadata(meta_path, data)
+        merge_metadata(meta_path, data, loaded)
     ranks.close()
 
 

@@ -20,6 +20,7 @@ The engine reads the architecture from the weights; a mismatch between the flags
 --num_scales 2 on its own, other split counts and other flag mixes stay refused.
 """
 import argparse
+import copy
 import os
 import sys
 
@@ -33,7 +34,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
 import flow_raft as _loop  # noqa: E402  (process_video and its writers; its module globals carry this band's model / metadata)
 from common.io import check_overwrite  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, write_metadata  # noqa: E402
+from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
 BAND = "flow_gmflow"
@@ -183,6 +184,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     check_arch(args)
     data = load_metadata(args.input)
+    loaded = copy.deepcopy(data)
     if data:
         folder = args.input
         args.input = get_url(folder, data, "rgba")
@@ -209,7 +211,7 @@ def main(argv=None):
     init_model(args, device=ranks.device)
     process_video(args)
     if ranks.main:
-        write_metadata(meta_path, data)
+        merge_metadata(meta_path, data, loaded)
     ranks.close()
 
 

@@ -7,6 +7,7 @@ infer()).  Frames are pushed to libprisma_bands.so in overlapping chunks; every 
 fnet / cnet once instead of twice per pair.
 """
 import argparse
+import copy
 import os
 import sys
 
@@ -19,7 +20,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 from common.io import FrameReader, VideoWriter, check_overwrite, write_flo, write_flow_png  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, write_metadata  # noqa: E402
+from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
 from common.pipe import AsyncSink, prefetch  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
@@ -231,6 +232,7 @@ def main(argv=None):
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights when the checkpoint is missing (tests / benchmarks)")
     args = ap.parse_args(argv)
     data = load_metadata(args.input)
+    loaded = copy.deepcopy(data)
     if data:
         folder = args.input
         args.input = get_url(folder, data, "rgba")
@@ -257,7 +259,7 @@ def main(argv=None):
     init_model(args, device=ranks.device)
     process_video(args)
     if ranks.main:
-        write_metadata(meta_path, data)
+        merge_metadata(meta_path, data, loaded)
     ranks.close()
 
 

@@ -8,6 +8,7 @@ mmdet's init_detector / inference_detector are replaced by libprisma_bands.so th
 are pushed in batches instead of one by one.
 """
 import argparse
+import copy
 import os
 import sys
 
@@ -20,7 +21,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, write_metadata  # noqa: E402
+from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
 from common.pipe import AsyncSink, prefetch  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
@@ -135,6 +136,7 @@ def main(argv=None):
     args = ap.parse_args(argv)
     _SYNTH[0] = args.synthetic
     data = load_metadata(args.input)
+    loaded = copy.deepcopy(data)
     meta_path = args.input
     if data:
         print("PRISMA metadata found and loaded")
@@ -154,7 +156,7 @@ def main(argv=None):
     elif ranks.main:
         process_image(args)
     if ranks.main:
-        write_metadata(meta_path, data)
+        merge_metadata(meta_path, data, loaded)
     ranks.close()
 
 

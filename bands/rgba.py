@@ -15,6 +15,7 @@ crop like the colour half and no GPU is touched.  As in the reference the frame 
 honoured here).
 """
 import argparse
+import copy
 import os
 import sys
 
@@ -22,7 +23,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_rgb  # noqa: E402
-from common.meta import add_band, get_target, is_video, load_metadata, write_metadata  # noqa: E402
+from common.meta import add_band, get_target, is_video, load_metadata, merge_metadata  # noqa: E402
 from common.pipe import AsyncSink, prefetch  # noqa: E402
 
 BAND = "rgba"
@@ -124,11 +125,12 @@ def main(argv=None):
                   file=sys.stderr)
         write_rgb(args.output, open_rgb(args.input))
     data = load_metadata(os.path.dirname(args.output))
+    loaded = copy.deepcopy(data)
     if data is not None:
         get_target(args.output, data, band=BAND, target=args.output)
         if depth_file:
             add_band(data, "depth", url=os.path.basename(depth_file))
-        write_metadata(os.path.dirname(args.output), data)
+        merge_metadata(os.path.dirname(args.output), data, loaded)
 
 
 if __name__ == "__main__":

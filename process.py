@@ -19,12 +19,20 @@ Bands this repo builds: rgba, depth_anything, flow_raft, flow
 and this script's), mask_mmdet.  The reference's default for still images (depth_patchfusion) and camera_colmap are out of scope
 (SURVEY section 2): a request for a band that is not built is reported and skipped; a default that is not built falls back to the
 built band of the same kind.
+
+Beyond the reference: `--jobs N` runs the bands of one input side by side, N at a time (they only read the rgba band; each ends with a
+locked merge into metadata.json, bands/common/meta.py merge_metadata), and `--gpus G` launches every video band that shards its frames
+under `torch.distributed.run` with G ranks on this node.  Both default to 1, which is the reference's shape: one band after the other,
+each a plain process.  The folder a parallel run leaves is byte-identical to the serial run's.
 """
 import argparse
 import os
+import queue
 import shlex
+import socket
 import subprocess
 import sys
+import threading
 
 import numpy as np
 
@@ -32,7 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 from bands.common.io import get_image_size, get_video_data  # noqa: E402
 from bands.common.meta import (add_band, create_metadata, get_record3d_data, is_video, load_metadata,  # noqa: E402
-                               set_default_band, write_metadata)
+                               set_default_band, update_metadata, write_metadata)
 
 # Default BANDS & MODELS (reference :17-30; defaults narrowed to what is built here)
 BUILT = ("rgba", "depth_anything", "flow_raft", "flow_gmflow", "mask_mmdet")
@@ -55,9 +63,36 @@ COMMANDS = []        # every command run() issued, in order (tests read it)
 RESULTS = []         # (band, return code) of every BUILT band run() launched; unbuilt bands are "skipped", not failures
 
 
-def build_command(band, input_folder, output_file="", subpath=False, extra_args=""):
-    """The argv of reference run() (:60-73): bands/<band>.py -i <input> [--output <file>] <extra> [--subpath <SUBFOLDERS[band]>]."""
-    cmd = [sys.executable, os.path.join(ROOT, "bands", band + ".py"), "-i", input_folder]
+SHARDED = ("depth_anything", "flow_raft", "flow_gmflow", "mask_mmdet")     # bands whose video loop shards frames by rank (prisma_amd/shard.py)
+MAX_GPU_PROCESSES = 16           # a shared box allows this many processes holding a GPU at once: bands in flight x ranks per band
+DEVICE_TROUBLE = (124, 134, 137, 139)     # time limit, abort, kill, segmentation fault: with --jobs > 1 no further band starts after one
+_PORTS = set()                   # rendezvous ports handed out by this process: a fresh one per band
+
+
+def plan_width(jobs, gpus):
+    """Bands in flight at once: --jobs, cut so that bands x ranks stays within MAX_GPU_PROCESSES (--gpus 8 --jobs 3: two at a time)."""
+    return min(jobs, max(1, MAX_GPU_PROCESSES // gpus))
+
+
+def free_port():
+    """A free TCP port for one band's rendezvous: bind port 0 and read back what the kernel gave, never the same one twice."""
+    while True:
+        with socket.socket() as s:
+            s.bind(("127.0.0.1", 0))
+            port = s.getsockname()[1]
+        if port not in _PORTS:
+            _PORTS.add(port)
+            return port
+
+
+def build_command(band, input_folder, output_file="", subpath=False, extra_args="", gpus=1):
+    """The argv of reference run() (:60-73): bands/<band>.py -i <input> [--output <file>] <extra> [--subpath <SUBFOLDERS[band]>].
+    gpus > 1 puts a sharding band under `torch.distributed.run` with that many ranks on this node; the band's own arguments stay."""
+    cmd = [sys.executable]
+    if gpus > 1 and band in SHARDED:
+        cmd += ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=%d" % gpus, "--master-addr", "127.0.0.1",
+                "--master-port", str(free_port())]
+    cmd += [os.path.join(ROOT, "bands", band + ".py"), "-i", input_folder]
     if output_file != "":
         cmd += ["--output", output_file]
     if extra_args != "":
@@ -67,17 +102,108 @@ def build_command(band, input_folder, output_file="", subpath=False, extra_args=
     return cmd
 
 
-def run(band, input_folder, output_file="", subpath=False, extra_args=""):
+def run(band, input_folder, output_file="", subpath=False, extra_args="", gpus=1):
     print("\n# ", band.upper())
     if band not in BUILT:
         print(f"band '{band}' is not built in this repo (out of scope, SURVEY section 2): skipped")
         return 1
-    cmd = build_command(band, input_folder, output_file, subpath, extra_args)
+    cmd = build_command(band, input_folder, output_file, subpath, extra_args, gpus)
     COMMANDS.append(cmd)
     print(" ".join(shlex.quote(c) for c in cmd), "\n")
     rc = subprocess.run(cmd, cwd=ROOT).returncode
     RESULTS.append((band, rc))
     return rc
+
+
+_PRINT = threading.Lock()
+
+
+def _relay(stream, band, out):
+    """One child stream, line by line, each line prefixed with its band; whole lines only, so bands never mix within one."""
+    for line in iter(stream.readline, ""):
+        with _PRINT:
+            out.write("[%s] %s" % (band, line if line.endswith("\n") else line + "\n"))
+            out.flush()
+    stream.close()
+
+
+def run_jobs(jobs, width):
+    """Run `jobs`, dicts of {band, kwargs of run(), after: callables}, at most `width` at a time, started in list order.  A job's
+    `after` steps run here, in the parent, as soon as that job ends.  A band that exits non-zero is recorded and the others go on;
+    one that is killed by a signal or exits with a DEVICE_TROUBLE code stops further starts, the running ones finish."""
+    done = queue.Queue()
+    pending = list(jobs)
+    running = {}
+    stop = False
+
+    def wait(job, proc, readers):
+        for t in readers:
+            t.join()
+        done.put((job, proc.wait()))
+
+    try:
+        while pending or running:
+            while pending and not stop and len(running) < width:
+                job = pending.pop(0)
+                band = job["band"]
+                cmd = build_command(band, **job["kwargs"])
+                COMMANDS.append(cmd)
+                with _PRINT:
+                    print("\n# ", band.upper())
+                    print(" ".join(shlex.quote(c) for c in cmd), "\n", flush=True)
+                proc = subprocess.Popen(cmd, cwd=ROOT, stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                                        text=True, errors="replace", bufsize=1)
+                readers = [threading.Thread(target=_relay, args=(proc.stdout, band, sys.stdout), daemon=True),
+                           threading.Thread(target=_relay, args=(proc.stderr, band, sys.stderr), daemon=True)]
+                for t in readers:
+                    t.start()
+                running[id(job)] = proc
+                threading.Thread(target=wait, args=(job, proc, readers), daemon=True).start()
+            if not running:          # stopped with bands still pending: they are not started
+                break
+            job, rc = done.get()
+            del running[id(job)]
+            job["rc"] = rc
+            if rc < 0 or rc in DEVICE_TROUBLE:
+                stop = True
+                with _PRINT:
+                    print("process.py: %s ended with %d: no further band is started" % (job["band"], rc), file=sys.stderr, flush=True)
+            for step in job["after"]:
+                step()
+    except KeyboardInterrupt:
+        for proc in running.values():
+            proc.terminate()
+        for proc in running.values():
+            proc.wait()
+        raise
+    finally:
+        RESULTS.extend((j["band"], j["rc"]) for j in jobs if "rc" in j)
+    if pending:
+        with _PRINT:
+            print("process.py: not started: %s" % ", ".join(j["band"] for j in pending), file=sys.stderr, flush=True)
+    return [j["band"] for j in pending]
+
+
+def order_bands(folder, first, steps):
+    """Rewrite metadata.json once, under the lock, with the keys of `bands` in the order a serial run inserts them: the keys in
+    `first` (what the folder held before the band jobs) where they are, then by owning step in `steps` - the band names in serial
+    order with "=alias" entries where set_default_band follows.  `mask` belongs to mask_mmdet; otherwise the owner is the longest
+    band name that prefixes the key, and an alias belongs to the step that sets it.  Keys nobody owns go last.  The sort is stable,
+    so a band's own keys keep the order the band gave them."""
+    def rank(key):
+        if key in first:
+            return -1
+        if "=" + key in steps:
+            return steps.index("=" + key)
+        if key == "mask" and "mask_mmdet" in steps:
+            return steps.index("mask_mmdet")
+        owners = [s for s in steps if not s.startswith("=") and key.startswith(s)]
+        return steps.index(max(owners, key=len)) if owners else len(steps)
+
+    def reorder(data):
+        bands = data.get("bands", {})
+        data["bands"] = {k: bands[k] for k in sorted(bands, key=rank)}
+    update_metadata(folder, reorder)
 
 
 def main(argv=None):
@@ -95,7 +221,12 @@ def main(argv=None):
     parser.add_argument("--flo", help="Save flo files for raft", action="store_true")
     parser.add_argument("--flow_backwards", "-b", help="Save backwards video", action="store_true")
     parser.add_argument("--flow_mask", "-m", help="Save mask of videos", action="store_true")
+    parser.add_argument("--jobs", "-j", help="Bands of one input run side by side, this many at a time", type=int, default=1)
+    parser.add_argument("--gpus", "-g", help="GPUs of this node every video band shards its frames across (default $PRISMA_GPUS, else 1)",
+                        type=int, default=int(os.environ.get("PRISMA_GPUS") or 1))
     args = parser.parse_args(argv)
+    if args.jobs < 1 or args.gpus < 1:
+        parser.error("--jobs and --gpus must be at least 1")
     del COMMANDS[:]
     del RESULTS[:]
 
@@ -163,7 +294,9 @@ def main(argv=None):
     if args.extra > 2:
         args.npy = True
 
-    run("mask_mmdet", folder_name, subpath=True, extra_args=EXTRA_ARGS["mask_mmdet"])
+    # the plan, in serial order: ("band", name, arguments of run()) and ("alias", name, band it points at, band whose end it follows)
+    gpus = args.gpus if video else 1             # a still image never shards
+    plan = [("band", "mask_mmdet", dict(subpath=True, extra_args=EXTRA_ARGS["mask_mmdet"]))]
 
     depth_args = ""
     if args.ply:
@@ -176,9 +309,10 @@ def main(argv=None):
         extra_args = depth_args + EXTRA_ARGS.get(band, "")
         if band == "depth_patchfusion" and video:
             extra_args += "--mode=p49 "
-        run(band, folder_name, subpath=args.extra, extra_args=extra_args)
+        plan.append(("band", band, dict(subpath=args.extra, extra_args=extra_args)))
     if args.rgbd is None:           # reference :243: a measured depth half keeps the `depth` name; the estimated band stays under its own
-        set_default_band(folder_name, "depth", (DEPTH_VIDEO_DEFAULT if video else DEPTH_IMAGE_DEFAULT) if args.depth == "all" else args.depth)
+        ddef = (DEPTH_VIDEO_DEFAULT if video else DEPTH_IMAGE_DEFAULT) if args.depth == "all" else args.depth
+        plan.append(("alias", "depth", ddef, ddef))
 
     if video:
         if args.flow is None:
@@ -189,12 +323,32 @@ def main(argv=None):
         if args.flow_mask:
             flow_args += "--mask "
         for band in (FLOW_BANDS if args.flow == "all" else [args.flow]):
-            run(band, folder_name, subpath=args.flo, extra_args=flow_args + EXTRA_ARGS.get(band, ""))
+            plan.append(("band", band, dict(subpath=args.flo, extra_args=flow_args + EXTRA_ARGS.get(band, ""))))
         fdef = FLOW_DEFAULT if args.flow == "all" else args.flow
-        set_default_band(folder_name, "flow", fdef)
-        set_default_band(folder_name, "flow_bwd", fdef + "_bwd")
-        set_default_band(folder_name, "flow_mask", fdef + "_mask")
-        set_default_band(folder_name, "flow_mask_bwd", fdef + "_mask_bwd")
+        plan += [("alias", "flow" + suffix, fdef + suffix, fdef) for suffix in ("", "_bwd", "_mask", "_mask_bwd")]
+
+    if args.jobs == 1:              # one band after the other, each alias where the reference sets it
+        for step in plan:
+            if step[0] == "band":
+                run(step[1], folder_name, gpus=gpus, **step[2])
+            else:
+                set_default_band(folder_name, step[1], step[2])
+    else:                           # side by side: an alias is set as soon as the band it points at has finished
+        first = list(load_metadata(folder_name)["bands"])
+        jobs, late = {}, []
+        for step in plan:
+            if step[0] == "band" and step[1] in BUILT:
+                jobs[step[1]] = {"band": step[1], "kwargs": dict(step[2], input_folder=folder_name, gpus=gpus), "after": []}
+            elif step[0] == "band":
+                run(step[1], folder_name)       # reports the unbuilt band and skips it
+            else:
+                (jobs[step[3]]["after"] if step[3] in jobs else late).append(
+                    lambda name=step[1], target=step[2]: set_default_band(folder_name, name, target))
+        run_jobs(list(jobs.values()), plan_width(args.jobs, gpus))
+        for step in late:
+            step()
+        order_bands(folder_name, first, [s[1] if s[0] == "band" else "=" + s[1] for s in plan])
+    if video:
         run("camera_colmap", folder_name, subpath=True)
     # a band that failed (missing checkpoint, bad input ...) leaves a PRISMA folder without its entries: say so and fail the run
     # (the reference's os.system() ignores band failures; a drop-in that now refuses to run without weights must not exit 0 on them)
