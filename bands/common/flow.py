@@ -1,0 +1,94 @@
+"""The flow bands' video loop (flow_raft, flow_gmflow: the two reference scripts share theirs line for line, flow_raft.py:69-166 and
+flow_gmflow.py:121-218): videos, .flo / 16-bit PNG dumps, the max-displacement CSV and the metadata entries, on common/loop.py."""
+import os
+
+import numpy as np
+
+from prisma_amd import engine
+
+from .io import FrameReader, VideoWriter, write_flo, write_flow_png
+from .loop import run_sharded
+
+
+def _mask_rgb(mask):
+    """reference bands/common/flow.py:75-78: True -> 255, three equal channels."""
+    return np.repeat((mask.astype(np.uint8) * 255)[..., None], 3, axis=-1)
+
+
+def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterations):
+    """Pairs (i, i+1) shard by rank in contiguous blocks with a one-frame halo.  Every chunk is written as soon
+    as it is done: rank 0 feeds its own chunks to the VideoWriters from a sink thread (the next chunk is already on the
+    GPU) and then muxes the other ranks' chunks in frame order through shard.Relay; only the per-pair max displacements
+    (4 bytes each) go through a collective.  No list or tensor ever holds the whole video."""
+    src = FrameReader(args.input)
+    n = len(src)
+    h, w = src[0].shape[:2]
+    base, ext = args.output.rsplit(".", 1)
+    want_mask = bool(args.output_mask or args.subpath_mask)
+    # flow_gmflow predicts the backward flow only for --backwards / masks (reference flow_gmflow.py:86); with --subpath alone (what
+    # process.py passes) a second global matching would be computed and thrown away
+    both = args.backwards or want_mask or (subpath_needs_both and bool(args.subpath))
+    want_flow = bool(args.subpath or args.subpath_mask)
+    sh, sw = engine.flow_out_size(h, w, args.scale)
+    first, last = rk.frames(n - 1)                       # pair indices owned by this rank
+    dirs = ("f", "b") if args.backwards else ("f",)
+    # the videos, in the order a pair's frames go out; the key names the array of a chunk (rgb / mask) and its direction
+    files = {"rgb_" + d: (args.output if d == "f" else base + "_bwd." + ext) for d in dirs}
+    if args.output_mask:
+        mbase, mext = args.output_mask.rsplit(".", 1)
+        files.update({"mask_" + d: (args.output_mask if d == "f" else mbase + "_bwd." + mext) for d in dirs})
+    videos = {k: VideoWriter(width=w, height=h, frame_rate=src.fps, filename=f) for k, f in files.items()} if rk.main else {}
+
+    def step(_s, frames):
+        mask = None
+        if want_mask:
+            flow, rgb, mx, mask = model.infer_sequence_masks(frames, scale=args.scale, iters=iterations, want_flow=want_flow, want_rgb=True)
+        else:
+            flow, rgb, mx = model.infer_sequence(frames, scale=args.scale, iters=iterations, backward=both, want_flow=want_flow, want_rgb=True)
+        c = {k: (rgb if k.startswith("rgb") else mask)[:, "fb".index(k[-1])] for k in files}
+        return c, (flow, mask), mx[:, :1]
+
+    def write_chunk(_s, c):          # rank 0 only: one chunk of encoded pairs into every open video, in order
+        for j in range(len(c["rgb_f"])):
+            for k, v in videos.items():
+                v.write(c[k][j] if k.startswith("rgb") else _mask_rgb(c[k][j]))
+
+    def dump(s, payload):
+        flow, mask = payload
+        for j in range(len(flow)):
+            if args.subpath:    # the reference crashes here (common/flow.py:91 shadows io.write_flow); write the .flo it meant to
+                write_flo(os.path.join(args.subpath + "_fwd", "%04d.flo" % (s + j)), flow[j, 0])
+                if args.backwards:
+                    write_flo(os.path.join(args.subpath + "_bwd", "%04d.flo" % (s + j)), flow[j, 1])
+            if args.subpath_mask:
+                write_flow_png(os.path.join(args.subpath_mask + "_fwd", "%04d.png" % (s + j)), flow[j, 0], mask[j, 0])
+                if args.backwards:
+                    write_flow_png(os.path.join(args.subpath_mask + "_bwd", "%04d.png" % (s + j)), flow[j, 1], mask[j, 1])
+
+    mx_all = run_sharded(rk, src, n - 1, chunk, 1, args.output, ((n - 1) - (last - first)) * sh * sw * 3 * len(files),
+                         step, write_chunk, dump if want_flow else None, n_scalars=1, ctx=model)
+    if not rk.main:
+        return
+    # last frame: zero flow -> 0/0 -> NaN -> uint8 0, max displacement 0.0, all-False masks (reference :116-131)
+    for v in videos.values():
+        v.write(np.zeros((sh, sw, 3), np.uint8))
+    # the reference appends np.float32 scalars and formats them with "{}" (:138-141): '12.148', not the float64 repr
+    max_disps = [np.float32(v) for v in mx_all.reshape(-1)] + [np.float32(0.0)]
+    if want_flow:
+        dump(n - 1, (np.zeros((1, 2, sh, sw, 2), np.float32), np.zeros((1, 2, sh, sw), bool)))
+    for v in videos.values():
+        v.close()
+    with open(base + ".csv", "w") as f:
+        f.writelines("{}\n".format(e) for e in max_disps)
+    if data:
+        data["bands"][band] = {"url": band + "." + ext, "values": {"dist": {"type": "float", "url": band + ".csv"}}}
+        if args.subpath:
+            data["bands"][band]["folder"] = args.subpath
+        if args.backwards:
+            data["bands"][band + "_bwd"] = {"url": band + "_bwd." + ext}
+            if args.subpath:
+                data["bands"][band + "_bwd"]["folder"] = args.subpath + "_bwd"
+        if args.output_mask:
+            data["bands"][band + "_mask"] = {"url": band + "_mask." + ext}
+            if args.backwards:
+                data["bands"][band + "_mask_bwd"] = {"url": band + "_mask_bwd." + ext}

@@ -7,7 +7,6 @@ The PyTorch model and the numpy post-process are replaced by libprisma_bands.so 
 prisma_amd.engine (C ABI, include/prisma_bands.h); frames are pushed in batches instead of one by one.
 """
 import argparse
-import copy
 import os
 import sys
 
@@ -18,10 +17,11 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_ply, write_rgb  # noqa: E402
+from common.io import FrameReader, VideoWriter, create_folder, open_rgb, write_ply, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
-from common.pipe import AsyncSink, prefetch  # noqa: E402
+from common.cli import begin, end, synthetic_or_exit  # noqa: E402
+from common.loop import run_sharded  # noqa: E402
+from common.meta import is_video  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
 BAND = "depth_anything"
@@ -52,9 +52,7 @@ def load_weights(encoder, path=""):
     for c in cands:
         if c and os.path.exists(c):
             return load_checkpoint(c)
-    if not shard.synthetic_allowed(getattr(args, "synthetic", False)):
-        raise SystemExit(f"[{BAND}] no checkpoint found ({cands}); pass --weights, or --synthetic / PRISMA_SYNTH=1 for seeded synthetic weights")
-    print(f"[{BAND}] no checkpoint found ({cands}); using seeded synthetic weights (--synthetic)", file=sys.stderr)
+    synthetic_or_exit(BAND, f"no checkpoint found ({cands})", "--weights", getattr(args, "synthetic", False))
     return synth.depth_anything_weights(encoder, seed=1234)
 
 
@@ -75,9 +73,7 @@ def load_metric_weights(path):
     """ZoeDepth state dict (`core.core.*` + the metric head); `model_io.load_state_from_resource` keeps it under 'model'."""
     if path and os.path.exists(path):
         return load_checkpoint(path, wrappers=("model",))
-    if not shard.synthetic_allowed(getattr(args, "synthetic", False)):
-        raise SystemExit(f"[{BAND}] metric checkpoint {path!r} not found; pass --weights, or --synthetic / PRISMA_SYNTH=1")
-    print(f"[{BAND}] metric checkpoint {path!r} not found; using seeded synthetic weights (--synthetic)", file=sys.stderr)
+    synthetic_or_exit(BAND, f"metric checkpoint {path!r} not found", "--weights", getattr(args, "synthetic", False), what="")
     return synth.zoe_weights()
 
 
@@ -150,44 +146,27 @@ def process_video(a):
     if model is None:
         init_model(device=rk.device)
     first, last = rk.frames(n)
-    lo, hi = [], []
     want_depth = bool(a.npy or a.subpath)
-    relay = shard.Relay(rk, a.output, est_bytes=(n - (last - first)) * h * w * 3)
 
-    def emit(s, depth, rgb):
-        # runs on the sink thread, chunk after chunk in order: video frames, .npy / .png dumps (reference :215-225)
-        if not rk.main:
-            relay.put(s, {"rgb": rgb})
-        for j in range(len(rgb)):
-            if rk.main:
-                out.write(rgb[j])
-            if a.npy and a.subpath:
-                np.save(os.path.join(a.subpath, "{:05d}.npy".format(s + j)), depth[j])
-            if a.subpath:
-                write_depth_png(os.path.join(a.subpath, "{:05d}.png".format(s + j)), depth[j])
-
-    # the decode of chunk i+1 and the encode / writes of chunk i-1 overlap the engine's work on chunk i
-    sink = AsyncSink(depth=2)
-    load = lambda s: np.stack([src[i] for i in range(s, min(last, s + BATCH))])      # noqa: E731
-    for s, frames in prefetch(load, range(first, last, BATCH)):
+    def step(_s, frames):
         depth, rgb, mn, mx = model.infer_batch(frames, want_depth=want_depth, want_rgb=True, flip=_flip())
-        sink.submit(emit, s, depth, rgb)
-        lo += [float(v) for v in mn]
-        hi += [float(v) for v in mx]
-    sink.close()
-    if rk.world > 1:
-        # scalars first (every rank gets here when its own compute is done), then rank 0 muxes the other ranks' chunks while they
-        # wait on a file signal in relay.close() - no collective is pending during the mux
-        # (with a bounded spool, PRISMA_SPOOL_MAX_CHUNKS, the drain has to run DURING the gather: Relay.drain_begin)
-        if rk.main:
-            relay.drain_begin(n, BATCH, lambda s, c: [out.write(f) for f in c["rgb"]])
-        mm = rk.gather(np.asarray([lo, hi], np.float32).T.reshape(-1, 2), n, ctx=model)
-        if rk.main:
-            lo, hi = [float(v) for v in mm[:, 0]], [float(v) for v in mm[:, 1]]
-            relay.drain_end()
-    relay.close()
+        return {"rgb": rgb}, depth, np.stack([mn, mx], 1)
+
+    def write_chunk(_s, c):          # rank 0 only: the video frames, chunk after chunk in order
+        for f in c["rgb"]:
+            out.write(f)
+
+    def dump(s, depth):              # sink thread: .npy / .png dumps (reference :215-225)
+        for j in range(len(depth)):
+            if a.npy:
+                np.save(os.path.join(a.subpath, "{:05d}.npy".format(s + j)), depth[j])
+            write_depth_png(os.path.join(a.subpath, "{:05d}.png".format(s + j)), depth[j])
+
+    mm = run_sharded(rk, src, n, BATCH, 0, a.output, (n - (last - first)) * h * w * 3, step, write_chunk,
+                     dump if a.subpath else None, n_scalars=2, ctx=model)
     if not rk.main:
         return
+    lo, hi = [float(v) for v in mm[:, 0]], [float(v) for v in mm[:, 1]]
     out.close()
     with open(os.path.join(out_folder, BAND + "_min.csv"), "w") as f:
         f.writelines("{}\n".format(v) for v in lo)
@@ -211,30 +190,13 @@ def main(argv=None):
     ap.add_argument("--weights", help="checkpoint (.npz / .pth state dict); default models/depth_anything_<encoder>14.*", default="")
     ap.add_argument("--synthetic", help="seeded synthetic weights when no checkpoint is found (tests / benchmarks)", action="store_true")
     args = ap.parse_args(argv)
-    data = load_metadata(args.input)
-    loaded = copy.deepcopy(data)
-    if data:
-        print("PRISMA metadata found and loaded")
-        folder = args.input
-        args.input = get_url(folder, data, "rgba")
-        args.output = get_target(args.input, data, band=BAND, target=args.output, force_extension="png")
-        meta_path = folder
-    else:
-        meta_path = args.input
-        if not args.output:
-            ext = os.path.basename(args.input).rsplit(".", 1)[1]
-            args.output = os.path.join(os.path.dirname(args.input), BAND + "." + (ext if is_video(args.input) else "png"))
-    ranks = shard.Ranks()
-    if ranks.main:
-        check_overwrite(args.output)
+    data, loaded, meta_path, ranks = begin(args, BAND)
     init_model(args.encoder, args.weights, device=ranks.device)
     if is_video(args.output):
         process_video(args)
     elif ranks.main:
         process_image(args)
-    if ranks.main:
-        merge_metadata(meta_path, data, loaded)
-    ranks.close()
+    end(ranks, meta_path, data, loaded)
 
 
 if __name__ == "__main__":

@@ -6,8 +6,8 @@ engine builds, or the one flag set of GMFlow's refinement model, REFINE below; t
 tokens and --prop_radius_list r, 1 .. 2, local-window flow propagation, -1 = global, reference bands/gmflow/gmflow.py:128-157), same outputs
 (<BAND>.mp4, <BAND>.csv with the per-frame max displacement, optional <BAND>_bwd / _mask / _mask_bwd
 videos, .flo / 16-bit PNG dumps, metadata entries :195-218), same module API (BAND, init_model(), infer()).  The frame loop, the file
-writers and the multi-rank relay are flow_raft's (bands/flow_raft.py process_video: the two reference scripts share them line for line,
-flow_gmflow.py:121-218 vs flow_raft.py:69-166); the model is libprisma_bands.so's GmflowEngine through prisma_amd.engine.FlowGMFlow.
+writers and the multi-rank relay are the ones flow_raft uses (bands/common/flow.py process_video: the two reference scripts share them line
+for line, flow_gmflow.py:121-218 vs flow_raft.py:69-166); the model is libprisma_bands.so's GmflowEngine through prisma_amd.engine.FlowGMFlow.
 
 --backwards / --mask with a matching radius: the reference raises there (pred_bidir_flow: local_correlation_softmax returns B flows while
 the features were concatenated to 2 B, gmflow.py:142,153-157).  This band computes the backward direction as the forward direction of the
@@ -20,7 +20,6 @@ The engine reads the architecture from the weights; a mismatch between the flags
 --num_scales 2 on its own, other split counts and other flag mixes stay refused.
 """
 import argparse
-import copy
 import os
 import sys
 
@@ -31,14 +30,14 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-import flow_raft as _loop  # noqa: E402  (process_video and its writers; its module globals carry this band's model / metadata)
-from common.io import check_overwrite  # noqa: E402
+from common import flow  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
+from common.cli import begin, end, synthetic_or_exit  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
 BAND = "flow_gmflow"
 MODEL = "models/gmflow_sintel-0c07dcb3.pth"      # reference :35
+CHUNK = int(os.environ.get("PRISMA_BATCH", "16"))
 # the model flags of reference :239-249 and the only values the engine implements (the band's defaults); corr_radius_list and
 # prop_radius_list are also taken as one radius each (RADII: the largest the engine's kernels are built for)
 ARCH = {"feature_channels": 128, "num_scales": 1, "upsample_factor": 8, "num_head": 1, "attention_type": "swin", "ffn_dim_expansion": 4,
@@ -60,9 +59,7 @@ def load_weights(path):
     """reference :57-61: torch.load(checkpoint)['model'] if present, else the dict itself."""
     if path and os.path.exists(path):
         return load_checkpoint(path, wrappers=("model",))
-    if not shard.synthetic_allowed(_SYNTH[0]):
-        raise SystemExit(f"[{BAND}] checkpoint {path!r} not found; pass --model, or --synthetic / PRISMA_SYNTH=1 for seeded synthetic weights")
-    print(f"[{BAND}] checkpoint {path!r} not found; using seeded synthetic weights (--synthetic)", file=sys.stderr)
+    synthetic_or_exit(BAND, f"checkpoint {path!r} not found", "--model", _SYNTH[0])
     return synth.gmflow_weights(seed=2468, num_scales=_SCALES[0])
 
 
@@ -144,14 +141,12 @@ def infer(args, image1, image2):
 
 
 def process_video(args):
-    """The shared flow loop with this band's name, model, metadata and ranks."""
-    saved = (_loop.BAND, _loop.model, _loop.data, _loop.ranks, _loop.SUBPATH_NEEDS_BOTH)
-    _loop.BAND, _loop.model, _loop.data, _loop.ranks, _loop.SUBPATH_NEEDS_BOTH = BAND, model, data, ranks, False
-    args.iterations = 1                    # GMFlow is not iterative; the loop passes it through to the engine, which ignores it
-    try:
-        _loop.process_video(args)
-    finally:                               # a process may run both flow bands (tests do): leave flow_raft's globals as they were
-        _loop.BAND, _loop.model, _loop.data, _loop.ranks, _loop.SUBPATH_NEEDS_BOTH = saved
+    """The flow bands' loop (common/flow.py) with this band's name, model, metadata and ranks as they are now.  The backward flow is predicted
+    only when it is asked for; GMFlow is not iterative: the engine ignores the count the loop passes through."""
+    rk = ranks or shard.Ranks()
+    if model is None:
+        init_model(args, device=rk.device)
+    flow.process_video(args, BAND, model, data, rk, CHUNK, subpath_needs_both=False, iterations=1)
 
 
 def main(argv=None):
@@ -183,36 +178,10 @@ def main(argv=None):
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights when the checkpoint is missing (tests / benchmarks)")
     args = ap.parse_args(argv)
     check_arch(args)
-    data = load_metadata(args.input)
-    loaded = copy.deepcopy(data)
-    if data:
-        folder = args.input
-        args.input = get_url(folder, data, "rgba")
-        args.output = get_target(args.input, data, band=BAND, target=args.output)
-        if args.mask:
-            args.output_mask = get_target(args.input, data, band=BAND + "_mask")
-        meta_path = folder
-    else:
-        meta_path = args.input
-        if not args.output:
-            args.output = os.path.join(os.path.dirname(args.input), BAND + "." + os.path.basename(args.input).rsplit(".", 1)[1])
-    if not is_video(args.output):
-        raise SystemExit(f"[{BAND}] needs a video input")
-    ranks = shard.Ranks()
-    if ranks.main:
-        check_overwrite(args.output)
-    input_folder = os.path.dirname(args.input)
-    for attr in ("subpath", "subpath_mask"):
-        if getattr(args, attr):
-            setattr(args, attr, os.path.join(input_folder, getattr(args, attr)))
-            os.makedirs(getattr(args, attr) + "_fwd", exist_ok=True)
-            if args.backwards:
-                os.makedirs(getattr(args, attr) + "_bwd", exist_ok=True)
+    data, loaded, meta_path, ranks = begin(args, BAND, flow=True)
     init_model(args, device=ranks.device)
     process_video(args)
-    if ranks.main:
-        merge_metadata(meta_path, data, loaded)
-    ranks.close()
+    end(ranks, meta_path, data, loaded)
 
 
 if __name__ == "__main__":

@@ -7,7 +7,6 @@ infer()).  Frames are pushed to libprisma_bands.so in overlapping chunks; every 
 fnet / cnet once instead of twice per pair.
 """
 import argparse
-import copy
 import os
 import sys
 
@@ -18,10 +17,9 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, check_overwrite, write_flo, write_flow_png  # noqa: E402
+from common import flow  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
-from common.pipe import AsyncSink, prefetch  # noqa: E402
+from common.cli import begin, end, synthetic_or_exit  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
 BAND = "flow_raft"
@@ -33,16 +31,13 @@ model = None
 data = None
 _SYNTH = [False]      # --synthetic
 ranks = None          # shard.Ranks(): one process per GPU under torchrun, world 1 otherwise
-SUBPATH_NEEDS_BOTH = True   # flow_gmflow's wrapper clears it around its call of process_video
 
 
 def load_weights(path):
     """Checkpoint keys carry a `module.` prefix from DataParallel (reference :42-44): strip it."""
     if path and os.path.exists(path):
         return load_checkpoint(path, strip_prefix="module.")
-    if not shard.synthetic_allowed(_SYNTH[0]):
-        raise SystemExit(f"[{BAND}] checkpoint {path!r} not found; pass --model, or --synthetic / PRISMA_SYNTH=1 for seeded synthetic weights")
-    print(f"[{BAND}] checkpoint {path!r} not found; using seeded synthetic weights (--synthetic)", file=sys.stderr)
+    synthetic_or_exit(BAND, f"checkpoint {path!r} not found", "--model", _SYNTH[0])
     return synth.raft_weights(seed=4321)
 
 
@@ -80,135 +75,13 @@ def infer(args, image1, image2):
     return flow[0, 0], flow[0, 1], None, None
 
 
-def _mask_rgb(mask):
-    """bands/common/flow.py:75-78: True -> 255, three equal channels."""
-    return np.repeat((mask.astype(np.uint8) * 255)[..., None], 3, axis=-1)
-
-
 def process_video(args):
-    """Pairs (i, i+1) shard by rank in contiguous blocks with a one-frame halo.  Every chunk is written as soon
-    as it is done: rank 0 feeds its own chunks to the VideoWriters from a sink thread (the next chunk is already on the
-    GPU) and then muxes the other ranks' chunks in frame order through shard.Relay; only the per-pair max displacements
-    (4 bytes each) go through a collective.  No list or tensor ever holds the whole video."""
+    """The flow bands' loop (common/flow.py) with this band's name, model, metadata and ranks as they are now.  RAFT always predicts both
+    directions for the --subpath dumps; the iterations are the command line's."""
     rk = ranks or shard.Ranks()
-    src = FrameReader(args.input)
-    n = len(src)
-    h, w = src[0].shape[:2]
-    base = args.output.rsplit(".", 1)[0]
-    ext = args.output.rsplit(".", 1)[1]
-    want_mask = bool(args.output_mask or args.subpath_mask)
-    # flow_gmflow predicts the backward flow only for --backwards / masks (reference flow_gmflow.py:86); with --subpath alone (what
-    # process.py passes) a second global matching would be computed and thrown away (ADVICE r3)
-    both = args.backwards or want_mask or (SUBPATH_NEEDS_BOTH and bool(args.subpath))
-    want_flow = bool(args.subpath or args.subpath_mask)
     if model is None:
         init_model(args, device=rk.device)
-    sh, sw = engine.flow_out_size(h, w, args.scale)
-    first, last = rk.frames(n - 1)                       # pair indices owned by this rank
-    fwd_video = bwd_video = fwd_mask_video = bwd_mask_video = None
-    if rk.main:
-        fwd_video = VideoWriter(width=w, height=h, frame_rate=src.fps, filename=args.output)
-        bwd_video = VideoWriter(width=w, height=h, frame_rate=src.fps, filename=base + "_bwd." + ext) if args.backwards else None
-        if args.output_mask:
-            mbase, mext = args.output_mask.rsplit(".", 1)
-            fwd_mask_video = VideoWriter(width=w, height=h, frame_rate=src.fps, filename=args.output_mask)
-            if args.backwards:
-                bwd_mask_video = VideoWriter(width=w, height=h, frame_rate=src.fps, filename=mbase + "_bwd." + mext)
-    streams = (1 + bool(args.backwards)) * (1 + bool(args.output_mask))
-    relay = shard.Relay(rk, args.output, est_bytes=((n - 1) - (last - first)) * sh * sw * 3 * streams)
-    mxs = []
-
-    def write_chunk(_s, c):          # rank 0 only: one chunk of encoded pairs into every open video, in order
-        for j in range(len(c["rgb_f"])):
-            fwd_video.write(c["rgb_f"][j])
-            if bwd_video:
-                bwd_video.write(c["rgb_b"][j])
-            if fwd_mask_video:
-                fwd_mask_video.write(_mask_rgb(c["mask_f"][j]))
-            if bwd_mask_video:
-                bwd_mask_video.write(_mask_rgb(c["mask_b"][j]))
-
-    def emit(s, flow, rgb, mask):    # sink thread, chunks in order
-        c = {"rgb_f": rgb[:, 0]}
-        if args.backwards:
-            c["rgb_b"] = rgb[:, 1]
-        if args.output_mask:
-            c["mask_f"] = mask[:, 0]
-            if args.backwards:
-                c["mask_b"] = mask[:, 1]
-        if rk.main:
-            write_chunk(s, c)
-        else:
-            relay.put(s, c)
-        for j in range(len(rgb)):
-            if args.subpath:    # the reference crashes here (common/flow.py:91 shadows io.write_flow); write the .flo it meant to
-                write_flo(os.path.join(args.subpath + "_fwd", "%04d.flo" % (s + j)), flow[j, 0])
-                if args.backwards:
-                    write_flo(os.path.join(args.subpath + "_bwd", "%04d.flo" % (s + j)), flow[j, 1])
-            if args.subpath_mask:
-                write_flow_png(os.path.join(args.subpath_mask + "_fwd", "%04d.png" % (s + j)), flow[j, 0], mask[j, 0])
-                if args.backwards:
-                    write_flow_png(os.path.join(args.subpath_mask + "_bwd", "%04d.png" % (s + j)), flow[j, 1], mask[j, 1])
-
-    sink = AsyncSink(depth=2)
-    load = lambda s: np.stack([src[i] for i in range(s, min(last, s + CHUNK) + 1)])  # noqa: E731  (1-frame halo)
-    for s, frames in prefetch(load, range(first, last, CHUNK)):     # the next chunk decodes while this one is on the GPU (SURVEY 8 f-4)
-        mask = None
-        if want_mask:
-            flow, rgb, mx, mask = model.infer_sequence_masks(frames, scale=args.scale, iters=args.iterations,
-                                                             want_flow=want_flow, want_rgb=True)
-        else:
-            flow, rgb, mx = model.infer_sequence(frames, scale=args.scale, iters=args.iterations, backward=both,
-                                                 want_flow=want_flow, want_rgb=True)
-        sink.submit(emit, s, flow, rgb, mask)
-        mxs += [np.float32(v) for v in mx[:, 0]]
-    sink.close()
-    mx_all = np.asarray(mxs, np.float32)
-    if rk.world > 1:
-        # the gather comes before the drain: no collective pending while rank 0 muxes (ADVICE r2) - unless the spool is bounded
-        # (PRISMA_SPOOL_MAX_CHUNKS), in which case the drain has to run during the gather (Relay.drain_begin, ADVICE r3)
-        if rk.main:
-            relay.drain_begin(n - 1, CHUNK, write_chunk)
-        mx_all = rk.gather(mx_all, n - 1, ctx=model)
-        if rk.main:
-            relay.drain_end()
-    relay.close()
-    if not rk.main:
-        return
-    zero = np.zeros((sh, sw, 3), np.uint8)
-    # last frame: zero flow -> 0/0 -> NaN -> uint8 0, max displacement 0.0, all-False masks (reference :116-131)
-    for v in (fwd_video, bwd_video, fwd_mask_video, bwd_mask_video):
-        if v:
-            v.write(zero)
-    # the reference appends np.float32 scalars and formats them with "{}" (:138-141): '12.148', not the float64 repr
-    max_disps = [np.float32(v) for v in np.asarray(mx_all).reshape(-1)] + [np.float32(0.0)]
-    zf = np.zeros((sh, sw, 2), np.float32)
-    if args.subpath:
-        write_flo(os.path.join(args.subpath + "_fwd", "%04d.flo" % (n - 1)), zf)
-        if args.backwards:
-            write_flo(os.path.join(args.subpath + "_bwd", "%04d.flo" % (n - 1)), zf)
-    if args.subpath_mask:
-        zm = np.zeros((sh, sw), bool)
-        write_flow_png(os.path.join(args.subpath_mask + "_fwd", "%04d.png" % (n - 1)), zf, zm)
-        if args.backwards:
-            write_flow_png(os.path.join(args.subpath_mask + "_bwd", "%04d.png" % (n - 1)), zf, zm)
-    for v in (fwd_video, bwd_video, fwd_mask_video, bwd_mask_video):
-        if v:
-            v.close()
-    with open(base + ".csv", "w") as f:
-        f.writelines("{}\n".format(e) for e in max_disps)
-    if data:
-        data["bands"][BAND] = {"url": BAND + "." + ext, "values": {"dist": {"type": "float", "url": BAND + ".csv"}}}
-        if args.subpath:
-            data["bands"][BAND]["folder"] = args.subpath
-        if args.backwards:
-            data["bands"][BAND + "_bwd"] = {"url": BAND + "_bwd." + ext}
-            if args.subpath:
-                data["bands"][BAND + "_bwd"]["folder"] = args.subpath + "_bwd"
-        if args.output_mask:
-            data["bands"][BAND + "_mask"] = {"url": BAND + "_mask." + ext}
-            if args.backwards:
-                data["bands"][BAND + "_mask_bwd"] = {"url": BAND + "_mask_bwd." + ext}
+    flow.process_video(args, BAND, model, data, rk, CHUNK, subpath_needs_both=True, iterations=args.iterations)
 
 
 def main(argv=None):
@@ -231,36 +104,10 @@ def main(argv=None):
     ap.add_argument("--alternate_corr", action="store_true", help="use efficent correlation implementation")
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights when the checkpoint is missing (tests / benchmarks)")
     args = ap.parse_args(argv)
-    data = load_metadata(args.input)
-    loaded = copy.deepcopy(data)
-    if data:
-        folder = args.input
-        args.input = get_url(folder, data, "rgba")
-        args.output = get_target(args.input, data, band=BAND, target=args.output)
-        if args.mask:
-            args.output_mask = get_target(args.input, data, band=BAND + "_mask")
-        meta_path = folder
-    else:
-        meta_path = args.input
-        if not args.output:
-            args.output = os.path.join(os.path.dirname(args.input), BAND + "." + os.path.basename(args.input).rsplit(".", 1)[1])
-    if not is_video(args.output):
-        raise SystemExit(f"[{BAND}] needs a video input")
-    ranks = shard.Ranks()
-    if ranks.main:
-        check_overwrite(args.output)
-    input_folder = os.path.dirname(args.input)
-    for attr in ("subpath", "subpath_mask"):
-        if getattr(args, attr):
-            setattr(args, attr, os.path.join(input_folder, getattr(args, attr)))
-            os.makedirs(getattr(args, attr) + "_fwd", exist_ok=True)
-            if args.backwards:
-                os.makedirs(getattr(args, attr) + "_bwd", exist_ok=True)
+    data, loaded, meta_path, ranks = begin(args, BAND, flow=True)
     init_model(args, device=ranks.device)
     process_video(args)
-    if ranks.main:
-        merge_metadata(meta_path, data, loaded)
-    ranks.close()
+    end(ranks, meta_path, data, loaded)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,6 @@ mmdet's init_detector / inference_detector are replaced by libprisma_bands.so th
 are pushed in batches instead of one by one.
 """
 import argparse
-import copy
 import os
 import sys
 
@@ -19,10 +18,11 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_rgb  # noqa: E402
+from common.io import FrameReader, VideoWriter, create_folder, open_rgb, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
-from common.meta import get_target, get_url, is_video, load_metadata, merge_metadata  # noqa: E402
-from common.pipe import AsyncSink, prefetch  # noqa: E402
+from common.cli import begin, end, synthetic_or_exit  # noqa: E402
+from common.loop import run_sharded  # noqa: E402
+from common.meta import is_video  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
 BAND = "mask"
@@ -41,9 +41,7 @@ def load_weights(path, cfg):
     """mmdet checkpoints keep the tensors under 'state_dict'."""
     if path and os.path.exists(path):
         return load_checkpoint(path, wrappers=("state_dict",))
-    if not shard.synthetic_allowed(_SYNTH[0]):
-        raise SystemExit(f"[{BAND}] checkpoint {path!r} not found; pass --weights, or --synthetic / PRISMA_SYNTH=1 for seeded synthetic weights")
-    print(f"[{BAND}] checkpoint {path!r} not found; using seeded synthetic weights (--synthetic)", file=sys.stderr)
+    synthetic_or_exit(BAND, f"checkpoint {path!r} not found", "--weights", _SYNTH[0])
     return synth.solov2_weights(cfg)
 
 
@@ -93,28 +91,21 @@ def process_video(args):
         create_folder(args.subpath)
     first, last = rk.frames(n)
     out = VideoWriter(width=w, height=h, frame_rate=src.fps, filename=args.output) if rk.main else None
-    relay = shard.Relay(rk, args.output, est_bytes=(n - (last - first)) * h * w * 3)
-
     set_sdf(args.sdf)
 
-    def emit(s, masks):              # sink thread, chunks in order (the SDF, if asked for, is already in G: set_sdf)
-        if rk.main:
-            for f in masks:
-                out.write(f)
-        else:
-            relay.put(s, {"mask": masks})
-        if args.subpath:
-            for j in range(len(masks)):
-                write_rgb(os.path.join(args.subpath, "{:05d}.png".format(s + j)), _colmap(masks[j]))
+    def step(_s, frames):            # the SDF, if asked for, is already in G: set_sdf
+        masks = model.infer_batch(frames, args.confidence, keep_ids())
+        return {"mask": masks}, masks, None
 
-    sink = AsyncSink(depth=2)
-    load = lambda s: np.stack([src[i] for i in range(s, min(last, s + BATCH))])      # noqa: E731
-    for s, frames in prefetch(load, range(first, last, BATCH)):      # the next chunk decodes while this one is on the GPU
-        sink.submit(emit, s, model.infer_batch(frames, args.confidence, keep_ids()))
-    sink.close()
-    if rk.world > 1 and rk.main:
-        relay.drain(n, BATCH, lambda s, c: [out.write(f) for f in c["mask"]])
-    relay.close()
+    def write_chunk(_s, c):          # rank 0 only: the video frames, chunk after chunk in order
+        for f in c["mask"]:
+            out.write(f)
+
+    def dump(s, masks):              # sink thread: the COLMAP frames
+        for j in range(len(masks)):
+            write_rgb(os.path.join(args.subpath, "{:05d}.png".format(s + j)), _colmap(masks[j]))
+
+    run_sharded(rk, src, n, BATCH, 0, args.output, (n - (last - first)) * h * w * 3, step, write_chunk, dump if args.subpath else None)
     if not rk.main:
         return
     out.close()
@@ -135,29 +126,15 @@ def main(argv=None):
     ap.add_argument("--synthetic", action="store_true", help="seeded synthetic weights when the checkpoint is missing (tests / benchmarks)")
     args = ap.parse_args(argv)
     _SYNTH[0] = args.synthetic
-    data = load_metadata(args.input)
-    loaded = copy.deepcopy(data)
-    meta_path = args.input
-    if data:
-        print("PRISMA metadata found and loaded")
-        args.input = get_url(meta_path, data, "rgba")
-        args.output = get_target(args.input, data, band=BAND, target=args.output, force_extension="png")
-    else:
+    data, loaded, meta_path, ranks = begin(args, BAND)
+    if not data:
         data = {"bands": {}}
-        if not args.output:
-            ext = os.path.basename(args.input).rsplit(".", 1)[1]
-            args.output = os.path.join(os.path.dirname(args.input), BAND + "." + (ext if is_video(args.input) else "png"))
-    ranks = shard.Ranks()
-    if ranks.main:
-        check_overwrite(args.output)
     init_model(args.arch, args.weights, device=ranks.device)
     if is_video(args.output):
         process_video(args)
     elif ranks.main:
         process_image(args)
-    if ranks.main:
-        merge_metadata(meta_path, data, loaded)
-    ranks.close()
+    end(ranks, meta_path, data, loaded)
 
 
 if __name__ == "__main__":

@@ -24,7 +24,8 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from common.io import FrameReader, VideoWriter, check_overwrite, create_folder, open_rgb, write_rgb  # noqa: E402
 from common.meta import add_band, get_target, is_video, load_metadata, merge_metadata  # noqa: E402
-from common.pipe import AsyncSink, prefetch  # noqa: E402
+from common.loop import chunks  # noqa: E402
+from common.pipe import AsyncSink  # noqa: E402
 
 BAND = "rgba"
 CHUNK = int(os.environ.get("PRISMA_BATCH", "32"))      # frames per engine call, like the other bands' loops
@@ -58,7 +59,6 @@ def split(src, args, ext):
     fps = int(args.fps)                                                            # :113
     half = (w / 2, h) if args.rgbd in ("left", "right") else (w, h / 2)             # :30-40: the sizes both writers get
     outs = [VideoWriter(width=half[0], height=half[1], frame_rate=fps, filename=f) for f in (args.output, depth_file)]
-    n = len(src)
 
     def emit(s, rgb, dep):
         # sink thread, chunk after chunk in order: both videos and the frame dumps (:65-72)
@@ -69,9 +69,8 @@ def split(src, args, ext):
                 out.write(frame)
 
     sink = AsyncSink(depth=2)
-    load = lambda s: np.stack([src[i] for i in range(s, min(n, s + CHUNK))])      # noqa: E731
     try:
-        for s, frames in prefetch(load, range(0, n, CHUNK)):
+        for s, frames in chunks(src, 0, len(src), CHUNK):
             dep = ctx.rgbd_depth(frames, args.rgbd) if ctx else frames[:, db[0]:db[1], db[2]:db[3]]
             sink.submit(emit, s, frames[:, rb[0]:rb[1], rb[2]:rb[3]], dep)
         sink.close()

@@ -131,3 +131,80 @@ def test_flow_loop_pairs_and_halo(tmp_path, monkeypatch):
     assert out.shape[0] == 6 and list(out[:5, 0, 0, 0]) == [0, 1, 2, 3, 4] and not out[5].any()   # last frame: zero flow
     disp = [float(x) for x in open(folder / "flow_raft.csv")]
     assert disp == [0.5, 1.5, 2.5, 3.5, 4.5, 0.0]
+
+
+class _FakeFlow:
+    """infer_sequence of a flow engine: pair i's frame and max displacement carry i + `offset`; records what it was asked for"""
+
+    def __init__(self, offset=0):
+        self.offset, self.asked = offset, []
+
+    def infer_sequence(self, fr, scale=1.0, iters=12, backward=False, want_flow=False, want_rgb=True):
+        idx = fr[:-1, 0, 0, 0]
+        self.asked.append({"backward": bool(backward), "iters": iters, "want_flow": bool(want_flow)})
+        n, dirs = len(fr) - 1, 2 if backward else 1
+        rgb = np.zeros((n, dirs) + fr.shape[1:], np.uint8)
+        rgb[:, 0, 0, 0, 0] = idx + self.offset
+        mx = np.zeros((n, dirs), np.float32)
+        mx[:, 0] = idx + self.offset + 0.5
+        flow = np.zeros((n, dirs) + fr.shape[1:3] + (2,), np.float32) if want_flow else None
+        return flow, rgb, mx
+
+
+def _flow_run(band, monkeypatch, folder, fake, ranks, subpath=""):
+    data = {"bands": {"rgba": {"url": "rgba.npy"}}}
+    monkeypatch.setattr(band, "CHUNK", 2)
+    monkeypatch.setattr(band, "model", fake)
+    monkeypatch.setattr(band, "ranks", ranks)
+    monkeypatch.setattr(band, "data", data)
+    monkeypatch.setattr(band.engine, "flow_out_size", lambda h, w, s: (h, w))
+    if subpath:
+        os.makedirs(str(folder / subpath) + "_fwd", exist_ok=True)
+    a = types.SimpleNamespace(input=str(folder / "rgba.npy"), output=str(folder / (band.BAND + ".npy")), scale=1.0, iterations=12,
+                              backwards=False, mask=False, output_mask="", subpath=str(folder / subpath) if subpath else "", subpath_mask="")
+    band.process_video(a)
+    return data
+
+
+def test_gmflow_loop_through_its_own_entry_point(tmp_path, monkeypatch):
+    """--subpath without --backwards: RAFT predicts both directions for the dumps, GMFlow only the forward one; each band writes under its
+    own name and GMFlow passes one iteration"""
+    import flow_gmflow
+    import flow_raft
+    folder, _ = _clip(tmp_path, 6)
+    gm, raft = _FakeFlow(), _FakeFlow()
+    data = _flow_run(flow_gmflow, monkeypatch, folder, gm, _Ranks(), subpath="flo")
+    assert gm.asked == [{"backward": False, "iters": 1, "want_flow": True}] * 3
+    assert [float(x) for x in open(folder / "flow_gmflow.csv")] == [0.5, 1.5, 2.5, 3.5, 4.5, 0.0]
+    assert list(np.load(folder / "flow_gmflow.npy")[:, 0, 0, 0]) == [0, 1, 2, 3, 4, 0]
+    assert data["bands"]["flow_gmflow"] == {"url": "flow_gmflow.npy", "values": {"dist": {"type": "float", "url": "flow_gmflow.csv"}},
+                                            "folder": str(folder / "flo")}
+    assert "flow_raft" not in data["bands"] and not os.path.exists(folder / "flow_raft.csv")
+    assert sorted(os.listdir(folder / "flo_fwd")) == ["%04d.flo" % i for i in range(6)]
+    _flow_run(flow_raft, monkeypatch, folder, raft, _Ranks(), subpath="flo_raft")
+    assert raft.asked == [{"backward": True, "iters": 12, "want_flow": True}] * 3
+
+
+def test_both_flow_bands_in_one_process(tmp_path, monkeypatch):
+    """The GMFlow loop, then the RAFT loop, with different engines: neither touches the other's module"""
+    import flow_gmflow
+    import flow_raft
+    folder, _ = _clip(tmp_path, 5)
+    raft, raft_ranks, raft_data = _FakeFlow(100), _Ranks(), {"bands": {"mine": {}}}
+    monkeypatch.setattr(flow_raft, "model", raft)
+    monkeypatch.setattr(flow_raft, "ranks", raft_ranks)
+    monkeypatch.setattr(flow_raft, "data", raft_data)
+    gm = _FakeFlow(10)
+    gm_data = _flow_run(flow_gmflow, monkeypatch, folder, gm, _Ranks())
+    assert flow_raft.model is raft and flow_raft.ranks is raft_ranks and flow_raft.data is raft_data and raft_data == {"bands": {"mine": {}}}
+    assert raft.asked == [] and flow_raft.BAND == "flow_raft"
+    raft_data = _flow_run(flow_raft, monkeypatch, folder, raft, raft_ranks)
+    assert len(gm.asked) == 2 and len(raft.asked) == 2                      # 4 pairs, chunk 2: each engine saw its own run only
+    assert list(np.load(folder / "flow_gmflow.npy")[:, 0, 0, 0]) == [10, 11, 12, 13, 0]
+    assert list(np.load(folder / "flow_raft.npy")[:, 0, 0, 0]) == [100, 101, 102, 103, 0]
+    assert [float(x) for x in open(folder / "flow_gmflow.csv")] == [10.5, 11.5, 12.5, 13.5, 0.0]
+    assert [float(x) for x in open(folder / "flow_raft.csv")] == [100.5, 101.5, 102.5, 103.5, 0.0]
+    assert set(gm_data["bands"]) == {"rgba", "flow_gmflow"} and set(raft_data["bands"]) == {"rgba", "flow_raft"}
+    assert not hasattr(flow_gmflow, "_loop") and not hasattr(flow_raft, "SUBPATH_NEEDS_BOTH")
+    src = open(flow_gmflow.__file__).read()
+    assert "import flow_raft" not in src and "from flow_raft" not in src
