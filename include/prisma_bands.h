@@ -567,6 +567,38 @@ int pb_op_mask_dynconv(pb_ctx *ctx, const float *kernels, int src_rows, const in
                        int guard_rows, float *out);
 int pb_op_mask_band_accumulate(pb_ctx *ctx, const float *sig, const uint8_t *use, int k, int fh, int fw, int h, int w, int H, int W, float thr,
                                int guard, uint8_t *out, uint8_t *inst);
+/* The depth bands' own kernels one by one (tests/test_gpu_depth_ops.py): the launchers of kernels.h / zoe_kernels.h with arguments the caller chooses,
+ * in the modes DepthEngine uses.  Inputs are float32 host arrays staged into the engine's layouts; every `out` is the RAW buffer, preset to 0xFF bytes,
+ * with guard rows (or guard elements) behind the last row.
+ * depth_layernorm: x [B, ntp, D] -> rows of ldy halfs, (B ntp + guard) of them, or with drop_cls (B (ntok - 1) + guard): output row b (ntok - 1) + t - 1
+ *   holds token t.  lo_off: the rounding residual at half lo_off (lo8 = 0) or the e4m3 parts at bytes 2 lo_off / 3 lo_off (lo8 = 1, scale 2^*lo8_pa,
+ *   the engine's); o8_off: e4m3(hi o8_scale) at byte o8_off of the row.
+ * depth_attention: q, k, v [B, heads, N, 64] -> (B ntp + guard) rows of ldo halfs, ntp = N rounded up to 16; variant 1: the 8-wave kernel, 2: the 4-wave one.
+ * depth_cls_rows: -> the residual stream (B ntp + guard) x D floats, of which only row 0 of every image is written.
+ * depth_dpt_tail: z [B, H, W, 288] in pixels of ldz halfs, layout 0 [hi], 1 [hi | lo], 2 [hi | hi8 | lo8] (parts 320 wide) -> B OH OW + guard floats.
+ * depth_resize_minmax: net [B, nh, nw] -> out B H W + guard floats, mnmx [B, 2] the decoded per-frame min / max.
+ * zoe_softplus: x is the whole buffer [(rows + guard), ld], in and out.  zoe_dot32_relu / zoe_bilerp_add / zoe_cat: fp16 inputs in rows of the given
+ *   strides.  zoe_attractor: A [n H W, ldA], bprev [n, h, w, 64] -> (n H W + guard) x 64 floats.  zoe_logbinom_depth: pt [n H W, ld_pt], bins [n, h, w, 64]
+ *   -> n H W + guard floats.  zoe_pil_resize: in [n, h, w] -> n H W + guard floats; the tap tables are built by the engine's own functions. */
+int pb_op_depth_layernorm(pb_ctx *ctx, const float *x, const float *g, const float *b, int B, int ntp, int ntok, int D, int drop_cls, int ldy, int lo_off,
+                          int o8_off, float o8_scale, int lo8, int guard_rows, void *out, int *lo8_pa);
+int pb_op_depth_attention(pb_ctx *ctx, const float *q, const float *k, const float *v, int B, int heads, int N, int variant, int ldo, int o8_off,
+                          float o8_scale, int guard_rows, void *out);
+int pb_op_depth_cls_rows(pb_ctx *ctx, const float *cls, const float *pos, int B, int ntp, int D, int guard_rows, float *out);
+int pb_op_depth_dpt_tail(pb_ctx *ctx, const float *z, const float *bias, const float *w2, float b2, int B, int H, int W, int OH, int OW, int layout,
+                         int ldz, int guard, float *out, int *lo8_pa);
+int pb_op_depth_resize_minmax(pb_ctx *ctx, const float *net, int B, int nh, int nw, int H, int W, int guard, float *out, float *mnmx);
+int pb_op_zoe_softplus(pb_ctx *ctx, float *x, int rows, int cols, int ld, int guard_rows);
+int pb_op_zoe_dot32_relu(pb_ctx *ctx, const float *act, int ld, const float *w2, float b2, int rows, int guard, float *out);
+int pb_op_zoe_bilerp_add(pb_ctx *ctx, const float *a, const float *src, int n, int h, int w, int H, int W, int C, int lda, int lds, int ldo,
+                         int guard_rows, void *out);
+int pb_op_zoe_attractor(pb_ctx *ctx, const float *A, int ldA, int nA, const float *bprev, int n, int h, int w, int H, int W, float alpha,
+                        int guard_rows, float *out);
+int pb_op_zoe_cat(pb_ctx *ctx, const float *act, int ld_act, const float *rel, const float *emb, int ld_emb, int n, int h, int w, int H, int W,
+                  int guard_rows, void *out);
+int pb_op_zoe_logbinom_depth(pb_ctx *ctx, const float *pt, int ld_pt, const float *bins, int n, int h, int w, int H, int W, float min_temp,
+                             float max_temp, int guard, float *out);
+int pb_op_zoe_pil_resize(pb_ctx *ctx, const float *in, int n, int h, int w, int H, int W, int guard, float *out);
 /* bilinear resize NCHW float32, align_corners 0/1 (torch F.interpolate semantics). */
 int pb_op_bilinear(pb_ctx *ctx, const float *x, float *y, int B, int C, int H, int W, int OH, int OW,
                    int align_corners);

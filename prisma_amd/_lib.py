@@ -165,6 +165,18 @@ SYMBOLS = {
     "pb_op_mask_sigmoid_rows": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_op_mask_dynconv": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_op_mask_band_accumulate": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [C.c_float, C.c_int, _P, _P]),
+    "pb_op_depth_layernorm": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 8 + [C.c_float, C.c_int, C.c_int, _P, _P]),
+    "pb_op_depth_attention": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
+    "pb_op_depth_cls_rows": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P]),
+    "pb_op_depth_dpt_tail": (C.c_int, [_P, _P, _P, _P, C.c_float] + [C.c_int] * 8 + [_P, _P]),
+    "pb_op_depth_resize_minmax": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
+    "pb_op_zoe_softplus": (C.c_int, [_P, _P] + [C.c_int] * 4),
+    "pb_op_zoe_dot32_relu": (C.c_int, [_P, _P, C.c_int, _P, C.c_float, C.c_int, C.c_int, _P]),
+    "pb_op_zoe_bilerp_add": (C.c_int, [_P, _P, _P] + [C.c_int] * 10 + [_P]),
+    "pb_op_zoe_attractor": (C.c_int, [_P, _P, C.c_int, C.c_int, _P] + [C.c_int] * 5 + [C.c_float, C.c_int, _P]),
+    "pb_op_zoe_cat": (C.c_int, [_P, _P, C.c_int, _P, _P] + [C.c_int] * 7 + [_P]),
+    "pb_op_zoe_logbinom_depth": (C.c_int, [_P, _P, C.c_int, _P] + [C.c_int] * 5 + [C.c_float, C.c_float, C.c_int, _P]),
+    "pb_op_zoe_pil_resize": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P]),
     "pb_op_bilinear": (C.c_int, [_P, _P, _P] + [C.c_int] * 7),
     "pb_op_preprocess": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, C.c_int]),
     "pb_op_encode_depth": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),

@@ -8,6 +8,7 @@
 #include "abi_ctx.h"
 #include "gmflow_engine.h"
 #include "mask_kernels.h"
+#include "zoe_kernels.h"
 
 namespace {
 // ---- one layer through EngineBase's own packing and launch code (pb_op_conv2d_split / pb_op_dense_split) ------------------------------
@@ -846,6 +847,161 @@ int time_launches(hipStream_t s, int iters, double *ms_out, Launch launch) {
     *ms_out = ms / iters;
     return 0;
 }
+
+// ---- the depth bands' own kernels one by one (pb_op_depth_*, pb_op_zoe_*) ---------------------------------------------------------------
+// Every entry point calls the launcher DepthEngine calls (kernels.h, zoe_kernels.h) with arguments the test chooses, in the modes the engine
+// uses: token rows wider than the payload with an fp8 copy behind it, the compacted class-token-free tap maps, the three pixel layouts of
+// the DPT tail.  Inputs are staged as above (build_map / to_map: 0xFFFF wherever a map defines nothing), outputs are preset to 0xFF bytes
+// and carry guard rows.
+class DepthOpEngine : public MaskOpEngine {
+  public:
+    explicit DepthOpEngine(int device) : MaskOpEngine(device) {}
+    int lo8_pa() const { return kLo8Pa; }
+
+    int layernorm(const float *x, const float *g, const float *b, int B, int ntp, int ntok, int D, int drop_cls, int ldy, int lo_off, int o8_off,
+                  float o8_scale, int lo8, int guard, void *out) {
+        const int64_t rows = drop_cls ? (int64_t)B * (ntok - 1) : (int64_t)B * ntp;
+        DevMem dx, dg, db, dout;
+        PB_TRY(up(dx, x, (size_t)B * ntp * D * 4)); PB_TRY(up(dg, g, (size_t)D * 4)); PB_TRY(up(db, b, (size_t)D * 4));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * ldy * 2));
+        PB_TRY(launch_layernorm(stream, dx.as<float>(), dg.as<float>(), db.as<float>(), dout.as<f16>(), B, ntp, ntok, D, 1e-6f, drop_cls, ldy, lo_off, o8_off,
+                                o8_scale, lo8 ? kLo8Pa : -1));
+        return finish(out, dout, (size_t)(rows + guard) * ldy * 2);
+    }
+
+    // q, k, v [B, heads, N, 64] -> the engine's Q (pre-scaled by PB_QSCALE as the qkv epilogue does) / K [B heads, ntp, 64] and Vt [B heads, 64, ntp],
+    // pad tokens zero; the output rows [B ntp, ldo] raw
+    int attention(const float *q, const float *k, const float *v, int B, int heads, int N, int variant, int ldo, int o8_off, float o8_scale, int guard,
+                  void *out) {
+        const int ntp = (int)round_up(N, 16);
+        const size_t bh = (size_t)B * heads;
+        std::vector<f16> hq(bh * ntp * 64, (f16)0.f), hk(bh * ntp * 64, (f16)0.f), hv(bh * 64 * ntp, (f16)0.f);
+        for (size_t i = 0; i < bh; ++i)
+            for (int t = 0; t < N; ++t)
+                for (int d = 0; d < 64; ++d) {
+                    const size_t s = (i * N + t) * 64 + d;
+                    hq[(i * ntp + t) * 64 + d] = (f16)(q[s] * PB_QSCALE);
+                    hk[(i * ntp + t) * 64 + d] = (f16)k[s];
+                    hv[(i * 64 + d) * ntp + t] = (f16)v[s];
+                }
+        DevMem dq, dk, dv, dout;
+        const size_t slack = 32768;
+        PB_TRY(dq.alloc(hq.size() * 2 + slack)); PB_TRY(dk.alloc(hk.size() * 2 + slack)); PB_TRY(dv.alloc(hv.size() * 2 + slack));
+        PB_HIP(hipMemcpy(dq.p, hq.data(), hq.size() * 2, hipMemcpyHostToDevice));
+        PB_HIP(hipMemcpy(dk.p, hk.data(), hk.size() * 2, hipMemcpyHostToDevice));
+        PB_HIP(hipMemcpy(dv.p, hv.data(), hv.size() * 2, hipMemcpyHostToDevice));
+        const size_t bytes = ((size_t)B * ntp + guard) * ldo * 2;
+        PB_TRY(preset(dout, bytes));
+        PB_TRY(launch_attention(stream, dq.as<f16>(), dk.as<f16>(), dv.as<f16>(), dout.as<f16>(), B, heads, ntp, N, ldo, variant, o8_off, o8_scale));
+        return finish(out, dout, bytes);
+    }
+
+    int cls_rows(const float *cls, const float *pos, int B, int ntp, int D, int guard, float *out) {
+        DevMem dc, dp, dr;
+        PB_TRY(up(dc, cls, (size_t)D * 4)); PB_TRY(up(dp, pos, (size_t)D * 4));
+        PB_TRY(preset(dr, ((size_t)B * ntp + guard) * D * 4));
+        PB_TRY(launch_cls_rows(stream, dr.as<float>(), dc.as<float>(), dp.as<float>(), B, ntp, D));
+        return finish(out, dr, ((size_t)B * ntp + guard) * D * 4);
+    }
+
+    // layout 0: [hi], 1: [hi | lo], 2: [hi | hi8 | lo8]; 288 channels in the engine's 320-wide parts, pixels ldz halfs apart
+    int dpt_tail(const float *z, const float *bias, const float *w2, float b2, int B, int H, int W, int OH, int OW, int layout, int ldz, int guard,
+                 float *out) {
+        const int Zp = 320, lo_off = layout ? Zp : 0;
+        const int64_t P = (int64_t)B * H * W, px = (int64_t)B * OH * OW;
+        std::vector<float> zp((size_t)P * Zp, 0.f);
+        for (int64_t p = 0; p < P; ++p) memcpy(&zp[(size_t)p * Zp], z + p * 288, 288 * 4);
+        std::vector<f16> hz((size_t)P * ldz);
+        memset(hz.data(), 0xFF, hz.size() * 2);
+        build_map(zp.data(), P, Zp, Zp, layout == 0 ? SL_F16 : (layout == 1 ? SL_SPLIT16 : SL_MX3), 1, ldz, hz);
+        DevMem dz, dbias, dw2, dout;
+        PB_TRY(up(dz, hz.data(), hz.size() * 2)); PB_TRY(up(dbias, bias, 32 * 4)); PB_TRY(up(dw2, w2, 32 * 4));
+        PB_TRY(preset(dout, (size_t)(px + guard) * 4));
+        PB_TRY(launch_dpt_tail(stream, dz.as<f16>(), B, H, W, ldz, lo_off, layout == 2 ? kLo8Pa : -1, dbias.as<float>(), dw2.as<float>(), b2, dout.as<float>(),
+                               OH, OW));
+        return finish(out, dout, (size_t)(px + guard) * 4);
+    }
+
+    int resize_minmax(const float *net, int B, int nh, int nw, int H, int W, int guard, float *out, float *mnmx) {
+        const int64_t px = (int64_t)B * H * W;
+        DevMem dn, dout, dmm;
+        PB_TRY(up(dn, net, (size_t)B * nh * nw * 4));
+        PB_TRY(preset(dout, (size_t)(px + guard) * 4));
+        PB_TRY(dmm.alloc((size_t)B * 2 * 4));
+        PB_TRY(launch_init_minmax(stream, dmm.as<unsigned>(), B));
+        PB_TRY(launch_depth_resize_minmax(stream, dn.as<float>(), B, nh, nw, dout.as<float>(), H, W, dmm.as<unsigned>()));
+        PB_TRY(finish(out, dout, (size_t)(px + guard) * 4));
+        std::vector<unsigned> mm((size_t)B * 2);
+        PB_TRY(down(mm.data(), dmm, mm.size() * 4));
+        for (size_t i = 0; i < mm.size(); ++i) {            // the ordered-uint encoding of elementwise.hip f2ord, undone
+            const unsigned u = (mm[i] & 0x80000000u) ? (mm[i] & 0x7fffffffu) : ~mm[i];
+            memcpy(mnmx + i, &u, 4);
+        }
+        return 0;
+    }
+
+    // x arrives as the whole buffer [rows + guard, ld] (the caller presets what the kernel does not own) and is returned whole
+    int softplus(float *x, int64_t rows, int cols, int ld, int guard) {
+        DevMem dx;
+        PB_TRY(up(dx, x, (size_t)(rows + guard) * ld * 4));
+        PB_TRY(launch_softplus(stream, dx.as<float>(), rows, cols, ld));
+        return finish(x, dx, (size_t)(rows + guard) * ld * 4);
+    }
+    int dot32_relu(const float *act, int ld, const float *w2, float b2, int64_t rows, int guard, float *out) {
+        DevMem da, dw, dout;
+        PB_TRY(to_map(da, act, rows, 32, ld, 0)); PB_TRY(up(dw, w2, 32 * 4));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * 4));
+        PB_TRY(launch_dot32_relu(stream, da.as<f16>(), ld, dw.as<float>(), b2, dout.as<float>(), rows));
+        return finish(out, dout, (size_t)(rows + guard) * 4);
+    }
+    int bilerp_add(const float *a, const float *src, int n, int h, int w, int H, int W, int C, int lda, int lds, int ldo, int guard, void *out) {
+        const int64_t rows = (int64_t)n * H * W;
+        DevMem da, ds, dout;
+        PB_TRY(to_map(da, a, rows, C, lda, 0)); PB_TRY(to_map(ds, src, (int64_t)n * h * w, C, lds, 0));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * ldo * 2));
+        PB_TRY(launch_bilerp_add(stream, da.as<f16>(), ds.as<f16>(), dout.as<f16>(), n, h, w, H, W, C, lda, lds, ldo));
+        return finish(out, dout, (size_t)(rows + guard) * ldo * 2);
+    }
+    int attractor(const float *A, int ldA, int nA, const float *bprev, int n, int h, int w, int H, int W, float alpha, int guard, float *out) {
+        const int64_t rows = (int64_t)n * H * W;
+        DevMem dA, db, dout;
+        PB_TRY(up(dA, A, (size_t)rows * ldA * 4)); PB_TRY(up(db, bprev, (size_t)n * h * w * 64 * 4));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * 64 * 4));
+        PB_TRY(launch_attractor(stream, dA.as<float>(), ldA, nA, db.as<float>(), h, w, dout.as<float>(), n, H, W, alpha));
+        return finish(out, dout, (size_t)(rows + guard) * 64 * 4);
+    }
+    int cat(const float *act, int ld_act, const float *rel, const float *emb, int ld_emb, int n, int h, int w, int H, int W, int guard, void *out) {
+        const int64_t rows = (int64_t)n * H * W;
+        DevMem da, dr, de, dout;
+        PB_TRY(to_map(da, act, rows, 32, ld_act, 0)); PB_TRY(up(dr, rel, (size_t)rows * 4)); PB_TRY(to_map(de, emb, (int64_t)n * h * w, 128, ld_emb, 0));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * 192 * 2));
+        PB_TRY(launch_zoe_cat(stream, da.as<f16>(), ld_act, dr.as<float>(), de.as<f16>(), ld_emb, h, w, dout.as<f16>(), n, H, W));
+        return finish(out, dout, (size_t)(rows + guard) * 192 * 2);
+    }
+    int logbinom(const float *pt, int ld_pt, const float *bins, int n, int h, int w, int H, int W, float min_temp, float max_temp, int guard, float *out) {
+        const int64_t rows = (int64_t)n * H * W;
+        DevMem dp, db, dout;
+        PB_TRY(up(dp, pt, (size_t)rows * ld_pt * 4)); PB_TRY(up(db, bins, (size_t)n * h * w * 64 * 4));
+        PB_TRY(preset(dout, (size_t)(rows + guard) * 4));
+        PB_TRY(launch_logbinom_depth(stream, dp.as<float>(), ld_pt, db.as<float>(), h, w, dout.as<float>(), n, H, W, min_temp, max_temp));
+        return finish(out, dout, (size_t)(rows + guard) * 4);
+    }
+    // the tables come from pil_coeffs / pil_ksize, the functions DepthEngine::metric_tables builds them with
+    int pil_resize(const float *in, int n, int h, int w, int H, int W, int guard, float *out) {
+        std::vector<int> xb, yb;
+        std::vector<double> xk, yk;
+        pil_coeffs(w, W, xb, xk); pil_coeffs(h, H, yb, yk);
+        const int64_t px = (int64_t)n * H * W;
+        DevMem di, dt, dout, dxb, dyb, dxk, dyk;
+        PB_TRY(up(di, in, (size_t)n * h * w * 4));
+        PB_TRY(preset(dt, (size_t)n * h * W * 4)); PB_TRY(preset(dout, (size_t)(px + guard) * 4));
+        PB_TRY(up(dxb, xb.data(), xb.size() * 4)); PB_TRY(up(dyb, yb.data(), yb.size() * 4));
+        PB_TRY(up(dxk, xk.data(), xk.size() * 8)); PB_TRY(up(dyk, yk.data(), yk.size() * 8));
+        PB_TRY(launch_pil_resize(stream, di.as<float>(), dt.as<float>(), dout.as<float>(), n, h, w, H, W, dxb.as<int>(), dxk.as<double>(), pil_ksize(w, W),
+                                 dyb.as<int>(), dyk.as<double>(), pil_ksize(h, H)));
+        return finish(out, dout, (size_t)(px + guard) * 4);
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -1506,6 +1662,92 @@ int pb_op_mask_band_accumulate(pb_ctx *c, const float *sig, const uint8_t *use, 
              "op_mask_band_accumulate: bad arguments");
     MASK_OP_ENGINE(e);
     return e.band_accumulate(sig, use, k, fh, fw, h, w, H, W, thr, guard, out, inst);
+}
+
+// ---- the depth bands' kernels one by one (DepthOpEngine above) ----
+#define DEPTH_OP_ENGINE(e) PB_HIP(hipSetDevice(c->device)); DepthOpEngine e(c->device); PB_TRY(e.setup(nullptr, 0, SL_F16, 0))
+int pb_op_depth_layernorm(pb_ctx *c, const float *x, const float *g, const float *b, int B, int ntp, int ntok, int D, int drop_cls, int ldy, int lo_off,
+                          int o8_off, float o8_scale, int lo8, int guard_rows, void *out, int *lo8_pa) {
+    PB_CHECK(c && x && g && b && out && B > 0 && ntok > (drop_cls ? 1 : 0) && ntok <= ntp && D > 0 && D % 4 == 0 && D <= 1024 && ldy >= D && ldy % 4 == 0 &&
+                 guard_rows >= 0, PB_ERR_ARG, "op_depth_layernorm: bad arguments");
+    // every part of a row the kernel stores must lie inside the row: lo at half lo_off, hi8 / lo8 at bytes 2 lo_off / 3 lo_off, the fp8 copy at byte o8_off
+    PB_CHECK(lo_off == 0 || (lo_off >= D && lo_off % 4 == 0 && (lo8 ? 3 * lo_off + D <= 2 * ldy : lo_off + D <= ldy)), PB_ERR_ARG,
+             "op_depth_layernorm: residual part at %d outside a row of %d halfs", lo_off, ldy);
+    PB_CHECK(!lo8 || lo_off, PB_ERR_ARG, "op_depth_layernorm: e4m3 residual parts need lo_off");
+    PB_CHECK(o8_off == 0 || (o8_off >= 2 * D && o8_off % 4 == 0 && o8_off + D <= 2 * ldy && !lo_off), PB_ERR_ARG,
+             "op_depth_layernorm: fp8 copy at byte %d outside a row of %d halfs", o8_off, ldy);
+    DEPTH_OP_ENGINE(e);
+    if (lo8_pa) *lo8_pa = e.lo8_pa();
+    return e.layernorm(x, g, b, B, ntp, ntok, D, drop_cls, ldy, lo_off, o8_off, o8_scale, lo8, guard_rows, out);
+}
+int pb_op_depth_attention(pb_ctx *c, const float *q, const float *k, const float *v, int B, int heads, int N, int variant, int ldo, int o8_off,
+                          float o8_scale, int guard_rows, void *out) {
+    PB_CHECK(c && q && k && v && out && B > 0 && heads > 0 && N > 0 && (variant == 1 || variant == 2) && ldo >= heads * 64 && ldo % 8 == 0 && guard_rows >= 0,
+             PB_ERR_ARG, "op_depth_attention: bad arguments (variant 1: 8 waves, 2: 4 waves)");
+    PB_CHECK(o8_off == 0 || (o8_off >= heads * 128 && o8_off % 4 == 0 && o8_off + heads * 64 <= 2 * ldo), PB_ERR_ARG,
+             "op_depth_attention: fp8 copy at byte %d outside a row of %d halfs", o8_off, ldo);
+    DEPTH_OP_ENGINE(e);
+    return e.attention(q, k, v, B, heads, N, variant, ldo, o8_off, o8_scale, guard_rows, out);
+}
+int pb_op_depth_cls_rows(pb_ctx *c, const float *cls, const float *pos, int B, int ntp, int D, int guard_rows, float *out) {
+    PB_CHECK(c && cls && pos && out && B > 0 && ntp > 0 && D > 0 && guard_rows >= 0, PB_ERR_ARG, "op_depth_cls_rows: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.cls_rows(cls, pos, B, ntp, D, guard_rows, out);
+}
+int pb_op_depth_dpt_tail(pb_ctx *c, const float *z, const float *bias, const float *w2, float b2, int B, int H, int W, int OH, int OW, int layout,
+                         int ldz, int guard, float *out, int *lo8_pa) {
+    PB_CHECK(c && z && bias && w2 && out && B > 0 && H > 0 && W > 0 && OH > 0 && OW > 0 && layout >= 0 && layout <= 2 && ldz % 8 == 0 &&
+                 ldz >= (layout ? 640 : 320) && guard >= 0, PB_ERR_ARG, "op_depth_dpt_tail: bad arguments (a pixel is 320 halfs per part)");
+    DEPTH_OP_ENGINE(e);
+    if (lo8_pa) *lo8_pa = e.lo8_pa();
+    return e.dpt_tail(z, bias, w2, b2, B, H, W, OH, OW, layout, ldz, guard, out);
+}
+int pb_op_depth_resize_minmax(pb_ctx *c, const float *net, int B, int nh, int nw, int H, int W, int guard, float *out, float *mnmx) {
+    PB_CHECK(c && net && out && mnmx && B > 0 && nh > 0 && nw > 0 && H > 0 && W > 0 && guard >= 0, PB_ERR_ARG, "op_depth_resize_minmax: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.resize_minmax(net, B, nh, nw, H, W, guard, out, mnmx);
+}
+int pb_op_zoe_softplus(pb_ctx *c, float *x, int rows, int cols, int ld, int guard_rows) {
+    PB_CHECK(c && x && rows > 0 && cols > 0 && ld >= cols && guard_rows >= 0, PB_ERR_ARG, "op_zoe_softplus: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.softplus(x, rows, cols, ld, guard_rows);
+}
+int pb_op_zoe_dot32_relu(pb_ctx *c, const float *act, int ld, const float *w2, float b2, int rows, int guard, float *out) {
+    PB_CHECK(c && act && w2 && out && rows > 0 && ld >= 32 && ld % 8 == 0 && guard >= 0, PB_ERR_ARG, "op_zoe_dot32_relu: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.dot32_relu(act, ld, w2, b2, rows, guard, out);
+}
+int pb_op_zoe_bilerp_add(pb_ctx *c, const float *a, const float *src, int n, int h, int w, int H, int W, int C, int lda, int lds, int ldo, int guard_rows,
+                         void *out) {
+    PB_CHECK(c && a && src && out && n > 0 && h > 0 && w > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0 && lda >= C && lds >= C && ldo >= C && lda % 8 == 0 &&
+                 lds % 8 == 0 && ldo % 8 == 0 && guard_rows >= 0, PB_ERR_ARG, "op_zoe_bilerp_add: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.bilerp_add(a, src, n, h, w, H, W, C, lda, lds, ldo, guard_rows, out);
+}
+int pb_op_zoe_attractor(pb_ctx *c, const float *A, int ldA, int nA, const float *bprev, int n, int h, int w, int H, int W, float alpha, int guard_rows,
+                        float *out) {
+    PB_CHECK(c && A && bprev && out && nA > 0 && nA <= ldA && n > 0 && h > 0 && w > 0 && H > 0 && W > 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_zoe_attractor: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.attractor(A, ldA, nA, bprev, n, h, w, H, W, alpha, guard_rows, out);
+}
+int pb_op_zoe_cat(pb_ctx *c, const float *act, int ld_act, const float *rel, const float *emb, int ld_emb, int n, int h, int w, int H, int W, int guard_rows,
+                  void *out) {
+    PB_CHECK(c && act && rel && emb && out && ld_act >= 32 && ld_act % 8 == 0 && ld_emb >= 128 && n > 0 && h > 0 && w > 0 && H > 0 && W > 0 && guard_rows >= 0,
+             PB_ERR_ARG, "op_zoe_cat: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.cat(act, ld_act, rel, emb, ld_emb, n, h, w, H, W, guard_rows, out);
+}
+int pb_op_zoe_logbinom_depth(pb_ctx *c, const float *pt, int ld_pt, const float *bins, int n, int h, int w, int H, int W, float min_temp, float max_temp,
+                             int guard, float *out) {
+    PB_CHECK(c && pt && bins && out && ld_pt >= 4 && n > 0 && h > 0 && w > 0 && H > 0 && W > 0 && guard >= 0, PB_ERR_ARG, "op_zoe_logbinom_depth: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.logbinom(pt, ld_pt, bins, n, h, w, H, W, min_temp, max_temp, guard, out);
+}
+int pb_op_zoe_pil_resize(pb_ctx *c, const float *in, int n, int h, int w, int H, int W, int guard, float *out) {
+    PB_CHECK(c && in && out && n > 0 && h > 0 && w > 0 && H > 0 && W > 0 && guard >= 0, PB_ERR_ARG, "op_zoe_pil_resize: bad arguments");
+    DEPTH_OP_ENGINE(e);
+    return e.pil_resize(in, n, h, w, H, W, guard, out);
 }
 
 }  // extern "C"

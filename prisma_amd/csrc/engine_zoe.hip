@@ -21,7 +21,9 @@ double pil_bicubic(double x) {           // libImaging/Resample.c bicubic_filter
     if (x < 2.0) return (((x - 5) * x + 8) * x - 4) * a;
     return 0.0;
 }
+}  // namespace
 
+// (external linkage: pb_op_zoe_pil_resize builds its tables with these two, so the op-level test covers the host tables with the kernels)
 int pil_ksize(int in, int out) {
     double fs = (double)in / out;
     if (fs < 1.0) fs = 1.0;
@@ -56,7 +58,6 @@ void pil_coeffs(int in, int out, std::vector<int> &bounds, std::vector<double> &
         bounds[(size_t)xx * 2 + 1] = xmax;
     }
 }
-}  // namespace
 
 int DepthEngine::load_metric() {
     PB_CHECK(cfg_.features == 256 && cfg_.embed_dim == 1024, PB_ERR_ARG, "the metric head is built on the ViT-L core only");

@@ -31,8 +31,8 @@ int launch_bilinear_nhwc(hipStream_t s, const f16 *x, f16 *y, int B, int H, int 
 int launch_dpt_tail(hipStream_t s, const f16 *z, int B, int H, int W, int ldz, int lo_off, int lo8_pa, const float *bias, const float *w2, float b2,
                     float *out, int OH, int OW);
 
-// net depth [B, nh, nw] fp32 -> bilinear(align_corners=False) -> [B, H, W] fp32 (optional) and
-// per-frame min/max (ordered-uint atomics in mm[2*B]); then heat encode to uint8 RGB.
+// net depth [B, nh, nw] fp32 -> bilinear(align_corners=False) -> out [B, H, W] fp32 (required: every pixel is stored) and
+// per-frame min/max (ordered-uint atomics in mm[2*B], initialised by launch_init_minmax); then heat encode to uint8 RGB.
 int launch_depth_resize_minmax(hipStream_t s, const float *net, int B, int nh, int nw, float *out, int H, int W,
                                unsigned *mm);
 int launch_minmax_only(hipStream_t s, const float *x, int B, int64_t per, unsigned *mm);

@@ -1,5 +1,7 @@
 // Launchers of the ZoeDepth metric head's non-GEMM kernels (zoe_kernels.hip).
 #pragma once
+#include <vector>
+
 #include "common.h"
 
 int launch_softplus(hipStream_t s, float *x, int64_t rows, int cols, int ld);
@@ -20,3 +22,7 @@ int launch_logbinom_depth(hipStream_t s, const float *pt, int ld_pt, const float
 // Pillow resize of float32 maps: horizontal pass then vertical pass, double accumulation, float32 intermediate
 int launch_pil_resize(hipStream_t s, const float *in, float *tmp, float *out, int n, int h, int w, int H, int W, const int *xb,
                       const double *xk, int xks, const int *yb, const double *yk, int yks);
+// host tables of launch_pil_resize (engine_zoe.hip): Pillow's precompute_coeffs for one axis - bounds {first source index, tap count} and
+// pil_ksize(in, out) coefficients per output index
+int pil_ksize(int in, int out);
+void pil_coeffs(int in, int out, std::vector<int> &bounds, std::vector<double> &kk);

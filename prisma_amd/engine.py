@@ -809,6 +809,108 @@ class Ops(_Ctx):
         check(self.lib.pb_op_mask_band_accumulate(self.ctx, _ptr(sig), _ptr(use), k, fh, fw, h, w, H, W, thr, guard, _ptr(out), _ptr(inst)))
         return out, inst
 
+    # ---- the depth bands' kernels one by one (pb_op_depth_*, pb_op_zoe_*; tests/test_gpu_depth_ops.py) ----
+    # raw buffers as above: 0xFF wherever the kernel did not write, guard rows / elements behind the last row
+    def depth_layernorm(self, x, g, b, ntok: int, drop_cls: bool, ldy: int, lo_off: int = 0, o8_off: int = 0, o8_scale: float = 1.0,
+                        lo8: bool = False, guard_rows: int = 8):
+        """x [B, ntp, D] -> (raw uint8 [rows + guard, 2 ldy], the engine's lo8 scale exponent); rows = B ntp, or B (ntok - 1) with drop_cls"""
+        x, g, b = _f32(x), _f32(g), _f32(b)
+        B, ntp, D = x.shape
+        rows = B * (ntok - 1) if drop_cls else B * ntp
+        out = np.empty((rows + guard_rows, 2 * ldy), np.uint8)
+        pa = C.c_int(-1)
+        check(self.lib.pb_op_depth_layernorm(self.ctx, _ptr(x), _ptr(g), _ptr(b), B, ntp, ntok, D, int(drop_cls), ldy, lo_off, o8_off, o8_scale,
+                                             int(lo8), guard_rows, _ptr(out), C.byref(pa)))
+        return out, pa.value
+
+    def depth_attention(self, q, k, v, variant: int, ldo: int, o8_off: int = 0, o8_scale: float = 1.0, guard_rows: int = 8) -> np.ndarray:
+        """q, k, v [B, heads, N, 64] -> raw uint8 [B ntp + guard, 2 ldo]; variant 1: the 8-wave kernel, 2: the 4-wave kernel"""
+        q, k, v = _f32(q), _f32(k), _f32(v)
+        B, Hh, N, d = q.shape
+        assert d == 64 and k.shape == q.shape and v.shape == q.shape
+        ntp = -(-N // 16) * 16
+        out = np.empty((B * ntp + guard_rows, 2 * ldo), np.uint8)
+        check(self.lib.pb_op_depth_attention(self.ctx, _ptr(q), _ptr(k), _ptr(v), B, Hh, N, variant, ldo, o8_off, o8_scale, guard_rows, _ptr(out)))
+        return out
+
+    def depth_cls_rows(self, cls, pos, B: int, ntp: int, guard_rows: int = 2) -> np.ndarray:
+        """-> raw float32 [B ntp + guard, D]: the residual stream, preset, after cls_rows"""
+        cls, pos = _f32(cls), _f32(pos)
+        out = np.empty((B * ntp + guard_rows, cls.shape[0]), np.float32)
+        check(self.lib.pb_op_depth_cls_rows(self.ctx, _ptr(cls), _ptr(pos), B, ntp, cls.shape[0], guard_rows, _ptr(out)))
+        return out
+
+    def depth_dpt_tail(self, z, bias, w2, b2: float, OH: int, OW: int, layout: int, ldz: int, guard: int = 64):
+        """z [B, H, W, 288] -> (raw float32 [B OH OW + guard], the engine's lo8 scale exponent); layout 0 [hi], 1 [hi | lo], 2 [hi | hi8 | lo8]"""
+        z, bias, w2 = _f32(z), _f32(bias), _f32(w2)
+        B, H, W, Cc = z.shape
+        assert Cc == 288 and bias.shape == (32,) and w2.shape == (32,)
+        out = np.empty(B * OH * OW + guard, np.float32)
+        pa = C.c_int(-1)
+        check(self.lib.pb_op_depth_dpt_tail(self.ctx, _ptr(z), _ptr(bias), _ptr(w2), b2, B, H, W, OH, OW, layout, ldz, guard, _ptr(out), C.byref(pa)))
+        return out, pa.value
+
+    def depth_resize_minmax(self, net, H: int, W: int, guard: int = 64):
+        """net [B, nh, nw] -> (raw float32 [B H W + guard], mnmx float32 [B, 2])"""
+        net = _f32(net)
+        B, nh, nw = net.shape
+        out = np.empty(B * H * W + guard, np.float32)
+        mm = np.empty((B, 2), np.float32)
+        check(self.lib.pb_op_depth_resize_minmax(self.ctx, _ptr(net), B, nh, nw, H, W, guard, _ptr(out), _ptr(mm)))
+        return out, mm
+
+    def zoe_softplus(self, buf, rows: int, cols: int) -> np.ndarray:
+        """buf float32 [rows + guard, ld], whole: columns [0, cols) of rows [0, rows) are replaced by their softplus"""
+        buf = _f32(buf).copy()
+        check(self.lib.pb_op_zoe_softplus(self.ctx, _ptr(buf), rows, cols, buf.shape[1], buf.shape[0] - rows))
+        return buf
+
+    def zoe_dot32_relu(self, act, ld: int, w2, b2: float, guard: int = 8) -> np.ndarray:
+        act, w2 = _f32(act), _f32(w2)
+        out = np.empty(act.shape[0] + guard, np.float32)
+        check(self.lib.pb_op_zoe_dot32_relu(self.ctx, _ptr(act), ld, _ptr(w2), b2, act.shape[0], guard, _ptr(out)))
+        return out
+
+    def zoe_bilerp_add(self, a, src, lda: int, lds: int, ldo: int, guard_rows: int = 8) -> np.ndarray:
+        """a [n, H, W, C] + bilinear(src [n, h, w, C], align_corners) -> raw uint8 [n H W + guard, 2 ldo]"""
+        a, src = _f32(a), _f32(src)
+        n, H, W, Cc = a.shape
+        out = np.empty((n * H * W + guard_rows, 2 * ldo), np.uint8)
+        check(self.lib.pb_op_zoe_bilerp_add(self.ctx, _ptr(a), _ptr(src), n, src.shape[1], src.shape[2], H, W, Cc, lda, lds, ldo, guard_rows, _ptr(out)))
+        return out
+
+    def zoe_attractor(self, A, nA: int, bprev, H: int, W: int, alpha: float, guard_rows: int = 2) -> np.ndarray:
+        """A [n H W, ldA], bprev [n, h, w, 64] -> raw float32 [n H W + guard, 64]"""
+        A, bprev = _f32(A), _f32(bprev)
+        n, h, w, _ = bprev.shape
+        out = np.empty((n * H * W + guard_rows, 64), np.float32)
+        check(self.lib.pb_op_zoe_attractor(self.ctx, _ptr(A), A.shape[1], nA, _ptr(bprev), n, h, w, H, W, alpha, guard_rows, _ptr(out)))
+        return out
+
+    def zoe_cat(self, act, ld_act: int, rel, emb, ld_emb: int, H: int, W: int, guard_rows: int = 4) -> np.ndarray:
+        """act [n H W, 32], rel [n H W], emb [n, h, w, 128] -> raw uint8 [n H W + guard, 384]"""
+        act, rel, emb = _f32(act), _f32(rel), _f32(emb)
+        n, h, w, _ = emb.shape
+        out = np.empty((n * H * W + guard_rows, 384), np.uint8)
+        check(self.lib.pb_op_zoe_cat(self.ctx, _ptr(act), ld_act, _ptr(rel), _ptr(emb), ld_emb, n, h, w, H, W, guard_rows, _ptr(out)))
+        return out
+
+    def zoe_logbinom_depth(self, pt, bins, H: int, W: int, min_temp: float = 0.0212, max_temp: float = 50.0, guard: int = 8) -> np.ndarray:
+        """pt [n H W, ld_pt], bins [n, h, w, 64] -> raw float32 [n H W + guard]"""
+        pt, bins = _f32(pt), _f32(bins)
+        n, h, w, _ = bins.shape
+        out = np.empty(n * H * W + guard, np.float32)
+        check(self.lib.pb_op_zoe_logbinom_depth(self.ctx, _ptr(pt), pt.shape[1], _ptr(bins), n, h, w, H, W, min_temp, max_temp, guard, _ptr(out)))
+        return out
+
+    def zoe_pil_resize(self, x, H: int, W: int, guard: int = 8) -> np.ndarray:
+        """x [n, h, w] -> raw float32 [n H W + guard]: Pillow's bicubic resize of float32 maps"""
+        x = _f32(x)
+        n, h, w = x.shape
+        out = np.empty(n * H * W + guard, np.float32)
+        check(self.lib.pb_op_zoe_pil_resize(self.ctx, _ptr(x), n, h, w, H, W, guard, _ptr(out)))
+        return out
+
     def bilinear(self, x, OH: int, OW: int, align_corners: bool) -> np.ndarray:
         x = _f32(x)
         B, Cc, H, W = x.shape
