@@ -198,8 +198,7 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
             delete c;
             return r;
         }
-        c->stream = c->depth->stream;
-        c->zero = (f16 *)c->depth->zero_page();
+        c->band = c->depth;
     } else if (!strcmp(band, "flow_raft") || !strcmp(band, "flow_gmflow")) {
         const bool gm = band[5] == 'g';
         if (!weights || n_weights <= 0 || (cfg && cfg_bytes != sizeof(pb_flow_cfg))) {
@@ -223,8 +222,7 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
             delete c;
             return r;
         }
-        c->stream = c->raft->stream;
-        c->zero = (f16 *)c->raft->zero_page();
+        c->band = c->raft;
     } else if (!strcmp(band, "mask_mmdet")) {
         if (!cfg || cfg_bytes != sizeof(pb_mask_cfg) || !weights || n_weights <= 0) {
             delete c;
@@ -238,8 +236,7 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
             delete c;
             return r;
         }
-        c->stream = c->mask->stream;
-        c->zero = (f16 *)c->mask->zero_page();
+        c->band = c->mask;
     } else if (!strcmp(band, "ops")) {
         // kernel-level context for the parity tests: a stream and a zero page, no model
         hipError_t e1 = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -256,6 +253,10 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
     } else {
         delete c;
         PB_CHECK(false, PB_ERR_ARG, "unknown band '%s' (depth_anything | flow_raft | flow_gmflow | mask_mmdet | ops)", band);
+    }
+    if (c->band) {
+        c->stream = c->band->stream;
+        c->zero = (f16 *)c->band->zero_page();
     }
     *out = c;
     return 0;
@@ -420,14 +421,12 @@ int64_t pb_depth_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap,
 }
 
 int pb_set_profiling(pb_ctx *c, int enabled) {
-    PB_CHECK(c && (c->depth || c->raft || c->mask), PB_ERR_STATE, "ctx has no band");
-    KernelTimer *t = c->depth ? &c->depth->timer : (c->raft ? &c->raft->timer : &c->mask->timer);
-    t->enabled = (enabled & 1) != 0;
-    t->accumulate = (enabled & 4) != 0;
-    t->clear();
-    if (c->depth) c->depth->debug = (enabled & 2) != 0;
-    if (c->raft) c->raft->debug = (enabled & 2) != 0;
-    if (c->mask) c->mask->debug = (enabled & 2) != 0;
+    PB_CHECK(c && c->band, PB_ERR_STATE, "ctx has no band");
+    KernelTimer &t = c->band->timer;
+    t.enabled = (enabled & 1) != 0;
+    t.accumulate = (enabled & 4) != 0;
+    t.clear();
+    c->band->debug = (enabled & 2) != 0;
     return 0;
 }
 
@@ -668,10 +667,8 @@ int64_t pb_flow_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, 
 
 int pb_set_option(pb_ctx *c, const char *key, int value) {
     PB_CHECK(c && key, PB_ERR_ARG, "set_option: bad arguments");
-    int *g = c->depth ? &c->depth->gemm_tile : &c->gemm_tile;
-    int *v = c->depth ? &c->depth->conv_tile : (c->raft ? &c->raft->conv_tile : (c->mask ? &c->mask->conv_tile : &c->conv_tile));
-    if (!strcmp(key, "gemm_tile")) *g = value;
-    else if (!strcmp(key, "conv_tile")) *v = value;
+    if (!strcmp(key, "gemm_tile")) (c->band ? c->band->dense_tile : c->gemm_tile) = value;
+    else if (!strcmp(key, "conv_tile")) (c->band ? c->band->conv_tile : c->conv_tile) = value;
     else if (!strcmp(key, "host_chunk")) c->host_chunk = value;
     else if (!strcmp(key, "op_splitk")) c->op_splitk = value;
     else if (!strcmp(key, "tile_n96")) pb_gemm_set_n96(value);         // process-wide (gemm.h): A/B of the 128 x 96 tile inside one test process
@@ -680,8 +677,8 @@ int pb_set_option(pb_ctx *c, const char *key, int value) {
 }
 
 int pb_get_kernel_stats(pb_ctx *c, pb_kernel_stat *out, int cap) {
-    PB_CHECK(c && (c->depth || c->raft || c->mask) && out, PB_ERR_STATE, "ctx has no band");
-    return c->depth ? c->depth->stats(out, cap) : (c->raft ? c->raft->stats(out, cap) : c->mask->stats(out, cap));
+    PB_CHECK(c && c->band && out, PB_ERR_STATE, "ctx has no band");
+    return c->band->stats(out, cap);
 }
 
 int pb_dev_alloc(pb_ctx *c, void **ptr, size_t bytes) {
@@ -750,7 +747,7 @@ int pb_depth_point_cloud_dev(pb_ctx *c, const float *depth, const uint8_t *rgb, 
         c->pcl_mm_cap = n;
     }
     // with a band on the ctx and pb_set_profiling on, the call is one record of pb_get_kernel_stats (22 algorithmic bytes per pixel)
-    KernelTimer *t = c->depth ? &c->depth->timer : (c->raft ? &c->raft->timer : (c->mask ? &c->mask->timer : nullptr));
+    KernelTimer *t = c->band ? &c->band->timer : nullptr;
     if (t && !t->enabled) t = nullptr;
     if (t) {
         t->reset();

@@ -136,6 +136,7 @@ struct pb_ctx {
     DepthEngine *depth = nullptr;
     RaftEngine *raft = nullptr;
     MaskEngine *mask = nullptr;
+    EngineBase *band = nullptr;     // whichever of the three was created: what every band has (timer, debug, tiles, stats)
     hipStream_t stream = nullptr;   // == depth->stream when a band is loaded
     f16 *zero = nullptr;
     bool own_stream = false;

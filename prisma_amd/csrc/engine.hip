@@ -14,232 +14,37 @@
 namespace {
 // families follow the kernel symbols rocprofv3 reports: gemm8_kernel<0,0,0> (fp16-out GEMMs: fc1, DPT 1x1 / convT),
 // <0,1,0> (residual-accumulating proj / fc2), <0,2,0> (qkv), <1,0,0> (implicit-GEMM convs), attnq_kernel, ...
-const char *kFam[] = {"gemm_f16", "conv_igemm_f16", "attention", "layernorm", "elementwise", "prepost", "gemm_f16_resid",
-                      "gemm_f16_qkv"};
-enum { F_GEMM = 0, F_CONV = 1, F_ATTN = 2, F_LN = 3, F_ELT = 4, F_PP = 5, F_GEMM_RESID = 6, F_GEMM_QKV = 7, F_COUNT = 8 };
+const char *const kFam[] = {"gemm_f16", "conv_igemm_f16", "attention", "layernorm", "elementwise", "prepost", "gemm_f16_resid",
+                            "gemm_f16_qkv"};
+enum { F_GEMM_RESID = 6, F_GEMM_QKV = 7 };      // (the depth band's use of EngineBase's last two families)
 inline int cp64(int c) { return (int)round_up(c, 64); }
 }  // namespace
 
-hipEvent_t KernelTimer::get() {
-    if (used == pool.size()) {
-        hipEvent_t e;
-        hipEventCreate(&e);
-        pool.push_back(e);
-    }
-    return pool[used++];
-}
-KernelTimer::~KernelTimer() {
-    for (auto e : pool) hipEventDestroy(e);
-}
-
-void DepthEngine::tic(int fam, double flops, double bytes, double passes) {
-    if (!timer.enabled) return;
-    KernelTimer::Rec r{fam, timer.get(), timer.get(), flops, bytes, flops * passes, nullptr};
-    hipEventRecord(r.a, stream);
-    timer.recs.push_back(r);
-}
-void DepthEngine::toc() {
-    if (!timer.enabled) return;
-    hipEventRecord(timer.recs.back().b, stream);
-}
-
-int KernelTimer::collect(const char *const *fam_names, int nfam, pb_kernel_stat *out, int cap) {
-    std::vector<pb_kernel_stat> acc;
-    auto slot = [&](const char *name) -> pb_kernel_stat & {
-        for (auto &a : acc)
-            if (a.name == name || !strcmp(a.name, name)) return a;
-        acc.push_back(pb_kernel_stat{name, 0, 0, 0, 0, 0});
-        return acc.back();
-    };
-    for (auto &r : recs) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, r.a, r.b);
-        pb_kernel_stat &a = slot(r.name && r.name[0] ? r.name : fam_names[r.fam < nfam ? r.fam : 0]);
-        a.ms += ms; a.flops += r.flops; a.exec_flops += r.exec; a.bytes += r.bytes; a.launches++;
-    }
-    int n = 0;
-    for (auto &a : acc)
-        if (n < cap) out[n++] = a;
-    return n;
-}
-
-int DepthEngine::stats(pb_kernel_stat *out, int cap) {
-    if (hipStreamSynchronize(stream) != hipSuccess) return -2;
-    return timer.collect(kFam, F_COUNT, out, cap);
-}
-
-DepthEngine::DepthEngine(int dev, const pb_depth_cfg &cfg) : device(dev), cfg_(cfg) {}
-
-void pb_rows_slice_major(f16 *rows, int64_t nrows, int64_t rowlen, int taps) {
-    const int64_t S = rowlen / (64 * (int64_t)taps);
-    std::vector<f16> row((size_t)rowlen);
-    for (int64_t n = 0; n < nrows; ++n) {
-        f16 *r = rows + n * rowlen;
-        for (int t = 0; t < taps; ++t)
-            for (int64_t sidx = 0; sidx < S; ++sidx) std::copy_n(r + ((int64_t)t * S + sidx) * 64, 64, row.data() + (sidx * taps + t) * 64);
-        std::copy_n(row.data(), (size_t)rowlen, r);
-    }
-}
-
-unsigned char pb_f32_to_e4m3(float x) {
-    const unsigned char s = x < 0.f ? 0x80 : 0x00;
-    const float a = fabsf(x);
-    if (!(a == a)) return 0x7F;
-    if (a >= 448.f) return s | 0x7E;
-    int e;
-    const float m = frexpf(a, &e);                  // a = m 2^e, m in [0.5, 1)
-    int E = e - 1;                                  // a = (2 m) 2^E
-    if (a == 0.f || E < -6) {                       // subnormal range: multiples of 2^-9
-        const int q = (int)nearbyintf(a * 512.f);
-        return s | (unsigned char)(q >= 8 ? 0x08 : q);
-    }
-    int q = (int)nearbyintf((2.f * m - 1.f) * 8.f);
-    if (q == 8) { q = 0; ++E; }
-    unsigned char code = (unsigned char)(((E + 7) << 3) | q);
-    if (E > 8 || code > 0x7E) code = 0x7E;
-    return s | code;
-}
-
-int DepthEngine::pack_mx(const float *src, int N, int K, PackedW &out, const float *bias) {
-    PB_CHECK(K % 128 == 0, PB_ERR_ARG, "pack_mx: K %d", K);
-    const int64_t Np = round_up(N, 256), ld = K + K / 2;           // halfs per row: K fp16 + K fp8 bytes
-    float mlo = 0.f;
-    for (int64_t i = 0; i < (int64_t)N * K; ++i) {
-        const float v = src[i];
-        mlo = fmaxf(mlo, fabsf(v - (float)(f16)v));
-    }
-    int pw = 0;
-    if (mlo > 0.f) { int e; frexpf(mlo, &e); pw = 8 - e; }          // max |w_lo| 2^pw in [128, 256)
-    std::vector<f16> h((size_t)Np * ld, (f16)0.f);
-    for (int n = 0; n < N; ++n) {
-        f16 *d = h.data() + (int64_t)n * ld;
-        unsigned char *d8 = (unsigned char *)(d + K);
-        for (int k = 0; k < K; ++k) {
-            const float v = src[(int64_t)n * K + k];
-            const f16 hi = (f16)v;
-            d[k] = hi;
-            d8[k] = pb_f32_to_e4m3(ldexpf(v - (float)hi, pw));
-        }
-    }
-    void *p = nullptr;
-    PB_HIP(hipMalloc(&p, h.size() * 2));
-    owned_.push_back(p);
-    PB_HIP(hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    out.w = (f16 *)p; out.N = N; out.K = (int)ld; out.Kreal = K; out.sa = 0; out.sw = 0; out.Cseg = K;
-    out.nk16 = K / 64; out.mx_pw = pw;
-    out.bias = nullptr;
-    if (bias) return upload_f32(bias, N, &out.bias);
-    return 0;
-}
+DepthEngine::DepthEngine(int dev, const pb_depth_cfg &cfg) : EngineBase(dev, kFam), cfg_(cfg) {}
 
 DepthEngine::~DepthEngine() {
     hipSetDevice(device);
     if (stream) hipStreamSynchronize(stream);
-    for (auto p : owned_) hipFree(p);
     for (auto &kv : snaps_) hipFree(kv.second);
-    if (arena_) hipFree(arena_);
-    if (stream) hipStreamDestroy(stream);
 }
 
-int DepthEngine::dev_alloc(void **p, size_t bytes) {
-    PB_HIP(hipMalloc(p, bytes));
-    return 0;
+PackSpec DepthEngine::spec(int sa, int sw, int mx2) const {
+    PackSpec s;
+    s.sa = sa; s.sw = sw; s.mx = head_mx_; s.mx2 = mx2; s.tapin = head_tapin_;
+    return s;
 }
 
-const pb_tensor *DepthEngine::find(const std::string &name) const {
-    auto it = tmap_.find(name);
-    return it == tmap_.end() ? nullptr : it->second;
-}
-
-int DepthEngine::upload_f32(const float *src, size_t n, float **dst) {
-    void *p = nullptr;
-    PB_HIP(hipMalloc(&p, std::max<size_t>(n * 4, 256)));
-    owned_.push_back(p);
-    PB_HIP(hipMemcpy(p, src, n * 4, hipMemcpyHostToDevice));
-    *dst = (float *)p;
-    return 0;
-}
-
-// src: host fp32 [N, K] row-major (already in GEMM order; K = taps x channels).  Pads rows to a multiple of 256 and every
-// tap to Kpad / taps channels.  Split-fp16 (sa / sw): each tap becomes the segments [w_hi | w_hi | w_lo] (PackedW, gemm.h).
-int DepthEngine::pack(const float *src, int N, int K, int Kpad, PackedW &out, const float *bias, int taps, int sa, int sw) {
-    const int64_t Np = round_up(N, 256);
-    const int segs = 1 + sa + sw, Cin = K / taps, Cp = Kpad / taps;
-    PB_CHECK(K % taps == 0 && Kpad % taps == 0 && Cp >= Cin && (segs == 1 || Cp % 64 == 0), PB_ERR_ARG, "pack: K %d / Kpad %d / taps %d", K, Kpad, taps);
-    // 3x3 convolutions: slice-major K order (gemm.h cTapInner) - the taps of a 64-channel slice back to back, so the 256-channel maps'
-    // lines are re-used out of the XCD L2 instead of being fetched once per tap
-    const int tapin = head_tapin_ && taps > 1 && Cp % 64 == 0 ? 1 : 0;
-    out.tapin = tapin; out.taps = taps;
-    if (head_mx_ && sa && sw) {        // mx3 layout: per tap [w_hi fp16 | w_lo e4m3 2^pw | w_hi e4m3 2^(pw - 12)]
-        float mlo = 0.f, mhi = 0.f;
-        for (int64_t i = 0; i < (int64_t)N * K; ++i) {
-            const float v = src[i];
-            mhi = fmaxf(mhi, fabsf(v));
-            mlo = fmaxf(mlo, fabsf(v - (float)(f16)v));
-        }
-        int pw = 0, e = 0;
-        if (mlo > 0.f) { frexpf(mlo, &e); pw = 8 - e; }
-        if (mhi > 0.f) { frexpf(mhi, &e); pw = std::min(pw, 20 - e); }     // max |w_hi| 2^(pw - 12) < 256 too
-        const int64_t Kt = (int64_t)taps * 2 * Cp;
-        std::vector<f16> h((size_t)Np * Kt, (f16)0.f);
-        for (int n = 0; n < N; ++n)
-            for (int t = 0; t < taps; ++t) {
-                const float *s = src + (int64_t)n * K + (int64_t)t * Cin;
-                f16 *d = h.data() + (int64_t)n * Kt + (int64_t)t * 2 * Cp;
-                unsigned char *d8 = (unsigned char *)(d + Cp);
-                for (int k = 0; k < Cin; ++k) {
-                    const f16 hi = (f16)s[k];
-                    d[k] = hi;
-                    d8[k] = pb_f32_to_e4m3(ldexpf(s[k] - (float)hi, pw));
-                    d8[Cp + k] = pb_f32_to_e4m3(ldexpf((float)hi, pw - 12));
-                }
-            }
-        if (tapin) pb_rows_slice_major(h.data(), Np, Kt, taps);
-        void *p = nullptr;
-        PB_HIP(hipMalloc(&p, h.size() * 2));
-        owned_.push_back(p);
-        PB_HIP(hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-        out.w = (f16 *)p; out.N = N; out.K = (int)Kt; out.Kreal = K; out.sa = 1; out.sw = 1; out.Cseg = Cp; out.mx3 = 1; out.mx_pw = pw;
-        out.nk16 = Cp / 64;
-        out.bias = nullptr;
-        if (bias) return upload_f32(bias, N, &out.bias);
-        return 0;
-    }
-    const int64_t Kt = (int64_t)taps * segs * Cp;
-    std::vector<f16> h((size_t)Np * Kt, (f16)0.f);
-    for (int n = 0; n < N; ++n)
-        for (int t = 0; t < taps; ++t) {
-            const float *s = src + (int64_t)n * K + (int64_t)t * Cin;
-            f16 *d = h.data() + (int64_t)n * Kt + (int64_t)t * segs * Cp;
-            for (int k = 0; k < Cin; ++k) {
-                const f16 hi = (f16)s[k];
-                d[k] = hi;
-                if (sa) d[Cp + k] = hi;
-                if (sw) d[(1 + sa) * Cp + k] = (f16)(s[k] - (float)hi);
-            }
-        }
-    if (tapin) pb_rows_slice_major(h.data(), Np, Kt, taps);
-    void *p = nullptr;
-    PB_HIP(hipMalloc(&p, h.size() * 2));
-    owned_.push_back(p);
-    PB_HIP(hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    out.w = (f16 *)p;
-    out.N = N;
-    out.K = (int)Kt;
-    out.Kreal = K;
-    out.sa = sa; out.sw = sw; out.Cseg = Cp;
-    out.bias = nullptr;
-    if (bias) return upload_f32(bias, N, &out.bias);
-    return 0;
+// one ViT linear: split-fp16 weights, or with vit_mx_ the mx2 layout where the layer keeps its weight residual (vit_res_) and a single fp16
+// pass where it does not
+int DepthEngine::pack_vit(const float *wt, int N, int K, PackedW &out, const float *bias, bool keep_res) {
+    if (vit_mx_) return pack_spec(wt, N, K, K, out, bias, 1, keep_res ? spec(0, 1, 1) : spec(0, 0));
+    return pack_spec(wt, N, K, K, out, bias, 1, spec(0, vit_sw_));
 }
 
 int DepthEngine::load(const pb_tensor *w, int n) {
-    PB_HIP(hipSetDevice(device));
-    PB_HIP(pb_create_stream(&stream, "PB_CU_MASK_DEPTH"));
-    for (int i = 0; i < n; ++i) {
-        PB_CHECK(w[i].dtype == PB_F32 && w[i].data && w[i].name, PB_ERR_ARG, "weight %d: only host float32 tensors", i);
-        tmap_[w[i].name] = &w[i];
-    }
+    for (int i = 0; i < n; ++i) PB_CHECK(w[i].dtype == PB_F32 && w[i].data && w[i].name, PB_ERR_ARG, "weight %d: only host float32 tensors", i);
+    int r0 = begin_load(w, n, "PB_CU_MASK_DEPTH");
+    if (r0) return r0;
     const int D = cfg_.embed_dim, Hd = 4 * D, F = cfg_.features;
     if (const char *e = getenv("PB_TAPIN")) head_tapin_ = e[0] != '0';
     PB_CHECK(cfg_.precision == PB_PREC_F16 || cfg_.precision == PB_PREC_SPLIT, PB_ERR_ARG, "precision %d unknown", cfg_.precision);
@@ -273,25 +78,17 @@ int DepthEngine::load(const pb_tensor *w, int n) {
     };
 #define NEED(var, name, numel) const float *var = need(name, numel); if (!var) return PB_ERR_ARG
 #define UP(dst, name, numel) { NEED(_p, name, numel); int _r = upload_f32(_p, numel, &dst); if (_r) return _r; }
-    // zero page
-    {
-        void *z = nullptr;
-        PB_HIP(hipMalloc(&z, 4096));
-        PB_HIP(hipMemset(z, 0, 4096));
-        owned_.push_back(z);
-        zero_ = (f16 *)z;
-    }
-    if ((cfg_.max_batch <= 1 || pb_env_int("PB_SPLITK_ALWAYS", 0)) && pb_env_int("PB_SPLITK", 8) > 1) {      // split-K workspace (engine.h sk_ws_)
+    if ((cfg_.max_batch <= 1 || pb_env_int("PB_SPLITK_ALWAYS", 0)) && pb_env_int("PB_SPLITK", 8) > 1) {      // split-K workspace (engine.h kSkFloats)
         void *w = nullptr;
         PB_HIP(hipMalloc(&w, (size_t)kSkFloats * 4));
         owned_.push_back(w);
-        sk_ws_ = (float *)w;
+        sk_ws_ = (float *)w; sk_cap_ = kSkFloats;
     }
     const std::string P = "pretrained.";
     {   // patch embedding: conv weight [D,3,14,14] is already [N, K=588] in (c, py, px) order
         NEED(wt, P + "patch_embed.proj.weight", (int64_t)D * 588);
         NEED(bs, P + "patch_embed.proj.bias", D);
-        int r = pack(wt, D, 588, 640, patch_, bs, 1, 0, vit_sw_);
+        int r = pack_spec(wt, D, 588, 640, patch_, bs, 1, spec(0, vit_sw_));
         if (r) return r;
         UP(cls_, P + "cls_token", D);
         const int g = cfg_.pos_grid;
@@ -307,9 +104,7 @@ int DepthEngine::load(const pb_tensor *w, int n) {
         UP(B.ls1, b + "ls1.gamma", D);     UP(B.ls2, b + "ls2.gamma", D);
         int r;
         { NEED(wt, b + "attn.qkv.weight", (int64_t)3 * D * D); NEED(bs, b + "attn.qkv.bias", 3 * D);
-          if (vit_mx_ && !(vit_res_ & 1)) r = pack(wt, 3 * D, D, D, B.qkv, bs, 1, 0, 0);       // single fp16 pass (vit_res_)
-          else r = vit_mx_ ? pack_mx(wt, 3 * D, D, B.qkv, bs) : pack(wt, 3 * D, D, D, B.qkv, bs, 1, 0, vit_sw_);
-          if (r) return r; }
+          if ((r = pack_vit(wt, 3 * D, D, B.qkv, bs, (vit_res_ & 1) != 0))) return r; }
         // LayerScale (layer_scale.py:27-28) is folded into the weights: x + g*(W y + b) = x + (g.W) y + g.b, so the GEMM
         // can accumulate straight onto the residual stream
         auto pack_scaled = [&](const float *wt, const float *bs, const float *g, int N, int K, PackedW &out, bool keep_res) -> int {
@@ -318,21 +113,15 @@ int DepthEngine::load(const pb_tensor *w, int n) {
                 for (int k = 0; k < K; ++k) ws[(size_t)n * K + k] = wt[(size_t)n * K + k] * g[n];
                 bb[n] = bs[n] * g[n];
             }
-            if (vit_mx_ && !keep_res) return pack(ws.data(), N, K, K, out, bb.data(), 1, 0, 0);
-            return vit_mx_ ? pack_mx(ws.data(), N, K, out, bb.data()) : pack(ws.data(), N, K, K, out, bb.data(), 1, 0, vit_sw_);
+            return pack_vit(ws.data(), N, K, out, bb.data(), keep_res);
         };
         { NEED(wt, b + "attn.proj.weight", (int64_t)D * D); NEED(bs, b + "attn.proj.bias", D); NEED(g1, b + "ls1.gamma", D);
           if ((r = pack_scaled(wt, bs, g1, D, D, B.proj, (vit_res_ & 2) != 0))) return r; }
         { NEED(wt, b + "mlp.fc1.weight", (int64_t)Hd * D); NEED(bs, b + "mlp.fc1.bias", Hd);
-          if (vit_mx_ && !(vit_res_ & 4)) {
-              r = pack(wt, Hd, D, D, B.fc1, bs, 1, 0, 0);
-              // no fp8 tiles of its own, but fc2 wants the e4m3 copy of fc1's output: that epilogue lives in the MX build of the kernel,
-              // which nk16 = K / 64 selects (every K tile is an fp16 tile; gemm.h nk16)
-              if (!r && (vit_res_ & 8)) B.fc1.nk16 = D / 64;
-          } else {
-              r = vit_mx_ ? pack_mx(wt, Hd, D, B.fc1, bs) : pack(wt, Hd, D, D, B.fc1, bs, 1, 0, vit_sw_);
-          }
-          if (r) return r; }
+          if ((r = pack_vit(wt, Hd, D, B.fc1, bs, (vit_res_ & 4) != 0))) return r;
+          // run without a residual it has no fp8 tiles of its own, but fc2 wants the e4m3 copy of fc1's output: that epilogue lives in the MX
+          // build of the kernel, which nk16 = K / 64 selects (every K tile is an fp16 tile; gemm.h nk16)
+          if (vit_mx_ && !(vit_res_ & 4) && (vit_res_ & 8)) B.fc1.nk16 = D / 64; }
         { NEED(wt, b + "mlp.fc2.weight", (int64_t)D * Hd); NEED(bs, b + "mlp.fc2.bias", D); NEED(g2, b + "ls2.gamma", D);
           if ((r = pack_scaled(wt, bs, g2, D, Hd, B.fc2, (vit_res_ & 8) != 0))) return r; }
     }
@@ -348,12 +137,8 @@ int DepthEngine::load(const pb_tensor *w, int n) {
         if (!wt) return PB_ERR_ARG;
         const float *bs = nullptr;
         if (has_bias && !(bs = need(name + ".bias", co))) return PB_ERR_ARG;
-        const int cip = cp64(ci), K = ks * ks * cip;
-        std::vector<float> g((size_t)co * K, 0.f);
-        for (int o = 0; o < co; ++o)
-            for (int c = 0; c < ci; ++c)
-                for (int t = 0; t < ks * ks; ++t) g[(size_t)o * K + t * cip + c] = wt[((size_t)o * ci + c) * ks * ks + t];
-        int r = pack(g.data(), co, K, K, out, bs, ks * ks, head_sa_, head_sw_);
+        const int K = ks * ks * cp64(ci);
+        int r = pack_spec(pb_conv_rows(wt, co, ci, ks * ks, cp64(ci)).data(), co, K, K, out, bs, ks * ks, spec(head_sa_, head_sw_));
         out.Kreal = ks * ks * ci;
         return r;
     };
@@ -367,7 +152,7 @@ int DepthEngine::load(const pb_tensor *w, int n) {
         for (int ci = 0; ci < c; ++ci)
             for (int o = 0; o < c; ++o)
                 for (int t = 0; t < s * s; ++t) g[((size_t)t * c + o) * cip + ci] = wt[((size_t)ci * c + o) * s * s + t];
-        int r = pack(g.data(), s * s * c, cip, cip, out, nullptr, 1, head_sa_, head_sw_);
+        int r = pack_spec(g.data(), s * s * c, cip, cip, out, nullptr, 1, spec(head_sa_, head_sw_));
         out.Kreal = c;
         if (r) return r;
         return upload_f32(bs, c, &out.bias);
@@ -398,7 +183,7 @@ int DepthEngine::load(const pb_tensor *w, int n) {
         for (int c = 0; c < 32; ++c)
             for (int k = 0; k < ci; ++k)
                 for (int t = 0; t < 9; ++t) g[((size_t)t * 32 + c) * cip + k] = wt[((size_t)c * ci + k) * 9 + t];
-        if ((r = pack(g.data(), 288, cip, cip, wz_, nullptr, 1, head_sa_, head_sw_))) return r;
+        if ((r = pack_spec(g.data(), 288, cip, cip, wz_, nullptr, 1, spec(head_sa_, head_sw_)))) return r;
         wz_.Kreal = ci;
     }
     UP(w2_, Hh + "scratch.output_conv2.2.weight", 32);
@@ -417,12 +202,6 @@ int DepthEngine::load(const pb_tensor *w, int n) {
 // ------------------------------------------------------------------------------------------------
 // planning
 // ------------------------------------------------------------------------------------------------
-void *DepthEngine::carve(size_t bytes) {
-    const size_t off = arena_off_;
-    arena_off_ += round_up((int64_t)bytes, 256);
-    return planning_ ? nullptr : (void *)(arena_ + off);
-}
-
 namespace {
 // OpenCV INTER_CUBIC taps (see oracle/depth_oracle.py cubic_taps): float32 coefficients, A = -0.75.
 void cubic_taps(int src, int dst, std::vector<int> &idx, std::vector<float> &wt) {
@@ -592,18 +371,7 @@ int DepthEngine::prepare(int B, int H, int W) {
         full_ = (float *)carve((size_t)HB * H * W * 4);
         mm_ = (unsigned *)carve((size_t)HB * 8);
         if (cfg_.metric && (r = plan_metric(HB, H, W))) return r;
-        if (pass == 0) {
-            if (arena_off_ > arena_bytes_) {
-                if (arena_) PB_HIP(hipFree(arena_));
-                arena_ = nullptr;
-                arena_bytes_ = 0;
-                hipError_t e = hipMalloc((void **)&arena_, arena_off_);
-                PB_CHECK(e == hipSuccess, PB_ERR_MEMORY, "arena of %zu bytes: %s", arena_off_, hipGetErrorString(e));
-                arena_bytes_ = arena_off_;
-            }
-            // stale bit patterns must never be read as fp16 NaN/Inf by masked attention / padded tiles
-            PB_HIP(hipMemsetAsync(arena_, 0, arena_bytes_, stream));
-        }
+        if (pass == 0 && (r = commit_arena("depth"))) return r;
     }
     std::vector<int> xi, yi;
     std::vector<float> xw, yw, pos;
@@ -630,45 +398,21 @@ int DepthEngine::prepare(int B, int H, int W) {
 // launches
 // ------------------------------------------------------------------------------------------------
 int DepthEngine::gemm(int amode, int epi, GemmArgs &a, const PackedW &w, int tile) {
-    a.W = w.w;
-    a.K = w.K;
-    if (w.mx3) {                 // [hi | hi8 | lo8] maps x [w_hi | w_lo8 | w_hi8] weights: fp16 tiles then fp8 tiles, per tap (gemm.h)
-        a.nk16 = w.nk16; a.mx_scale_a = 127 - kLo8Pa; a.mx_scale_b = 127 - w.mx_pw;
-        if (amode == A_CONV) {
-            PB_CHECK(a.cC == w.Cseg, PB_ERR_STATE, "mx conv: %d channels per part, weights packed for %d", a.cC, w.Cseg);
-            if (!a.cLd) a.cLd = 2 * a.cC;
-            a.cC = 2 * w.Cseg;
-            a.mx_period = 2 * w.Cseg / 64;
-            if (w.tapin) { a.mx_period = 0; a.nk16 = w.nk16 * w.taps; }       // every fp16 slice of all taps, then the fp8 slices
-        }
-    } else if (w.sa || w.sw) {          // split-fp16 segments along K (gemm.h): the callers pass cC / lda of ONE part
-        if (amode == A_CONV) {
-            PB_CHECK(a.cC == w.Cseg, PB_ERR_STATE, "split conv: %d channels per part, weights packed for %d", a.cC, w.Cseg);
-            if (!a.cLd) a.cLd = (1 + w.sa) * a.cC;
-            a.cC = (1 + w.sa + w.sw) * w.Cseg;
-            a.kwrap = w.sw ? (1 + w.sa) * w.Cseg : 0;
-            a.kshift = -a.kwrap;
-        } else {
-            a.kwrap = w.sw ? (1 + w.sa) * w.Cseg / 64 : 0;
-        }
-    }
-    if (amode == A_CONV && w.tapin) { a.cTapInner = 1; a.cKH = w.taps / a.cKW; }
-    if (w.nk16 && !w.mx3) { a.nk16 = w.nk16; a.mx_scale_a = 127 - kMxPa; a.mx_scale_b = 127 - w.mx_pw; }
+    PB_CHECK(amode != A_CONV || !(w.sa || w.sw) || a.cC == w.Cseg, PB_ERR_STATE, "split conv: %d channels per part, weights packed for %d", a.cC, w.Cseg);
+    set_weights(a, w, amode == A_CONV);
     if (a.lo_off && head_mx_) { a.lo8 = 1; a.lo8_pa = kLo8Pa; }
     if (!a.N) a.N = w.N;
-    if (!a.bias) a.bias = w.bias;
-    a.zero = zero_;
+    a.sk_ws = sk_ws_; a.sk_cap = sk_cap_;
     const double flops = 2.0 * a.M * (double)a.N * w.Kreal;
     // algorithmic bytes: the A operand once (a convolution reads its input MAP once - not the im2col matrix: VERDICT r3 item 9), the
     // weights once, the output once (the fused head writes one float per pixel)
     const int taps = w.taps > 0 ? w.taps : 1;
     const double a_elems = amode == A_CONV ? (double)(a.M / ((int64_t)a.cOH * a.cOW)) * a.cH * a.cW * (w.Kreal / taps) : (double)a.M * w.Kreal;
     const double bytes = 2.0 * (a_elems + (double)a.N * w.Kreal) + (epi == EPI_HEAD ? 4.0 * a.M : 2.0 * (double)a.M * a.N);
-    tic(amode == A_CONV ? F_CONV : (epi == EPI_RESID ? F_GEMM_RESID : (epi == EPI_QKV ? F_GEMM_QKV : F_GEMM)), flops, bytes, w.mx3 ? 2.0 : 1.0 + w.sa + w.sw + (w.nk16 && w.K > w.Kreal ? 0.5 : 0.0));
-    if (tile == TILE_AUTO) tile = amode == A_CONV ? conv_tile : gemm_tile;
-    if (sk_ws_) { a.sk_ws = sk_ws_; a.sk_cap = kSkFloats; }
+    tic(amode == A_CONV ? F_CONV : (epi == EPI_RESID ? F_GEMM_RESID : (epi == EPI_QKV ? F_GEMM_QKV : F_GEMM)), flops, bytes, w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
+    if (tile == TILE_AUTO) tile = amode == A_CONV ? conv_tile : dense_tile;
     int r = launch_gemm(stream, amode, epi, tile, a);
-    if (timer.enabled && !r) timer.recs.back().name = pb_gemm_last_kernel();
+    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
     toc();
     return r;
 }
@@ -709,13 +453,13 @@ int DepthEngine::vit(int n) {
     }
     snapshot("tokens");
     const double ln_bytes = (double)n * ntok_ * D * 6.0;
-    // MX mode: rows of Y_ / AO_ / Hd_ are [fp16 (K) | fp8 (K bytes)], i.e. 1.5 K halfs apart; the fp8 copy is stored x 2^kMxPa.  A buffer
+    // MX mode: rows of Y_ / AO_ / Hd_ are [fp16 (K) | fp8 (K bytes)], i.e. 1.5 K halfs apart; the fp8 copy is stored x 2^kMx2Pa.  A buffer
     // whose consumers run without a weight residual (vit_res_) is plain fp16: Y_ feeds qkv (after norm1) and fc1 (after norm2)
     const bool y8 = vit_mx_ && (vit_res_ & 5) != 0, ao8 = vit_mx_ && (vit_res_ & 2), hd8 = vit_mx_ && (vit_res_ & 8);
     PB_CHECK(!vit_mx_ || (vit_res_ & 5) == 0 || (vit_res_ & 5) == 5, PB_ERR_ARG, "PB_VIT_RES: qkv and fc1 share their input buffer - keep or drop both residuals");
     const int ldy = vit_mx_ ? D + D / 2 : D, o8 = vit_mx_ ? 2 * D : 0;
     const int ldY = y8 ? ldy : D, o8Y = y8 ? o8 : 0, ldA = ao8 ? ldy : D, o8A = ao8 ? o8 : 0, ldH = hd8 ? 4 * ldy : 4 * D;
-    const float o8s = (float)(1 << kMxPa);
+    const float o8s = (float)(1 << kMx2Pa);
     for (int i = 0; i < cfg_.depth; ++i) {
         const Block &b = blocks_[i];
         tic(F_LN, 0, ln_bytes);

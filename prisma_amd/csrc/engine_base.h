@@ -1,15 +1,71 @@
-// Shared plumbing of the convolutional band engines (flow_raft, mask_mmdet): the named-weight map, fp16 GEMM packing with
-// folded BatchNorm, a two-pass arena, per-family kernel timing, and the implicit-GEMM / dense GEMM launch helpers.
+// Shared plumbing of the band engines (depth_anything, flow_raft, flow_gmflow, mask_mmdet): the ctx stream, the named-weight map, the upload
+// of packed GEMM weights (pack_layout.h has the layouts) with folded BatchNorm, a two-pass arena, per-family kernel timing, and the
+// implicit-GEMM / dense GEMM launch helpers.
 #pragma once
 #include <map>
 #include <string>
 #include <vector>
 
-#include "engine.h"
+#include "../../include/prisma_bands.h"
+#include "common.h"
+#include "gemm.h"
+#include "kernels.h"
+#include "pack_layout.h"
+
+// The ctx stream of a band engine.  `mask_env` names an environment variable with a CU mask as comma-separated 32-bit hex words (bit i of the
+// concatenation = CU i of the queue's mask; on gfx950 the driver deals the bits round-robin over the 8 XCDs, so 0f0f0f0f,... keeps XCDs 0-3):
+// an experiment switch for running two bands on disjoint parts of the chip (tools/overlap_bench.py --cu-masks).  Unset = the whole device.
+static inline hipError_t pb_create_stream(hipStream_t *s, const char *mask_env) {
+    const char *e = mask_env ? getenv(mask_env) : nullptr;
+    if (e && *e) {
+        uint32_t words[8];
+        int n = 0;
+        for (const char *p = e; *p && n < 8;) {
+            char *end = nullptr;
+            words[n++] = (uint32_t)strtoul(p, &end, 16);
+            if (!end || end == p) break;
+            p = *end == ',' ? end + 1 : end;
+        }
+        if (n > 0) return hipExtStreamCreateWithCUMask(s, (uint32_t)n, words);
+    }
+    // <mask_env>_PRIO = -1 / 1: a higher- / lower-priority queue (hipStreamCreateWithPriority; 0 or unset = default).  Experiment switch: with two
+    // bands at once the band with the large persistent GEMMs gets more than half of the chip (tools/overlap_bench.py 2way-fprio / 2way-dprio)
+    if (mask_env) {
+        const std::string pe = std::string(mask_env) + "_PRIO";
+        const char *p = getenv(pe.c_str());
+        if (p && *p && atoi(p) != 0) {
+            int lo = 0, hi = 0;
+            if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) return hipStreamCreateWithPriority(s, hipStreamNonBlocking, atoi(p) < 0 ? hi : lo);
+        }
+    }
+    return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
+}
+
+struct Stage {
+    const void *ptr;
+    int kind;                // 0: fp32 rows [n, rows, cols] with batch stride; 1: NHWC fp16 map; 2: fp32 map [n,h,w]; 3: fp16 rows
+    int64_t n, c, h, w, ld, bstride;
+};
+
+struct KernelTimer {
+    struct Rec { int fam; hipEvent_t a, b; double flops, bytes, exec; const char *name; };   // name: GEMM launches, the kernel symbol (gemm.h)
+    // per family (non-GEMM kernels) / per GEMM kernel symbol sums of the records
+    int collect(const char *const *fam_names, int nfam, pb_kernel_stat *out, int cap);
+    std::vector<Rec> recs;
+    std::vector<hipEvent_t> pool;
+    size_t used = 0;
+    bool enabled = false;
+    bool accumulate = false;      // keep the records of earlier infer calls (one query after a timed loop)
+    hipEvent_t get();
+    void reset() { if (accumulate) return; recs.clear(); used = 0; }
+    void clear() { recs.clear(); used = 0; }
+    ~KernelTimer();
+};
 
 class EngineBase {
   public:
-    explicit EngineBase(int device) : device(device) {}
+    // fam_names: the F_COUNT family names stats() reports (default: the convolutional bands' table, engine_base.hip)
+    explicit EngineBase(int device, const char *const *fam_names = nullptr);
     virtual ~EngineBase();
     int stats(pb_kernel_stat *out, int cap);
 
@@ -18,8 +74,8 @@ class EngineBase {
     bool debug = false;
     KernelTimer timer;
     int conv_tile = TILE_AUTO;
-    int dense_tile = TILE_AUTO;  // dense()'s tile (the engines keep TILE_AUTO; the split-precision op entry points force one)
-    float *sk_ws_ = nullptr;     // split-K workspace conv() / dense() lend launch_gemm (gemm.h sk_ws; null in the engines)
+    int dense_tile = TILE_AUTO;  // tile of the dense GEMMs (pb_set_option "gemm_tile"; the split-precision op entry points force one)
+    float *sk_ws_ = nullptr;     // split-K workspace the launches lend launch_gemm (gemm.h sk_ws; null in the convolutional engines)
     int64_t sk_cap_ = 0;
     int split_w_ = 0;            // PB_PREC_SPLIT: weights packed as hi + lo fp16, two passes over K (set before load)
     int mx_ = 0;                 // ... and where activations are split too (sa) the residual parts are e4m3: maps [hi | hi8 | lo8],
@@ -36,15 +92,19 @@ class EngineBase {
     const f16 *zero_page() const { return zero_; }
 
   protected:
-    // kernel families of the per-launch timer; convolutions are split by the GEMM kernel that runs them (launch_gemm's choice)
+    // kernel families of the per-launch timer; convolutions are split by the GEMM kernel that runs them (launch_gemm's choice).  Indices 6
+    // and 7 are the band's own: the depth band counts its residual / qkv GEMMs there (engine.hip)
     enum { F_GEMM = 0, F_CONV = 1, F_ATTN = 2, F_LN = 3, F_ELT = 4, F_PP = 5, F_CONV128 = 6, F_CONV64 = 7, F_COUNT = 8 };
 
-    // create the ctx stream, index the float32 tensors by name, allocate the zero page
-    int begin_load(const pb_tensor *w, int n);
+    // create the ctx stream (cu_mask_env: pb_create_stream), index the float32 tensors by name, allocate the zero page
+    int begin_load(const pb_tensor *w, int n, const char *cu_mask_env = "PB_CU_MASK_FLOW");
     const pb_tensor *find(const std::string &name) const;
-    // src: host fp32 [N, K] in GEMM order -> device fp16 [round_up(N, 256), Kpad] (+ fp32 bias, zero padded)
-    // taps: src is [N][taps][K / taps] (only matters with split_w_: the hi / lo segments alternate per tap)
-    // sa: the activation operand of this weight is a split-fp16 map [hi | lo] (per tap [w_hi | w_hi | w_lo]; only with split_w_)
+    int upload_f32(const float *src, size_t n, float **dst);
+    // src: host fp32 [N, K] in GEMM order -> device fp16 [round_up(N, 256), out.K] in the layout `spec` asks for (pack_layout.h pack_rows)
+    // and a zero-padded fp32 bias of round_up(N, 256)
+    int pack_spec(const float *src, int N, int K, int Kpad, PackedW &out, const float *bias, int taps, const PackSpec &spec);
+    // the same with the layout derived from the engine's flags (split_w_, mx_, pack_mx2_, pack_tapin_): weights are split where the sizes
+    // allow it, and sa (the activation operand is a split map [hi | lo]) only counts with split weights
     int pack(const float *src, int N, int K, int Kpad, PackedW &out, const float *bias, int taps = 1, int sa = 0);
     // eval-mode BatchNorm2d (eps 1e-5) as a per-channel (scale, shift)
     int fold_bn(const std::string &bn, int C, std::vector<float> &scale, std::vector<float> &shift);
@@ -52,8 +112,8 @@ class EngineBase {
     // ci_pad: input channels the rows are padded to (default round_up(ci, 64))
     int pack_conv(const std::string &name, bool has_bias, const float *scale, const float *shift, PackedW &out, int sa = 0, int ci_pad = 0);
 
-    // direct launch_gemm callers: K, and with split-fp16 weights the K wrap / channel bookkeeping of gemm.h (a.cC, a.cLd of
-    // ONE part must be set before the call for convolutions)
+    // direct launch_gemm callers: W, K, bias, the zero page, and with split weights the K wrap / channel / MX bookkeeping of gemm.h.
+    // Convolutions set a.cC (and a.cLd, unless the map is exactly its parts) of ONE part before the call, and check a.cC == w.Cseg
     void set_weights(GemmArgs &a, const PackedW &w, bool is_conv) const;
 
     void *carve(size_t bytes);
@@ -75,6 +135,7 @@ class EngineBase {
     int dense(const f16 *A, int lda, int64_t M, const PackedW &w, f16 *out, int ldo, int act, const f16 *add1 = nullptr, int o8_off = 0,
               int a_pa = -1, int lo_off = 0);          // a_pa: power-of-two scale the A operand's fp8 copy was stored with (default kMx2Pa)
 
+    const char *const *fam_names_;
     std::map<std::string, const pb_tensor *> tmap_;
     std::vector<void *> owned_;                 // permanent device allocations (weights), freed by the destructor
     f16 *zero_ = nullptr;
@@ -84,4 +145,7 @@ class EngineBase {
     bool planning_ = false;
     hipStream_t cur_ = nullptr;
     std::vector<size_t> open_;                  // tic / toc nesting across streams
+
+  private:
+    int upload_rows(const std::vector<f16> &rows, f16 **dst);
 };

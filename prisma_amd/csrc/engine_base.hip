@@ -2,14 +2,49 @@
 #include "conv_walk.h"      // cw3_tiles16 / cw3_tiles8: the packed-channel K axis the kernels walk
 
 #include <math.h>
+#include <string.h>
 
 #include <algorithm>
 
 namespace {
-const char *kFam[] = {"gemm_f16", "conv_igemm_f16", "attention", "layernorm", "elementwise", "prepost", "conv_igemm_f16_tile128",
+const char *const kFam[] = {"gemm_f16", "conv_igemm_f16", "attention", "layernorm", "elementwise", "prepost", "conv_igemm_f16_tile128",
                       "conv_igemm_f16_tile256x64"};
 inline int cp64(int c) { return (int)round_up(c, 64); }
 }  // namespace
+
+hipEvent_t KernelTimer::get() {
+    if (used == pool.size()) {
+        hipEvent_t e;
+        hipEventCreate(&e);
+        pool.push_back(e);
+    }
+    return pool[used++];
+}
+KernelTimer::~KernelTimer() {
+    for (auto e : pool) hipEventDestroy(e);
+}
+
+int KernelTimer::collect(const char *const *fam_names, int nfam, pb_kernel_stat *out, int cap) {
+    std::vector<pb_kernel_stat> acc;
+    auto slot = [&](const char *name) -> pb_kernel_stat & {
+        for (auto &a : acc)
+            if (a.name == name || !strcmp(a.name, name)) return a;
+        acc.push_back(pb_kernel_stat{name, 0, 0, 0, 0, 0});
+        return acc.back();
+    };
+    for (auto &r : recs) {
+        float ms = 0;
+        hipEventElapsedTime(&ms, r.a, r.b);
+        pb_kernel_stat &a = slot(r.name && r.name[0] ? r.name : fam_names[r.fam < nfam ? r.fam : 0]);
+        a.ms += ms; a.flops += r.flops; a.exec_flops += r.exec; a.bytes += r.bytes; a.launches++;
+    }
+    int n = 0;
+    for (auto &a : acc)
+        if (n < cap) out[n++] = a;
+    return n;
+}
+
+EngineBase::EngineBase(int device, const char *const *fam_names) : device(device), fam_names_(fam_names ? fam_names : kFam) {}
 
 EngineBase::~EngineBase() {
     hipSetDevice(device);
@@ -34,12 +69,12 @@ void EngineBase::toc() {
 
 int EngineBase::stats(pb_kernel_stat *out, int cap) {
     if (hipStreamSynchronize(stream) != hipSuccess) return -2;
-    return timer.collect(kFam, F_COUNT, out, cap);
+    return timer.collect(fam_names_, F_COUNT, out, cap);
 }
 
-int EngineBase::begin_load(const pb_tensor *w, int n) {
+int EngineBase::begin_load(const pb_tensor *w, int n, const char *cu_mask_env) {
     PB_HIP(hipSetDevice(device));
-    PB_HIP(pb_create_stream(&stream, "PB_CU_MASK_FLOW"));        // (the convolutional bands: flow_raft, flow_gmflow, mask_mmdet)
+    PB_HIP(pb_create_stream(&stream, cu_mask_env));
     cur_ = stream;
     for (int i = 0; i < n; ++i) {
         PB_CHECK(w[i].data && w[i].name, PB_ERR_ARG, "weight %d: null", i);
@@ -58,104 +93,53 @@ const pb_tensor *EngineBase::find(const std::string &name) const {
     return it == tmap_.end() ? nullptr : it->second;
 }
 
-int EngineBase::pack(const float *src, int N, int K, int Kpad, PackedW &out, const float *bias, int taps, int sa_req) {
-    const int64_t Np = round_up(N, 256);
-    // split_w_ (PB_PREC_SPLIT): every tap's channels are followed by the fp16 rounding residuals of the same weights, and the
-    // GEMM reads the activations twice (gemm.h kwrap): a w_hi + a w_lo in one accumulator
-    const int sw = split_w_ && Kpad % (64 * taps) == 0 && K % taps == 0 ? 1 : 0, sa = sw && sa_req ? 1 : 0, segs = 1 + sa + sw;
-    const int Cin = sw ? K / taps : K, Cp = sw ? Kpad / taps : Kpad, tp = sw ? taps : 1;
-    // slice-major K order (gemm.h cTapInner): rows are (taps x S) grids of 128-byte blocks in every layout below - transpose them
-    const int tapin = pack_tapin_ && taps > 1 && Kpad % (64 * taps) == 0 ? 1 : 0;
-    auto to_slice_major = [&](std::vector<f16> &h, int64_t rowlen) {
-        if (tapin) pb_rows_slice_major(h.data(), Np, rowlen, taps);
-    };
-    out.tapin = tapin; out.taps = taps;
-    if (!sa && sw && mx_ && pack_mx2_ && Cp % 128 == 0) {        // mx2 layout: per tap [w_hi fp16 | w_lo e4m3 2^pw]
-        float mlo = 0.f;
-        for (int64_t i = 0; i < (int64_t)N * K; ++i) mlo = fmaxf(mlo, fabsf(src[i] - (float)(f16)src[i]));
-        int pw = 0, e = 0;
-        if (mlo > 0.f) { frexpf(mlo, &e); pw = 8 - e; }
-        const int64_t K2 = (int64_t)tp * (Cp + Cp / 2);
-        std::vector<f16> h2((size_t)Np * K2, (f16)0.f);
-        for (int n = 0; n < N; ++n)
-            for (int t = 0; t < tp; ++t) {
-                f16 *d = h2.data() + (size_t)n * K2 + (size_t)t * (Cp + Cp / 2);
-                unsigned char *d8 = (unsigned char *)(d + Cp);
-                for (int k = 0; k < Cin; ++k) {
-                    const float v = src[(size_t)n * K + (size_t)t * Cin + k];
-                    const f16 hi = (f16)v;
-                    d[k] = hi;
-                    d8[k] = pb_f32_to_e4m3(ldexpf(v - (float)hi, pw));
-                }
-            }
-        to_slice_major(h2, K2);
-        void *p2 = nullptr;
-        PB_HIP(hipMalloc(&p2, h2.size() * 2));
-        owned_.push_back(p2);
-        PB_HIP(hipMemcpy(p2, h2.data(), h2.size() * 2, hipMemcpyHostToDevice));
-        out.w = (f16 *)p2; out.N = N; out.K = (int)K2; out.Kreal = K; out.bias = nullptr;
-        out.sa = 0; out.sw = 1; out.Cseg = Cp; out.mx2 = 1; out.mx_pw = pw; out.nk16 = Cp / 64;
-    } else if (sa && mx_) {             // mx3 layout (engine.hip DepthEngine::pack has the same one)
-        float mlo = 0.f, mhi = 0.f;
-        for (int64_t i = 0; i < (int64_t)N * K; ++i) {
-            const float v = src[i];
-            mhi = fmaxf(mhi, fabsf(v));
-            mlo = fmaxf(mlo, fabsf(v - (float)(f16)v));
-        }
-        int pw = 0, e = 0;
-        if (mlo > 0.f) { frexpf(mlo, &e); pw = 8 - e; }
-        if (mhi > 0.f) { frexpf(mhi, &e); pw = std::min(pw, 20 - e); }
-        const int64_t K3 = (int64_t)tp * 2 * Cp;
-        std::vector<f16> h3((size_t)Np * K3, (f16)0.f);
-        for (int n = 0; n < N; ++n)
-            for (int t = 0; t < tp; ++t) {
-                f16 *d = h3.data() + (size_t)n * K3 + (size_t)t * 2 * Cp;
-                unsigned char *d8 = (unsigned char *)(d + Cp);
-                for (int k = 0; k < Cin; ++k) {
-                    const float v = src[(size_t)n * K + (size_t)t * Cin + k];
-                    const f16 hi = (f16)v;
-                    d[k] = hi;
-                    d8[k] = pb_f32_to_e4m3(ldexpf(v - (float)hi, pw));
-                    d8[Cp + k] = pb_f32_to_e4m3(ldexpf((float)hi, pw - 12));
-                }
-            }
-        to_slice_major(h3, K3);
-        void *p3 = nullptr;
-        PB_HIP(hipMalloc(&p3, h3.size() * 2));
-        owned_.push_back(p3);
-        PB_HIP(hipMemcpy(p3, h3.data(), h3.size() * 2, hipMemcpyHostToDevice));
-        out.w = (f16 *)p3; out.N = N; out.K = (int)K3; out.Kreal = K; out.bias = nullptr;
-        out.sa = 1; out.sw = 1; out.Cseg = Cp; out.mx3 = 1; out.mx_pw = pw; out.nk16 = Cp / 64;
-    } else {
-    const int64_t Kt = (int64_t)tp * segs * Cp;
-    std::vector<f16> h((size_t)Np * Kt, (f16)0.f);
-    for (int n = 0; n < N; ++n)
-        for (int t = 0; t < tp; ++t)
-            for (int k = 0; k < Cin; ++k) {
-                const float v = src[(size_t)n * K + (size_t)t * Cin + k];
-                const f16 hi = (f16)v;
-                f16 *d = h.data() + (size_t)n * Kt + (size_t)t * segs * Cp;
-                d[k] = hi;
-                if (sa) d[Cp + k] = hi;
-                if (sw) d[(1 + sa) * Cp + k] = (f16)(v - (float)hi);
-            }
-    to_slice_major(h, Kt);
+int EngineBase::upload_f32(const float *src, size_t n, float **dst) {
     void *p = nullptr;
-    PB_HIP(hipMalloc(&p, h.size() * 2));
+    PB_HIP(hipMalloc(&p, std::max<size_t>(n * 4, 256)));
     owned_.push_back(p);
-    PB_HIP(hipMemcpy(p, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-    out.w = (f16 *)p; out.N = N; out.K = (int)Kt; out.Kreal = K; out.bias = nullptr;
-    out.sa = sa; out.sw = sw; out.Cseg = Cp;
-    }
+    PB_HIP(hipMemcpy(p, src, n * 4, hipMemcpyHostToDevice));
+    *dst = (float *)p;
+    return 0;
+}
+
+int EngineBase::upload_rows(const std::vector<f16> &rows, f16 **dst) {
+    void *p = nullptr;
+    PB_HIP(hipMalloc(&p, rows.size() * 2));
+    owned_.push_back(p);
+    PB_HIP(hipMemcpy(p, rows.data(), rows.size() * 2, hipMemcpyHostToDevice));
+    *dst = (f16 *)p;
+    return 0;
+}
+
+int EngineBase::pack_spec(const float *src, int N, int K, int Kpad, PackedW &out, const float *bias, int taps, const PackSpec &spec) {
+    const std::vector<f16> rows = pack_rows(src, N, K, Kpad, taps, spec, out);
+    PB_CHECK(!rows.empty(), PB_ERR_ARG, "pack: N %d / K %d / Kpad %d / taps %d do not fit the layout (sa %d, sw %d, mx2 %d)", N, K, Kpad, taps, spec.sa,
+             spec.sw, spec.mx2);
+    int r = upload_rows(rows, &out.w);
+    if (r) return r;
+    out.bias = nullptr;
     if (bias) {
+        const size_t Np = (size_t)round_up(N, 256);
         void *b = nullptr;
-        PB_HIP(hipMalloc(&b, std::max<size_t>((size_t)Np * 4, 256)));
+        PB_HIP(hipMalloc(&b, std::max<size_t>(Np * 4, 256)));
         owned_.push_back(b);
-        PB_HIP(hipMemset(b, 0, (size_t)Np * 4));
+        PB_HIP(hipMemset(b, 0, Np * 4));
         PB_HIP(hipMemcpy(b, bias, (size_t)N * 4, hipMemcpyHostToDevice));
         out.bias = (float *)b;
     }
     return 0;
+}
+
+int EngineBase::pack(const float *src, int N, int K, int Kpad, PackedW &out, const float *bias, int taps, int sa_req) {
+    PackSpec s;
+    // split_w_ (PB_PREC_SPLIT): every tap's channels are followed by the rounding residuals of the same weights, and the GEMM reads the
+    // activations twice (gemm.h kwrap): a w_hi + a w_lo in one accumulator
+    s.sw = split_w_ && Kpad % (64 * taps) == 0 && K % taps == 0;
+    s.sa = s.sw && sa_req;
+    s.mx = mx_;
+    s.mx2 = !s.sa && s.sw && mx_ && pack_mx2_ && Kpad / taps % 128 == 0;
+    s.tapin = pack_tapin_;
+    return pack_spec(src, N, K, Kpad, out, bias, taps, s);
 }
 
 int EngineBase::fold_bn(const std::string &bn, int C, std::vector<float> &scale, std::vector<float> &shift) {
@@ -188,13 +172,9 @@ int EngineBase::pack_conv(const std::string &name, bool has_bias, const float *s
     const float *w = (const float *)t->data;
     const int cip = ci_pad ? ci_pad : cp64(ci), K = kh * kw * cip;
     PB_CHECK(cip >= ci && cip % 64 == 0, PB_ERR_ARG, "pack_conv '%s': %d input channels padded to %d", name.c_str(), ci, cip);
-    std::vector<float> g((size_t)co * K, 0.f), bb(co);
-    for (int o = 0; o < co; ++o) {
-        const float s = scale ? scale[o] : 1.f;
-        for (int c = 0; c < ci; ++c)
-            for (int tp = 0; tp < kh * kw; ++tp) g[(size_t)o * K + tp * cip + c] = w[((size_t)o * ci + c) * kh * kw + tp] * s;
-        bb[o] = (b ? b[o] : 0.f) * s + (shift ? shift[o] : 0.f);
-    }
+    const std::vector<float> g = pb_conv_rows(w, co, ci, kh * kw, cip, scale);
+    std::vector<float> bb(co);
+    for (int o = 0; o < co; ++o) bb[o] = (b ? b[o] : 0.f) * (scale ? scale[o] : 1.f) + (shift ? shift[o] : 0.f);
     int r = pack(g.data(), co, K, K, out, bb.data(), kh * kw, sa);
     out.Kreal = kh * kw * ci;
     if (r) return r;
@@ -212,16 +192,13 @@ int EngineBase::pack_conv(const std::string &name, bool has_bias, const float *s
                 for (int c = 0; c < ci; ++c) {
                     const float v = g[(size_t)o * K + tp * cip + c];
                     const f16 hi = (f16)v;
-                    row[tp * ci + c] = hi;                                                   // fp16 chunks: tap-major, ci / 8 per tap
-                    row8[(tp * 2 + 0) * ci + c] = pb_f32_to_e4m3(ldexpf(v - (float)hi, pw));   // meets the map's hi8 chunks
-                    row8[(tp * 2 + 1) * ci + c] = pb_f32_to_e4m3(ldexpf((float)hi, pw - 12));  // ... and its lo8 chunks
+                    row[tp * ci + c] = hi;                                      // fp16 chunks: tap-major, ci / 8 per tap
+                    row8[(tp * 2 + 0) * ci + c] = pb_w_lo8(v, hi, pw);          // meets the map's hi8 chunks
+                    row8[(tp * 2 + 1) * ci + c] = pb_w_hi8(hi, pw);             // ... and its lo8 chunks
                 }
         }
-        void *pc = nullptr;
-        PB_HIP(hipMalloc(&pc, h.size() * 2));
-        owned_.push_back(pc);
-        PB_HIP(hipMemcpy(pc, h.data(), h.size() * 2, hipMemcpyHostToDevice));
-        out.wcw = (f16 *)pc; out.Kcw = (int)Kc; out.nk16cw = nk16; out.cwC = ci;
+        if ((r = upload_rows(h, &out.wcw))) return r;
+        out.Kcw = (int)Kc; out.nk16cw = nk16; out.cwC = ci;
     }
     return 0;
 }
@@ -251,14 +228,17 @@ void EngineBase::set_weights(GemmArgs &a, const PackedW &w, bool is_conv) const 
         }
         return;
     }
-    if (!w.sw) return;
-    if (is_conv) {               // per tap [w_hi | w_hi (if sa) | w_lo]: the channel cursor wraps back onto the pixel's hi part
+    // an fp16 weight with nk16 (every K tile an fp16 tile): the MX build of the kernel, for the fp8 copy its epilogue stores (PackedW::nk16)
+    if (w.nk16) { a.nk16 = w.nk16; a.mx_scale_a = 127 - kMx2Pa; a.mx_scale_b = 127 - w.mx_pw; }
+    if (!w.sa && !w.sw) return;
+    // per tap [w_hi | w_hi (if sa) | w_lo (if sw)]: after the activation's parts the channel cursor wraps back onto the pixel's hi part
+    if (is_conv) {
         if (!a.cLd) a.cLd = (1 + w.sa) * a.cC;
-        a.kwrap = (1 + w.sa) * a.cC;
+        a.kwrap = w.sw ? (1 + w.sa) * a.cC : 0;
         a.kshift = -a.kwrap;
-        a.cC = (2 + w.sa) * a.cC;
+        a.cC = (1 + w.sa + w.sw) * a.cC;
     } else {
-        a.kwrap = (1 + w.sa) * w.Cseg / 64;
+        a.kwrap = w.sw ? (1 + w.sa) * w.Cseg / 64 : 0;
     }
 }
 

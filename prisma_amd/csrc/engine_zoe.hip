@@ -12,8 +12,6 @@
 #include "engine.h"
 
 namespace {
-enum { F_GEMM = 0, F_ELT = 4, F_PP = 5 };
-
 double pil_bicubic(double x) {           // libImaging/Resample.c bicubic_filter, a = -0.5
     const double a = -0.5;
     if (x < 0.0) x = -x;
@@ -65,8 +63,7 @@ int DepthEngine::load_metric() {
         const pb_tensor *tw = find(name + ".weight"), *tb = find(name + ".bias");
         PB_CHECK(tw && tb && tw->shape[0] == co && tw->shape[1] == ci, PB_ERR_ARG, "missing or mis-shaped weight '%s' [%d, %d]",
                  name.c_str(), co, ci);
-        int r = pack((const float *)tw->data, co, ci, kpad, out, (const float *)tb->data, 1, 0, vit_sw_);
-        return r;
+        return pack_spec((const float *)tw->data, co, ci, kpad, out, (const float *)tb->data, 1, spec(0, vit_sw_));
     };
     auto mlp = [&](const std::string &name, int cin, int kin, int mid, int kmid, int cout, Mlp2 &m) -> int {
         int r = conv1(name + ".0", mid, cin, kin, m.a);
