@@ -210,7 +210,7 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
             delete c;
             PB_CHECK(false, PB_ERR_ARG, "%s: precision %d unknown", band, prec);
         }
-        c->raft = gm ? new GmflowEngine(device_id) : new RaftEngine(device_id);      // GmflowEngine overrides load / infer / get_stage
+        c->raft = gm ? new GmflowEngine(device_id) : new RaftEngine(device_id);      // GmflowEngine overrides load / infer
         c->raft->split_w_ = prec == PB_PREC_SPLIT;
         {
             const char *mx = getenv("PB_MX");
@@ -414,10 +414,15 @@ int pb_wait(pb_ctx *c) {
     return 0;
 }
 
-int64_t pb_depth_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {
-    PB_CHECK(c && c->depth && name && out && shape_out, PB_ERR_ARG, "get_stage: bad arguments");
+// pb_depth_get_stage / pb_flow_get_stage / pb_mask_get_stage: `own` is the ctx's engine of the band the entry point belongs to (null: another band's ctx)
+static int64_t band_stage(pb_ctx *c, const EngineBase *own, const char *what, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {
+    PB_CHECK(c && own && name && out && shape_out, PB_ERR_ARG, "%sget_stage: bad arguments", what);
     PB_HIP(hipSetDevice(c->device));
-    return c->depth->get_stage(name, out, cap, shape_out);
+    return c->band->get_stage(name, out, cap, shape_out);
+}
+
+int64_t pb_depth_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {
+    return band_stage(c, c ? c->depth : nullptr, "", name, out, cap, shape_out);
 }
 
 int pb_set_profiling(pb_ctx *c, int enabled) {
@@ -622,8 +627,7 @@ int pb_mask_get_instances(pb_ctx *c, int frame, int cap, float *scores_out, int3
 }
 
 int64_t pb_mask_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {
-    PB_CHECK(c && c->mask && name && out && shape_out, PB_ERR_ARG, "mask get_stage: bad arguments");
-    return c->mask->get_stage(name, out, cap, shape_out);
+    return band_stage(c, c ? c->mask : nullptr, "mask ", name, out, cap, shape_out);
 }
 
 int pb_flow_set_inference_size(pb_ctx *c, int h, int w) {
@@ -660,9 +664,7 @@ int64_t pb_flow_arena_bytes(pb_ctx *c) {
 }
 
 int64_t pb_flow_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {
-    PB_CHECK(c && c->raft && name && out && shape_out, PB_ERR_ARG, "flow get_stage: bad arguments");
-    PB_HIP(hipSetDevice(c->device));
-    return c->raft->get_stage(name, out, cap, shape_out);
+    return band_stage(c, c ? c->raft : nullptr, "flow ", name, out, cap, shape_out);
 }
 
 int pb_set_option(pb_ctx *c, const char *key, int value) {

@@ -13,18 +13,6 @@ void pb_cubic_taps(int src, int dst, int *idx, float *wt);   // engine.hip
 
 #define PB_TRY(expr) do { int _r = (expr); if (_r) return _r; } while (0)
 
-struct DevMem {
-    void *p = nullptr;
-    ~DevMem() { if (p) hipFree(p); }
-    int alloc(size_t bytes) {
-        PB_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes));
-        PB_HIP(hipMemset(p, 0, bytes < 256 ? 256 : bytes));
-        PB_HIP(hipDeviceSynchronize());     // memset runs on the null stream; kernels use the ctx stream
-        return 0;
-    }
-    template <class T> T *as() { return (T *)p; }
-};
-
 // Streams, events and double-buffered slots of the chunked host-pointer entry points (pb_depth_infer_batch, pb_flow_infer_sequence and their
 // submit forms; run_chunks in abi.hip is the schedule).  A lane is one array of the call - the frames in, each result out - with a device
 // buffer per slot and, for callers whose own array is pageable, a pinned staging buffer per slot.

@@ -10,11 +10,9 @@
 class DepthEngine : public EngineBase {
   public:
     DepthEngine(int device, const pb_depth_cfg &cfg);
-    ~DepthEngine() override;
     int load(const pb_tensor *w, int n);
     int infer(const uint8_t *frames_dev, int n, int H, int W, float *depth_out, uint8_t *rgb_out, float *mn,
               float *mx, int flip);
-    int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]);
     int max_batch() const { return cfg_.max_batch > 0 ? cfg_.max_batch : 1; }
 
   private:
@@ -34,7 +32,7 @@ class DepthEngine : public EngineBase {
     // the layout of one weight (pack_layout.h): sa / sw / mx2 as given, e4m3 residual parts and slice-major rows as the head runs them
     PackSpec spec(int sa, int sw, int mx2 = 0) const;
     int pack_vit(const float *wt, int N, int K, PackedW &out, const float *bias, bool keep_res);
-    void snapshot(const std::string &name);
+    int snapshot_tokens(const std::string &name, int n);      // debug copy of the residual stream X_ as stage `name`
 
     pb_depth_cfg cfg_;
     // PB_PREC_SPLIT (tools/precision_budget.py): ViT linears and the metric head keep their weights as hi + lo (2 passes);
@@ -72,7 +70,7 @@ class DepthEngine : public EngineBase {
     static constexpr int64_t kSkFloats = (int64_t)512 * 128 * 128;      // 512 slices of a 128 x 128 fp32 tile: 32 MB
 
     // plan
-    int pB_ = 0, pH_ = 0, pW_ = 0, last_n_ = 0;
+    int pB_ = 0, pH_ = 0, pW_ = 0;
     int hB_ = 1;                                // frames per DPT-head chunk (<= batch_cap: 32-bit offsets of the high-resolution split maps)
     int nh_ = 0, nw_ = 0, gh_ = 0, gw_ = 0, ntok_ = 0, ntp_ = 0, P_ = 0;
     int lh_[4] = {0, 0, 0, 0}, lw_[4] = {0, 0, 0, 0};      // DPT level sizes (level 0 = finest)
@@ -87,8 +85,6 @@ class DepthEngine : public EngineBase {
     f16 *o1_ = nullptr, *up_ = nullptr;
     float *netd_ = nullptr, *full_ = nullptr;
     unsigned *mm_ = nullptr;
-    std::map<std::string, Stage> stages_;
-    std::map<std::string, float *> snaps_;
     // metric head: weights, buffers (arena), Pillow resize tables
     struct Mlp2 { PackedW a, b; };
     PackedW zconv2_;

@@ -22,12 +22,6 @@ inline int cp64(int c) { return (int)round_up(c, 64); }
 
 DepthEngine::DepthEngine(int dev, const pb_depth_cfg &cfg) : EngineBase(dev, kFam), cfg_(cfg) {}
 
-DepthEngine::~DepthEngine() {
-    hipSetDevice(device);
-    if (stream) hipStreamSynchronize(stream);
-    for (auto &kv : snaps_) hipFree(kv.second);
-}
-
 PackSpec DepthEngine::spec(int sa, int sw, int mx2) const {
     PackSpec s;
     s.sa = sa; s.sw = sw; s.mx = head_mx_; s.mx2 = mx2; s.tapin = head_tapin_;
@@ -429,13 +423,9 @@ int DepthEngine::conv3(const f16 *in, int inC, int n, int H, int W, const Packed
     return gemm(A_CONV, EPI_STD, a, w, TILE_AUTO);
 }
 
-void DepthEngine::snapshot(const std::string &name) {
-    if (!debug) return;
-    const size_t bytes = (size_t)pB_ * ntp_ * cfg_.embed_dim * 4;
-    float *&p = snaps_[name];
-    if (!p) hipMalloc((void **)&p, bytes);
-    hipMemcpyAsync(p, X_, bytes, hipMemcpyDeviceToDevice, stream);
-    stages_[name] = Stage{p, 0, last_n_, ntok_, 1, cfg_.embed_dim, cfg_.embed_dim, (int64_t)ntp_ * cfg_.embed_dim};
+int DepthEngine::snapshot_tokens(const std::string &name, int n) {
+    const int64_t D = cfg_.embed_dim;
+    return snapshot(name, X_, (size_t)n * ntp_ * D * 4, Stage::f32_rows(nullptr, n, ntok_, D, ntp_ * D));
 }
 
 int DepthEngine::vit(int n) {
@@ -451,7 +441,7 @@ int DepthEngine::vit(int n) {
         toc();
         if (r) return r;
     }
-    snapshot("tokens");
+    if (debug && (r = snapshot_tokens("tokens", n))) return r;
     const double ln_bytes = (double)n * ntok_ * D * 6.0;
     // MX mode: rows of Y_ / AO_ / Hd_ are [fp16 (K) | fp8 (K bytes)], i.e. 1.5 K halfs apart; the fp8 copy is stored x 2^kMx2Pa.  A buffer
     // whose consumers run without a weight residual (vit_res_) is plain fp16: Y_ feeds qkv (after norm1) and fc1 (after norm2)
@@ -496,7 +486,7 @@ int DepthEngine::vit(int n) {
             a.A = Hd_; a.lda = ldH; a.M = M; a.resid = X_; a.ldr = D; a.gamma = b.ls2;
             if ((r = gemm(A_DENSE, EPI_RESID, a, b.fc2))) return r;
         }
-        if (debug) snapshot("block" + std::to_string(i));
+        if (debug && (r = snapshot_tokens("block" + std::to_string(i), n))) return r;
         const int tap = i - (cfg_.depth - 4);
         if (tap >= 0) {
             tic(F_LN, 0, ln_bytes);
@@ -504,7 +494,7 @@ int DepthEngine::vit(int n) {
                                  head_mx_ ? kLo8Pa : -1);
             toc();
             if (r) return r;
-            stages_["feat" + std::to_string(tap)] = Stage{feat_[tap], 3, last_n_, P_, 1, D, hs_ * D, (int64_t)P_ * D};
+            stages_["feat" + std::to_string(tap)] = Stage::f16_rows(feat_[tap], n, P_, D, hs_ * D);
         }
     }
     return 0;
@@ -518,7 +508,7 @@ int DepthEngine::head(int f0, int n) {
     const int hs = hs_;                                  // 2: maps are [hi | lo] per pixel (split fp16), lo at + padded channels
     auto lo = [&](int cp) { return head_sa_ ? cp : 0; };
     auto nhwc = [&](const std::string &name, const f16 *p, int c, int h, int w, int ld, bool split = true) {
-        stages_[name] = Stage{p, 1, last_n_, c, h, w, (split ? hs : 1) * ld, 0};
+        stages_[name] = Stage::f16_nhwc(p, n, c, h, w, (split ? hs : 1) * ld);      // split maps: the hi part
     };
     auto bil = [&](const f16 *x, f16 *y, int h, int w, int oh, int ow, int c, int ld) -> int {
         tic(F_ELT, 0, (double)n * ((double)h * w + (double)oh * ow) * c * 2.0 * hs);
@@ -581,7 +571,7 @@ int DepthEngine::head(int f0, int n) {
         r = launch_dpt_tail(stream, z_, n, h1, w1, hs * Zp, lo(Zp), head_mx_ ? kLo8Pa : -1, oc2_.bias, w2_, b2_, netd_, nh_, nw_);
         toc();
         if (r) return r;
-        stages_["net_depth"] = Stage{netd_, 2, last_n_, 1, nh_, nw_, 0, 0};
+        stages_["net_depth"] = Stage::f32_rows(netd_, n, nh_, nw_);
         return 0;
     }
     if ((r = bil(o1_, up_, h1, w1, nh_, nw_, F2, F2p))) return r;
@@ -604,7 +594,7 @@ int DepthEngine::head(int f0, int n) {
         a.w2 = w2_; a.b2 = b2_; a.depth = netd_;
         if ((r = gemm(A_CONV, EPI_HEAD, a, oc2_))) return r;
     }
-    stages_["net_depth"] = Stage{netd_, 2, last_n_, 1, nh_, nw_, 0, 0};
+    stages_["net_depth"] = Stage::f32_rows(netd_, n, nh_, nw_);
     return 0;
 }
 
@@ -612,7 +602,6 @@ int DepthEngine::run_chunk(const uint8_t *frames, int n, float *depth_out, uint8
                            int flip) {
     int r;
     stages_.clear();
-    last_n_ = n;
     tic(F_PP, 0, (double)n * ((double)pH_ * pW_ * 3 + (double)nh_ * nw_ * 3 * 2));
     r = launch_preprocess(stream, frames, n, pH_, pW_, nh_, nw_, xi_, xw_, yi_, yw_, patchA_, 640, nullptr);
     toc();
@@ -623,8 +612,7 @@ int DepthEngine::run_chunk(const uint8_t *frames, int n, float *depth_out, uint8
     const int64_t px = (int64_t)pH_ * pW_;
     for (int f0 = 0; f0 < n; f0 += step) {
         const int c = std::min(step, n - f0);
-        last_n_ = c;                                     // the head's stages hold the last head chunk
-        if ((r = head(f0, c))) return r;
+        if ((r = head(f0, c))) return r;                 // (its stages hold the last head chunk)
         if ((r = tail(c, depth_out ? depth_out + f0 * px : nullptr, rgb_out ? rgb_out + f0 * px * 3 : nullptr, mn ? mn + f0 : nullptr,
                       mx ? mx + f0 : nullptr, flip)))
             return r;
@@ -678,50 +666,4 @@ int DepthEngine::infer(const uint8_t *frames, int n, int H, int W, float *depth_
         if (r) return r;
     }
     return 0;
-}
-
-int64_t DepthEngine::get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) {
-    auto it = stages_.find(name);
-    PB_CHECK(it != stages_.end(), PB_ERR_ARG, "unknown stage '%s'", name);
-    const Stage &s = it->second;
-    // frames the stage holds: the whole call for the ViT's stages, the LAST head chunk (frames n - s.n ... n - 1 of the call) for the
-    // DPT head's when the call ran its head in more than one chunk - recorded when the stage was registered
-    const int n = s.n > 0 ? (int)s.n : last_n_;
-    PB_HIP(hipStreamSynchronize(stream));
-    int64_t total = 0;
-    if (s.kind == 0 || s.kind == 3) {
-        total = (int64_t)n * s.c * s.w;                       // [n, rows = s.c, cols = s.w]
-        shape[0] = n; shape[1] = s.c; shape[2] = s.w; shape[3] = 1;
-        PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small (%lld > %lld)", (long long)total, (long long)cap);
-        if (s.kind == 0) {
-            for (int b = 0; b < n; ++b)
-                PB_HIP(hipMemcpy(out + (int64_t)b * s.c * s.w, (const float *)s.ptr + b * s.bstride, (size_t)s.c * s.w * 4,
-                                 hipMemcpyDeviceToHost));
-        } else {
-            float *tmp = nullptr;
-            PB_HIP(hipMalloc((void **)&tmp, total * 4));
-            int r = launch_f16_to_f32(stream, (const f16 *)s.ptr, tmp, (int64_t)n * s.c, (int)s.w, (int)s.ld);
-            if (r) return r;
-            PB_HIP(hipStreamSynchronize(stream));
-            PB_HIP(hipMemcpy(out, tmp, total * 4, hipMemcpyDeviceToHost));
-            PB_HIP(hipFree(tmp));
-        }
-    } else if (s.kind == 1) {
-        total = (int64_t)n * s.c * s.h * s.w;
-        shape[0] = n; shape[1] = s.c; shape[2] = s.h; shape[3] = s.w;
-        PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small (%lld > %lld)", (long long)total, (long long)cap);
-        float *tmp = nullptr;
-        PB_HIP(hipMalloc((void **)&tmp, total * 4));
-        int r = launch_nhwc_f16_to_nchw_f32(stream, (const f16 *)s.ptr, tmp, n, (int)s.c, (int)s.h, (int)s.w, (int)s.ld);
-        if (r) return r;
-        PB_HIP(hipStreamSynchronize(stream));
-        PB_HIP(hipMemcpy(out, tmp, total * 4, hipMemcpyDeviceToHost));
-        PB_HIP(hipFree(tmp));
-    } else {
-        total = (int64_t)n * s.h * s.w;
-        shape[0] = n; shape[1] = s.h; shape[2] = s.w; shape[3] = 1;
-        PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small (%lld > %lld)", (long long)total, (long long)cap);
-        PB_HIP(hipMemcpy(out, s.ptr, total * 4, hipMemcpyDeviceToHost));
-    }
-    return total;
 }

@@ -1,6 +1,6 @@
 // Shared plumbing of the band engines (depth_anything, flow_raft, flow_gmflow, mask_mmdet): the ctx stream, the named-weight map, the upload
-// of packed GEMM weights (pack_layout.h has the layouts) with folded BatchNorm, a two-pass arena, per-family kernel timing, and the
-// implicit-GEMM / dense GEMM launch helpers.
+// of packed GEMM weights (pack_layout.h has the layouts) with folded BatchNorm, a two-pass arena, per-family kernel timing, the
+// implicit-GEMM / dense GEMM launch helpers, and the debug-stage registry behind pb_*_get_stage.
 #pragma once
 #include <map>
 #include <string>
@@ -41,10 +41,57 @@ static inline hipError_t pb_create_stream(hipStream_t *s, const char *mask_env) 
     return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
 
+// A device allocation freed when it goes out of scope.  alloc: a zeroed buffer (the op-level entry points); reserve: at least `bytes` of
+// undefined contents, grown by free + malloc and never shrunk (debug snapshots, get_stage temporaries)
+struct DevMem {
+    void *p = nullptr;
+    size_t cap = 0;
+    DevMem() = default;
+    DevMem(const DevMem &) = delete;
+    DevMem &operator=(const DevMem &) = delete;
+    ~DevMem() { if (p) hipFree(p); }
+    int alloc(size_t bytes) {
+        PB_HIP(hipMalloc(&p, bytes < 256 ? 256 : bytes));
+        PB_HIP(hipMemset(p, 0, bytes < 256 ? 256 : bytes));
+        PB_HIP(hipDeviceSynchronize());     // memset runs on the null stream; kernels use the ctx stream
+        return 0;
+    }
+    int reserve(size_t bytes) {
+        if (bytes <= cap) return 0;
+        if (p) PB_HIP(hipFree(p));
+        p = nullptr; cap = 0;
+        PB_HIP(hipMalloc(&p, bytes));
+        cap = bytes;
+        return 0;
+    }
+    template <class T> T *as() { return (T *)p; }
+};
+
+// A debug stage (pb_*_get_stage): a device buffer of the last infer call and how EngineBase::get_stage turns it into the caller's fp32
+// array.  One kind = one source layout and one shape_out in every band; `n` (frames, pairs x directions, ... - prisma_bands.h says which per
+// stage) is what the buffer held when the stage was registered.
 struct Stage {
+    enum Kind {
+        F32_ROWS,            // fp32 [n, rows, cols], batch elements bstride floats apart            -> [n, rows, cols, 1]
+        F16_ROWS,            // fp16 [n * rows, ld], the first cols of every row                     -> [n, rows, cols, 1]
+        F16_NHWC,            // fp16 [n, h, w, ld], the first c of every pixel; lo_off != 0: a split map, the residual parts lo_off halfs
+                             // further on are added in fp32 on the host                             -> [n, c, h, w]
+        F32_NCHW,            // fp32 [n, c, h, w], contiguous                                        -> [n, c, h, w]
+        F32_NHWC,            // fp32 [n, h, w, ld], the first c of every pixel                       -> [n, c, h, w]
+    };
+    Kind kind;
     const void *ptr;
-    int kind;                // 0: fp32 rows [n, rows, cols] with batch stride; 1: NHWC fp16 map; 2: fp32 map [n,h,w]; 3: fp16 rows
-    int64_t n, c, h, w, ld, bstride;
+    int64_t n, c, h, w;      // the row kinds keep rows in h and cols in w (c = 1)
+    int64_t ld, bstride, lo_off;
+    static Stage f32_rows(const void *p, int64_t n, int64_t rows, int64_t cols, int64_t bstride = 0) {
+        return Stage{F32_ROWS, p, n, 1, rows, cols, cols, bstride ? bstride : rows * cols, 0};
+    }
+    static Stage f16_rows(const void *p, int64_t n, int64_t rows, int64_t cols, int64_t ld) { return Stage{F16_ROWS, p, n, 1, rows, cols, ld, 0, 0}; }
+    static Stage f16_nhwc(const void *p, int64_t n, int64_t c, int64_t h, int64_t w, int64_t ld, int64_t lo_off = 0) {
+        return Stage{F16_NHWC, p, n, c, h, w, ld, 0, lo_off};
+    }
+    static Stage f32_nchw(const void *p, int64_t n, int64_t c, int64_t h, int64_t w) { return Stage{F32_NCHW, p, n, c, h, w, 0, 0, 0}; }
+    static Stage f32_nhwc(const void *p, int64_t n, int64_t c, int64_t h, int64_t w, int64_t ld) { return Stage{F32_NHWC, p, n, c, h, w, ld, 0, 0}; }
 };
 
 struct KernelTimer {
@@ -68,6 +115,9 @@ class EngineBase {
     explicit EngineBase(int device, const char *const *fam_names = nullptr);
     virtual ~EngineBase();
     int stats(pb_kernel_stat *out, int cap);
+    // the stage `name` of the last infer call as fp32 in out[cap] (floats): returns the element count and the dimensions in shape, or a
+    // negative pb error ("unknown stage", "stage buffer too small") that leaves the registry as it was
+    int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]);
 
     hipStream_t stream = nullptr;
     int device = 0;
@@ -135,6 +185,12 @@ class EngineBase {
     int dense(const f16 *A, int lda, int64_t M, const PackedW &w, f16 *out, int ldo, int act, const f16 *add1 = nullptr, int o8_off = 0,
               int a_pa = -1, int lo_off = 0);          // a_pa: power-of-two scale the A operand's fp8 copy was stored with (default kMx2Pa)
 
+    // The debug-stage registry: infer() clears stages_ and registers views of arena buffers as it goes (`as.ptr` of a snapshot is ignored).
+    // snapshot() registers a copy instead - of a buffer that later launches overwrite - made on `stream` into a buffer kept under `name`,
+    // which grows when a call needs more; engines call it only while `debug` is set.
+    int snapshot(const std::string &name, const void *src, size_t bytes, Stage as);
+    std::map<std::string, Stage> stages_;
+
     const char *const *fam_names_;
     std::map<std::string, const pb_tensor *> tmap_;
     std::vector<void *> owned_;                 // permanent device allocations (weights), freed by the destructor
@@ -148,4 +204,5 @@ class EngineBase {
 
   private:
     int upload_rows(const std::vector<f16> &rows, f16 **dst);
+    std::map<std::string, DevMem> snaps_;
 };

@@ -49,6 +49,7 @@ EngineBase::EngineBase(int device, const char *const *fam_names) : device(device
 EngineBase::~EngineBase() {
     hipSetDevice(device);
     if (stream) hipStreamSynchronize(stream);
+    snaps_.clear();
     for (auto p : owned_) hipFree(p);
     if (arena_) hipFree(arena_);
     if (stream) hipStreamDestroy(stream);
@@ -70,6 +71,72 @@ void EngineBase::toc() {
 int EngineBase::stats(pb_kernel_stat *out, int cap) {
     if (hipStreamSynchronize(stream) != hipSuccess) return -2;
     return timer.collect(fam_names_, F_COUNT, out, cap);
+}
+
+int EngineBase::snapshot(const std::string &name, const void *src, size_t bytes, Stage as) {
+    DevMem &buf = snaps_[name];
+    int r = buf.reserve(bytes);
+    if (r) return r;
+    PB_HIP(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyDeviceToDevice, stream));
+    as.ptr = buf.p;
+    stages_[name] = as;
+    return 0;
+}
+
+int64_t EngineBase::get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) {
+    auto it = stages_.find(name);
+    PB_CHECK(it != stages_.end(), PB_ERR_ARG, "unknown stage '%s'", name);
+    const Stage &s = it->second;
+    const bool rows = s.kind == Stage::F32_ROWS || s.kind == Stage::F16_ROWS;
+    const int64_t plane = s.h * s.w, total = s.n * s.c * plane;
+    shape[0] = s.n; shape[1] = rows ? s.h : s.c; shape[2] = rows ? s.w : s.h; shape[3] = rows ? 1 : s.w;
+    PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small (%lld > %lld)", (long long)total, (long long)cap);
+    PB_HIP(hipStreamSynchronize(stream));
+    DevMem tmp;                         // fp32 copy of an fp16 stage
+    int r;
+    auto fetch = [&](float *dst) -> int {
+        PB_HIP(hipStreamSynchronize(stream));
+        PB_HIP(hipMemcpy(dst, tmp.p, (size_t)total * 4, hipMemcpyDeviceToHost));
+        return 0;
+    };
+    switch (s.kind) {
+    case Stage::F32_ROWS:
+        if (s.bstride == plane) {
+            PB_HIP(hipMemcpy(out, s.ptr, (size_t)total * 4, hipMemcpyDeviceToHost));
+        } else {
+            for (int64_t b = 0; b < s.n; ++b)
+                PB_HIP(hipMemcpy(out + b * plane, (const float *)s.ptr + b * s.bstride, (size_t)plane * 4, hipMemcpyDeviceToHost));
+        }
+        break;
+    case Stage::F32_NCHW:
+        PB_HIP(hipMemcpy(out, s.ptr, (size_t)total * 4, hipMemcpyDeviceToHost));
+        break;
+    case Stage::F16_ROWS:
+        if ((r = tmp.reserve((size_t)total * 4))) return r;
+        if ((r = launch_f16_to_f32(stream, (const f16 *)s.ptr, tmp.as<float>(), s.n * s.h, (int)s.w, (int)s.ld))) return r;
+        if ((r = fetch(out))) return r;
+        break;
+    case Stage::F16_NHWC:
+        if ((r = tmp.reserve((size_t)total * 4))) return r;
+        if ((r = launch_nhwc_f16_to_nchw_f32(stream, (const f16 *)s.ptr, tmp.as<float>(), (int)s.n, (int)s.c, (int)s.h, (int)s.w, (int)s.ld))) return r;
+        if ((r = fetch(out))) return r;
+        if (s.lo_off) {                 // split map: hi + lo in fp32
+            std::vector<float> lo_part((size_t)total);
+            if ((r = launch_nhwc_f16_to_nchw_f32(stream, (const f16 *)s.ptr + s.lo_off, tmp.as<float>(), (int)s.n, (int)s.c, (int)s.h, (int)s.w, (int)s.ld))) return r;
+            if ((r = fetch(lo_part.data()))) return r;
+            for (int64_t i = 0; i < total; ++i) out[i] += lo_part[(size_t)i];
+        }
+        break;
+    case Stage::F32_NHWC: {
+        std::vector<float> px((size_t)(s.n * plane * s.ld));
+        PB_HIP(hipMemcpy(px.data(), s.ptr, px.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t b = 0; b < s.n; ++b)
+            for (int64_t c = 0; c < s.c; ++c)
+                for (int64_t p = 0; p < plane; ++p) out[(b * s.c + c) * plane + p] = px[(size_t)((b * plane + p) * s.ld + c)];
+        break;
+    }
+    }
+    return total;
 }
 
 int EngineBase::begin_load(const pb_tensor *w, int n, const char *cu_mask_env) {

@@ -139,15 +139,7 @@ int DepthEngine::metric_head(int n) {
     };
     // the two bin buffers ping-pong, so intermediate levels are only kept (copied) for parity dumps
     auto keep_bins = [&](const std::string &name, const float *src, int hh, int ww) -> int {
-        if (!debug) return 0;
-        const size_t bytes = (size_t)n * hh * ww * 64 * 4;
-        float *&p = snaps_["zoe." + name];
-        if (p) PB_HIP(hipFree(p));
-        p = nullptr;
-        PB_HIP(hipMalloc((void **)&p, bytes));
-        PB_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyDeviceToDevice, stream));
-        stages_[name] = Stage{p, 0, last_n_, (int64_t)hh * ww, 1, 64, 64, (int64_t)hh * ww * 64};
-        return 0;
+        return debug ? snapshot(name, src, (size_t)n * hh * ww * 64 * 4, Stage::f32_rows(nullptr, n, (int64_t)hh * ww, 64)) : 0;
     };
     const int Fp = 256 * hs_;            // row stride of the DPT head's maps ([hi | lo] per pixel in split-fp16 mode; hi is read)
     // ---- bottleneck, seed bins, seed embedding (zoedepth_v1.py:170-182) ----
@@ -196,6 +188,6 @@ int DepthEngine::metric_head(int n) {
     r = launch_logbinom_depth(stream, zpt_, 8, zbins_[cb], h, w, md_, n, nh_, nw_, 0.0212f, 50.f);
     toc();
     if (r) return r;
-    stages_["metric_net"] = Stage{md_, 2, last_n_, 1, nh_, nw_, 0, 0};
+    stages_["metric_net"] = Stage::f32_rows(md_, n, nh_, nw_);
     return 0;
 }

@@ -22,11 +22,11 @@ class GmflowEngine : public RaftEngine {
     // same contract as RaftEngine::infer; `iters` is ignored (GMFlow is not iterative)
     int infer(const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward, float *flow_out, uint8_t *rgb_out,
               float *maxdisp, uint8_t *mask_out = nullptr, float alpha1 = 0.05f, float alpha2 = 0.5f) override;
-    // fp32 stages of the last call as [n, rows, cols]: "feat" [F, P, 128], "block0" / "tfeat" [2 pairs, P, 128] (token stream after the
-    // first / last transformer block), "flow_match" / "flow_prop" [pairs * dirs, P, 2] - with two scales these are the coarse scale's, and
+    // It registers its own stages only, all fp32 rows [n, rows, cols]: "feat" [F, P, 128], "block0" / "tfeat" [2 pairs, P, 128] (token stream after
+    // the first / last transformer block), "flow_match" / "flow_prop" [pairs * dirs, P, 2] - with two scales these are the coarse scale's, and
     // the fine scale adds (B = pairs * dirs, P4 = 4 P): "feat4" [F, P4, 128], "flow_up" [B, P4, 2], "warp" [B, P4, 128], "block0_4" / "tfeat4"
     // [2 B, P4, 128], "flow_match4" (enlarged flow + matched residual) / "flow_prop4" [B, P4, 2]
-    int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) override;
+
     // --inference_size of the band (reference flow_gmflow.py:76-100): the network runs on a bilinear (align_corners) resize of the scaled frame to
     // (h, w) - multiples of 16, no padding - and the flow is resized back and rescaled; (0, 0) = off (InputPadder(16), the default)
     int set_inference_size(int h, int w);
@@ -56,7 +56,6 @@ class GmflowEngine : public RaftEngine {
     int conv32(const f16 *in, int n, int H, int W, int stride, const PackedW &w, float *out);
     int blocks(const GmGeom &g, int NPs, const int8_t *region, const char *blk0);
     int fine_scale(int B, int dirs);
-    struct FStage { const float *ptr; int64_t n, rows, cols; };
 
     Layer layers_[6];
     PackedW ffq_, ffk_, up0_, up2_;
@@ -83,5 +82,4 @@ class GmflowEngine : public RaftEngine {
         *Hs_ = nullptr, *gridvt_ = nullptr, *Vtf_ = nullptr, *qs_ = nullptr, *ks_ = nullptr, *umap_ = nullptr, *u1_ = nullptr;
     int8_t *region_ = nullptr;
     unsigned *gmaxd_ = nullptr;
-    std::map<std::string, FStage> fstages_;
 };

@@ -380,7 +380,7 @@ int GmflowEngine::blocks(const GmGeom &g, int NPs, const int8_t *region, const c
         if (r) return r;
         if (debug && li == 0) {
             PB_HIP(hipMemcpyAsync(blk0_, X_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
-            fstages_[blk0] = FStage{blk0_, (int64_t)NPs * 2, g.P, 128};
+            stages_[blk0] = Stage::f32_rows(blk0_, (int64_t)NPs * 2, g.P, 128);
         }
     }
     return 0;
@@ -395,14 +395,13 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     int r = prepare_g(F, H, W, scale, dirs);
     if (r) return r;
     timer.reset();
-    fstages_.clear();
+    stages_.clear();
     const int NP = F - 1, B = NP * dirs, P = P_;
     const int64_t R = (int64_t)NP * 2 * P;
     const int split = split_w_ ? 1 : 0;
     const int es = split_w_ ? 2 : 1;
     const bool fine = scales_ == 2;
     const int corr_r = fine ? -1 : corr_r_, prop_r = fine ? -1 : prop_r_;       // two scales: the coarse scale is always global
-    last_nd_ = B;
 
     // ---- frame prep (resize, replicate pad to /16 - two scales: /32 -, ImageNet normalisation) and the backbone, once per frame ----
     tic(F_PP, 0, (double)F * H * W * 3);
@@ -420,9 +419,9 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
         if ((r = gemm16(x, es * 128, (int64_t)F * P4_, fnet_.out, c2_, 256, ACT_NONE, split_w_ ? 128 : 0))) return r;
         if ((r = conv32(c2_, F, h4_, w4_, 1, trident_, feat4_))) return r;
         if ((r = conv32(c2_, F, h4_, w4_, 2, trident_, feat_))) return r;
-        fstages_["feat4"] = FStage{feat4_, F, P4_, 128};
+        stages_["feat4"] = Stage::f32_rows(feat4_, F, P4_, 128);
     }
-    fstages_["feat"] = FStage{feat_, F, P, 128};
+    stages_["feat"] = Stage::f32_rows(feat_, F, P, 128);
 
     // ---- tokens + per-window sine positions; the six transformer blocks ----
     tic(F_ELT, 0, 0);
@@ -430,14 +429,14 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     toc();
     if (r) return r;
     if ((r = blocks(g_, NP, region_, "block0"))) return r;
-    fstages_["tfeat"] = FStage{X_, (int64_t)NP * 2, P, 128};
+    stages_["tfeat"] = Stage::f32_rows(X_, (int64_t)NP * 2, P, 128);
     if (fine) {                       // X_ and blk0_ are the fine scale's next: the coarse "tfeat" / "block0" stages exist as debug copies only
-        fstages_.erase("tfeat");
+        stages_.erase("tfeat");
         if (debug) {
             PB_HIP(hipMemcpyAsync(tfeat8_, X_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
-            fstages_["tfeat"] = FStage{tfeat8_, (int64_t)NP * 2, P, 128};
+            stages_["tfeat"] = Stage::f32_rows(tfeat8_, (int64_t)NP * 2, P, 128);
             PB_HIP(hipMemcpyAsync(blk08_, blk0_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
-            fstages_["block0"] = FStage{blk08_, (int64_t)NP * 2, P, 128};
+            stages_["block0"] = Stage::f32_rows(blk08_, (int64_t)NP * 2, P, 128);
         }
     }
 
@@ -464,7 +463,7 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
         toc();
         if (r) return r;
     }
-    fstages_["flow_match"] = FStage{flowm_, B, P, 2};
+    stages_["flow_match"] = Stage::f32_rows(flowm_, B, P, 2);
 
     // ---- flow propagation (transformer.py:316-337 global, :376-409 local window): self-similarity of the source frame's features spreads the
     // matched flow ----
@@ -501,7 +500,7 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     r = launch_gm_upsampler_in(stream, Om_, X_, flowp_, umap_, B, P, img_step);
     toc();
     if (r) return r;
-    fstages_["flow_prop"] = FStage{flowp_, B, P, 2};
+    stages_["flow_prop"] = Stage::f32_rows(flowp_, B, P, 2);
     int hu = h8_, wu = w8_, Pu = P, factor = 8;            // the grid the upsampler runs on
     const float *flow_lo = flowp_;
     if (fine) {
@@ -543,14 +542,14 @@ int GmflowEngine::fine_scale(int B, int dirs) {
     if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_warp_kernel";
     toc();
     if (r) return r;
-    fstages_["flow_up"] = FStage{flowu_, B, P4_, 2};
-    fstages_["warp"] = FStage{warp_, B, P4_, 128};
+    stages_["flow_up"] = Stage::f32_rows(flowu_, B, P4_, 2);
+    stages_["warp"] = Stage::f32_rows(warp_, B, P4_, 128);
     tic(F_ELT, 0, 0);
     r = launch_gm_tokens(stream, feat4_, pos4_, X_, Xs_, B, P4_, warp_, dirs);
     toc();
     if (r) return r;
     if ((r = blocks(g4_, B, region4_, "block0_4"))) return r;
-    fstages_["tfeat4"] = FStage{X_, (int64_t)B * 2, P4_, 128};
+    stages_["tfeat4"] = Stage::f32_rows(X_, (int64_t)B * 2, P4_, 128);
     // local matching of (source, warped target): images 2 b and 2 b + 1 of the stream; the residual adds to the enlarged flow (:145)
     const double nc = (2.0 * corr_r4_ + 1) * (2.0 * corr_r4_ + 1);
     tic(F_ATTN, 2.0 * B * (double)P4_ * nc * 128.0, 2.0 * (double)B * P4_ * 128 * 4);
@@ -562,7 +561,7 @@ int GmflowEngine::fine_scale(int B, int dirs) {
     r = launch_gm_flow_add(stream, flowu_, flowm4_, flowf_, (int64_t)B * P4_);
     toc();
     if (r) return r;
-    fstages_["flow_match4"] = FStage{flowf_, B, P4_, 2};
+    stages_["flow_match4"] = Stage::f32_rows(flowf_, B, P4_, 2);
     // the two projections run over the whole stream in one launch each, as at the coarse scale; gm_local_prop reads the source images only
     // (every other block of P4 rows, which one GEMM launch cannot address), so half of these 2 x 128 x 128 products per row - 0.5 % of the
     // six blocks' GEMM work on the same rows - go unread
@@ -578,18 +577,6 @@ int GmflowEngine::fine_scale(int B, int dirs) {
     r = launch_gm_upsampler_in(stream, Om_, X_, flowp4_, umap_, B, P4_, 2);
     toc();
     if (r) return r;
-    fstages_["flow_prop4"] = FStage{flowp4_, B, P4_, 2};
+    stages_["flow_prop4"] = Stage::f32_rows(flowp4_, B, P4_, 2);
     return 0;
-}
-
-int64_t GmflowEngine::get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) {
-    auto it = fstages_.find(name);
-    PB_CHECK(it != fstages_.end(), PB_ERR_ARG, "unknown stage '%s'", name);
-    const FStage &s = it->second;
-    const int64_t total = s.n * s.rows * s.cols;
-    PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small");
-    PB_HIP(hipStreamSynchronize(stream));
-    PB_HIP(hipMemcpy(out, s.ptr, (size_t)total * 4, hipMemcpyDeviceToHost));
-    shape[0] = s.n; shape[1] = s.rows; shape[2] = s.cols; shape[3] = 1;
-    return total;
 }

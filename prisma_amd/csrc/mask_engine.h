@@ -15,7 +15,6 @@ class MaskEngine : public EngineBase {
     int load(const pb_tensor *w, int n);
     // frames: device uint8 [n, H, W, 3] RGB.  mask_out: device uint8 [n, H, W, 3] (the band's "mask ids" image).
     int infer(const uint8_t *frames, int n, int H, int W, float confidence, const int32_t *keep, int n_keep, uint8_t *mask_out);
-    int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]);
     // --sdf of the band (reference mask_mmdet.py:64-69,150-152): with tables set (n_tab = ncap + 1 bytes each; 0 turns it off) every
     // infer() writes the clamped signed distance field of each frame's id image into its green channel before returning;
     // sdf_green applies it to id images already on the device (mask_kernels.hip sdf_*_kernel)
@@ -109,6 +108,4 @@ class MaskEngine : public EngineBase {
     size_t sdf_px_ = 0;
 
     std::vector<Instances> results_;
-    int last_n_ = 0;
-    std::map<std::string, Stage> stages_;
 };

@@ -334,7 +334,7 @@ int MaskEngine::backbone(int n) {
         }
         PB_CHECK(hi == lh_[s] && wi == lw_[s], PB_ERR_STATE, "backbone: stage %d size %dx%d != %dx%d", s, hi, wi, lh_[s], lw_[s]);
         c_[s] = x;
-        stages_["c" + std::to_string(s + 2)] = Stage{x, 1, 0, 256 << s, lh_[s], lw_[s], L(256 << s), lo(256 << s)};
+        stages_["c" + std::to_string(s + 2)] = Stage::f16_nhwc(x, n, 256 << s, lh_[s], lw_[s], L(256 << s), lo(256 << s));
     }
     return 0;
 }
@@ -354,7 +354,7 @@ int MaskEngine::neck(int n) {
     tic(F_ELT, 0, 0);
     r = launch_subsample2(stream, p_[3], p_[4], n, lh_[3], lw_[3], L(256));         // whole rows: both parts of a split map
     toc();
-    for (int i = 0; i < 5; ++i) stages_["p" + std::to_string(i + 2)] = Stage{p_[i], 1, 0, 256, lh_[i], lw_[i], L(256), lo(256)};
+    for (int i = 0; i < 5; ++i) stages_["p" + std::to_string(i + 2)] = Stage::f16_nhwc(p_[i], n, 256, lh_[i], lw_[i], L(256), lo(256));
     return r;
 }
 
@@ -385,7 +385,7 @@ int MaskEngine::head(int n) {
         PB_CHECK(h == lh_[0] && w == lw_[0], PB_ERR_STATE, "mask feature level %d ends at %dx%d", i, h, w);
     }
     if ((r = conv_gn_relu(macc_, mfc, mfc, n, lh_[0], lw_[0], 1, mfpred_, mt_[0], mf_, 256, 1))) return r;
-    stages_["mask_feats"] = Stage{mf_, 1, 0, 256, lh_[0], lw_[0], sa_ ? 768 : 256, sa_ ? 512 : 0};
+    stages_["mask_feats"] = Stage::f16_nhwc(mf_, n, 256, lh_[0], lw_[0], sa_ ? 768 : 256, sa_ ? 512 : 0);
 
     return 0;
 }
@@ -432,8 +432,8 @@ int MaskEngine::head_level(int n, int lvl) {
     r = launch_cls_points_nms(cur_, cl, cs_, n, pts_, goff_[lvl], g, Cp);
     toc();
     if (r) return r;
-    stages_["kernel_pred" + std::to_string(lvl)] = Stage{kp, 3, 0, 256, g, g, 256, 0};
-    stages_["cls_logit" + std::to_string(lvl)] = Stage{cl, 3, 0, cfg_.num_classes, g, g, Cp, 0};
+    stages_["kernel_pred" + std::to_string(lvl)] = Stage::f32_nhwc(kp, n, 256, g, g, 256);
+    stages_["cls_logit" + std::to_string(lvl)] = Stage::f32_nhwc(cl, n, cfg_.num_classes, g, g, Cp);
     return 0;
 }
 
@@ -645,12 +645,11 @@ int MaskEngine::post_chunk(int n, int first, float confidence, const std::vector
 int MaskEngine::run_chunk(const uint8_t *frames, int n, int first, float confidence, const std::vector<uint8_t> &keep_class,
                           uint8_t *mask_out) {
     int r;
-    last_n_ = n;
     tic(F_PP, 0, (double)n * ((double)pH_ * pW_ * 3 + (double)Hp_ * Wp_ * 8));
     r = launch_mask_prep(stream, frames, n, pH_, pW_, nh_, nw_, Hp_, Wp_, xt_, yt_, img_, chw_, sa_);
     toc();
     if (r) return r;
-    if (chw_) stages_["input"] = Stage{chw_, 2, 0, 3, Hp_, Wp_, 0, 0};
+    if (chw_) stages_["input"] = Stage::f32_nchw(chw_, n, 3, Hp_, Wp_);
     if ((r = backbone(n)) || (r = neck(n))) return r;
     // fork: the five levels' prediction branches only read the FPN outputs and are small (n * g^2 rows each), so they
     // run on their own streams beside the mask-feature branch on the main stream
@@ -733,43 +732,4 @@ int MaskEngine::sdf_green(uint8_t *masks, int n, int H, int W) {
                                    sdf_tab_ + sdf_ncap_ + 1, sdf_ncap_);
     toc();
     return r;
-}
-
-int64_t MaskEngine::get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) {
-    auto it = stages_.find(name);
-    PB_CHECK(it != stages_.end(), PB_ERR_ARG, "unknown stage '%s'", name);
-    const Stage &s = it->second;
-    PB_HIP(hipStreamSynchronize(stream));
-    const int n = last_n_;
-    const int64_t total = (int64_t)n * s.c * s.h * s.w;
-    shape[0] = n; shape[1] = s.c; shape[2] = s.h; shape[3] = s.w;
-    PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small");
-    if (s.kind == 2) {          // fp32 NCHW already
-        PB_HIP(hipMemcpy(out, s.ptr, total * 4, hipMemcpyDeviceToHost));
-        return total;
-    }
-    if (s.kind == 3) {          // fp32 rows [n*h*w][ld] -> NCHW on the host
-        std::vector<float> tmp((size_t)n * s.h * s.w * s.ld);
-        PB_HIP(hipMemcpy(tmp.data(), s.ptr, tmp.size() * 4, hipMemcpyDeviceToHost));
-        for (int b = 0; b < n; ++b)
-            for (int64_t c = 0; c < s.c; ++c)
-                for (int64_t p = 0; p < s.h * s.w; ++p) out[((int64_t)b * s.c + c) * s.h * s.w + p] = tmp[((int64_t)b * s.h * s.w + p) * s.ld + c];
-        return total;
-    }
-    float *tmp = nullptr;
-    PB_HIP(hipMalloc((void **)&tmp, total * 4));
-    int r = launch_nhwc_f16_to_nchw_f32(stream, (const f16 *)s.ptr, tmp, n, (int)s.c, (int)s.h, (int)s.w, (int)s.ld);
-    if (r) return r;
-    PB_HIP(hipStreamSynchronize(stream));
-    PB_HIP(hipMemcpy(out, tmp, total * 4, hipMemcpyDeviceToHost));
-    if (s.bstride) {             // split map: add the residual parts (bstride = their half offset)
-        std::vector<float> lo_part((size_t)total);
-        r = launch_nhwc_f16_to_nchw_f32(stream, (const f16 *)s.ptr + s.bstride, tmp, n, (int)s.c, (int)s.h, (int)s.w, (int)s.ld);
-        if (r) return r;
-        PB_HIP(hipStreamSynchronize(stream));
-        PB_HIP(hipMemcpy(lo_part.data(), tmp, total * 4, hipMemcpyDeviceToHost));
-        for (int64_t i = 0; i < total; ++i) out[i] += lo_part[(size_t)i];
-    }
-    PB_HIP(hipFree(tmp));
-    return total;
 }

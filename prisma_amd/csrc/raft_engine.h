@@ -10,14 +10,12 @@
 class RaftEngine : public EngineBase {
   public:
     explicit RaftEngine(int device) : EngineBase(device) {}
-    ~RaftEngine() override { for (auto &kv : snaps_) if (kv.second) hipFree(kv.second); }
     virtual int load(const pb_tensor *w, int n);
     // frames: device uint8 [F, H, W, 3].  Outputs are device pointers (any may be null):
     //   flow_out [F-1, dirs, sh, sw, 2] fp32, rgb_out [F-1, dirs, sh, sw, 3] u8, maxdisp [F-1, dirs]
     virtual int infer(const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward, float *flow_out,
                       uint8_t *rgb_out, float *maxdisp, uint8_t *mask_out = nullptr, float alpha1 = 0.05f,
                       float alpha2 = 0.5f);
-    virtual int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]);
     static void out_size(int H, int W, float scale, int *sh, int *sw);
     // --alternate_corr (raft.py:103-106): the lookup computes its window entries from the feature maps (corr_otf.hip) and prepare() carves no
     // correlation volume.  Part of the plan key: the next call re-plans.
@@ -69,11 +67,7 @@ class RaftEngine : public EngineBase {
     f16 *hx_ = nullptr, *hx2_ = nullptr, *corr_ = nullptr, *c1_ = nullptr, *corflo_ = nullptr, *fa_ = nullptr, *f1_ = nullptr,
         *zrb_ = nullptr, *fh_ = nullptr, *m0_ = nullptr;
     unsigned *maxd_ = nullptr;
-    int last_nd_ = 0;
     int upd8_ = 0;               // the update block's maps carry fp8 copies and its weights e4m3 residuals (MX segments; raft_engine.hip load)
-    std::map<std::string, Stage> stages_;
-    // debug snapshots (pb_set_profiling bit 2): copies of buffers later iterations overwrite - the initial hidden state, the first
-    // lookup's output and the flow after the first iteration, the intermediates the reference goldens hold (tests/golden/raft_*.npz)
-    std::map<std::string, void *> snaps_;
-    int snapshot(const char *name, const void *src, size_t bytes, const Stage &as);
+    // (debug snapshots - EngineBase::snapshot, pb_set_profiling bit 2 - keep what later iterations overwrite: the initial hidden state, the
+    // first lookup's output and the flow after the first iteration, the intermediates the reference goldens hold: tests/golden/raft_*.npz)
 };

@@ -439,7 +439,6 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
     timer.reset();
     stages_.clear();
     const int ND = (F - 1) * dirs;
-    last_nd_ = ND;
     const int64_t rows = (int64_t)ND * P_;
 
     // ---- frame prep + stem im2col (shared by fnet and cnet) ----
@@ -463,7 +462,7 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         if ((r = run_encoder(E, e == 0, Fe, &x))) return r;
         if ((r = dense(x, es * 128, (int64_t)Fe * P_, E.out, e == 0 ? fmap_ : ctx_, 256, ACT_NONE))) return r;
     }
-    stages_["fmap"] = Stage{fmap_, 1, 0, 256, h8_, w8_, 256, 0};
+    stages_["fmap"] = Stage::f16_nhwc(fmap_, F, 256, h8_, w8_, 256);
 
     // ---- all-pairs correlation pyramid, recurrent state ----
     // corr.py:22-27 pools the volume over the target dims; pooling is linear, so level l is the correlation of fmap1 with the
@@ -504,7 +503,7 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
             if (r) return r;
         }
 
-    if (debug && (r = snapshot("net0", h32_, (size_t)ND * P_ * 128 * 4, Stage{nullptr, 0, 0, P_, 1, 128, 128, (int64_t)P_ * 128}))) return r;
+    if (debug && (r = snapshot("net0", h32_, (size_t)ND * P_ * 128 * 4, Stage::f32_rows(nullptr, ND, P_, 128)))) return r;
 
     // ---- the context features' share of the SepConvGRU gates, once per call (hoist_, see load()) ----
     const int mot = hoist_ ? 128 : 256;                     // channel offset of the motion features inside hx_ / hx2_
@@ -535,7 +534,7 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         }
         toc();
         if (r) return r;
-        if (debug && it == 0 && (r = snapshot("corr0", corr_, (size_t)ND * P_ * Lhx * 2, Stage{nullptr, 1, ND, 324, h8_, w8_, Lhx, 0}))) return r;
+        if (debug && it == 0 && (r = snapshot("corr0", corr_, (size_t)ND * P_ * Lhx * 2, Stage::f16_nhwc(nullptr, ND, 324, h8_, w8_, Lhx)))) return r;
         // BasicMotionEncoder.  With upd8_ every map is [a16 (C) | a8 (C bytes)] per pixel (pixel stride 1.5 C halfs): the conv epilogues
         // store the fp8 copy too (o8 = its byte offset from the output row: 2 Ctot - slice offset) and the MX segments read it
         if ((r = conv(corr_, 384, Lhx, ND, h8_, w8_, 1, 1, 1, convc1_, c1_, L256, ACT_RELU, 0, nullptr, nullptr, 0, 0, upd8_ ? 512 : 0))) return r;
@@ -581,9 +580,9 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         if (timer.enabled && !r) timer.recs[open_.back()].name = fh2_.sw ? "flow_head2_kernel<true>" : "flow_head2_kernel<false>";
         toc();
         if (r) return r;
-        if (debug && it == 0 && (r = snapshot("flow_it0", flow_, (size_t)ND * P_ * 2 * 4, Stage{nullptr, 0, 0, P_, 1, 2, 2, (int64_t)P_ * 2}))) return r;
+        if (debug && it == 0 && (r = snapshot("flow_it0", flow_, (size_t)ND * P_ * 2 * 4, Stage::f32_rows(nullptr, ND, P_, 2)))) return r;
     }
-    stages_["flow_lo"] = Stage{flow_, 0, 0, P_, 1, 2, 2, (int64_t)P_ * 2};
+    stages_["flow_lo"] = Stage::f32_rows(flow_, ND, P_, 2);
 
     // ---- mask head (last iteration only) + convex upsample + unpad + encode ----
     if ((r = conv(hx_, 128, Lhx, ND, h8_, w8_, 3, 3, 1, mk0_, m0_, 256, ACT_RELU, 0, nullptr, nullptr, 0, upd8_ ? 384 : 0))) return r;
@@ -611,42 +610,4 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
     r = launch_fwdbwd_mask(stream, up, F - 1, sh_, sw_, alpha1, alpha2, mask_out);
     toc();
     return r;
-}
-
-int RaftEngine::snapshot(const char *name, const void *src, size_t bytes, const Stage &as) {
-    void *&p = snaps_[name];
-    if (p) PB_HIP(hipFree(p));
-    p = nullptr;
-    PB_HIP(hipMalloc(&p, bytes));
-    PB_HIP(hipMemcpyAsync(p, src, bytes, hipMemcpyDeviceToDevice, stream));
-    Stage st = as;
-    st.ptr = p;
-    stages_[name] = st;
-    return 0;
-}
-
-int64_t RaftEngine::get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]) {
-    auto it = stages_.find(name);
-    PB_CHECK(it != stages_.end(), PB_ERR_ARG, "unknown stage '%s'", name);
-    const Stage &s = it->second;
-    PB_HIP(hipStreamSynchronize(stream));
-    if (s.kind == 0) {
-        const int64_t total = (int64_t)last_nd_ * s.c * s.w;
-        shape[0] = last_nd_; shape[1] = s.c; shape[2] = s.w; shape[3] = 1;
-        PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small");
-        PB_HIP(hipMemcpy(out, s.ptr, total * 4, hipMemcpyDeviceToHost));
-        return total;
-    }
-    const int n = s.n > 0 ? (int)s.n : pF_;
-    const int64_t total = (int64_t)n * s.c * s.h * s.w;
-    shape[0] = n; shape[1] = s.c; shape[2] = s.h; shape[3] = s.w;
-    PB_CHECK(total <= cap, PB_ERR_ARG, "stage buffer too small");
-    float *tmp = nullptr;
-    PB_HIP(hipMalloc((void **)&tmp, total * 4));
-    int r = launch_nhwc_f16_to_nchw_f32(stream, (const f16 *)s.ptr, tmp, n, (int)s.c, (int)s.h, (int)s.w, (int)s.ld);
-    if (r) return r;
-    PB_HIP(hipStreamSynchronize(stream));
-    PB_HIP(hipMemcpy(out, tmp, total * 4, hipMemcpyDeviceToHost));
-    PB_HIP(hipFree(tmp));
-    return total;
 }

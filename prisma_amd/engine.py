@@ -215,6 +215,22 @@ class _Ctx:
         earlier infer calls so that a timed loop can be queried once after it ends"""
         check(self.lib.pb_set_profiling(self.ctx, (1 if timing else 0) | (2 if debug_stages else 0) | (4 if accumulate else 0)))
 
+    # debug stages of the last call (pb_*_get_stage): the band classes name their symbol, the default capacity in floats and whether
+    # trailing 1-dims of shape_out are dropped
+    _stage_sym: Optional[str] = None
+    _stage_cap = 1 << 26
+    _stage_squeeze = True
+
+    def stage(self, name: str, cap: Optional[int] = None) -> np.ndarray:
+        cap = self._stage_cap if cap is None else cap
+        out = np.empty(cap, np.float32)
+        shape = (C.c_int64 * 4)()
+        n = check(getattr(self.lib, self._stage_sym)(self.ctx, name.encode(), _ptr(out), cap, shape))
+        dims = [int(s) for s in shape]
+        while self._stage_squeeze and len(dims) > 1 and dims[-1] == 1:
+            dims.pop()
+        return out[:n].reshape(dims).copy()
+
     def kernel_stats(self) -> List[dict]:
         arr = (_lib.pb_kernel_stat * 64)()
         n = check(self.lib.pb_get_kernel_stats(self.ctx, arr, 64))
@@ -942,6 +958,7 @@ class DepthAnything(_Ctx):
 
     weights: reference state_dict naming -> float32 ndarray (bands/d_anything/dpt.py:139-171).
     """
+    _stage_sym = "pb_depth_get_stage"
 
     def __init__(self, weights: Dict[str, np.ndarray], cfg: DepthCfg | str = "vitl", device: int = 0,
                  max_batch: int = 1, metric: bool = False, precision: Optional[int] = None):
@@ -1014,15 +1031,6 @@ class DepthAnything(_Ctx):
         check(self.lib.pb_depth_infer_batch_dev(self.ctx, v(frames_ptr), n, H, W, v(depth_ptr), v(rgb_ptr),
                                                 v(min_ptr), v(max_ptr), int(flip)))
 
-    def stage(self, name: str, cap: int = 1 << 26) -> np.ndarray:
-        out = np.empty(cap, np.float32)
-        shape = (C.c_int64 * 4)()
-        n = check(self.lib.pb_depth_get_stage(self.ctx, name.encode(), _ptr(out), cap, shape))
-        dims = [int(s) for s in shape]
-        while len(dims) > 1 and dims[-1] == 1:
-            dims.pop()
-        return out[:n].reshape(dims).copy()
-
 
 def flow_out_size(H: int, W: int, scale: float) -> Tuple[int, int]:
     sh, sw = C.c_int(), C.c_int()
@@ -1035,6 +1043,7 @@ class FlowRaft(_Ctx):
 
     weights: reference checkpoint naming without the `module.` prefix (fnet.*, cnet.*, update_block.*).
     """
+    _stage_sym = "pb_flow_get_stage"
 
     BAND = b"flow_raft"
 
@@ -1131,15 +1140,6 @@ class FlowRaft(_Ctx):
         """bytes of the arena the current plan (the last call's size, pair count and mode) committed; 0 before the first call"""
         return int(check(self.lib.pb_flow_arena_bytes(self.ctx)))
 
-    def stage(self, name: str, cap: int = 1 << 26) -> np.ndarray:
-        out = np.empty(cap, np.float32)
-        shape = (C.c_int64 * 4)()
-        n = check(self.lib.pb_flow_get_stage(self.ctx, name.encode(), _ptr(out), cap, shape))
-        dims = [int(s) for s in shape]
-        while len(dims) > 1 and dims[-1] == 1:
-            dims.pop()
-        return out[:n].reshape(dims).copy()
-
 
 class FlowGMFlow(FlowRaft):
     """GMFlow optical-flow band on one GPU (bands/flow_gmflow.py:42-118 init_model / infer; the model at the band's default flags, or - when
@@ -1213,6 +1213,9 @@ class MaskMMDet(_Ctx):
 
     weights: mmdet state_dict naming (backbone.*, neck.*, mask_head.*) -> float32 ndarray.
     """
+    _stage_sym = "pb_mask_get_stage"
+    _stage_cap = 1 << 27
+    _stage_squeeze = False      # always 4-D
 
     def __init__(self, weights: Dict[str, np.ndarray], cfg: MaskCfg | str = "r101", device: int = 0, max_batch: int = 4,
                  precision: Optional[int] = None):
@@ -1282,9 +1285,3 @@ class MaskMMDet(_Ctx):
             masks = np.empty((cap, H, W), np.uint8)
         k = check(self.lib.pb_mask_get_instances(self.ctx, frame, cap, _ptr(sc), _ptr(lb), _ptr(masks), C.byref(cand)))
         return sc[:k].copy(), lb[:k].copy(), (masks[:k].view(np.bool_) if with_masks else None), cand.value
-
-    def stage(self, name: str, cap: int = 1 << 27) -> np.ndarray:
-        out = np.empty(cap, np.float32)
-        shape = (C.c_int64 * 4)()
-        n = check(self.lib.pb_mask_get_stage(self.ctx, name.encode(), _ptr(out), cap, shape))
-        return out[:n].reshape([int(s) for s in shape]).copy()
