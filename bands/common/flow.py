@@ -7,7 +7,7 @@ import numpy as np
 from prisma_amd import engine
 
 from .io import FrameReader, VideoWriter, write_flo, write_flow_png
-from .loop import run_sharded
+from .loop import Stream, run_sharded, stream_enabled
 
 
 def _mask_rgb(mask):
@@ -15,7 +15,7 @@ def _mask_rgb(mask):
     return np.repeat((mask.astype(np.uint8) * 255)[..., None], 3, axis=-1)
 
 
-def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterations):
+def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterations, stream_min_chunks=0):
     """Pairs (i, i+1) shard by rank in contiguous blocks with a one-frame halo.  Every chunk is written as soon
     as it is done: rank 0 feeds its own chunks to the VideoWriters from a sink thread (the next chunk is already on the
     GPU) and then muxes the other ranks' chunks in frame order through shard.Relay; only the per-pair max displacements
@@ -45,8 +45,30 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
             flow, rgb, mx, mask = model.infer_sequence_masks(frames, scale=args.scale, iters=iterations, want_flow=want_flow, want_rgb=True)
         else:
             flow, rgb, mx = model.infer_sequence(frames, scale=args.scale, iters=iterations, backward=both, want_flow=want_flow, want_rgb=True)
-        c = {k: (rgb if k.startswith("rgb") else mask)[:, "fb".index(k[-1])] for k in files}
-        return c, (flow, mask), mx[:, :1]
+        return by_file(rgb, mask), (flow, mask), mx[:, :1]
+
+    def by_file(rgb, mask):          # a chunk's video arrays: the key's array (rgb / mask) and direction
+        return {k: (rgb if k.startswith("rgb") else mask)[:, "fb".index(k[-1])] for k in files}
+
+    # the streamed loop (common/loop.py): the same calls as submit_sequence(_masks) / wait on the loop's page-locked rings - one array per result
+    # asked for, [directions, ...] per pair
+    nd = 2 if both else 1
+    results = {"rgb": ((nd, sh, sw, 3), np.uint8), "mx": ((nd,), np.float32)}
+    if want_flow:
+        results["flow"] = ((nd, sh, sw, 2), np.float32)
+    if want_mask:
+        results["mask"] = ((2, sh, sw), np.uint8)
+
+    def submit(_s, frames, res):
+        if want_mask:
+            model.submit_sequence_masks(frames, scale=args.scale, iters=iterations, out_flow=res.get("flow"), out_rgb=res["rgb"], out_max=res["mx"],
+                                        out_mask=res["mask"])
+        else:
+            model.submit_sequence(frames, scale=args.scale, iters=iterations, backward=both, out_flow=res.get("flow"), out_rgb=res["rgb"], out_max=res["mx"])
+
+    def collect(_s, res):
+        mask = res["mask"].view(np.bool_) if want_mask else None
+        return by_file(res["rgb"], mask), (res.get("flow"), mask), res["mx"][:, :1]
 
     def write_chunk(_s, c):          # rank 0 only: one chunk of encoded pairs into every open video, in order
         for j in range(len(c["rgb_f"])):
@@ -65,8 +87,9 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
                 if args.backwards:
                     write_flow_png(os.path.join(args.subpath_mask + "_bwd", "%04d.png" % (s + j)), flow[j, 1], mask[j, 1])
 
+    stream = Stream(model, (src[0].shape, np.uint8), results, submit, collect) if stream_enabled(stream_min_chunks, -(-(last - first) // chunk)) else None
     mx_all = run_sharded(rk, src, n - 1, chunk, 1, args.output, ((n - 1) - (last - first)) * sh * sw * 3 * len(files),
-                         step, write_chunk, dump if want_flow else None, n_scalars=1, ctx=model)
+                         step, write_chunk, dump if want_flow else None, n_scalars=1, ctx=model, stream=stream)
     if not rk.main:
         return
     # last frame: zero flow -> 0/0 -> NaN -> uint8 0, max displacement 0.0, all-False masks (reference :116-131)

@@ -102,7 +102,7 @@ class VideoWriter:
 
     def write(self, rgb):
         if self._frames is not None:
-            self._frames.append(np.ascontiguousarray(rgb))
+            self._frames.append(np.array(rgb))      # a copy, always: the caller's frame may be a view of a ring slot that a later chunk overwrites
             return
         import av
         frame = av.VideoFrame.from_ndarray(np.ascontiguousarray(rgb, np.uint8), format="rgb24")

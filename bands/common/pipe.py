@@ -61,6 +61,11 @@ class AsyncSink:
                 except BaseException as e:      # noqa: BLE001 - re-raised by submit / close
                     self._err = e
 
+    @property
+    def failed(self):
+        """a job has raised: the next submit() or close() re-raises it (a caller that blocks elsewhere polls this)"""
+        return self._err is not None
+
     def submit(self, fn, *args):
         if self._err is not None:
             self.close()

@@ -20,12 +20,13 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
 from common.io import FrameReader, VideoWriter, create_folder, open_rgb, write_ply, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.cli import begin, end, synthetic_or_exit  # noqa: E402
-from common.loop import run_sharded  # noqa: E402
+from common.loop import Stream, run_sharded, stream_enabled  # noqa: E402
 from common.meta import is_video  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
 BAND = "depth_anything"
 BATCH = int(os.environ.get("PRISMA_BATCH", "32"))
+STREAM_MIN_CHUNKS = 16      # PRISMA_STREAM unset: the streamed loop for shards of at least this many chunks (EXPERIMENTS.md 6.19: slower on 6, faster on 16)
 
 model = None
 data = None
@@ -152,18 +153,30 @@ def process_video(a):
         depth, rgb, mn, mx = model.infer_batch(frames, want_depth=want_depth, want_rgb=True, flip=_flip())
         return {"rgb": rgb}, depth, np.stack([mn, mx], 1)
 
+    # the streamed loop (common/loop.py): the same call as submit_batch / wait on the loop's page-locked rings - one array per result asked for
+    results = {"rgb": ((h, w, 3), np.uint8), "mn": ((), np.float32), "mx": ((), np.float32)}
+    if want_depth:
+        results["depth"] = ((h, w), np.float32)
+
+    def submit(_s, frames, res):
+        model.submit_batch(frames, out_rgb=res["rgb"], out_depth=res.get("depth"), out_min=res["mn"], out_max=res["mx"], flip=_flip())
+
+    def collect(_s, res):
+        return {"rgb": res["rgb"]}, res.get("depth"), np.stack([res["mn"], res["mx"]], 1)
+
     def write_chunk(_s, c):          # rank 0 only: the video frames, chunk after chunk in order
         for f in c["rgb"]:
             out.write(f)
 
-    def dump(s, depth):              # sink thread: .npy / .png dumps (reference :215-225)
+    def dump(s, depth):              # sink thread: .npy / .png dumps (reference :215-225); nothing of `depth` is kept past the return
         for j in range(len(depth)):
             if a.npy:
                 np.save(os.path.join(a.subpath, "{:05d}.npy".format(s + j)), depth[j])
             write_depth_png(os.path.join(a.subpath, "{:05d}.png".format(s + j)), depth[j])
 
+    stream = Stream(model, (src[0].shape, np.uint8), results, submit, collect) if stream_enabled(STREAM_MIN_CHUNKS, -(-(last - first) // BATCH)) else None
     mm = run_sharded(rk, src, n, BATCH, 0, a.output, (n - (last - first)) * h * w * 3, step, write_chunk,
-                     dump if a.subpath else None, n_scalars=2, ctx=model)
+                     dump if a.subpath else None, n_scalars=2, ctx=model, stream=stream)
     if not rk.main:
         return
     lo, hi = [float(v) for v in mm[:, 0]], [float(v) for v in mm[:, 1]]

@@ -38,6 +38,7 @@ from prisma_amd import engine, shard, synth  # noqa: E402
 BAND = "flow_gmflow"
 MODEL = "models/gmflow_sintel-0c07dcb3.pth"      # reference :35
 CHUNK = int(os.environ.get("PRISMA_BATCH", "16"))
+STREAM_MIN_CHUNKS = 16      # PRISMA_STREAM unset: the streamed loop for shards of at least this many chunks (EXPERIMENTS.md 6.19: slower on 6, faster on 16)
 # the model flags of reference :239-249 and the only values the engine implements (the band's defaults); corr_radius_list and
 # prop_radius_list are also taken as one radius each (RADII: the largest the engine's kernels are built for)
 ARCH = {"feature_channels": 128, "num_scales": 1, "upsample_factor": 8, "num_head": 1, "attention_type": "swin", "ffn_dim_expansion": 4,
@@ -146,7 +147,7 @@ def process_video(args):
     rk = ranks or shard.Ranks()
     if model is None:
         init_model(args, device=rk.device)
-    flow.process_video(args, BAND, model, data, rk, CHUNK, subpath_needs_both=False, iterations=1)
+    flow.process_video(args, BAND, model, data, rk, CHUNK, subpath_needs_both=False, iterations=1, stream_min_chunks=STREAM_MIN_CHUNKS)
 
 
 def main(argv=None):

@@ -26,6 +26,7 @@ BAND = "flow_raft"
 MODEL = "models/raft-sintel.pth"            # reference :31
 ITERATIONS = 20
 CHUNK = int(os.environ.get("PRISMA_BATCH", "16"))
+STREAM_MIN_CHUNKS = 16      # PRISMA_STREAM unset: the streamed loop for shards of at least this many chunks (EXPERIMENTS.md 6.19: slower on 6, faster on 16)
 
 model = None
 data = None
@@ -81,7 +82,7 @@ def process_video(args):
     rk = ranks or shard.Ranks()
     if model is None:
         init_model(args, device=rk.device)
-    flow.process_video(args, BAND, model, data, rk, CHUNK, subpath_needs_both=True, iterations=args.iterations)
+    flow.process_video(args, BAND, model, data, rk, CHUNK, subpath_needs_both=True, iterations=args.iterations, stream_min_chunks=STREAM_MIN_CHUNKS)
 
 
 def main(argv=None):

@@ -21,7 +21,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
 from common.io import FrameReader, VideoWriter, create_folder, open_rgb, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.cli import begin, end, synthetic_or_exit  # noqa: E402
-from common.loop import run_sharded  # noqa: E402
+from common.loop import Stream, run_sharded, stream_enabled  # noqa: E402
 from common.meta import is_video  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
@@ -30,6 +30,7 @@ MODEL = "models/solov2_r101_fpn_3x_coco_20220511_095119-c559a076.pth"
 CLASSES = list(synth.BAND_CLASSES)
 CONFIDENCE_THRESHOLD = 0.5
 BATCH = int(os.environ.get("PRISMA_BATCH", "32"))
+STREAM_MIN_CHUNKS = 16      # PRISMA_STREAM unset: the streamed loop for shards of at least this many chunks (EXPERIMENTS.md 6.19: slower on 6, faster on 16)
 
 model = None
 data = None
@@ -97,6 +98,15 @@ def process_video(args):
         masks = model.infer_batch(frames, args.confidence, keep_ids())
         return {"mask": masks}, masks, None
 
+    # the streamed loop (common/loop.py).  There is no asynchronous mask call (include/prisma_bands.h: SOLOv2 synchronises with the host many
+    # times per call, its candidate counts depend on the data): "submit" is the blocking call, which pipelines its own chunks and addresses the
+    # page-locked ring slots directly - no staging copy in, none out - and "wait" has nothing left to wait for
+    def submit(_s, frames, res):
+        model.infer_batch(frames, args.confidence, keep_ids(), out=res["mask"])
+
+    def collect(_s, res):
+        return {"mask": res["mask"]}, res["mask"], None
+
     def write_chunk(_s, c):          # rank 0 only: the video frames, chunk after chunk in order
         for f in c["mask"]:
             out.write(f)
@@ -105,7 +115,9 @@ def process_video(args):
         for j in range(len(masks)):
             write_rgb(os.path.join(args.subpath, "{:05d}.png".format(s + j)), _colmap(masks[j]))
 
-    run_sharded(rk, src, n, BATCH, 0, args.output, (n - (last - first)) * h * w * 3, step, write_chunk, dump if args.subpath else None)
+    stream = Stream(model, (src[0].shape, np.uint8), {"mask": ((h, w, 3), np.uint8)}, submit, collect, wait=lambda: None) if stream_enabled(STREAM_MIN_CHUNKS, -(-(last - first) // BATCH)) else None
+    run_sharded(rk, src, n, BATCH, 0, args.output, (n - (last - first)) * h * w * 3, step, write_chunk, dump if args.subpath else None,
+                stream=stream)
     if not rk.main:
         return
     out.close()

@@ -9,7 +9,8 @@
  * Conventions
  *   - every function returns 0 on success or a negative pb_status; pb_last_error() holds the
  *     message of the last failure on the calling thread.
- *   - the caller owns every host buffer; the library owns device memory, streams and events
+ *   - the caller owns every host buffer (pb_host_alloc blocks excepted: page-locked memory the ctx
+ *     lends and frees); the library owns device memory, streams and events
  *     inside pb_ctx.  One pb_ctx per GPU per process; a ctx is not re-entrant.
  *   - no CPU fallback: without a usable HIP device pb_create fails (PB_ERR_DEVICE).
  */
@@ -149,6 +150,22 @@ int pb_depth_submit_batch(pb_ctx *ctx, const uint8_t *frames, int n, int H, int 
 int pb_flow_submit_sequence(pb_ctx *ctx, const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward,
                             float *flow_out, uint8_t *rgb_out, float *maxdisp_out);
 int pb_wait(pb_ctx *ctx);
+/* pb_flow_submit_sequence_masks: the asynchronous form of pb_flow_infer_sequence_masks (below) - its arguments and argument checks, the
+ * rules of the two submit calls above (mask_out page-locked like every other buffer), on flow_raft and flow_gmflow contexts alike.
+ * There is no submit form of pb_mask_infer_batch, on purpose: the SOLOv2 engine synchronises with the host many times per call (its
+ * candidate counts depend on the data), so an "asynchronous" call would block its caller anyway; the blocking call already pipelines its
+ * own chunks and already addresses page-locked caller arrays directly.  The mask band's loop therefore uses page-locked rings with the
+ * blocking call (bands/common/loop.py). */
+int pb_flow_submit_sequence_masks(pb_ctx *ctx, const uint8_t *frames, int F, int H, int W, float scale, int iters,
+                                  float alpha1, float alpha2, float *flow_out, uint8_t *rgb_out, float *maxdisp_out,
+                                  uint8_t *mask_out);
+/* Page-locked host memory owned by the ctx, for callers that stream (the band loops' input and output rings: a Python host gets
+ * what torch's pin_memory would give it without importing torch).  pb_host_alloc: *ptr = a block of `bytes` bytes every submit call
+ * accepts and every blocking host-pointer call addresses without staging (PB_ERR_MEMORY when the allocation fails).  pb_host_free: the
+ * caller has waited for every submission that reads or writes the block; a pointer this ctx does not own is PB_ERR_ARG and nothing is
+ * freed.  pb_destroy waits for the outstanding submissions and then frees the blocks that are left: they die with the ctx. */
+int pb_host_alloc(pb_ctx *ctx, void **ptr, size_t bytes);
+int pb_host_free(pb_ctx *ctx, void *ptr);
 /* Several bands at once: contexts share nothing, every *_dev entry point returns after the enqueue, so a caller enqueues on two or three
  * contexts and then pb_sync()s each (prisma_amd.engine.run_concurrently; replaces the reference's strictly sequential band order,
  * process.py:205-290, where the bands of one video are independent).  Results are those of running the bands one after the other. */

@@ -69,6 +69,10 @@ SYMBOLS = {
     "pb_depth_submit_batch": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, _P, C.c_int]),
     "pb_flow_submit_sequence": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_int, _P, _P, _P]),
     "pb_wait": (C.c_int, [_P]),
+    "pb_flow_submit_sequence_masks": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float,
+                                                _P, _P, _P, _P]),
+    "pb_host_alloc": (C.c_int, [_P, C.POINTER(_P), C.c_size_t]),
+    "pb_host_free": (C.c_int, [_P, _P]),
     "pb_comm_unique_id": (C.c_int, [_P]),
     "pb_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
     "pb_gather_scalars": (C.c_int, [_P, _P, C.c_int, _P]),

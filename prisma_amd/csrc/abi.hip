@@ -337,6 +337,8 @@ void pb_destroy(pb_ctx *c) {
     for (hipEvent_t e : c->pending) { hipEventSynchronize(e); hipEventDestroy(e); }
     c->pipe.release();
     c->mpipe.release();
+    // pb_host_alloc blocks: the submissions that wrote into them were waited for above and the copy streams are drained and gone
+    for (void *p : c->host_blocks) hipHostFree(p);
     if (c->depth) delete c->depth;
     if (c->raft) delete c->raft;
     if (c->mask) delete c->mask;
@@ -511,6 +513,13 @@ int pb_flow_infer_sequence_masks(pb_ctx *c, const uint8_t *frames, int F, int H,
     PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
     PB_CHECK(frames && F >= 2 && H > 0 && W > 0 && mask_out, PB_ERR_ARG, "flow masks: bad arguments");
     return flow_host_pipeline(c, frames, F, H, W, scale, iters, 1, flow_out, rgb_out, maxdisp_out, mask_out, alpha1, alpha2);
+}
+
+int pb_flow_submit_sequence_masks(pb_ctx *c, const uint8_t *frames, int F, int H, int W, float scale, int iters, float alpha1,
+                                  float alpha2, float *flow_out, uint8_t *rgb_out, float *maxdisp_out, uint8_t *mask_out) {
+    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
+    PB_CHECK(frames && F >= 2 && H > 0 && W > 0 && mask_out, PB_ERR_ARG, "flow masks submit: bad arguments");
+    return flow_host_pipeline(c, frames, F, H, W, scale, iters, 1, flow_out, rgb_out, maxdisp_out, mask_out, alpha1, alpha2, true);
 }
 
 int pb_flow_fwdbwd_mask(pb_ctx *c, const float *flows, int n, int sh, int sw, float alpha1, float alpha2, uint8_t *mask_out) {
@@ -694,6 +703,31 @@ int pb_dev_free(pb_ctx *c, void *ptr) {
     PB_CHECK(c, PB_ERR_ARG, "null ctx");
     PB_HIP(hipSetDevice(c->device));
     PB_HIP(hipFree(ptr));
+    return 0;
+}
+int pb_host_alloc(pb_ctx *c, void **ptr, size_t bytes) {
+    PB_CHECK(c && ptr, PB_ERR_ARG, "host_alloc: bad arguments");
+    *ptr = nullptr;
+    PB_HIP(hipSetDevice(c->device));
+    void *p = nullptr;
+    hipError_t e = hipHostMalloc(&p, bytes ? bytes : 1, hipHostMallocDefault);
+    if (e != hipSuccess) (void)hipGetLastError();
+    PB_CHECK(e == hipSuccess && p, PB_ERR_MEMORY, "hipHostMalloc(%zu): %s", bytes, hipGetErrorString(e));
+    std::lock_guard<std::mutex> lock(c->host_mu);
+    c->host_blocks.push_back(p);
+    *ptr = p;
+    return 0;
+}
+int pb_host_free(pb_ctx *c, void *ptr) {
+    PB_CHECK(c, PB_ERR_ARG, "null ctx");
+    {
+        std::lock_guard<std::mutex> lock(c->host_mu);
+        auto it = std::find(c->host_blocks.begin(), c->host_blocks.end(), ptr);
+        PB_CHECK(ptr && it != c->host_blocks.end(), PB_ERR_ARG, "host_free: %p is not a block pb_host_alloc gave this ctx", ptr);
+        c->host_blocks.erase(it);
+    }
+    PB_HIP(hipSetDevice(c->device));
+    PB_HIP(hipHostFree(ptr));
     return 0;
 }
 int pb_memcpy_h2d(pb_ctx *c, void *dst, const void *src, size_t bytes) {

@@ -134,6 +134,8 @@ struct pb_ctx {
     ChunkPipe pipe;                 // depth / flow bands (a ctx has one band)
     MaskPipe mpipe;
     std::deque<hipEvent_t> pending;     // completion events of pb_*_submit_* calls not yet waited for (pb_wait pops the oldest)
+    std::vector<void *> host_blocks;    // pb_host_alloc: page-locked blocks the ctx owns (the band loops' rings); pb_destroy frees what pb_host_free did not
+    std::mutex host_mu;
     // pb_comm_init: RCCL communicator of the ranks (one process per GPU) for pb_gather_scalars
     void *comm = nullptr;
     int comm_rank = 0, comm_world = 0;

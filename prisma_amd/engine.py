@@ -89,9 +89,18 @@ class _Ctx:
     def __init__(self):
         self.lib = _lib.load()
         self.ctx = C.c_void_p()
+        self._host = {}                 # host_empty(): address -> (weak reference to the array, bytes)
 
     def close(self):
+        """pb_destroy: waits for the submissions still outstanding, then frees everything the context owns - the host_empty() arrays
+        included.  They die with the context: an array still referenced afterwards points at freed memory, so it is made read-only
+        here and must not be touched again (host_free() the arrays, or drop them, before close() where that matters)."""
         if self.ctx:
+            for ref, _ in getattr(self, "_host", {}).values():
+                arr = ref()
+                if arr is not None:
+                    arr.flags.writeable = False
+            self._host = {}
             self.lib.pb_destroy(self.ctx)
             self.ctx = C.c_void_p()
 
@@ -136,6 +145,32 @@ class _Ctx:
     def d2h(self, arr: np.ndarray, ptr: int):
         assert arr.flags.c_contiguous
         check(self.lib.pb_memcpy_d2h(self.ctx, _ptr(arr), C.c_void_p(ptr), arr.nbytes))
+
+    # page-locked host memory owned by the context (pb_host_alloc): what submit_* demands and the blocking calls address without staging
+    def host_empty(self, shape, dtype) -> np.ndarray:
+        """An uninitialised C-contiguous array of `shape` / `dtype` over a page-locked block of the context (the band loops' rings; no
+        torch pin_memory needed).  host_free(arr) releases it; close() releases whatever is left - the array does not own its memory and
+        dies with the context (see close)."""
+        import weakref
+        shape = (int(shape),) if np.isscalar(shape) else tuple(int(s) for s in shape)
+        dt = np.dtype(dtype)
+        nbytes = int(np.prod(shape, dtype=np.int64)) * dt.itemsize
+        p = C.c_void_p()
+        check(self.lib.pb_host_alloc(self.ctx, C.byref(p), nbytes))
+        arr = np.frombuffer((C.c_ubyte * max(nbytes, 1)).from_address(p.value), np.uint8, nbytes).view(dt).reshape(shape)
+        self._host[p.value] = (weakref.ref(arr), nbytes)
+        return arr
+
+    def host_free(self, arr: np.ndarray):
+        """Releases a host_empty() array (pb_host_free; anything else is refused with PB_ERR_ARG).  No submission may still use it, and
+        the array - with every view of it - must not be touched afterwards."""
+        ptr = arr.ctypes.data
+        check(self.lib.pb_host_free(self.ctx, C.c_void_p(ptr)))
+        getattr(self, "_host", {}).pop(ptr, None)
+
+    def host_bytes(self) -> int:
+        """bytes of the host_empty() blocks the context holds"""
+        return sum(n for _, n in getattr(self, "_host", {}).values())
 
     def sync(self):
         check(self.lib.pb_sync(self.ctx))
@@ -1006,7 +1041,7 @@ class DepthAnything(_Ctx):
     def submit_batch(self, frames: np.ndarray, out_rgb: Optional[np.ndarray] = None, out_depth: Optional[np.ndarray] = None,
                      out_min: Optional[np.ndarray] = None, out_max: Optional[np.ndarray] = None, flip: bool = True):
         """Asynchronous infer_batch (pb_depth_submit_batch): every array - `frames` and each given output - must be a C-contiguous view of
-        PAGE-LOCKED memory (torch `pin_memory()` + `.numpy()`); returns after the enqueue, `wait()` returns (depth, rgb, min, max) once they are
+        PAGE-LOCKED memory (`host_empty()`, or torch `pin_memory()` + `.numpy()`); returns after the enqueue, `wait()` returns (depth, rgb, min, max) once they are
         filled.  Up to two submissions may be in flight per context: the second one's uploads run under the first one's kernels."""
         n, H, W, ch = frames.shape
         assert ch == 3 and frames.dtype == np.uint8 and frames.flags.c_contiguous
@@ -1115,6 +1150,22 @@ class FlowRaft(_Ctx):
                                                     C.c_float(alpha_1), C.c_float(alpha_2), _ptr(flow), _ptr(rgb), _ptr(mx),
                                                     _ptr(mask)))
         return flow, rgb, mx, mask.view(np.bool_)
+
+    def submit_sequence_masks(self, frames: np.ndarray, scale: float = 0.75, iters: int = 12, alpha_1: float = 0.05, alpha_2: float = 0.5,
+                              out_flow: Optional[np.ndarray] = None, out_rgb: Optional[np.ndarray] = None, out_max: Optional[np.ndarray] = None,
+                              out_mask: Optional[np.ndarray] = None):
+        """Asynchronous infer_sequence_masks (pb_flow_submit_sequence_masks): page-locked arrays only (see DepthAnything.submit_batch;
+        host_empty() gives them); out_mask (uint8 [F-1, 2, sh, sw]) is required.  `wait()` returns (flow, rgb, maxdisp, mask.view(bool))."""
+        F, H, W, ch = frames.shape
+        assert ch == 3 and F >= 2 and frames.dtype == np.uint8 and frames.flags.c_contiguous
+        assert out_mask is not None, "submit_sequence_masks: out_mask is required"
+        sh, sw = flow_out_size(H, W, scale)
+        for a, dt, shp in ((out_flow, np.float32, (F - 1, 2, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, 2, sh, sw, 3)), (out_max, np.float32, (F - 1, 2)),
+                           (out_mask, np.uint8, (F - 1, 2, sh, sw))):
+            assert a is None or (a.dtype == dt and a.shape == shp and a.flags.c_contiguous)
+        check(self.lib.pb_flow_submit_sequence_masks(self.ctx, _ptr(frames), F, H, W, C.c_float(scale), iters, C.c_float(alpha_1), C.c_float(alpha_2),
+                                                     _ptr(out_flow), _ptr(out_rgb), _ptr(out_max), _ptr(out_mask)))
+        self._hold((out_flow, out_rgb, out_max, out_mask.view(np.bool_)), frames, out_flow, out_rgb, out_max, out_mask)
 
     def fwdbwd_mask(self, flows: np.ndarray, alpha_1: float = 0.05, alpha_2: float = 0.5) -> np.ndarray:
         """flows f32 [n,2,sh,sw,2] (forward, backward) -> bool [n,2,sh,sw] (bands/common/flow.py:28-40)."""
