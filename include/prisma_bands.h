@@ -439,6 +439,48 @@ int pb_op_conv2d_split(pb_ctx *ctx, const float *x, const float *w, const float 
                        int pre_relu, int rows_out, void *out, int *info, char *kernel, int kernel_cap);
 int pb_op_dense_split(pb_ctx *ctx, const float *A, const float *w, const float *bias, const float *skip, int M, int K, int N, int layout,
                       int sa, int tile, int split_out, int act, int rows_out, void *out, int *info, char *kernel, int kernel_cap);
+/* The GEMM's fused ViT epilogues one by one, launched as DepthEngine::vit launches them (tests/test_gpu_epilogue_ops.py).  layout: 0 fp16, 1
+ * split16 (weights hi + lo fp16, activations [hi]), 3 mx2 (weights [w_hi | w_lo8], token rows [a16 | a8]); tile: a gemm.h TILE_* (1: 128 x 128, 2:
+ * the 256 x 256 ping-pong kernel); info[8] = {pw, a8 / lo8 pa, mx2, sw, packed K, nk16, mx3, split-K factor of the launch}; kernel = the symbol that ran.  Output buffers are preset to
+ * 0xFF bytes and carry guard_rows untouched rows behind the last one; pb_set_option "op_splitk" lends a split-K workspace.
+ * resid: X [M, N] (fp32, copied into rows of ldr floats) += A [M, K] (gamma . w [N, K])^T + gamma . bias, LayerScale folded on the host as
+ *   DepthEngine::load folds it and also passed as GemmArgs::gamma; out (M + guard) x ldr floats.
+ * qkv: A [B ntp, D] x w [3 D, D]^T + bias -> q (x PB_QSCALE) and k, (B D/64 ntp + guard) x 64 halfs as [b, head, t, 64]; vt (B D/64 64 + guard) x ntp
+ *   halfs as [b, head, 64, ntp].
+ * patch: A [B P, 588] x w [D, 588]^T + bias + pos [1 + P, D] rows 1 .. P -> rows b ntp + 1 + patch of out, (B ntp + guard) x D floats.
+ * conv_head: the DPT head's fused output_conv2 (EPI_HEAD): x NHWC [B, H, W, C], w [32, C, 3, 3], bias [32]; out[m] = relu(sum_n relu(conv + bias)[n]
+ *   w2[n] + b2), (B H W + guard) floats.  Here layout 1 is split16 with a split map [hi | lo] and 2 is mx3 ([hi | hi8 | lo8]).
+ * fc1: gelu(A [M, K] w [N, K]^T + bias) as the split ViT's fc1 runs (EPI_STD on the MX build with an all-fp16 K axis, nk16 = K / 64); out: (M + guard)
+ *   rows of [fp16 (N) | e4m3 (N bytes) of the stored fp16 x 2^(a8 pa)].
+ * pixshuf: the DPT head's transposed convolutions (kernel == stride == s) as a 1 x 1 GEMM with the pixel-shuffle epilogue (EPI_PIXSHUF): x [B h w, C],
+ *   wt [C, C, s, s] (ConvTranspose2d), bias [C]; out: (B h s w s + guard) pixels of ldo = (layout ? 2 : 1) x (C padded to 64) halfs, layouts as
+ *   conv_head's for the input map and the output alike. */
+int pb_op_gemm_resid(pb_ctx *ctx, const float *A, const float *w, const float *bias, const float *gamma, const float *X, int M, int N, int K, int ldr,
+                     int layout, int tile, int guard_rows, float *out, int *info, char *kernel, int kernel_cap);
+int pb_op_gemm_qkv(pb_ctx *ctx, const float *A, const float *w, const float *bias, int B, int ntp, int D, int layout, int tile, int guard_rows, void *q,
+                   void *k, void *vt, int *info, char *kernel, int kernel_cap);
+int pb_op_gemm_patch(pb_ctx *ctx, const float *A, const float *w, const float *bias, const float *pos, int B, int P, int ntp, int D, int layout,
+                     int guard_rows, float *out, int *info, char *kernel, int kernel_cap);
+/* SepConvGRU's fused epilogues (ACT_GRU_ZR / ACT_GRU_Q) through EngineBase::conv with the ConvFuse RaftEngine::infer builds.  x [n, H, W, 384]: the
+ * GRU input map, of which the kh x kw convolution reads the first gc (256 with the hoisted terms add1 / add2, else 384) channels; layout 0 fp16 or 3
+ * mx2 (map [a16 (384) | a8 (384 bytes)], row stride 576 halfs, fp8 twins stored at byte 768).  zr: w [256, gc, kh, kw]; z = sigmoid -> zrb columns
+ * [0, 128) ((rows + guard) x 256 halfs, the r half is not written), r h32 -> rh ((rows + guard) x 384 / 576 halfs).  q: w [128, gc, kh, kw], z
+ * [rows, 256]; h32 = (1 - z) h32 + z tanh(.) in place ((rows + guard) x 128 floats, guard rows preset by the caller), its fp16 (and fp8) copy -> out
+ * ((rows + guard) x 384 / 576 halfs).  add1 / add2: [rows, N] or NULL. */
+int pb_op_raft_gru_zr(pb_ctx *ctx, const float *x, const float *w, const float *bias, const float *add1, const float *add2, float *h32, int n, int H, int W,
+                      int gc, int kh, int kw, int layout, int tile, int guard_rows, void *zrb, void *rh, int *info, char *kernel, int kernel_cap);
+int pb_op_raft_gru_q(pb_ctx *ctx, const float *x, const float *w, const float *bias, const float *add1, const float *add2, const float *z, float *h32, int n,
+                     int H, int W, int gc, int kh, int kw, int layout, int tile, int guard_rows, void *out, int *info, char *kernel, int kernel_cap);
+/* conv_pixshuf: the convolution form of EPI_PIXSHUF (RAFT's encoder stem): x [B, H, W, 64], w [256, 64, 3, 3] with output channel (dy 2 + dx) 64 + co,
+ * bias [64], act 0 / 1 (ReLU); out: (B 2H 2W + guard) pixels of (layout ? 128 : 64) halfs, layouts as pb_op_gemm_pixshuf's. */
+int pb_op_conv_pixshuf(pb_ctx *ctx, const float *x, const float *w, const float *bias, int B, int H, int W, int layout, int act, int guard_rows, void *out,
+                       int *info, char *kernel, int kernel_cap);
+int pb_op_gemm_fc1(pb_ctx *ctx, const float *A, const float *w, const float *bias, int M, int K, int N, int tile, int guard_rows, void *out, int *info,
+                   char *kernel, int kernel_cap);
+int pb_op_gemm_pixshuf(pb_ctx *ctx, const float *x, const float *wt, const float *bias, int B, int h, int w, int C, int s, int layout, int tile,
+                       int guard_rows, void *out, int *info, char *kernel, int kernel_cap);
+int pb_op_conv_head(pb_ctx *ctx, const float *x, const float *w, const float *bias, const float *w2, float b2, int B, int H, int W, int C, int layout,
+                    int guard_rows, float *out, int *info, char *kernel, int kernel_cap);
 /* The flow_raft band's own kernels one by one, through the launchers and arguments RaftEngine::infer uses (tests/test_gpu_raft_ops.py).  Raw
  * output buffers are preset to 0xFF bytes (NaN as fp16, fp32 and e4m3) and carry guard_rows untouched rows behind the last one.
  * pb_op_raft_geometry (no GPU needed): geo[l * 5 + {0..4}] = {h, w, padded w, padded h, volume row stride} of pyramid level l over an h8 x w8

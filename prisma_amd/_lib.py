@@ -125,6 +125,15 @@ SYMBOLS = {
     "pb_op_conv2d": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 10),
     "pb_op_conv2d_split": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 18 + [_P, _P, _P, C.c_int]),
     "pb_op_dense_split": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P, _P, _P, C.c_int]),
+    "pb_op_gemm_resid": (C.c_int, [_P, _P, _P, _P, _P, _P] + [C.c_int] * 7 + [_P, _P, _P, C.c_int]),
+    "pb_op_gemm_qkv": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, _P, _P, C.c_int]),
+    "pb_op_gemm_patch": (C.c_int, [_P, _P, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int]),
+    "pb_op_raft_gru_zr": (C.c_int, [_P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P, _P, _P, _P, C.c_int]),
+    "pb_op_raft_gru_q": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P] + [C.c_int] * 9 + [_P, _P, _P, C.c_int]),
+    "pb_op_conv_pixshuf": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [_P, _P, _P, C.c_int]),
+    "pb_op_gemm_fc1": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P, _P, _P, C.c_int]),
+    "pb_op_gemm_pixshuf": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 8 + [_P, _P, _P, C.c_int]),
+    "pb_op_conv_head": (C.c_int, [_P, _P, _P, _P, _P, C.c_float] + [C.c_int] * 6 + [_P, _P, _P, C.c_int]),
     "pb_op_raft_geometry": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "pb_op_raft_lookup": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P, _P]),
     "pb_op_raft_lookup_otf": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 5 + [_P]),

@@ -1002,6 +1002,300 @@ class DepthOpEngine : public MaskOpEngine {
         return finish(out, dout, (size_t)(px + guard) * 4);
     }
 };
+
+// ---- the GEMM's fused epilogues one by one (pb_op_gemm_resid / _qkv / _patch / _pixshuf / _fc1, pb_op_conv_head) -----------------------------------------------------------
+// The ViT linears as DepthEngine::vit launches them: weights through pack_spec with the PackSpec DepthEngine::pack_vit fills (one fp16 pass,
+// hi + lo fp16 weights, or mx2 [w_hi | w_lo8] against token rows [a16 | a8]), LayerScale folded by pb_fold_layerscale, the GemmArgs of
+// engine.hip vit() and launch_gemm with the tile the test asks for.  Outputs are preset to 0xFF bytes and carry guard rows.
+class EpiOpEngine : public DepthOpEngine {
+  public:
+    explicit EpiOpEngine(int device) : DepthOpEngine(device) {}
+
+    static int vit_spec(int layout, PackSpec &s) {
+        PB_CHECK(layout == SL_F16 || layout == SL_SPLIT16 || layout == SL_MX2, PB_ERR_ARG, "epilogue op: a ViT linear is f16 (0), split16 (1) or mx2 (3), not %d", layout);
+        s = PackSpec();
+        s.sw = layout != SL_F16; s.mx2 = layout == SL_MX2;
+        return 0;
+    }
+    // A [M, K] -> token rows [a16 (Kp)] or, for mx2 weights, [a16 (Kp) | a8 (Kp bytes)]; the rows up to the next multiple of 256 are zero
+    int vit_rows(DevMem &d, const float *A, int64_t M, int K, int Kp, bool m2, int &lda) const {
+        lda = m2 ? Kp + Kp / 2 : Kp;
+        std::vector<f16> h((size_t)round_up(M, 256) * lda, (f16)0.f);
+        build_map(A, M, K, Kp, m2 ? SL_MX2 : SL_F16, 0, lda, h);
+        return up(d, h.data(), h.size() * 2);
+    }
+    int launch(const pb_ctx *c, int epi, int tile, GemmArgs &a, const PackedW &w, int *info, char *kname, int kcap, int amode = A_DENSE) {
+        a.N = w.N;
+        set_weights(a, w, amode == A_CONV);
+        DevMem dsk;
+        PB_TRY(lend_splitk(c, dsk, a));
+        PB_HIP(hipDeviceSynchronize());
+        pb_gemm_set_last_kernel("");
+        PB_TRY(launch_gemm(stream, amode, epi, tile, a));
+        PB_HIP(hipStreamSynchronize(stream));
+        if (info) {
+            const int v[8] = {w.mx_pw, w.mx3 ? kLo8Pa : kMx2Pa, w.mx2, w.sw, w.K, w.nk16, w.mx3, pb_gemm_last_splitk()};
+            memcpy(info, v, sizeof(v));
+        }
+        if (kname && kcap > 0) snprintf(kname, kcap, "%s", pb_gemm_last_kernel());
+        return 0;
+    }
+
+    int resid(const pb_ctx *c, const float *A, const float *W, const float *bias, const float *gamma, const float *X, int M, int N, int K, int ldr,
+              int layout, int tile, int guard, float *out, int *info, char *kname, int kcap) {
+        PackSpec s;
+        PB_TRY(vit_spec(layout, s));
+        std::vector<float> ws, bb;
+        pb_fold_layerscale(W, bias, gamma, N, K, ws, bb);
+        PackedW w;
+        PB_TRY(pack_spec(ws.data(), N, K, K, w, bb.data(), 1, s));
+        DevMem da, dg, dx;
+        int lda = 0;
+        PB_TRY(vit_rows(da, A, M, K, K, w.mx2 != 0, lda));
+        PB_TRY(up(dg, gamma, (size_t)N * 4));
+        std::vector<float> hx((size_t)(M + guard) * ldr);
+        memset(hx.data(), 0xFF, hx.size() * 4);
+        for (int64_t m = 0; m < M; ++m) memcpy(&hx[(size_t)m * ldr], X + m * N, (size_t)N * 4);
+        PB_TRY(up(dx, hx.data(), hx.size() * 4));
+        GemmArgs a;
+        a.A = da.as<f16>(); a.lda = lda; a.M = M; a.resid = dx.as<float>(); a.ldr = ldr; a.gamma = dg.as<float>();
+        PB_TRY(launch(c, EPI_RESID, tile, a, w, info, kname, kcap));
+        return down(out, dx, hx.size() * 4);
+    }
+
+    // q, k: (B heads ntp + guard) rows of 64 halfs; vt: (B heads 64 + guard) rows of ntp halfs
+    int qkv(const pb_ctx *c, const float *A, const float *W, const float *bias, int B, int ntp, int D, int layout, int tile, int guard, void *q, void *k,
+            void *vt, int *info, char *kname, int kcap) {
+        PackSpec s;
+        PB_TRY(vit_spec(layout, s));
+        PackedW w;
+        PB_TRY(pack_spec(W, 3 * D, D, D, w, bias, 1, s));
+        const int heads = D / 64;
+        const int64_t M = (int64_t)B * ntp;
+        DevMem da, dq, dk, dv;
+        int lda = 0;
+        PB_TRY(vit_rows(da, A, M, D, D, w.mx2 != 0, lda));
+        const size_t qb = ((size_t)B * heads * ntp + guard) * 64 * 2, vb = ((size_t)B * heads * 64 + guard) * ntp * 2;
+        PB_TRY(preset(dq, qb)); PB_TRY(preset(dk, qb)); PB_TRY(preset(dv, vb));
+        GemmArgs a;
+        a.A = da.as<f16>(); a.lda = lda; a.M = (int)M;
+        a.q = dq.as<f16>(); a.k = dk.as<f16>(); a.vt = dv.as<f16>(); a.ntp = ntp; a.heads = heads; a.D = D; a.qscale = PB_QSCALE;
+        PB_TRY(launch(c, EPI_QKV, tile, a, w, info, kname, kcap));
+        PB_TRY(down(q, dq, qb)); PB_TRY(down(k, dk, qb));
+        return down(vt, dv, vb);
+    }
+
+    // the 14 x 14 x 3 patch embedding: K = 588 carried as 640; rows (b, patch) land on rows b ntp + 1 + patch of the residual stream
+    int patch(const pb_ctx *c, const float *A, const float *W, const float *bias, const float *pos, int B, int P, int ntp, int D, int layout, int guard,
+              float *out, int *info, char *kname, int kcap) {
+        PackSpec s;
+        PB_TRY(vit_spec(layout, s));
+        PB_CHECK(!s.mx2, PB_ERR_ARG, "op_gemm_patch: the patch embedding is f16 (0) or split16 (1)");
+        PackedW w;
+        PB_TRY(pack_spec(W, D, 588, 640, w, bias, 1, s));
+        DevMem da, dp, dx;
+        int lda = 0;
+        PB_TRY(vit_rows(da, A, (int64_t)B * P, 588, 640, false, lda));
+        PB_TRY(up(dp, pos, (size_t)(1 + P) * D * 4));
+        const size_t xb = ((size_t)B * ntp + guard) * D * 4;
+        PB_TRY(preset(dx, xb));
+        GemmArgs a;
+        a.A = da.as<f16>(); a.lda = lda; a.M = B * P;
+        a.resid = dx.as<float>(); a.ldr = D; a.pos = dp.as<float>(); a.ppi = P; a.ntp = ntp; a.D = D;
+        PB_TRY(launch(c, EPI_PATCH, TILE_128, a, w, info, kname, kcap));
+        return down(out, dx, xb);
+    }
+
+    // output_conv2 as DepthEngine::head fuses it: 3 x 3 over C channels -> 32, ReLU, dot with w2, + b2, ReLU -> one float per pixel.  The map is
+    // [hi], [hi | lo] or [hi | hi8 | lo8] (layout 0 / 1 / 2), the weights slice-major as the head packs them
+    int head(const pb_ctx *c, const float *x, const float *W, const float *bias, const float *w2, float b2, int B, int H, int Wd, int C, int layout,
+             int guard, float *out, int *info, char *kname, int kcap) {
+        PB_CHECK(layout == SL_F16 || layout == SL_SPLIT16 || layout == SL_MX3, PB_ERR_ARG, "op_conv_head: layout %d (0 f16, 1 split16, 2 mx3)", layout);
+        PackSpec s;
+        s.sa = s.sw = layout != SL_F16; s.mx = layout == SL_MX3; s.tapin = 1;
+        const int Cp = (int)round_up(C, 64), K = 9 * Cp;
+        PackedW w;
+        PB_TRY(pack_spec(pb_conv_rows(W, 32, C, 9, Cp).data(), 32, K, K, w, bias, 9, s));
+        w.Kreal = 9 * C;
+        const int64_t P = (int64_t)B * H * Wd;
+        const int ld = layout == SL_F16 ? Cp : 2 * Cp;
+        std::vector<float> xp((size_t)P * Cp, 0.f);
+        for (int64_t p = 0; p < P; ++p) memcpy(&xp[(size_t)p * Cp], x + p * C, (size_t)C * 4);
+        std::vector<f16> hx((size_t)round_up(P, 256) * ld, (f16)0.f);
+        build_map(xp.data(), P, Cp, Cp, layout, 1, ld, hx);
+        DevMem dx, dw2, dout;
+        PB_TRY(up(dx, hx.data(), hx.size() * 2)); PB_TRY(up(dw2, w2, 32 * 4));
+        PB_TRY(preset(dout, (size_t)(P + guard) * 4));
+        GemmArgs a;
+        a.A = dx.as<f16>();
+        a.cH = H; a.cW = Wd; a.cC = Cp; a.cKW = 3; a.cStride = 1; a.cPad = 1; a.cOH = H; a.cOW = Wd;
+        a.M = (int)P; a.w2 = dw2.as<float>(); a.b2 = b2; a.depth = dout.as<float>();
+        PB_CHECK(a.cC == w.Cseg, PB_ERR_STATE, "op_conv_head: %d channels per part, weights packed for %d", a.cC, w.Cseg);
+        PB_TRY(launch(c, EPI_HEAD, TILE_AUTO, a, w, info, kname, kcap, A_CONV));
+        return down(out, dout, (size_t)(P + guard) * 4);
+    }
+
+    // the convolution form of the pixel shuffle (RAFT's encoder stem, raft_engine.hip encoder): a 3 x 3 convolution over 64 channels to 4 x 64 columns
+    // (dy, dx, co), s = 2, weights through EngineBase::pack with nine taps and sa = 1 as the stem's; bias [64]; maps and output as pixshuf's
+    int pixshuf_conv(const pb_ctx *c, const float *x, const float *W, const float *bias, int B, int H, int Wd, int layout, int act, int guard, void *out,
+                     int *info, char *kname, int kcap) {
+        PB_CHECK(layout == SL_F16 || layout == SL_SPLIT16 || layout == SL_MX3, PB_ERR_ARG, "op_conv_pixshuf: layout %d (0 f16, 1 split16, 2 mx3)", layout);
+        split_w_ = layout != SL_F16; mx_ = layout == SL_MX3; pack_mx2_ = 0; pack_tapin_ = 0;
+        std::vector<float> bb(256);
+        for (int n = 0; n < 256; ++n) bb[n] = bias[n % 64];
+        PackedW w;
+        PB_TRY(pack(pb_conv_rows(W, 256, 64, 9, 64).data(), 256, 576, 576, w, bb.data(), 9, 1));
+        const int es = layout == SL_F16 ? 1 : 2, ld = es * 64;
+        const int64_t M = (int64_t)B * H * Wd, px = M * 4;
+        std::vector<f16> hx((size_t)round_up(M, 256) * ld, (f16)0.f);
+        build_map(x, M, 64, 64, layout, 1, ld, hx);
+        DevMem dx, dout;
+        PB_TRY(up(dx, hx.data(), hx.size() * 2));
+        const size_t ob = (size_t)(px + guard) * ld * 2;
+        PB_TRY(preset(dout, ob));
+        GemmArgs a;
+        a.A = dx.as<f16>(); a.N = 256;
+        a.cH = H; a.cW = Wd; a.cC = 64; a.cLd = ld; a.cKW = 3; a.cStride = 1; a.cPad = 1; a.cPadX = 1;
+        set_weights(a, w, true);
+        a.cOH = H; a.cOW = Wd; a.M = (int)M;
+        a.out = dout.as<f16>(); a.ldo = ld; a.lo_off = layout == SL_F16 ? 0 : 64; a.act = act;
+        if (layout == SL_MX3) { a.lo8 = 1; a.lo8_pa = kLo8Pa; }
+        a.ps_h = H; a.ps_w = Wd; a.ps_s = 2; a.ps_co = 64;
+        PB_HIP(hipDeviceSynchronize());
+        pb_gemm_set_last_kernel("");
+        PB_TRY(launch_gemm(stream, A_CONV, EPI_PIXSHUF, TILE_AUTO, a));
+        PB_HIP(hipStreamSynchronize(stream));
+        if (info) {
+            const int v[8] = {w.mx_pw, kLo8Pa, w.mx2, w.sw, w.K, w.nk16, w.mx3, pb_gemm_last_splitk()};
+            memcpy(info, v, sizeof(v));
+        }
+        if (kname && kcap > 0) snprintf(kname, kcap, "%s", pb_gemm_last_kernel());
+        return down(out, dout, ob);
+    }
+
+    // SepConvGRU's fused epilogues (raft_engine.hip infer: ACT_GRU_ZR / ACT_GRU_Q through EngineBase::conv with a ConvFuse).  x [n, H, W, 384] is the
+    // GRU input map ([h | inp | motion] for ZR, [r h | inp | motion] for Q) of which the convolution reads the first gc channels; mx2 (layout 3): the
+    // map is [a16 (384) | a8 (384 bytes)] per pixel (576 halfs) and the epilogues store fp8 twins at byte 768.  add1 / add2 (or NULL): the hoisted
+    // terms, fp16 rows of the output's stride.  which 0: ZR - w [256, gc, kh, kw]; outA = zrb (rows + guard) x 256 halfs, outB = the r h buffer
+    // (rows + guard) x ld halfs.  which 1: Q - w [128, gc, kh, kw], z [rows, 256] (the z half is read); outA = the new map rows (rows + guard) x ld
+    // halfs, h32 [rows + guard, 128] floats is read and written in place (the caller presets the guard rows).
+    int gru(const pb_ctx *c, int which, const float *x, const float *W, const float *bias, const float *add1, const float *add2, const float *z, float *h32,
+            int n, int H, int Wd, int gc, int kh, int kw, int layout, int tile, int guard, void *outA, void *outB, int *info, char *kname, int kcap) {
+        PB_CHECK(layout == SL_F16 || layout == SL_MX2, PB_ERR_ARG, "op_raft_gru: layout %d (0 f16, 3 mx2)", layout);
+        const bool m2 = layout == SL_MX2;
+        const int N = which ? 128 : 256, ld = m2 ? 576 : 384, ldo = which ? ld : 256;
+        const int64_t rows = (int64_t)n * H * Wd;
+        LayerTensors l(W, bias, N, gc, kh, kw);
+        PB_TRY(begin_load(l.t, 2));
+        split_w_ = m2; mx_ = m2; pack_mx2_ = m2; pack_tapin_ = 0;
+        PackedW w;
+        PB_TRY(pack_conv("l", true, nullptr, nullptr, w, 0));
+        PB_CHECK((w.mx2 != 0) == m2, PB_ERR_STATE, "op_raft_gru: the weights did not take the layout");
+        std::vector<f16> hx((size_t)round_up(rows, 256) * ld, (f16)0.f);
+        build_map(x, rows, 384, 384, m2 ? SL_MX2 : SL_F16, 0, ld, hx);
+        DevMem dx, dh, da1, da2, dz, doA, doB;
+        PB_TRY(up(dx, hx.data(), hx.size() * 2));
+        PB_TRY(up(dh, h32, (size_t)(rows + guard) * 128 * 4));
+        auto skip = [&](DevMem &d, const float *a) -> int {        // fp16 rows of the output's stride, the layer's N columns
+            std::vector<f16> h((size_t)round_up(rows, 256) * ldo, (f16)0.f);
+            for (int64_t m = 0; m < rows; ++m)
+                for (int j = 0; j < N; ++j) h[(size_t)m * ldo + j] = (f16)a[m * N + j];
+            return up(d, h.data(), h.size() * 2);
+        };
+        if (add1) { PB_TRY(skip(da1, add1)); }
+        if (add2) { PB_TRY(skip(da2, add2)); }
+        const size_t ab = (size_t)(rows + guard) * ldo * 2, bb = (size_t)(rows + guard) * ld * 2;
+        PB_TRY(preset(doA, ab));
+        ConvFuse f;
+        f.gru_h = dh.as<float>(); f.add2 = da2.as<f16>();
+        if (which) {
+            std::vector<f16> hz((size_t)round_up(rows, 256) * 256, (f16)0.f);
+            for (int64_t m = 0; m < rows; ++m)
+                for (int j = 0; j < 256; ++j) hz[(size_t)m * 256 + j] = (f16)z[m * 256 + j];
+            PB_TRY(up(dz, hz.data(), hz.size() * 2));
+            f.gru_z = dz.as<f16>();
+        } else {
+            PB_TRY(preset(doB, bb));
+            f.gru_rh = doB.as<f16>(); f.gru_ld = ld;
+        }
+        DevMem dsk;
+        if (c->op_splitk) {
+            PB_TRY(dsk.alloc((size_t)512 * 128 * 128 * 4));
+            sk_ws_ = dsk.as<float>(); sk_cap_ = (int64_t)512 * 128 * 128;
+        }
+        PB_HIP(hipDeviceSynchronize());
+        pb_gemm_set_last_kernel("");
+        conv_tile = tile;
+        const int r = conv(dx.as<f16>(), gc, ld, n, H, Wd, kh, kw, 1, w, doA.as<f16>(), ldo, which ? ACT_GRU_Q : ACT_GRU_ZR, 0, da1.as<f16>(), &f, 0,
+                           m2 && gc != 384 ? 384 : 0, m2 ? 768 : 0);
+        sk_ws_ = nullptr; sk_cap_ = 0;
+        if (r) return r;
+        PB_HIP(hipStreamSynchronize(stream));
+        if (info) {
+            const int v[8] = {w.mx_pw, kMx2Pa, w.mx2, w.sw, w.K, w.nk16, w.mx3, pb_gemm_last_splitk()};
+            memcpy(info, v, sizeof(v));
+        }
+        if (kname && kcap > 0) snprintf(kname, kcap, "%s", pb_gemm_last_kernel());
+        PB_TRY(down(outA, doA, ab));
+        if (!which) { PB_TRY(down(outB, doB, bb)); }
+        return down(h32, dh, (size_t)(rows + guard) * 128 * 4);
+    }
+
+    // fc1 as the split ViT runs it with fc2 on mx2 weights (engine.hip load / vit): plain fp16 weights on the MX build of the kernel (nk16 = K / 64,
+    // every K tile an fp16 tile), GELU, and the e4m3 copy fc2 reads behind the row's fp16 part; out: (M + guard) rows of [fp16 (N) | e4m3 (N bytes)]
+    int fc1(const pb_ctx *c, const float *A, const float *W, const float *bias, int M, int K, int N, int tile, int guard, void *out, int *info, char *kname,
+            int kcap) {
+        PackedW w;
+        PB_TRY(pack_spec(W, N, K, K, w, bias, 1, PackSpec()));
+        w.nk16 = K / 64;
+        DevMem da, dout;
+        int lda = 0;
+        PB_TRY(vit_rows(da, A, M, K, K, false, lda));
+        const int ldo = N + N / 2;
+        const size_t ob = (size_t)(M + guard) * ldo * 2;
+        PB_TRY(preset(dout, ob));
+        GemmArgs a;
+        a.A = da.as<f16>(); a.lda = lda; a.M = M; a.out = dout.as<f16>(); a.ldo = ldo; a.act = ACT_GELU;
+        a.o8_off = N * 2; a.o8_scale = (float)(1 << kMx2Pa);
+        PB_TRY(launch(c, EPI_STD, tile, a, w, info, kname, kcap));
+        return down(out, dout, ob);
+    }
+
+    // a transposed convolution with kernel == stride == s as a 1 x 1 GEMM whose epilogue scatters column (dy, dx, co) of row (b, y, x) to pixel
+    // (b, y s + dy, x s + dx) (DepthEngine::head, resize_layers.0 / .1): x [B h w, C] and the output in the head's map layout (0 [hi], 1 [hi | lo],
+    // 2 [hi | hi8 | lo8]); Wt is ConvTranspose2d's [C, C, s, s], reordered as DepthEngine::load's pack_convT reorders it, bias [C] unpadded
+    int pixshuf(const pb_ctx *c, const float *x, const float *Wt, const float *bias, int B, int h, int wd, int C, int s, int layout, int tile, int guard,
+                void *out, int *info, char *kname, int kcap) {
+        PB_CHECK(layout == SL_F16 || layout == SL_SPLIT16 || layout == SL_MX3, PB_ERR_ARG, "op_gemm_pixshuf: layout %d (0 f16, 1 split16, 2 mx3)", layout);
+        PackSpec sp;
+        sp.sa = sp.sw = layout != SL_F16; sp.mx = layout == SL_MX3; sp.tapin = 1;
+        const int Cp = (int)round_up(C, 64), N = s * s * C;
+        std::vector<float> g((size_t)N * Cp, 0.f);
+        for (int ci = 0; ci < C; ++ci)
+            for (int o = 0; o < C; ++o)
+                for (int t = 0; t < s * s; ++t) g[((size_t)t * C + o) * Cp + ci] = Wt[((size_t)ci * C + o) * s * s + t];
+        PackedW w;
+        PB_TRY(pack_spec(g.data(), N, Cp, Cp, w, nullptr, 1, sp));
+        w.Kreal = C;
+        PB_TRY(upload_f32(bias, C, &w.bias));
+        const int64_t M = (int64_t)B * h * wd, px = M * s * s;
+        const int ld = layout == SL_F16 ? Cp : 2 * Cp;
+        std::vector<float> xp((size_t)M * Cp, 0.f);
+        for (int64_t m = 0; m < M; ++m) memcpy(&xp[(size_t)m * Cp], x + m * C, (size_t)C * 4);
+        std::vector<f16> hx((size_t)round_up(M, 256) * ld, (f16)0.f);
+        build_map(xp.data(), M, Cp, Cp, layout, 1, ld, hx);
+        DevMem dx, dout;
+        PB_TRY(up(dx, hx.data(), hx.size() * 2));
+        const size_t ob = (size_t)(px + guard) * ld * 2;
+        PB_TRY(preset(dout, ob));
+        GemmArgs a;
+        a.A = dx.as<f16>(); a.lda = ld; a.M = (int)M;
+        a.out = dout.as<f16>(); a.ldo = ld; a.lo_off = layout == SL_F16 ? 0 : Cp; a.ps_s = s; a.ps_h = h; a.ps_w = wd; a.ps_co = C;
+        if (layout == SL_MX3) { a.lo8 = 1; a.lo8_pa = kLo8Pa; }
+        PB_TRY(launch(c, EPI_PIXSHUF, tile, a, w, info, kname, kcap));
+        return down(out, dout, ob);
+    }
+};
 }  // namespace
 
 extern "C" {
@@ -1341,6 +1635,72 @@ int pb_op_dense_split(pb_ctx *c, const float *A, const float *w, const float *bi
     PB_TRY(e.setup(l.t, 2, layout, 0));
     return e.run(false, A, skip, M, 1, 1, K, K, 0, N, 1, 1, 1, layout, sa, tile, c->op_splitk, split_out, act, 0, rows_out, out, info, kernel,
                  kernel_cap);
+}
+
+// ---- the GEMM's fused epilogues one by one (EpiOpEngine above) ----
+#define EPI_OP_ENGINE(e) PB_HIP(hipSetDevice(c->device)); EpiOpEngine e(c->device); PB_TRY(e.setup(nullptr, 0, SL_F16, 0))
+int pb_op_gemm_resid(pb_ctx *c, const float *A, const float *w, const float *bias, const float *gamma, const float *X, int M, int N, int K, int ldr,
+                     int layout, int tile, int guard_rows, float *out, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && A && w && bias && gamma && X && out && M > 0 && N > 0 && N % 8 == 0 && K > 0 && K % 64 == 0 && ldr >= N && ldr % 4 == 0 && guard_rows >= 0,
+             PB_ERR_ARG, "op_gemm_resid: bad arguments");
+    EPI_OP_ENGINE(e);
+    return e.resid(c, A, w, bias, gamma, X, M, N, K, ldr, layout, tile, guard_rows, out, info, kernel, kernel_cap);
+}
+int pb_op_gemm_qkv(pb_ctx *c, const float *A, const float *w, const float *bias, int B, int ntp, int D, int layout, int tile, int guard_rows, void *q,
+                   void *k, void *vt, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && A && w && bias && q && k && vt && B > 0 && ntp > 0 && ntp % 16 == 0 && D > 0 && D % 128 == 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_gemm_qkv: bad arguments");
+    EPI_OP_ENGINE(e);
+    return e.qkv(c, A, w, bias, B, ntp, D, layout, tile, guard_rows, q, k, vt, info, kernel, kernel_cap);
+}
+int pb_op_gemm_patch(pb_ctx *c, const float *A, const float *w, const float *bias, const float *pos, int B, int P, int ntp, int D, int layout,
+                     int guard_rows, float *out, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && A && w && bias && pos && out && B > 0 && P > 0 && ntp >= P + 1 && D > 0 && D % 128 == 0 && guard_rows >= 0, PB_ERR_ARG,
+             "op_gemm_patch: bad arguments");
+    EPI_OP_ENGINE(e);
+    return e.patch(c, A, w, bias, pos, B, P, ntp, D, layout, guard_rows, out, info, kernel, kernel_cap);
+}
+int pb_op_conv_head(pb_ctx *c, const float *x, const float *w, const float *bias, const float *w2, float b2, int B, int H, int W, int C, int layout,
+                    int guard_rows, float *out, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && x && w && bias && w2 && out && B > 0 && H > 0 && W > 0 && C > 0 && guard_rows >= 0, PB_ERR_ARG, "op_conv_head: bad arguments");
+    EPI_OP_ENGINE(e);
+    return e.head(c, x, w, bias, w2, b2, B, H, W, C, layout, guard_rows, out, info, kernel, kernel_cap);
+}
+int pb_op_conv_pixshuf(pb_ctx *c, const float *x, const float *w, const float *bias, int B, int H, int W, int layout, int act, int guard_rows, void *out,
+                       int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && x && w && bias && out && B > 0 && H > 0 && W > 0 && (act == ACT_NONE || act == ACT_RELU) && guard_rows >= 0, PB_ERR_ARG,
+             "op_conv_pixshuf: bad arguments");
+    EPI_OP_ENGINE(e);
+    return e.pixshuf_conv(c, x, w, bias, B, H, W, layout, act, guard_rows, out, info, kernel, kernel_cap);
+}
+int pb_op_raft_gru_zr(pb_ctx *c, const float *x, const float *w, const float *bias, const float *add1, const float *add2, float *h32, int n, int H, int W,
+                      int gc, int kh, int kw, int layout, int tile, int guard_rows, void *zrb, void *rh, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && x && w && bias && h32 && zrb && rh && n > 0 && H > 0 && W > 0 && (gc == 256 || gc == 384) && kh >= 1 && kw >= 1 && guard_rows >= 0,
+             PB_ERR_ARG, "op_raft_gru_zr: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    EpiOpEngine e(c->device);
+    return e.gru(c, 0, x, w, bias, add1, add2, nullptr, h32, n, H, W, gc, kh, kw, layout, tile, guard_rows, zrb, rh, info, kernel, kernel_cap);
+}
+int pb_op_raft_gru_q(pb_ctx *c, const float *x, const float *w, const float *bias, const float *add1, const float *add2, const float *z, float *h32, int n,
+                     int H, int W, int gc, int kh, int kw, int layout, int tile, int guard_rows, void *out, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && x && w && bias && z && h32 && out && n > 0 && H > 0 && W > 0 && (gc == 256 || gc == 384) && kh >= 1 && kw >= 1 && guard_rows >= 0,
+             PB_ERR_ARG, "op_raft_gru_q: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    EpiOpEngine e(c->device);
+    return e.gru(c, 1, x, w, bias, add1, add2, z, h32, n, H, W, gc, kh, kw, layout, tile, guard_rows, out, nullptr, info, kernel, kernel_cap);
+}
+int pb_op_gemm_fc1(pb_ctx *c, const float *A, const float *w, const float *bias, int M, int K, int N, int tile, int guard_rows, void *out, int *info,
+                   char *kernel, int kernel_cap) {
+    PB_CHECK(c && A && w && bias && out && M > 0 && K > 0 && K % 64 == 0 && N > 0 && N % 64 == 0 && guard_rows >= 0, PB_ERR_ARG, "op_gemm_fc1: bad arguments");
+    EPI_OP_ENGINE(e);
+    return e.fc1(c, A, w, bias, M, K, N, tile, guard_rows, out, info, kernel, kernel_cap);
+}
+int pb_op_gemm_pixshuf(pb_ctx *c, const float *x, const float *wt, const float *bias, int B, int h, int w, int C, int s, int layout, int tile,
+                       int guard_rows, void *out, int *info, char *kernel, int kernel_cap) {
+    PB_CHECK(c && x && wt && bias && out && B > 0 && h > 0 && w > 0 && C > 0 && C % 8 == 0 && s >= 1 && s <= 4 && guard_rows >= 0, PB_ERR_ARG,
+             "op_gemm_pixshuf: bad arguments");
+    EPI_OP_ENGINE(e);
+    return e.pixshuf(c, x, wt, bias, B, h, w, C, s, layout, tile, guard_rows, out, info, kernel, kernel_cap);
 }
 
 // ---- the flow_raft band's kernels one by one (RaftOpEngine above) ----

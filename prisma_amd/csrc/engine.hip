@@ -99,14 +99,10 @@ int DepthEngine::load(const pb_tensor *w, int n) {
         int r;
         { NEED(wt, b + "attn.qkv.weight", (int64_t)3 * D * D); NEED(bs, b + "attn.qkv.bias", 3 * D);
           if ((r = pack_vit(wt, 3 * D, D, B.qkv, bs, (vit_res_ & 1) != 0))) return r; }
-        // LayerScale (layer_scale.py:27-28) is folded into the weights: x + g*(W y + b) = x + (g.W) y + g.b, so the GEMM
-        // can accumulate straight onto the residual stream
+        // LayerScale is folded into the weights (pack_layout.h pb_fold_layerscale)
         auto pack_scaled = [&](const float *wt, const float *bs, const float *g, int N, int K, PackedW &out, bool keep_res) -> int {
-            std::vector<float> ws((size_t)N * K), bb(N);
-            for (int n = 0; n < N; ++n) {
-                for (int k = 0; k < K; ++k) ws[(size_t)n * K + k] = wt[(size_t)n * K + k] * g[n];
-                bb[n] = bs[n] * g[n];
-            }
+            std::vector<float> ws, bb;
+            pb_fold_layerscale(wt, bs, g, N, K, ws, bb);
             return pack_vit(ws.data(), N, K, out, bb.data(), keep_res);
         };
         { NEED(wt, b + "attn.proj.weight", (int64_t)D * D); NEED(bs, b + "attn.proj.bias", D); NEED(g1, b + "ls1.gamma", D);

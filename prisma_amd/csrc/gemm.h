@@ -48,8 +48,8 @@ struct GemmArgs {
     // with lo_off: the residual parts of split maps are e4m3 - outputs store fp8(hi 2^lo8_pa) at byte lo_off * 2 + n and
     // fp8(lo 2^(lo8_pa + 12)) at byte lo_off * 3 + n of the pixel (lo_off = padded channels), skip tensors are read as hi + lo8
     int lo8 = 0, lo8_pa = 3;
-    // EPI_STD direct epilogue: also store fp8(v * o8_scale) - the A operand of a consumer's fp8 segment - at byte offset o8_off of
-    // the output row (after its fp16 part); 0 = off
+    // EPI_STD direct epilogue: also store fp8(fp16(v) * o8_scale) - the e4m3 of the STORED fp16, the A operand of a consumer's fp8 segment - at
+    // byte offset o8_off of the output row (after its fp16 part); 0 = off
     int o8_off = 0;
     float o8_scale = 16.f;
     // fp16 outputs (out, out2) also store the rounding residual (f16)(v - (float)(f16)v) at element offset +lo_off, and the
@@ -126,3 +126,5 @@ const char *pb_gemm_last_kernel();
 // 128 x 96 tile (same bytes); 2 (default) = ... and the packed-channel K axis where the weights carry one (GemmArgs::Wcw: another summation order)
 void pb_gemm_set_n96(int mode);
 void pb_gemm_set_last_kernel(const char *name);
+// split-K factor the last launch_gemm call of this thread chose (1 = one launch, no reduction): the op-level tests assert the path they mean to cover
+int pb_gemm_last_splitk();

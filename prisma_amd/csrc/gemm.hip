@@ -29,6 +29,8 @@ void pb_gemm_set_n96(int mode) { g_n96 = mode < 0 ? 0 : (mode > 2 ? 2 : mode); }
 static thread_local const char *g_last_kernel = "";
 const char *pb_gemm_last_kernel() { return g_last_kernel; }
 void pb_gemm_set_last_kernel(const char *name) { g_last_kernel = name; }
+static thread_local int g_last_splitk = 1;
+int pb_gemm_last_splitk() { return g_last_splitk; }
 
 int launch_gemm(hipStream_t stream, int amode, int epi, int tile, const GemmArgs &a_in) {
     GemmArgs a = a_in;
@@ -109,6 +111,7 @@ int launch_gemm(hipStream_t stream, int amode, int epi, int tile, const GemmArgs
             if (S > 1) a.splitk = S;
         }
     }
+    g_last_splitk = a.splitk;
     if (tile == TILE_128x96 && a.Wcw && g_n96 >= 2 && !a.cTapInner) {        // packed-channel K axis (gemm.h Wcw)
         a.W = a.Wcw; a.K = a.Kcw; a.nk16 = a.nk16cw; a.mx_period = 0; a.kwrap = 0; a.kshift = 0; a.cwalk = 1;
     }

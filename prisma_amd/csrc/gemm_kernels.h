@@ -680,7 +680,7 @@ __device__ __forceinline__ void direct_epilogue_f16_impl(const GemmArgs &p, f32x
                 if (p.act != ACT_GRU_ZR) {       // fp8 copy for a consumer's MX correction segment (gemm.h o8_off); z itself has none
 #pragma unroll
                     for (int q = 0; q < 8; ++q) {
-                        const unsigned short o8 = pb_fp8x2(v0[q] * p.o8_scale, v1[q] * p.o8_scale);
+                        const unsigned short o8 = pb_fp8x2((float)(f16)v0[q] * p.o8_scale, (float)(f16)v1[q] * p.o8_scale);       // of the STORED fp16, as every a8
                         if (!CHECK || ok[q]) *(unsigned short *)((char *)p.out + (off[q] - nc) * 2 + p.o8_off + nc) = o8;
                     }
                 }
@@ -973,7 +973,8 @@ __device__ __forceinline__ void direct_epilogue_buf(const GemmArgs &p, f32x16 (&
             if constexpr (EPI == EPI_STD && LOM == 3) {
                 if (act != ACT_GRU_ZR) {       // fp8 copy for a consumer's MX correction segment (gemm.h o8_off); z itself has none
 #pragma unroll
-                    for (int q = 0; q < 8; ++q) bs_u16(td, vo8 | pz[q], rowc[q] * ldo * 2, pb_fp8x2(v0[q] * p.o8_scale, v1[q] * p.o8_scale));
+                    for (int q = 0; q < 8; ++q)       // (of the STORED fp16, as every a8: the consumer's fp8 segment corrects the product with that value)
+                        bs_u16(td, vo8 | pz[q], rowc[q] * ldo * 2, pb_fp8x2((float)(f16)v0[q] * p.o8_scale, (float)(f16)v1[q] * p.o8_scale));
                 }
             }
             if constexpr (EPI == EPI_STD && (LOM == 1 || LOM == 2)) {       // split-fp16 consumers read [hi | lo] (or [hi | hi8 | lo8], gemm.h lo8)

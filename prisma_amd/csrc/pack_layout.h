@@ -102,6 +102,16 @@ inline std::vector<float> pb_conv_rows(const float *w, int co, int ci, int taps,
     return g;
 }
 
+// LayerScale (layer_scale.py:27-28) folded into a linear layer: x + g (W y + b) = x + (g.W) y + g.b, so the GEMM can accumulate straight onto the
+// residual stream (gemm.h EPI_RESID).  wt [N, K], bs / g [N] -> ws [N, K], bb [N]
+inline void pb_fold_layerscale(const float *wt, const float *bs, const float *g, int N, int K, std::vector<float> &ws, std::vector<float> &bb) {
+    ws.resize((size_t)N * K); bb.resize(N);
+    for (int n = 0; n < N; ++n) {
+        for (int k = 0; k < K; ++k) ws[(size_t)n * K + k] = wt[(size_t)n * K + k] * g[n];
+        bb[n] = bs[n] * g[n];
+    }
+}
+
 // src: host fp32 [N, K] in GEMM order, K = taps x channels -> rows [round_up(N, 256), out.K] fp16 and the metadata of `out` (every field but
 // the device pointers).  Every tap is padded to Kpad / taps channels Cp and becomes, by layout,
 //   fp16 / split-fp16   [w_hi | w_hi (sa) | w_lo (sw)]                      (1 + sa + sw) Cp halfs

@@ -282,6 +282,10 @@ def _split_info(info, M: int) -> dict:
     return d
 
 
+def _epi_info(info) -> dict:
+    return dict(zip(("pw", "pa", "mx2", "sw", "K", "nk16", "mx3", "splitk"), list(info)))
+
+
 def raft_geometry(h8: int, w8: int) -> List[dict]:
     """the flow_raft band's pyramid plan over an h8 x w8 feature grid (csrc corr_pyramid_geometry; needs no GPU): per level h, w, the tiled
     layout's padded wp / hp and the volume's row stride ld"""
@@ -436,6 +440,133 @@ class Ops(_Ctx):
         check(self.lib.pb_op_dense_split(self.ctx, _ptr(A), _ptr(w), _ptr(bias), _ptr(sk), M, K, N, layout, sa, tile, int(split_out), act, rows,
                                          _ptr(out), info, kname, 128))
         return out, _split_info(info, M), kname.value.decode()
+
+    # ---- the GEMM's fused ViT epilogues one by one (pb_op_gemm_resid / _qkv / _patch; tests/test_gpu_epilogue_ops.py) ----
+    def gemm_resid(self, A, w, bias, gamma, X, layout: int = 0, tile: int = 1, ldr: int = 0, guard_rows: int = 8):
+        """X [M, N] (fp32) += A [M, K] (gamma . w)^T + gamma . bias as DepthEngine's proj / fc2 run it (LayerScale folded on the host).
+        Returns (raw residual stream as uint8 [M + guard_rows, ldr * 4], info dict, kernel symbol)."""
+        A, w, bias, gamma, X = _f32(A), _f32(w), _f32(bias), _f32(gamma), _f32(X)
+        M, K = A.shape
+        N = w.shape[0]
+        ldr = ldr or N
+        assert w.shape == (N, K) and bias.shape == (N,) and gamma.shape == (N,) and X.shape == (M, N)
+        out = np.empty((M + guard_rows, ldr * 4), np.uint8)
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_gemm_resid(self.ctx, _ptr(A), _ptr(w), _ptr(bias), _ptr(gamma), _ptr(X), M, N, K, ldr, layout, tile, guard_rows, _ptr(out),
+                                        info, kname, 128))
+        return out, _epi_info(info), kname.value.decode()
+
+    def gemm_qkv(self, A, w, bias, B: int, ntp: int, layout: int = 0, tile: int = 1, guard_rows: int = 8):
+        """A [B ntp, D] x w [3 D, D]^T + bias through the qkv epilogue.  Returns (q, k as uint8 [B heads ntp + guard_rows, 128], vt as uint8
+        [B heads 64 + guard_rows, ntp * 2], info dict, kernel symbol)."""
+        A, w, bias = _f32(A), _f32(w), _f32(bias)
+        M, D = A.shape
+        heads = D // 64
+        assert M == B * ntp and w.shape == (3 * D, D) and bias.shape == (3 * D,)
+        q = np.empty((B * heads * ntp + guard_rows, 128), np.uint8)
+        k = np.empty_like(q)
+        vt = np.empty((B * heads * 64 + guard_rows, ntp * 2), np.uint8)
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_gemm_qkv(self.ctx, _ptr(A), _ptr(w), _ptr(bias), B, ntp, D, layout, tile, guard_rows, _ptr(q), _ptr(k), _ptr(vt), info,
+                                      kname, 128))
+        return q, k, vt, _epi_info(info), kname.value.decode()
+
+    def gemm_patch(self, A, w, bias, pos, B: int, ntp: int, layout: int = 0, guard_rows: int = 8):
+        """A [B P, 588] x w [D, 588]^T + bias + pos [1 + P, D] into rows b ntp + 1 + patch of the fp32 residual stream.  Returns (raw stream as
+        uint8 [B ntp + guard_rows, D * 4], info dict, kernel symbol)."""
+        A, w, bias, pos = _f32(A), _f32(w), _f32(bias), _f32(pos)
+        D = w.shape[0]
+        P = A.shape[0] // B
+        assert A.shape == (B * P, 588) and w.shape == (D, 588) and bias.shape == (D,) and pos.shape == (1 + P, D)
+        out = np.empty((B * ntp + guard_rows, D * 4), np.uint8)
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_gemm_patch(self.ctx, _ptr(A), _ptr(w), _ptr(bias), _ptr(pos), B, P, ntp, D, layout, guard_rows, _ptr(out), info, kname, 128))
+        return out, _epi_info(info), kname.value.decode()
+
+    def raft_gru(self, which: str, x, w, bias, h32, z=None, add1=None, add2=None, layout: int = 0, tile: int = 1, guard_rows: int = 8):
+        """SepConvGRU's fused epilogues (pb_op_raft_gru_zr / _q).  x [n, H, W, 384], w [256 | 128, gc, kh, kw], h32 [rows, 128]; "q" also takes z
+        [rows, 256].  Returns for "zr": (zrb uint8 [rows + guard, 512], rh uint8 [rows + guard, ld * 2], info, kernel); for "q": (out uint8
+        [rows + guard, ld * 2], h32 uint8 [rows + guard, 512] with its guard rows preset to 0xFF, info, kernel); ld = 576 for mx2 (3) else 384."""
+        x, w, bias = _f32(x), _f32(w), _f32(bias)
+        n, H, W, _ = x.shape
+        N, gc, kh, kw = w.shape
+        rows, ld = n * H * W, 576 if layout == 3 else 384
+        assert x.shape[3] == 384 and N == (256 if which == "zr" else 128) and bias.shape == (N,)
+        hb = np.full((rows + guard_rows, 128), np.nan, np.float32)
+        hb.view(np.uint8)[:] = 0xFF
+        hb[:rows] = _f32(h32)
+        a1 = None if add1 is None else _f32(add1)
+        a2 = None if add2 is None else _f32(add2)
+        assert all(a is None or a.shape == (rows, N) for a in (a1, a2))
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        if which == "zr":
+            zrb = np.empty((rows + guard_rows, 512), np.uint8)
+            rh = np.empty((rows + guard_rows, ld * 2), np.uint8)
+            check(self.lib.pb_op_raft_gru_zr(self.ctx, _ptr(x), _ptr(w), _ptr(bias), _ptr(a1), _ptr(a2), _ptr(hb), n, H, W, gc, kh, kw, layout, tile,
+                                             guard_rows, _ptr(zrb), _ptr(rh), info, kname, 128))
+            return zrb, rh, _epi_info(info), kname.value.decode()
+        zz = _f32(z)
+        assert zz.shape == (rows, 256)
+        out = np.empty((rows + guard_rows, ld * 2), np.uint8)
+        check(self.lib.pb_op_raft_gru_q(self.ctx, _ptr(x), _ptr(w), _ptr(bias), _ptr(a1), _ptr(a2), _ptr(zz), _ptr(hb), n, H, W, gc, kh, kw, layout, tile,
+                                        guard_rows, _ptr(out), info, kname, 128))
+        return out, hb.view(np.uint8).reshape(rows + guard_rows, 512), _epi_info(info), kname.value.decode()
+
+    def conv_pixshuf(self, x, w, bias, layout: int = 0, act: int = 0, guard_rows: int = 8):
+        """the convolution form of the pixel shuffle (RAFT's stem): x [B, H, W, 64], w [256, 64, 3, 3], bias [64], s = 2.  Returns (raw output as
+        uint8 [B 2H 2W + guard_rows, ldo * 2], info dict, kernel symbol)."""
+        x, w, bias = _f32(x), _f32(w), _f32(bias)
+        B, H, W, Cc = x.shape
+        assert Cc == 64 and w.shape == (256, 64, 3, 3) and bias.shape == (64,)
+        out = np.empty((B * H * W * 4 + guard_rows, (2 if layout else 1) * 128), np.uint8)
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_conv_pixshuf(self.ctx, _ptr(x), _ptr(w), _ptr(bias), B, H, W, layout, act, guard_rows, _ptr(out), info, kname, 128))
+        return out, _epi_info(info), kname.value.decode()
+
+    def gemm_fc1(self, A, w, bias, tile: int = 1, guard_rows: int = 8):
+        """gelu(A [M, K] w [N, K]^T + bias) as the split ViT's fc1 runs it: fp16 weights on the MX build of the kernel, an e4m3 copy of the
+        stored fp16 behind it.  Returns (raw rows as uint8 [M + guard_rows, 3 N], info dict, kernel symbol)."""
+        A, w, bias = _f32(A), _f32(w), _f32(bias)
+        M, K = A.shape
+        N = w.shape[0]
+        assert w.shape == (N, K) and bias.shape == (N,)
+        out = np.empty((M + guard_rows, 3 * N), np.uint8)
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_gemm_fc1(self.ctx, _ptr(A), _ptr(w), _ptr(bias), M, K, N, tile, guard_rows, _ptr(out), info, kname, 128))
+        return out, _epi_info(info), kname.value.decode()
+
+    def gemm_pixshuf(self, x, wt, bias, s: int, layout: int = 0, tile: int = 1, guard_rows: int = 8):
+        """a transposed convolution (kernel == stride == s) as a 1 x 1 GEMM with the pixel-shuffle epilogue (EPI_PIXSHUF).  x [B, h, w, C], wt
+        [C, C, s, s], bias [C]; layout 0 fp16, 1 split16 ([hi | lo]), 2 mx3 ([hi | hi8 | lo8]) for the input map and the output.  Returns (raw
+        output as uint8 [B h s w s + guard_rows, ldo * 2], info dict, kernel symbol)."""
+        x, wt, bias = _f32(x), _f32(wt), _f32(bias)
+        B, h, w, Cc = x.shape
+        assert wt.shape == (Cc, Cc, s, s) and bias.shape == (Cc,)
+        ldo = (2 if layout else 1) * (-(-Cc // 64) * 64)
+        out = np.empty((B * h * s * w * s + guard_rows, ldo * 2), np.uint8)
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_gemm_pixshuf(self.ctx, _ptr(x), _ptr(wt), _ptr(bias), B, h, w, Cc, s, layout, tile, guard_rows, _ptr(out), info, kname, 128))
+        return out, _epi_info(info), kname.value.decode()
+
+    def conv_head(self, x, w, bias, w2, b2: float, layout: int = 0, guard_rows: int = 8):
+        """the DPT head's fused output_conv2 (EPI_HEAD): x NHWC [B, H, W, C], w [32, C, 3, 3] -> relu(relu(conv + bias) . w2 + b2), one float per
+        pixel.  layout 0 fp16, 1 split16 (map [hi | lo]), 2 mx3.  Returns (float32 [B H W + guard_rows] raw, info dict, kernel symbol)."""
+        x, w, bias, w2 = _f32(x), _f32(w), _f32(bias), _f32(w2)
+        B, H, W, Cc = x.shape
+        assert w.shape == (32, Cc, 3, 3) and bias.shape == (32,) and w2.shape == (32,)
+        out = np.empty(B * H * W + guard_rows, np.float32)
+        info = (C.c_int * 8)()
+        kname = C.create_string_buffer(128)
+        check(self.lib.pb_op_conv_head(self.ctx, _ptr(x), _ptr(w), _ptr(bias), _ptr(w2), float(b2), B, H, W, Cc, layout, guard_rows, _ptr(out), info,
+                                       kname, 128))
+        return out, _epi_info(info), kname.value.decode()
 
     # ---- the flow_raft band's kernels one by one (pb_op_raft_*; tests/test_gpu_raft_ops.py) ----
     def raft_lookup(self, fmap1, fmap2, flow, o8: bool = False, guard_rows: int = 8, want_levels: bool = False):
