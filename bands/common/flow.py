@@ -6,8 +6,8 @@ import numpy as np
 
 from prisma_amd import engine
 
-from .io import FrameReader, VideoWriter, write_flo, write_flow_png
-from .loop import Stream, run_sharded, stream_enabled
+from .io import FrameReader, VideoWriter, is_y4m, write_flo, write_flow_png
+from .loop import Stream, frame_formats, i420_bytes, run_sharded, stream_enabled
 
 
 def _mask_rgb(mask):
@@ -37,14 +37,19 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
     if args.output_mask:
         mbase, mext = args.output_mask.rsplit(".", 1)
         files.update({"mask_" + d: (args.output_mask if d == "f" else mbase + "_bwd." + mext) for d in dirs})
-    videos = {k: VideoWriter(width=w, height=h, frame_rate=src.fps, filename=f) for k, f in files.items()} if rk.main else {}
+    videos = {k: VideoWriter(width=w, height=h, frame_rate=src.rate, filename=f) for k, f in files.items()} if rk.main else {}
+    # a .y4m on either side: its I420 frames go to / come from the engine as they are.  The mask videos and the trailing zero frame are small
+    # and rare: they are converted on the host (VideoWriter.write)
+    yin, yout = src.i420, is_y4m(args.output)
+    fmt = frame_formats(model, yin, yout, h, w)
+    frame = ((i420_bytes(h, w),), np.uint8) if yin else (src[0].shape, np.uint8)
 
     def step(_s, frames):
         mask = None
         if want_mask:
-            flow, rgb, mx, mask = model.infer_sequence_masks(frames, scale=args.scale, iters=iterations, want_flow=want_flow, want_rgb=True)
+            flow, rgb, mx, mask = model.infer_sequence_masks(frames, scale=args.scale, iters=iterations, want_flow=want_flow, want_rgb=True, **fmt)
         else:
-            flow, rgb, mx = model.infer_sequence(frames, scale=args.scale, iters=iterations, backward=both, want_flow=want_flow, want_rgb=True)
+            flow, rgb, mx = model.infer_sequence(frames, scale=args.scale, iters=iterations, backward=both, want_flow=want_flow, want_rgb=True, **fmt)
         return by_file(rgb, mask), (flow, mask), mx[:, :1]
 
     def by_file(rgb, mask):          # a chunk's video arrays: the key's array (rgb / mask) and direction
@@ -53,7 +58,7 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
     # the streamed loop (common/loop.py): the same calls as submit_sequence(_masks) / wait on the loop's page-locked rings - one array per result
     # asked for, [directions, ...] per pair
     nd = 2 if both else 1
-    results = {"rgb": ((nd, sh, sw, 3), np.uint8), "mx": ((nd,), np.float32)}
+    results = {"rgb": ((nd, i420_bytes(sh, sw)) if yout else (nd, sh, sw, 3), np.uint8), "mx": ((nd,), np.float32)}
     if want_flow:
         results["flow"] = ((nd, sh, sw, 2), np.float32)
     if want_mask:
@@ -62,9 +67,10 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
     def submit(_s, frames, res):
         if want_mask:
             model.submit_sequence_masks(frames, scale=args.scale, iters=iterations, out_flow=res.get("flow"), out_rgb=res["rgb"], out_max=res["mx"],
-                                        out_mask=res["mask"])
+                                        out_mask=res["mask"], **fmt)
         else:
-            model.submit_sequence(frames, scale=args.scale, iters=iterations, backward=both, out_flow=res.get("flow"), out_rgb=res["rgb"], out_max=res["mx"])
+            model.submit_sequence(frames, scale=args.scale, iters=iterations, backward=both, out_flow=res.get("flow"), out_rgb=res["rgb"], out_max=res["mx"],
+                                  **fmt)
 
     def collect(_s, res):
         mask = res["mask"].view(np.bool_) if want_mask else None
@@ -73,7 +79,10 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
     def write_chunk(_s, c):          # rank 0 only: one chunk of encoded pairs into every open video, in order
         for j in range(len(c["rgb_f"])):
             for k, v in videos.items():
-                v.write(c[k][j] if k.startswith("rgb") else _mask_rgb(c[k][j]))
+                if k.startswith("rgb") and yout:
+                    v.write_i420(c[k][j], sh, sw)
+                else:
+                    v.write(c[k][j] if k.startswith("rgb") else _mask_rgb(c[k][j]))
 
     def dump(s, payload):
         flow, mask = payload
@@ -87,9 +96,9 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
                 if args.backwards:
                     write_flow_png(os.path.join(args.subpath_mask + "_bwd", "%04d.png" % (s + j)), flow[j, 1], mask[j, 1])
 
-    stream = Stream(model, (src[0].shape, np.uint8), results, submit, collect) if stream_enabled(stream_min_chunks, -(-(last - first) // chunk)) else None
+    stream = Stream(model, frame, results, submit, collect, i420=yin) if stream_enabled(stream_min_chunks, -(-(last - first) // chunk)) else None
     mx_all = run_sharded(rk, src, n - 1, chunk, 1, args.output, ((n - 1) - (last - first)) * sh * sw * 3 * len(files),
-                         step, write_chunk, dump if want_flow else None, n_scalars=1, ctx=model, stream=stream)
+                         step, write_chunk, dump if want_flow else None, n_scalars=1, ctx=model, stream=stream, i420=yin)
     if not rk.main:
         return
     # last frame: zero flow -> 0/0 -> NaN -> uint8 0, max displacement 0.0, all-False masks (reference :116-131)

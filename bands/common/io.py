@@ -5,10 +5,22 @@ check_overwrite (:35-41), VideoWriter (:246-305, libx264 crf 15 yuv420p), write_
 write_ply (the file half of write_pcl :201-211; its arithmetic runs on the GPU, pb_depth_point_cloud).
 decord / PyAV / OpenCV are optional here (absent in the build image): .mp4 needs them, .npy
 frame stacks ([n,H,W,3] uint8) and .png work everywhere.
+
+.y4m (YUV4MPEG2) is the video container that needs no library: one text header line, then `FRAME\n` + the raw I420 planes per frame.
+It streams in both directions, ffmpeg / mpv / every encoder read and write it (`ffmpeg -i in.mp4 in.y4m` before a run,
+`ffmpeg -i depth_anything.y4m -crf 15 depth_anything.mp4` after it), and its frames are what the engines take and give with the
+"frames_i420" / "rgb_out_i420" options (include/prisma_bands.h) - half the bytes of RGB through PCIe and the page-locked rings.  8 bit,
+4:2:0, progressive, limited range only; the colour arithmetic is common/yuv.py's.
 """
 import os
+from fractions import Fraction
 
 import numpy as np
+
+from .yuv import i420_bytes, i420_to_rgb, rgb_to_i420
+
+Y4M_MAGIC = b"YUV4MPEG2"
+Y4M_CHROMA = ("C420", "C420jpeg", "C420mpeg2", "C420paldv")      # 8-bit 4:2:0; the siting they name is not acted on (nearest / block mean)
 
 
 def create_folder(path):
@@ -45,16 +57,127 @@ def get_image_size(path):
 def get_video_data(path):
     """(width, height, fps, total_frames) of a video (io.py:63-67)."""
     v = FrameReader(path)
+    if v.i420:                   # from the header and the file size: no frame is decoded
+        return v.width, v.height, v.fps, len(v)
     f0 = v[0]
     return f0.shape[1], f0.shape[0], v.fps, len(v)
 
 
+def is_y4m(path):
+    return bool(path) and path.endswith(".y4m")
+
+
+def y4m_header(width, height, rate):
+    """the header line VideoWriter writes; `rate` a Fraction"""
+    return ("YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" % (width, height, rate.numerator, rate.denominator)).encode("ascii")
+
+
+def as_rate(rate):
+    """A frame rate as an exact Fraction: a Fraction stays (a .y4m source's num:den), a float becomes the nearest ratio a header can carry."""
+    return rate if isinstance(rate, Fraction) else Fraction(rate).limit_denominator(1001000)
+
+
+class Y4MFile:
+    """The container side of a .y4m: header, frame index, raw planes.  .width / .height / .rate (Fraction) / len(); read_i420(i, out)."""
+
+    def __init__(self, path):
+        self.path = path
+        self._fd = os.open(path, os.O_RDONLY)
+        size = os.fstat(self._fd).st_size
+        head = os.pread(self._fd, 4096, 0)
+        end = head.find(b"\n")
+        if not head.startswith(Y4M_MAGIC + b" ") or end < 0:
+            raise RuntimeError("%s: not a YUV4MPEG2 file (no `YUV4MPEG2 ...` header line)" % path)
+        self.width = self.height = 0
+        self.rate = Fraction(24)
+        try:
+            for tok in head[:end].decode("ascii").split()[1:]:
+                k, v = tok[0], tok[1:]
+                if k == "W":
+                    self.width = int(v)
+                elif k == "H":
+                    self.height = int(v)
+                elif k == "F":
+                    num, den = v.split(":")
+                    self.rate = Fraction(int(num), int(den))
+                elif k == "I" and tok != "Ip":
+                    raise RuntimeError("%s: %s: interlaced material is not supported (progressive `Ip` only)" % (path, tok))
+                elif k == "C" and tok not in Y4M_CHROMA:
+                    raise RuntimeError("%s: %s: only 8-bit 4:2:0 is supported (%s)" % (path, tok, ", ".join(Y4M_CHROMA)))
+                elif k == "X" and tok.upper().startswith("XCOLORRANGE=") and tok.upper() != "XCOLORRANGE=LIMITED":
+                    raise RuntimeError("%s: %s: only limited range is supported (XCOLORRANGE=LIMITED)" % (path, tok))
+        except (ValueError, ZeroDivisionError) as e:
+            raise RuntimeError("%s: malformed YUV4MPEG2 header %r" % (path, head[:end])) from e
+        if self.width < 1 or self.height < 1:
+            raise RuntimeError("%s: the YUV4MPEG2 header carries no W / H" % path)
+        self.frame_bytes = fb = i420_bytes(self.height, self.width)
+        first = end + 1
+        # every frame line the bare `FRAME\n`: frame i is found by arithmetic (each supposed line is looked at once); otherwise one scan
+        n, rest = divmod(size - first, 6 + fb)
+        if rest == 0 and all(os.pread(self._fd, 6, first + i * (6 + fb)) == b"FRAME\n" for i in range(n)):
+            self._first, self._offsets, self._n = first + 6, None, n
+            return
+        self._offsets, pos = [], first
+        while pos < size:
+            line = os.pread(self._fd, 4096, pos)
+            nl = line.find(b"\n")
+            if not line.startswith(b"FRAME") or nl < 0 or line[5:6] not in (b"\n", b" "):
+                raise RuntimeError("%s: frame %d: no FRAME line at byte %d" % (path, len(self._offsets), pos))
+            if pos + nl + 1 + fb > size:
+                raise RuntimeError("%s: frame %d is truncated: %d of %d bytes" % (path, len(self._offsets), size - pos - nl - 1, fb))
+            self._offsets.append(pos + nl + 1)
+            pos += nl + 1 + fb
+        self._n = len(self._offsets)
+
+    def __len__(self):
+        return self._n
+
+    def read_i420(self, i, out):
+        """The three planes of frame i into `out`, a writable C-contiguous uint8 buffer of frame_bytes bytes (a page-locked ring slot's
+        row as well as a plain array).  pread: safe from the decode thread while another thread reads another frame."""
+        if not 0 <= i < self._n:
+            raise IndexError("%s: frame %d of %d" % (self.path, i, self._n))
+        view = memoryview(out).cast("B")
+        if len(view) != self.frame_bytes:
+            raise ValueError("%s: read_i420 needs %d bytes, got %d" % (self.path, self.frame_bytes, len(view)))
+        off = self._first + i * (6 + self.frame_bytes) if self._offsets is None else self._offsets[i]
+        got = 0
+        while got < self.frame_bytes:
+            k = os.preadv(self._fd, [view[got:]], off + got)
+            if k <= 0:
+                raise RuntimeError("%s: frame %d is truncated" % (self.path, i))
+            got += k
+        return out
+
+    def close(self):
+        if self._fd is not None:
+            os.close(self._fd)
+            self._fd = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001
+            pass
+
+
 class FrameReader:
-    """len() / [i] -> uint8 HxWx3 RGB; fps.  decord for .mp4 (reference), numpy memmap for .npy."""
+    """len() / [i] -> uint8 HxWx3 RGB; fps.  decord for .mp4 (reference), numpy memmap for .npy, Y4MFile for .y4m.
+    .rate is what a VideoWriter of the band's output takes: the exact Fraction of a .y4m source, else fps.
+    .i420: the source holds I420 frames (.y4m) - then .width / .height are known without a decode, read_i420(i, out) copies frame i's
+    planes into the caller's buffer of i420_bytes(height, width) bytes, and [i] converts them on the host (common/yuv.py)."""
 
     def __init__(self, path):
         self.fps = 24.0
-        if path.endswith(".npy"):
+        self.i420 = False
+        if is_y4m(path):
+            self._y4m = Y4MFile(path)
+            self.i420, self.width, self.height = True, self._y4m.width, self._y4m.height
+            self.fps = self._y4m.rate.numerator / self._y4m.rate.denominator
+            self.read_i420 = self._y4m.read_i420
+            self._n = len(self._y4m)
+            self._get = lambda i: i420_to_rgb(self._y4m.read_i420(i, np.empty(self._y4m.frame_bytes, np.uint8)), self.height, self.width)
+        elif path.endswith(".npy"):
             self._a = np.load(path, mmap_mode="r")
             assert self._a.ndim == 4 and self._a.shape[-1] == 3 and self._a.dtype == np.uint8
             self._get = lambda i: np.asarray(self._a[i])
@@ -69,6 +192,10 @@ class FrameReader:
             self._get = lambda i: self._v[i].asnumpy()
             self._n = len(self._v)
 
+    @property
+    def rate(self):
+        return self._y4m.rate if self.i420 else self.fps
+
     def __len__(self):
         return self._n
 
@@ -77,11 +204,17 @@ class FrameReader:
 
 
 class VideoWriter:
-    """write(uint8 HxWx3) / close().  .mp4 -> PyAV libx264 crf 15 (io.py:246-305); .npy -> frame stack."""
+    """write(uint8 HxWx3) / close().  .mp4 -> PyAV libx264 crf 15 (io.py:246-305); .npy -> frame stack; .y4m -> I420 frames appended to
+    the file as they come (nothing is kept in memory), the header written with the first frame and that frame's own size (no rescale, as
+    the .npy writer), write_i420(planes, h, w) for frames that already are I420 (the engines' "rgb_out_i420" results)."""
 
     def __init__(self, width, height, frame_rate, filename):
-        self.filename, self._frames, self._av = filename, None, None
-        if filename.endswith(".npy"):
+        self.filename, self._frames, self._av, self._y4m = filename, None, None, None
+        self.i420 = is_y4m(filename)
+        if self.i420:
+            self._rate, self._size = as_rate(frame_rate), None
+            self._y4m = open(filename, "wb")
+        elif filename.endswith(".npy"):
             self._frames = []
         else:
             try:
@@ -100,7 +233,24 @@ class VideoWriter:
             self._st.width, self._st.height, self._st.pix_fmt = self._w, self._h, "yuv420p"
             self._st.thread_type = "AUTO"
 
+    def write_i420(self, yuv, height, width):
+        """one I420 frame (uint8, i420_bytes(height, width) bytes: Y, Cb, Cr planes) of a .y4m"""
+        if self._y4m is None:
+            raise RuntimeError("%s: write_i420 is a .y4m writer's" % self.filename)
+        if self._size is None:
+            self._size = (height, width)
+            self._y4m.write(y4m_header(width, height, self._rate))
+        yuv = np.ascontiguousarray(yuv, np.uint8).reshape(-1)
+        if (height, width) != self._size or yuv.size != i420_bytes(height, width):
+            raise ValueError("%s: a %d x %d frame of %d bytes in a %d x %d video" % ((self.filename, height, width, yuv.size) + self._size))
+        self._y4m.write(b"FRAME\n")
+        self._y4m.write(memoryview(yuv))
+        self._y4m.flush()
+
     def write(self, rgb):
+        if self._y4m is not None:
+            self.write_i420(rgb_to_i420(np.asarray(rgb, np.uint8)), rgb.shape[0], rgb.shape[1])
+            return
         if self._frames is not None:
             self._frames.append(np.array(rgb))      # a copy, always: the caller's frame may be a view of a ring slot that a later chunk overwrites
             return
@@ -110,6 +260,9 @@ class VideoWriter:
             self._av.mux(pkt)
 
     def close(self):
+        if self._y4m is not None:
+            self._y4m.close()
+            return
         if self._frames is not None:
             np.save(self.filename, np.stack(self._frames) if self._frames else np.zeros((0, 0, 0, 3), np.uint8))
             return

@@ -7,7 +7,10 @@ The engine call comes in two forms.  `step` is one blocking call per chunk on ar
 copy, in series with the kernels).  `stream=Stream(...)` is the streamed schedule: the decode thread writes the frames straight into a
 ring of page-locked slots, the main thread submits chunk k + 1 before it waits for chunk k (the library's submit_* / wait, two submissions
 in flight: one's copies run under the other's kernels), and the results land in a second ring whose slots the sink thread gives back when
-the chunk has been written.  Both forms hand the same bytes to `write_chunk` and `dump`."""
+the chunk has been written.  Both forms hand the same bytes to `write_chunk` and `dump`.
+
+A source of I420 frames (a .y4m: FrameReader.i420) is read without a conversion: `i420=True` makes a frame its packed planes - read_i420
+straight into the stacked array or the ring slot - for an engine whose frame_format is "i420"."""
 import collections
 import os
 import queue
@@ -60,16 +63,36 @@ class Stream:
 
     Nothing a band keeps past the return of write_chunk / dump may be a view of `res`: the slot is overwritten by a later chunk."""
 
-    def __init__(self, host, frame, results, submit, collect, wait=None):
+    def __init__(self, host, frame, results, submit, collect, wait=None, i420=False):
         self.host, self.frame, self.results, self.submit, self.collect = host, frame, dict(results), submit, collect
+        self.i420 = i420            # frame = ((i420_bytes,), uint8): the decode thread fills a slot's rows with src.read_i420
         self.wait = wait if wait is not None else host.wait
 
 
-def chunks(src, first, last, chunk, halo=0):
+def frame_formats(model, yin, yout, h, w):
+    """Tells a band's engine what the loop will hand it (`yin`: the source is a .y4m, its frames are I420 planes) and wants back (`yout`: the
+    output is a .y4m): engine.frame_format / rgb_format.  -> the extra keyword arguments of the engine's calls: the frame size, which I420
+    arrays do not carry.  With neither, nothing is touched and nothing is passed: the calls are what they were before .y4m."""
+    if not (yin or yout) and getattr(model, "frame_format", "rgb") == "rgb" and getattr(model, "rgb_format", "rgb") == "rgb":
+        return {}
+    model.frame_format, model.rgb_format = "i420" if yin else "rgb", "i420" if yout else "rgb"
+    return {"size": (h, w)} if yin or yout else {}
+
+
+def i420_bytes(h, w):
+    return h * w + 2 * ((h + 1) // 2) * ((w + 1) // 2)
+
+
+def chunks(src, first, last, chunk, halo=0, i420=False):
     """(start, frames) for start in range(first, last, chunk): frames = src[start : min(last, start + chunk) + halo] as one array, read up to two
-    chunks ahead on one worker thread.  halo = 1 for pairs: chunk k's last frame is chunk k+1's first."""
+    chunks ahead on one worker thread.  halo = 1 for pairs: chunk k's last frame is chunk k+1's first.  i420: [frames, i420_bytes] planes."""
+    def load_i420(s):
+        a = np.empty((min(last, s + chunk) + halo - s, i420_bytes(src.height, src.width)), np.uint8)
+        for j in range(len(a)):
+            src.read_i420(s + j, a[j])
+        return a
     load = lambda s: np.stack([src[i] for i in range(s, min(last, s + chunk) + halo)])      # noqa: E731
-    return prefetch(load, range(first, last, chunk))
+    return prefetch(load_i420 if i420 else load, range(first, last, chunk))
 
 
 def _run_streamed(src, first, last, chunk, halo, st, emit, n_scalars):
@@ -125,7 +148,10 @@ def _run_streamed(src, first, last, chunk, halo, st, emit, n_scalars):
                         pass
                 m = min(last, s + chunk) - s
                 for j in range(m + halo):
-                    slot[j] = src[s + j]
+                    if st.i420:
+                        src.read_i420(s + j, slot[j])
+                    else:
+                        slot[j] = src[s + j]
                 ready.put((s, slot, m, None))
         except BaseException as e:          # noqa: BLE001 - handed to the main thread
             ready.put((None, None, 0, e))
@@ -199,7 +225,7 @@ def _run_streamed(src, first, last, chunk, halo, st, emit, n_scalars):
     return rows
 
 
-def run_sharded(rk, src, n_units, chunk, halo, out_path, est_bytes, step, write_chunk, dump=None, n_scalars=0, ctx=None, stream=None):
+def run_sharded(rk, src, n_units, chunk, halo, out_path, est_bytes, step, write_chunk, dump=None, n_scalars=0, ctx=None, stream=None, i420=False):
     """This rank's shard of `n_units` units (frames; pairs with halo = 1) of `src`, `chunk` units per engine call.
 
     step(start, frames) -> (video_chunk, dump_payload, scalar_rows)   main thread: the engine call.  video_chunk is {name: array}, what
@@ -208,6 +234,7 @@ def run_sharded(rk, src, n_units, chunk, halo, out_path, est_bytes, step, write_
                                                                        chunks, from the relay's drain for the other ranks'
     dump(start, dump_payload)                                          every rank, sink thread: the per-unit files
     stream                                                             a Stream: the streamed schedule instead of `step` (which is then unused)
+    i420                                                               the blocking loop's frames are src's I420 planes (chunks(i420=True))
 
     `out_path` and `est_bytes` (what the other ranks may park in the spool) are shard.Relay's; `ctx` is rk.gather's.  n_scalars is an argument
     because a rank with an empty shard has to know whether to join the gather.  Returns the float32 [n_units, n_scalars] rows of every rank in
@@ -230,7 +257,7 @@ def run_sharded(rk, src, n_units, chunk, halo, out_path, est_bytes, step, write_
         rows = np.concatenate(rows) if rows else []
     else:
         sink = AsyncSink(depth=2)
-        for s, frames in chunks(src, first, last, chunk, halo):
+        for s, frames in chunks(src, first, last, chunk, halo, i420=i420):
             video, payload, scalars = step(s, frames)
             sink.submit(emit, s, video, payload)
             if n_scalars:

@@ -43,8 +43,8 @@ def create_metadata(path):
 
 
 def is_video(path):
-    # the reference tests the suffix only (:65-67); .npy frame stacks are this repo's offline stand-in
-    return path.endswith(".mp4") or path.endswith(".npy")
+    # the reference tests the suffix only (:65-67); .npy frame stacks are this repo's offline stand-in, .y4m the container that needs no library
+    return path.endswith(".mp4") or path.endswith(".npy") or path.endswith(".y4m")
 
 
 def add_band(metadata, band, url="", folder=""):

@@ -17,10 +17,10 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, create_folder, open_rgb, write_ply, write_rgb  # noqa: E402
+from common.io import FrameReader, VideoWriter, create_folder, is_y4m, open_rgb, write_ply, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.cli import begin, end, synthetic_or_exit  # noqa: E402
-from common.loop import Stream, run_sharded, stream_enabled  # noqa: E402
+from common.loop import Stream, frame_formats, i420_bytes, run_sharded, stream_enabled  # noqa: E402
 from common.meta import is_video  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
@@ -137,7 +137,8 @@ def process_video(a):
     src = FrameReader(a.input)
     n = len(src)
     h, w = src[0].shape[:2]
-    out = VideoWriter(width=w, height=h, frame_rate=src.fps, filename=a.output) if rk.main else None
+    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=a.output) if rk.main else None
+    yin, yout = src.i420, is_y4m(a.output)      # a .y4m on either side: its I420 frames go to / come from the engine as they are
     out_folder = os.path.dirname(a.output)
     if a.subpath:
         if data:
@@ -148,25 +149,27 @@ def process_video(a):
         init_model(device=rk.device)
     first, last = rk.frames(n)
     want_depth = bool(a.npy or a.subpath)
+    fmt = frame_formats(model, yin, yout, h, w)
+    frame = ((i420_bytes(h, w),), np.uint8) if yin else (src[0].shape, np.uint8)
 
     def step(_s, frames):
-        depth, rgb, mn, mx = model.infer_batch(frames, want_depth=want_depth, want_rgb=True, flip=_flip())
+        depth, rgb, mn, mx = model.infer_batch(frames, want_depth=want_depth, want_rgb=True, flip=_flip(), **fmt)
         return {"rgb": rgb}, depth, np.stack([mn, mx], 1)
 
     # the streamed loop (common/loop.py): the same call as submit_batch / wait on the loop's page-locked rings - one array per result asked for
-    results = {"rgb": ((h, w, 3), np.uint8), "mn": ((), np.float32), "mx": ((), np.float32)}
+    results = {"rgb": ((i420_bytes(h, w),) if yout else (h, w, 3), np.uint8), "mn": ((), np.float32), "mx": ((), np.float32)}
     if want_depth:
         results["depth"] = ((h, w), np.float32)
 
     def submit(_s, frames, res):
-        model.submit_batch(frames, out_rgb=res["rgb"], out_depth=res.get("depth"), out_min=res["mn"], out_max=res["mx"], flip=_flip())
+        model.submit_batch(frames, out_rgb=res["rgb"], out_depth=res.get("depth"), out_min=res["mn"], out_max=res["mx"], flip=_flip(), **fmt)
 
     def collect(_s, res):
         return {"rgb": res["rgb"]}, res.get("depth"), np.stack([res["mn"], res["mx"]], 1)
 
     def write_chunk(_s, c):          # rank 0 only: the video frames, chunk after chunk in order
         for f in c["rgb"]:
-            out.write(f)
+            out.write_i420(f, h, w) if yout else out.write(f)
 
     def dump(s, depth):              # sink thread: .npy / .png dumps (reference :215-225); nothing of `depth` is kept past the return
         for j in range(len(depth)):
@@ -174,9 +177,9 @@ def process_video(a):
                 np.save(os.path.join(a.subpath, "{:05d}.npy".format(s + j)), depth[j])
             write_depth_png(os.path.join(a.subpath, "{:05d}.png".format(s + j)), depth[j])
 
-    stream = Stream(model, (src[0].shape, np.uint8), results, submit, collect) if stream_enabled(STREAM_MIN_CHUNKS, -(-(last - first) // BATCH)) else None
+    stream = Stream(model, frame, results, submit, collect, i420=yin) if stream_enabled(STREAM_MIN_CHUNKS, -(-(last - first) // BATCH)) else None
     mm = run_sharded(rk, src, n, BATCH, 0, a.output, (n - (last - first)) * h * w * 3, step, write_chunk,
-                     dump if a.subpath else None, n_scalars=2, ctx=model, stream=stream)
+                     dump if a.subpath else None, n_scalars=2, ctx=model, stream=stream, i420=yin)
     if not rk.main:
         return
     lo, hi = [float(v) for v in mm[:, 0]], [float(v) for v in mm[:, 1]]

@@ -17,6 +17,7 @@ honoured here).
 import argparse
 import copy
 import os
+import shutil
 import sys
 
 import numpy as np
@@ -110,14 +111,19 @@ def main(argv=None):
         if args.subpath:
             sub = os.path.join(os.path.dirname(args.output), args.subpath)
             create_folder(sub)
-        h, w = src[0].shape[:2]
-        out = VideoWriter(width=w, height=h, frame_rate=args.fps, filename=args.output)
-        for i in range(len(src)):
-            f = src[i]
-            if sub:
-                write_rgb(os.path.join(sub, str(i).zfill(6) + ".png"), (255 - f).astype(np.uint8))     # rgba.py:96
-            out.write(f)
-        out.close()
+        if src.i420:            # a .y4m carries no audio to drop and its frames are what the bands read: the file is copied, rate and all
+            shutil.copyfile(args.input, args.output)
+            for i in range(len(src) if sub else 0):
+                write_rgb(os.path.join(sub, str(i).zfill(6) + ".png"), (255 - src[i]).astype(np.uint8))
+        else:
+            h, w = src[0].shape[:2]
+            out = VideoWriter(width=w, height=h, frame_rate=args.fps, filename=args.output)
+            for i in range(len(src)):
+                f = src[i]
+                if sub:
+                    write_rgb(os.path.join(sub, str(i).zfill(6) + ".png"), (255 - f).astype(np.uint8))     # rgba.py:96
+                out.write(f)
+            out.close()
     else:
         if args.rgbd != "none":
             print("rgba: --rgbd %s is ignored for a still image, as in the reference (process_image): the whole image is the rgba band" % args.rgbd,

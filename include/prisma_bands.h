@@ -230,6 +230,32 @@ int pb_rgbd_boxes(int H, int W, int side, int rgb_box[4], int depth_box[4]);
 int pb_rgbd_depth(pb_ctx *ctx, const uint8_t *frames, int n, int H, int W, int side, uint8_t *depth_out, float *heat_out);
 int pb_rgbd_depth_dev(pb_ctx *ctx, const uint8_t *frames, int n, int H, int W, int side, uint8_t *depth_out, float *heat_out);
 
+/* I420 frames (YUV4MPEG2 `.y4m` clips; what decoders produce and encoders consume): 8 bit, 4:2:0, BT.601 limited range.  A frame is H W bytes
+ * of Y, then ceil(H / 2) ceil(W / 2) bytes of Cb, then as many of Cr - pb_i420_bytes(H, W) in all, 1.5 per pixel where RGB takes 3; frames are
+ * packed.  The arithmetic is the published 8-bit integer form, exact, `>>` an arithmetic shift, clip8 a clamp to 0 .. 255:
+ *   RGB -> I420   Y = ((66 R + 129 G + 25 B + 128) >> 8) + 16 per pixel; per 2 x 2 block, of R, G, B = (sum of the block's 4 samples + 2) >> 2 with
+ *                 pixel indices clamped to the frame: Cb = ((-38 R - 74 G + 112 B + 128) >> 8) + 128, Cr = ((112 R - 94 G - 18 B + 128) >> 8) + 128
+ *   I420 -> RGB   C = Y - 16, D = Cb - 128, E = Cr - 128 with the chroma sample plane[y >> 1][x >> 1]: R = clip8((298 C + 409 E + 128) >> 8),
+ *                 G = clip8((298 C - 100 D - 208 E + 128) >> 8), B = clip8((298 C + 516 D + 128) >> 8)
+ * It is not swscale's fixed-point code: against ffmpeg the bytes agree to an LSB or two (PARITY UNPINNED); tests/yuv_ref.py pins them by
+ * restatement, on all 2^24 inputs of either direction.
+ * pb_i420_to_rgb / pb_rgb_to_i420: host pointers, blocking, in chunks of "host_chunk" frames (default 8) whose copies overlap the kernel;
+ * page-locked caller arrays are addressed directly.  The *_dev forms: device pointers, asynchronous on the ctx stream; pb_sync() waits.  No
+ * alignment is needed (with W % 16 == 0 and 16-byte aligned device pointers the kernels move 16 bytes per access).  Work on any ctx.
+ *   yuv : n x pb_i420_bytes(H, W) bytes      rgb : n x H x W x 3 uint8
+ * Inside the bands: pb_set_option(ctx, "frames_i420", 1) makes the host-pointer and submit entry points of the ctx - pb_depth_infer_batch,
+ * pb_depth_submit_batch, pb_flow_infer_sequence(_masks), pb_flow_submit_sequence(_masks), pb_mask_infer_batch - take `frames` as n (F) x
+ * pb_i420_bytes(H, W) bytes; pb_set_option(ctx, "rgb_out_i420", 1) makes their rgb_out (the mask band's mask_out: its id image counts as one) hold
+ * I420 frames of the output size - pb_i420_bytes(H, W) per frame for depth and mask, pb_i420_bytes(sh, sw) per pair and direction for flow.  The
+ * I420 chunk crosses PCIe, the conversion runs on the ctx stream next to the band's kernels.  Every other output is untouched, and the *_dev band
+ * entry points keep RGB (their callers hold device memory and can call the *_dev conversions themselves).  Both options are 0 by default and can
+ * be set only while no submission is outstanding. */
+int64_t pb_i420_bytes(int H, int W);
+int pb_i420_to_rgb(pb_ctx *ctx, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out);
+int pb_i420_to_rgb_dev(pb_ctx *ctx, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out);
+int pb_rgb_to_i420(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
+int pb_rgb_to_i420_dev(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
+
 /* Network input size for an H x W frame: keep-aspect lower-bound resize to 518, each side a
  * multiple of 14 (bands/d_anything/util/transform.py:100-166). */
 int pb_depth_net_size(int H, int W, int *net_h, int *net_w);
@@ -391,7 +417,7 @@ int pb_set_profiling(pb_ctx *ctx, int enabled);
  * 12 128x96 (convolutions with N <= 96) (prisma_amd/csrc/gemm.h; the other round-1 variants were measured slower and
  * removed); "tile_n96" (process-wide) = 0: convolutions with 64 < N <= 96 stay on the 128x128 tile, 1: auto gives them
  * the 128x96 tile (same bytes), 2 (default): ... and the packed-channel K axis where the weights carry one (RAFT encoder
- * stage 2: another summation order); "host_chunk", "op_splitk": see INTEGRATION.md. */
+ * stage 2: another summation order); "host_chunk", "op_splitk": see INTEGRATION.md; "frames_i420", "rgb_out_i420" (0 | 1): see pb_i420_bytes. */
 int pb_set_option(pb_ctx *ctx, const char *key, int value);
 int pb_get_kernel_stats(pb_ctx *ctx, pb_kernel_stat *out, int cap);
 

@@ -337,6 +337,7 @@ void pb_destroy(pb_ctx *c) {
     for (hipEvent_t e : c->pending) { hipEventSynchronize(e); hipEventDestroy(e); }
     c->pipe.release();
     c->mpipe.release();
+    for (void *p : c->yuv) if (p) { hipStreamSynchronize(c->stream); hipFree(p); }
     // pb_host_alloc blocks: the submissions that wrote into them were waited for above and the copy streams are drained and gone
     for (void *p : c->host_blocks) hipHostFree(p);
     if (c->depth) delete c->depth;
@@ -372,21 +373,32 @@ static int depth_host_pipeline(pb_ctx *c, const uint8_t *frames, int n, int H, i
     // profiles/r06j_pcie_entry_points.txt; copies are hidden ACROSS calls by the asynchronous form instead.)
     const int mb = c->depth->max_batch();
     const int cap = std::min(n, c->host_chunk > 0 ? std::min(c->host_chunk, mb) : mb);
-    const bool pin_in = pb_is_pinned(frames, (size_t)n * px * 3), pin_d = pb_is_pinned(depth_out, (size_t)n * px * 4),
-               pin_r = pb_is_pinned(rgb_out, (size_t)n * px * 3);
+    // "frames_i420" / "rgb_out_i420": the lane carries I420 frames, converted on the ctx stream into / out of the RGB buffer the band works on
+    const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out;
+    const size_t fin = yin ? (size_t)i420_frame_bytes(H, W) : px * 3, fout = yout ? (size_t)i420_frame_bytes(H, W) : px * 3;
+    const bool pin_in = pb_is_pinned(frames, (size_t)n * fin), pin_d = pb_is_pinned(depth_out, (size_t)n * px * 4),
+               pin_r = pb_is_pinned(rgb_out, (size_t)n * fout);
     const bool pin_mm = (!min_out || pb_is_pinned(min_out, (size_t)n * 4)) && (!max_out || pb_is_pinned(max_out, (size_t)n * 4));
     if (submit) PB_CHECK(pin_in && (!depth_out || pin_d) && (!rgb_out || pin_r) && pin_mm, PB_ERR_ARG,
                          "depth submit: every buffer of an asynchronous call must be page-locked host memory (hipHostMalloc / hipHostRegister / torch pin_memory)");
-    const ChunkLane lanes[4] = {{(void *)frames, px * 3, false, pin_in},
+    const ChunkLane lanes[4] = {{(void *)frames, fin, false, pin_in},
                                 {depth_out, depth_out ? px * 4 : 0, true, pin_d},
-                                {rgb_out, rgb_out ? px * 3 : 0, true, pin_r},
+                                {rgb_out, rgb_out ? fout : 0, true, pin_r},
                                 {min_out, 4, true, pin_mm, true, max_out, 2}};
+    if (yin) PB_TRY(c->yuv_grow(0, (size_t)cap * px * 3));
+    if (yout) PB_TRY(c->yuv_grow(1, (size_t)cap * px * 3));
     TimerSpan span(c->depth->timer);
     const ChunkPipe::Lane *l = c->pipe.lane;
     return run_chunks(c, n, cap, 0, lanes, 4, submit, [&](int slot, int, int m) {
         float *mn = (float *)l[3].d[slot];
-        return c->depth->infer((const uint8_t *)l[0].d[slot], m, H, W, (float *)(depth_out ? l[1].d[slot] : nullptr),
-                               (uint8_t *)(rgb_out ? l[2].d[slot] : nullptr), mn, mn + cap, flip);
+        const uint8_t *in = (const uint8_t *)l[0].d[slot];
+        if (yin) {
+            PB_TRY(launch_i420_to_rgb(c->stream, in, m, H, W, (uint8_t *)c->yuv[0]));
+            in = (const uint8_t *)c->yuv[0];
+        }
+        uint8_t *enc = (uint8_t *)(rgb_out ? (yout ? c->yuv[1] : l[2].d[slot]) : nullptr);
+        PB_TRY(c->depth->infer(in, m, H, W, (float *)(depth_out ? l[1].d[slot] : nullptr), enc, mn, mn + cap, flip));
+        return yout ? launch_rgb_to_i420(c->stream, enc, m, H, W, (uint8_t *)l[2].d[slot]) : 0;
     });
 }
 
@@ -467,22 +479,33 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     // ... and no chunk larger than one infer() call accepts at this size (flow_chunk.h: 4K frames); a single pair that does not fit goes
     // through as it is and the engine refuses it
     cp = std::max(1, c->raft->chunk_pairs(cp, H, W, scale, dirs));
-    const size_t fpx = (size_t)H * W * 3, px = (size_t)sh * sw * dirs, np = (size_t)pairs;      // px: result pixels of a pair, all directions
-    const bool pin_in = pb_is_pinned(frames, (size_t)F * fpx), pin_f = pb_is_pinned(flow_out, np * px * 8), pin_r = pb_is_pinned(rgb_out, np * px * 3),
+    const size_t px = (size_t)sh * sw * dirs, np = (size_t)pairs;      // px: result pixels of a pair, all directions
+    // "frames_i420" / "rgb_out_i420": I420 frames in, I420 frames of the output size out (dirs of them per pair), converted on the ctx stream
+    const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out;
+    const size_t fpx = yin ? (size_t)i420_frame_bytes(H, W) : (size_t)H * W * 3, rpx = yout ? (size_t)i420_frame_bytes(sh, sw) * dirs : px * 3;
+    const bool pin_in = pb_is_pinned(frames, (size_t)F * fpx), pin_f = pb_is_pinned(flow_out, np * px * 8), pin_r = pb_is_pinned(rgb_out, np * rpx),
                pin_k = pb_is_pinned(mask_out, np * px), pin_m = !maxdisp_out || pb_is_pinned(maxdisp_out, np * dirs * 4);
     if (submit) PB_CHECK(pin_in && (!flow_out || pin_f) && (!rgb_out || pin_r) && (!mask_out || pin_k) && pin_m, PB_ERR_ARG,
                          "flow submit: every buffer of an asynchronous call must be page-locked host memory (hipHostMalloc / hipHostRegister / torch pin_memory)");
     const ChunkLane lanes[5] = {{(void *)frames, fpx, false, pin_in},
                                 {flow_out, flow_out ? px * 8 : 0, true, pin_f},
-                                {rgb_out, rgb_out ? px * 3 : 0, true, pin_r},
+                                {rgb_out, rgb_out ? rpx : 0, true, pin_r},
                                 {maxdisp_out, (size_t)dirs * 4, true, pin_m, true},
                                 {mask_out, mask_out ? px : 0, true, pin_k}};
+    if (yin) PB_TRY(c->yuv_grow(0, (size_t)(cp + 1) * H * W * 3));
+    if (yout) PB_TRY(c->yuv_grow(1, (size_t)cp * px * 3));
     TimerSpan span(c->raft->timer);
     const ChunkPipe::Lane *l = c->pipe.lane;
     return run_chunks(c, pairs, cp, 1, lanes, 5, submit, [&](int slot, int, int m) {
-        return c->raft->infer((const uint8_t *)l[0].d[slot], m + 1, H, W, scale, iters, backward, (float *)(flow_out ? l[1].d[slot] : nullptr),
-                              (uint8_t *)(rgb_out ? l[2].d[slot] : nullptr), (float *)l[3].d[slot], (uint8_t *)(mask_out ? l[4].d[slot] : nullptr),
-                              alpha1, alpha2);
+        const uint8_t *in = (const uint8_t *)l[0].d[slot];
+        if (yin) {
+            PB_TRY(launch_i420_to_rgb(c->stream, in, m + 1, H, W, (uint8_t *)c->yuv[0]));
+            in = (const uint8_t *)c->yuv[0];
+        }
+        uint8_t *enc = (uint8_t *)(rgb_out ? (yout ? c->yuv[1] : l[2].d[slot]) : nullptr);
+        PB_TRY(c->raft->infer(in, m + 1, H, W, scale, iters, backward, (float *)(flow_out ? l[1].d[slot] : nullptr), enc, (float *)l[3].d[slot],
+                              (uint8_t *)(mask_out ? l[4].d[slot] : nullptr), alpha1, alpha2));
+        return yout ? launch_rgb_to_i420(c->stream, enc, m * dirs, sh, sw, (uint8_t *)l[2].d[slot]) : 0;
     });
 }
 
@@ -559,35 +582,44 @@ int pb_mask_infer_batch(pb_ctx *c, const uint8_t *frames, int n, int H, int W, f
     PB_HIP(hipSetDevice(c->device));
     const size_t fb = (size_t)H * W * 3, bytes = (size_t)n * fb;
     const int cf = c->mask->frames_per_chunk(), chunks = (n + cf - 1) / cf;
-    const bool pin_in = pb_is_pinned(frames, bytes), pin_out = pb_is_pinned(mask_out, bytes);
+    // "frames_i420" / "rgb_out_i420": the copies move I420 frames (fi / fo bytes each) into / out of whole-batch I420 buffers (ctx yuv[0] / yuv[1]);
+    // the chunk's frames are converted into d_in once its copy has arrived, its id images out of d_out before they leave - both on the ctx stream
+    const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0;
+    const size_t fi = yin ? (size_t)i420_frame_bytes(H, W) : fb, fo = yout ? (size_t)i420_frame_bytes(H, W) : fb;
+    const bool pin_in = pb_is_pinned(frames, n * fi), pin_out = pb_is_pinned(mask_out, n * fo);
     MaskPipe &mp = c->mpipe;
     PB_TRY(mp.ensure(bytes, !pin_in, !pin_out, chunks));
+    if (yin) PB_TRY(c->yuv_grow(0, n * fi));
+    if (yout) PB_TRY(c->yuv_grow(1, n * fo));
     PipeDrain drain{mp.s_in, c->stream, mp.s_out};              // no exit, error or not, leaves a copy into caller memory in flight
+    char *up = yin ? (char *)c->yuv[0] : (char *)mp.d_in, *down = yout ? (char *)c->yuv[1] : (char *)mp.d_out;
     for (int i = 0; i < chunks; ++i) {
-        const size_t off = (size_t)i * cf * fb, len = (size_t)std::min(cf, n - i * cf) * fb;
+        const size_t off = (size_t)i * cf * fi, len = (size_t)std::min(cf, n - i * cf) * fi;
         const void *src = frames + off;
         if (!pin_in) { memcpy((char *)mp.h_in + off, src, len); src = (char *)mp.h_in + off; }
-        PB_HIP(hipMemcpyAsync((char *)mp.d_in + off, src, len, hipMemcpyHostToDevice, mp.s_in));
+        PB_HIP(hipMemcpyAsync(up + off, src, len, hipMemcpyHostToDevice, mp.s_in));
         PB_HIP(hipEventRecord(mp.ev_in[i], mp.s_in));
     }
     hipStream_t st = c->stream;
     char *dst = pin_out ? (char *)mask_out : (char *)mp.h_out;
-    c->mask->chunk_begin = [&mp, st, cf](int first, int) -> int {
+    c->mask->chunk_begin = [&mp, st, cf, yin, up, fi, fb, H, W](int first, int m) -> int {
         PB_HIP(hipStreamWaitEvent(st, mp.ev_in[first / cf], 0));
+        if (yin) PB_TRY(launch_i420_to_rgb(st, (const uint8_t *)up + (size_t)first * fi, m, H, W, (uint8_t *)mp.d_in + (size_t)first * fb));
         return 0;
     };
-    c->mask->chunk_end = [&mp, st, cf, fb, dst](int first, int m) -> int {
-        const size_t off = (size_t)first * fb;
+    c->mask->chunk_end = [&mp, st, cf, fb, fo, dst, yout, down, H, W](int first, int m) -> int {
+        const size_t off = (size_t)first * fo;
+        if (yout) PB_TRY(launch_rgb_to_i420(st, (const uint8_t *)mp.d_out + (size_t)first * fb, m, H, W, (uint8_t *)down + off));
         PB_HIP(hipEventRecord(mp.ev_done[first / cf], st));
         PB_HIP(hipStreamWaitEvent(mp.s_out, mp.ev_done[first / cf], 0));
-        PB_HIP(hipMemcpyAsync(dst + off, (char *)mp.d_out + off, (size_t)m * fb, hipMemcpyDeviceToHost, mp.s_out));
+        PB_HIP(hipMemcpyAsync(dst + off, down + off, (size_t)m * fo, hipMemcpyDeviceToHost, mp.s_out));
         return 0;
     };
     const int r = c->mask->infer((const uint8_t *)mp.d_in, n, H, W, confidence, keep, n_keep, (uint8_t *)mp.d_out);
     c->mask->chunk_begin = nullptr; c->mask->chunk_end = nullptr;     // (an argument error returns before infer() consumes them)
     if (r) return r;
     PB_HIP(hipStreamSynchronize(mp.s_out));
-    if (!pin_out) memcpy(mask_out, mp.h_out, bytes);
+    if (!pin_out) memcpy(mask_out, mp.h_out, n * fo);
     return 0;
 }
 
@@ -682,6 +714,11 @@ int pb_set_option(pb_ctx *c, const char *key, int value) {
     else if (!strcmp(key, "conv_tile")) (c->band ? c->band->conv_tile : c->conv_tile) = value;
     else if (!strcmp(key, "host_chunk")) c->host_chunk = value;
     else if (!strcmp(key, "op_splitk")) c->op_splitk = value;
+    else if (!strcmp(key, "frames_i420") || !strcmp(key, "rgb_out_i420")) {
+        PB_CHECK(value == 0 || value == 1, PB_ERR_ARG, "option '%s' is 0 or 1, not %d", key, value);
+        PB_CHECK(c->pending.empty(), PB_ERR_STATE, "option '%s': a submission of this ctx is still outstanding (pb_wait first)", key);
+        (key[0] == 'f' ? c->frames_i420 : c->rgb_out_i420) = value;
+    }
     else if (!strcmp(key, "tile_n96")) pb_gemm_set_n96(value);         // process-wide (gemm.h): A/B of the 128 x 96 tile inside one test process
     else PB_CHECK(false, PB_ERR_ARG, "unknown option '%s'", key);
     return 0;
@@ -864,5 +901,38 @@ int pb_rgbd_depth(pb_ctx *c, const uint8_t *frames, int n, int H, int W, int sid
                                (uint8_t *)(depth_out ? l[1].d[slot] : nullptr), (float *)(heat_out ? l[2].d[slot] : nullptr));
     });
 }
+
+// ---- I420 <-> RGB on their own (yuv.hip): .y4m frames for callers that hold them, the still dumps, the tests --------------------------------
+int64_t pb_i420_bytes(int H, int W) { return i420_frame_bytes(H, W); }
+
+int pb_i420_to_rgb_dev(pb_ctx *c, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out) {
+    PB_CHECK(c && yuv && rgb_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "i420_to_rgb: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    return launch_i420_to_rgb(c->stream, yuv, n, H, W, rgb_out);
+}
+
+int pb_rgb_to_i420_dev(pb_ctx *c, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out) {
+    PB_CHECK(c && rgb && yuv_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "rgb_to_i420: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    return launch_rgb_to_i420(c->stream, rgb, n, H, W, yuv_out);
+}
+
+// Host-pointer variants: run_chunks over chunks of "host_chunk" (default 8) frames; lanes: the frames in, the converted frames out.
+static int yuv_host_pipeline(pb_ctx *c, const uint8_t *in, int n, int H, int W, uint8_t *out, bool to_rgb) {
+    PB_CHECK(c && in && out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "%s: bad arguments", to_rgb ? "i420_to_rgb" : "rgb_to_i420");
+    PB_CHECK(c->pending.empty(), PB_ERR_STATE, "%s: a submission of this ctx is still outstanding (pb_wait first)", to_rgb ? "i420_to_rgb" : "rgb_to_i420");
+    PB_HIP(hipSetDevice(c->device));
+    const size_t fy = (size_t)i420_frame_bytes(H, W), fr = (size_t)H * W * 3, fi = to_rgb ? fy : fr, fo = to_rgb ? fr : fy;
+    const int cap = std::min(n, c->host_chunk > 0 ? c->host_chunk : 8);
+    const ChunkLane lanes[2] = {{(void *)in, fi, false, pb_is_pinned(in, n * fi)}, {out, fo, true, pb_is_pinned(out, n * fo)}};
+    const ChunkPipe::Lane *l = c->pipe.lane;
+    return run_chunks(c, n, cap, 0, lanes, 2, false, [&](int slot, int, int m) {
+        return to_rgb ? launch_i420_to_rgb(c->stream, (const uint8_t *)l[0].d[slot], m, H, W, (uint8_t *)l[1].d[slot])
+                      : launch_rgb_to_i420(c->stream, (const uint8_t *)l[0].d[slot], m, H, W, (uint8_t *)l[1].d[slot]);
+    });
+}
+
+int pb_i420_to_rgb(pb_ctx *c, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out) { return yuv_host_pipeline(c, yuv, n, H, W, rgb_out, true); }
+int pb_rgb_to_i420(pb_ctx *c, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out) { return yuv_host_pipeline(c, rgb, n, H, W, yuv_out, false); }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "engine.h"
 #include "mask_engine.h"
 #include "raft_engine.h"
+#include "yuv.h"
 
 void pb_cubic_taps(int src, int dst, int *idx, float *wt);   // engine.hip
 
@@ -147,6 +148,22 @@ struct pb_ctx {
     char *still_buf = nullptr;
     size_t still_cap = 0;
     std::mutex still_mu;
+    // pb_set_option("frames_i420" / "rgb_out_i420"): the host-pointer and submit entry points of the bands take their frames / give their rgb_out as
+    // I420.  The conversions run on the ctx stream between the copies and the band, through one RGB buffer per direction (yuv[0]: the frames the
+    // band reads - for the mask band the I420 frames instead, its pipeline keeps whole-batch RGB buffers of its own; yuv[1]: what it encodes).
+    // Work on one stream runs in order, so chunks and submissions share them; they grow only while the stream is idle.
+    int frames_i420 = 0, rgb_out_i420 = 0;
+    void *yuv[2] = {};
+    size_t yuv_cap[2] = {};
+    int yuv_grow(int k, size_t need) {
+        if (need <= yuv_cap[k]) return 0;
+        PB_HIP(hipStreamSynchronize(stream));
+        if (yuv[k]) PB_HIP(hipFree(yuv[k]));
+        yuv[k] = nullptr; yuv_cap[k] = 0;
+        PB_HIP(hipMalloc(&yuv[k], need));
+        yuv_cap[k] = need;
+        return 0;
+    }
     // pb_depth_point_cloud_dev: the per-frame min / max words of the un-flip, on the ctx stream (the host variant keeps its own in still_buf)
     unsigned *pcl_mm = nullptr;
     int pcl_mm_cap = 0;

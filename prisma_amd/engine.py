@@ -38,6 +38,14 @@ def net_size(H: int, W: int) -> Tuple[int, int]:
     return nh.value, nw.value
 
 
+def i420_bytes(H: int, W: int) -> int:
+    """bytes of one I420 frame (a .y4m's): H W of Y, then ceil(H / 2) ceil(W / 2) each of Cb and Cr (pb_i420_bytes, needs no GPU)"""
+    return int(_lib.load().pb_i420_bytes(int(H), int(W)))
+
+
+FORMATS = ("rgb", "i420")       # what `frames` / the encoded `rgb` results of a band context are: [..., H, W, 3] or [..., i420_bytes(H, W)] uint8
+
+
 RGBD_SIDES = ("left", "right", "top", "bottom")      # where the depth is: pb_rgbd_boxes' side 0 .. 3
 
 
@@ -90,6 +98,7 @@ class _Ctx:
         self.lib = _lib.load()
         self.ctx = C.c_void_p()
         self._host = {}                 # host_empty(): address -> (weak reference to the array, bytes)
+        self._formats = ["rgb", "rgb"]  # frame_format, rgb_format
 
     def close(self):
         """pb_destroy: waits for the submissions still outstanding, then frees everything the context owns - the host_empty() arrays
@@ -240,6 +249,78 @@ class _Ctx:
         n * Hd * Wd * 3 bytes (no alignment needed), heat_ptr n * Hd * Wd floats; 0 = not wanted"""
         check(self.lib.pb_rgbd_depth_dev(self.ctx, C.c_void_p(frames_ptr), n, H, W, _rgbd_side(side), C.c_void_p(depth_ptr or None),
                                          C.c_void_p(heat_ptr or None)))
+
+    # I420 <-> RGB (pb_i420_to_rgb / pb_rgb_to_i420: 8 bit, BT.601 limited range, exact integers; tests/yuv_ref.py restates them)
+    def i420_to_rgb(self, yuv: np.ndarray, H: int, W: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """I420 frames uint8 [n, i420_bytes(H, W)] (or one frame [i420_bytes]) -> RGB uint8 [n, H, W, 3] ([H, W, 3]); `out`: the caller's own
+        (page-locked) array"""
+        yuv = np.ascontiguousarray(yuv, np.uint8)
+        fb = i420_bytes(H, W)
+        assert yuv.ndim in (1, 2) and yuv.shape[-1] == fb, (yuv.shape, fb)
+        shape = yuv.shape[:-1] + (H, W, 3)
+        rgb = np.empty(shape, np.uint8) if out is None else out
+        assert rgb.shape == shape and rgb.dtype == np.uint8 and rgb.flags.c_contiguous
+        check(self.lib.pb_i420_to_rgb(self.ctx, _ptr(yuv), yuv.size // fb, H, W, _ptr(rgb)))
+        return rgb
+
+    def rgb_to_i420(self, rgb: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """RGB uint8 [n, H, W, 3] (or one frame [H, W, 3]) -> I420 frames uint8 [n, i420_bytes(H, W)] ([i420_bytes]); `out`: the caller's own
+        (page-locked) array"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert rgb.ndim in (3, 4) and rgb.shape[-1] == 3, rgb.shape
+        H, W = rgb.shape[-3:-1]
+        shape = rgb.shape[:-3] + (i420_bytes(H, W),)
+        yuv = np.empty(shape, np.uint8) if out is None else out
+        assert yuv.shape == shape and yuv.dtype == np.uint8 and yuv.flags.c_contiguous
+        check(self.lib.pb_rgb_to_i420(self.ctx, _ptr(rgb), rgb.size // (H * W * 3), H, W, _ptr(yuv)))
+        return yuv
+
+    def i420_to_rgb_dev(self, yuv_ptr: int, n: int, H: int, W: int, rgb_ptr: int):
+        """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_i420_to_rgb_dev): sync() waits"""
+        check(self.lib.pb_i420_to_rgb_dev(self.ctx, C.c_void_p(yuv_ptr), n, H, W, C.c_void_p(rgb_ptr)))
+
+    def rgb_to_i420_dev(self, rgb_ptr: int, n: int, H: int, W: int, yuv_ptr: int):
+        check(self.lib.pb_rgb_to_i420_dev(self.ctx, C.c_void_p(rgb_ptr), n, H, W, C.c_void_p(yuv_ptr)))
+
+    # what the band's host-pointer and submit calls take as `frames` and give as their encoded `rgb` (the mask band: its id images):
+    # "rgb" (the default) or "i420" - pb_set_option "frames_i420" / "rgb_out_i420".  With frame_format = "i420" those calls take
+    # [n, i420_bytes(H, W)] arrays and need `size=(H, W)`; with rgb_format = "i420" their rgb arrays are [..., i420_bytes(h, w)] of the output size.
+    @property
+    def frame_format(self) -> str:
+        return self._formats[0]
+
+    @frame_format.setter
+    def frame_format(self, fmt: str):
+        self._set_format(0, "frames_i420", fmt)
+
+    @property
+    def rgb_format(self) -> str:
+        return self._formats[1]
+
+    @rgb_format.setter
+    def rgb_format(self, fmt: str):
+        self._set_format(1, "rgb_out_i420", fmt)
+
+    def _set_format(self, which: int, key: str, fmt: str):
+        if fmt not in FORMATS:
+            raise ValueError("format %r: one of %s" % (fmt, ", ".join(FORMATS)))
+        self.set_option(key, FORMATS.index(fmt))
+        self._formats[which] = fmt
+
+    def _frames_in(self, frames: np.ndarray, size) -> Tuple[int, int, int]:
+        """(n, H, W) of a call's `frames` in the context's frame_format, shape checked"""
+        if self.frame_format == "i420":
+            assert size is not None, "frame_format 'i420': the call needs size=(H, W)"
+            H, W = int(size[0]), int(size[1])
+            assert frames.ndim == 2 and frames.shape[1] == i420_bytes(H, W), (frames.shape, H, W)
+            return frames.shape[0], H, W
+        n, H, W, ch = frames.shape
+        assert ch == 3 and (size is None or tuple(size) == (H, W))
+        return n, H, W
+
+    def rgb_shape(self, h: int, w: int) -> tuple:
+        """trailing shape of one encoded result frame in the context's rgb_format"""
+        return (i420_bytes(h, w),) if self.rgb_format == "i420" else (h, w, 3)
 
     def set_option(self, key: str, value: int):
         check(self.lib.pb_set_option(self.ctx, key.encode(), int(value)))
@@ -1153,30 +1234,29 @@ class DepthAnything(_Ctx):
         self.max_batch = max_batch
 
     def infer_batch(self, frames: np.ndarray, want_depth: bool = True, want_rgb: bool = True, flip: bool = True,
-                    out_depth: Optional[np.ndarray] = None, out_rgb: Optional[np.ndarray] = None):
+                    out_depth: Optional[np.ndarray] = None, out_rgb: Optional[np.ndarray] = None, size=None):
         """frames uint8 [n,H,W,3] RGB -> (depth f32 [n,H,W] | None, rgb u8 [n,H,W,3] | None, min [n], max [n]).
         out_depth / out_rgb: caller-owned result arrays (e.g. views of page-locked memory, which the library's copy engines then
-        write directly - no staging copy)."""
+        write directly - no staging copy).  frame_format / rgb_format "i420": frames [n, i420_bytes(H, W)] with size=(H, W) / rgb of that shape."""
         frames = np.ascontiguousarray(frames, np.uint8)
-        n, H, W, ch = frames.shape
-        assert ch == 3
+        n, H, W = self._frames_in(frames, size)
         depth = (out_depth if out_depth is not None else np.empty((n, H, W), np.float32)) if want_depth else None
-        rgb = (out_rgb if out_rgb is not None else np.empty((n, H, W, 3), np.uint8)) if want_rgb else None
+        rgb = (out_rgb if out_rgb is not None else np.empty((n,) + self.rgb_shape(H, W), np.uint8)) if want_rgb else None
         assert depth is None or (depth.dtype == np.float32 and depth.shape == (n, H, W) and depth.flags.c_contiguous)
-        assert rgb is None or (rgb.dtype == np.uint8 and rgb.shape == (n, H, W, 3) and rgb.flags.c_contiguous)
+        assert rgb is None or (rgb.dtype == np.uint8 and rgb.shape == (n,) + self.rgb_shape(H, W) and rgb.flags.c_contiguous)
         mn, mx = np.empty(n, np.float32), np.empty(n, np.float32)
         check(self.lib.pb_depth_infer_batch(self.ctx, _ptr(frames), n, H, W, _ptr(depth), _ptr(rgb), _ptr(mn),
                                             _ptr(mx), int(flip)))
         return depth, rgb, mn, mx
 
     def submit_batch(self, frames: np.ndarray, out_rgb: Optional[np.ndarray] = None, out_depth: Optional[np.ndarray] = None,
-                     out_min: Optional[np.ndarray] = None, out_max: Optional[np.ndarray] = None, flip: bool = True):
+                     out_min: Optional[np.ndarray] = None, out_max: Optional[np.ndarray] = None, flip: bool = True, size=None):
         """Asynchronous infer_batch (pb_depth_submit_batch): every array - `frames` and each given output - must be a C-contiguous view of
         PAGE-LOCKED memory (`host_empty()`, or torch `pin_memory()` + `.numpy()`); returns after the enqueue, `wait()` returns (depth, rgb, min, max) once they are
         filled.  Up to two submissions may be in flight per context: the second one's uploads run under the first one's kernels."""
-        n, H, W, ch = frames.shape
-        assert ch == 3 and frames.dtype == np.uint8 and frames.flags.c_contiguous
-        for a, dt, shp in ((out_rgb, np.uint8, (n, H, W, 3)), (out_depth, np.float32, (n, H, W)), (out_min, np.float32, (n,)), (out_max, np.float32, (n,))):
+        n, H, W = self._frames_in(frames, size)
+        assert frames.dtype == np.uint8 and frames.flags.c_contiguous
+        for a, dt, shp in ((out_rgb, np.uint8, (n,) + self.rgb_shape(H, W)), (out_depth, np.float32, (n, H, W)), (out_min, np.float32, (n,)), (out_max, np.float32, (n,))):
             assert a is None or (a.dtype == dt and a.shape == shp and a.flags.c_contiguous)
         check(self.lib.pb_depth_submit_batch(self.ctx, _ptr(frames), n, H, W, _ptr(out_depth), _ptr(out_rgb), _ptr(out_min), _ptr(out_max), int(flip)))
         self._hold((out_depth, out_rgb, out_min, out_max), frames, out_depth, out_rgb, out_min, out_max)
@@ -1230,52 +1310,55 @@ class FlowRaft(_Ctx):
 
     def infer_sequence(self, frames: np.ndarray, scale: float = 0.75, iters: int = 12, backward: bool = False,
                        want_flow: bool = True, want_rgb: bool = True, out_flow: Optional[np.ndarray] = None,
-                       out_rgb: Optional[np.ndarray] = None):
+                       out_rgb: Optional[np.ndarray] = None, size=None):
         """frames uint8 [F,H,W,3] -> (flow f32 [F-1,dirs,sh,sw,2] | None, rgb u8 [F-1,dirs,sh,sw,3] | None, maxdisp [F-1,dirs]).
-        out_flow / out_rgb: caller-owned result arrays (page-locked ones are written by the copy engines directly)."""
+        out_flow / out_rgb: caller-owned result arrays (page-locked ones are written by the copy engines directly).
+        frame_format / rgb_format "i420": frames [F, i420_bytes(H, W)] with size=(H, W) / rgb [F-1, dirs, i420_bytes(sh, sw)]."""
         frames = np.ascontiguousarray(frames, np.uint8)
-        F, H, W, ch = frames.shape
-        assert ch == 3 and F >= 2
+        F, H, W = self._frames_in(frames, size)
+        assert F >= 2
         sh, sw = flow_out_size(H, W, scale)
         d = 2 if backward else 1
+        rshape = (F - 1, d) + self.rgb_shape(sh, sw)
         flow = (out_flow if out_flow is not None else np.empty((F - 1, d, sh, sw, 2), np.float32)) if want_flow else None
-        rgb = (out_rgb if out_rgb is not None else np.empty((F - 1, d, sh, sw, 3), np.uint8)) if want_rgb else None
+        rgb = (out_rgb if out_rgb is not None else np.empty(rshape, np.uint8)) if want_rgb else None
         assert flow is None or (flow.dtype == np.float32 and flow.shape == (F - 1, d, sh, sw, 2) and flow.flags.c_contiguous)
-        assert rgb is None or (rgb.dtype == np.uint8 and rgb.shape == (F - 1, d, sh, sw, 3) and rgb.flags.c_contiguous)
+        assert rgb is None or (rgb.dtype == np.uint8 and rgb.shape == rshape and rgb.flags.c_contiguous)
         mx = np.empty((F - 1, d), np.float32)
         check(self.lib.pb_flow_infer_sequence(self.ctx, _ptr(frames), F, H, W, C.c_float(scale), iters, int(backward),
                                               _ptr(flow), _ptr(rgb), _ptr(mx)))
         return flow, rgb, mx
 
     def submit_sequence(self, frames: np.ndarray, scale: float = 0.75, iters: int = 12, backward: bool = False,
-                        out_flow: Optional[np.ndarray] = None, out_rgb: Optional[np.ndarray] = None, out_max: Optional[np.ndarray] = None):
+                        out_flow: Optional[np.ndarray] = None, out_rgb: Optional[np.ndarray] = None, out_max: Optional[np.ndarray] = None, size=None):
         """Asynchronous infer_sequence (pb_flow_submit_sequence): page-locked arrays only (see DepthAnything.submit_batch); `wait()` returns
         (flow, rgb, maxdisp)."""
-        F, H, W, ch = frames.shape
-        assert ch == 3 and F >= 2 and frames.dtype == np.uint8 and frames.flags.c_contiguous
+        F, H, W = self._frames_in(frames, size)
+        assert F >= 2 and frames.dtype == np.uint8 and frames.flags.c_contiguous
         sh, sw = flow_out_size(H, W, scale)
         d = 2 if backward else 1
-        for a, dt, shp in ((out_flow, np.float32, (F - 1, d, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, d, sh, sw, 3)), (out_max, np.float32, (F - 1, d))):
+        for a, dt, shp in ((out_flow, np.float32, (F - 1, d, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, d) + self.rgb_shape(sh, sw)), (out_max, np.float32, (F - 1, d))):
             assert a is None or (a.dtype == dt and a.shape == shp and a.flags.c_contiguous)
         check(self.lib.pb_flow_submit_sequence(self.ctx, _ptr(frames), F, H, W, C.c_float(scale), iters, int(backward), _ptr(out_flow), _ptr(out_rgb), _ptr(out_max)))
         self._hold((out_flow, out_rgb, out_max), frames, out_flow, out_rgb, out_max)
 
     def infer_sequence_masks(self, frames: np.ndarray, scale: float = 0.75, iters: int = 12, alpha_1: float = 0.05,
                              alpha_2: float = 0.5, want_flow: bool = True, want_rgb: bool = True, out_flow: Optional[np.ndarray] = None,
-                             out_rgb: Optional[np.ndarray] = None, out_mask: Optional[np.ndarray] = None):
+                             out_rgb: Optional[np.ndarray] = None, out_mask: Optional[np.ndarray] = None, size=None):
         """Both directions plus the forward/backward consistency masks (bands/flow_raft.py:58-64):
         -> (flow | None, rgb | None, maxdisp [F-1,2], mask bool [F-1,2,sh,sw]).  The same chunked three-stage pipeline as infer_sequence;
         out_flow / out_rgb / out_mask (uint8): caller-owned result arrays, page-locked ones are written by the copy engines directly."""
         frames = np.ascontiguousarray(frames, np.uint8)
-        F, H, W, ch = frames.shape
-        assert ch == 3 and F >= 2
+        F, H, W = self._frames_in(frames, size)
+        assert F >= 2
         sh, sw = flow_out_size(H, W, scale)
+        rshape = (F - 1, 2) + self.rgb_shape(sh, sw)
         flow = (out_flow if out_flow is not None else np.empty((F - 1, 2, sh, sw, 2), np.float32)) if want_flow else None
-        rgb = (out_rgb if out_rgb is not None else np.empty((F - 1, 2, sh, sw, 3), np.uint8)) if want_rgb else None
+        rgb = (out_rgb if out_rgb is not None else np.empty(rshape, np.uint8)) if want_rgb else None
         mx = np.empty((F - 1, 2), np.float32)
         mask = out_mask if out_mask is not None else np.empty((F - 1, 2, sh, sw), np.uint8)
         assert flow is None or (flow.dtype == np.float32 and flow.shape == (F - 1, 2, sh, sw, 2) and flow.flags.c_contiguous)
-        assert rgb is None or (rgb.dtype == np.uint8 and rgb.shape == (F - 1, 2, sh, sw, 3) and rgb.flags.c_contiguous)
+        assert rgb is None or (rgb.dtype == np.uint8 and rgb.shape == rshape and rgb.flags.c_contiguous)
         assert mask.dtype == np.uint8 and mask.shape == (F - 1, 2, sh, sw) and mask.flags.c_contiguous
         check(self.lib.pb_flow_infer_sequence_masks(self.ctx, _ptr(frames), F, H, W, C.c_float(scale), iters,
                                                     C.c_float(alpha_1), C.c_float(alpha_2), _ptr(flow), _ptr(rgb), _ptr(mx),
@@ -1284,14 +1367,14 @@ class FlowRaft(_Ctx):
 
     def submit_sequence_masks(self, frames: np.ndarray, scale: float = 0.75, iters: int = 12, alpha_1: float = 0.05, alpha_2: float = 0.5,
                               out_flow: Optional[np.ndarray] = None, out_rgb: Optional[np.ndarray] = None, out_max: Optional[np.ndarray] = None,
-                              out_mask: Optional[np.ndarray] = None):
+                              out_mask: Optional[np.ndarray] = None, size=None):
         """Asynchronous infer_sequence_masks (pb_flow_submit_sequence_masks): page-locked arrays only (see DepthAnything.submit_batch;
         host_empty() gives them); out_mask (uint8 [F-1, 2, sh, sw]) is required.  `wait()` returns (flow, rgb, maxdisp, mask.view(bool))."""
-        F, H, W, ch = frames.shape
-        assert ch == 3 and F >= 2 and frames.dtype == np.uint8 and frames.flags.c_contiguous
+        F, H, W = self._frames_in(frames, size)
+        assert F >= 2 and frames.dtype == np.uint8 and frames.flags.c_contiguous
         assert out_mask is not None, "submit_sequence_masks: out_mask is required"
         sh, sw = flow_out_size(H, W, scale)
-        for a, dt, shp in ((out_flow, np.float32, (F - 1, 2, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, 2, sh, sw, 3)), (out_max, np.float32, (F - 1, 2)),
+        for a, dt, shp in ((out_flow, np.float32, (F - 1, 2, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, 2) + self.rgb_shape(sh, sw)), (out_max, np.float32, (F - 1, 2)),
                            (out_mask, np.uint8, (F - 1, 2, sh, sw))):
             assert a is None or (a.dtype == dt and a.shape == shp and a.flags.c_contiguous)
         check(self.lib.pb_flow_submit_sequence_masks(self.ctx, _ptr(frames), F, H, W, C.c_float(scale), iters, C.c_float(alpha_1), C.c_float(alpha_2),
@@ -1417,16 +1500,15 @@ class MaskMMDet(_Ctx):
         check(self.lib.pb_create(C.byref(self.ctx), device, b"mask_mmdet", arr, len(keep), C.byref(c), C.sizeof(c)))
         self._hw = None
 
-    def infer_batch(self, frames: np.ndarray, confidence: float = 0.5, keep_classes=None, out: Optional[np.ndarray] = None) -> np.ndarray:
+    def infer_batch(self, frames: np.ndarray, confidence: float = 0.5, keep_classes=None, out: Optional[np.ndarray] = None, size=None) -> np.ndarray:
         """frames uint8 [n,H,W,3] RGB -> uint8 [n,H,W,3] accumulated masks of the kept classes.  Calls of more than max_batch frames are
         pipelined (chunk i's id images return while chunk i + 1 runs); `out`: a caller-owned result array (a page-locked one is written by
-        the copy engine directly)."""
+        the copy engine directly).  frame_format / rgb_format "i420": frames [n, i420_bytes(H, W)] with size=(H, W) / id images of that shape."""
         frames = np.ascontiguousarray(frames, np.uint8)
-        n, H, W, ch = frames.shape
-        assert ch == 3
+        n, H, W = self._frames_in(frames, size)
         if out is None:
-            out = np.empty_like(frames)
-        assert out.dtype == np.uint8 and out.shape == frames.shape and out.flags.c_contiguous
+            out = np.empty((n,) + self.rgb_shape(H, W), np.uint8)
+        assert out.dtype == np.uint8 and out.shape == (n,) + self.rgb_shape(H, W) and out.flags.c_contiguous
         ids = None if keep_classes is None else np.ascontiguousarray(keep_classes, np.int32)
         check(self.lib.pb_mask_infer_batch(self.ctx, _ptr(frames), n, H, W, C.c_float(confidence), _ptr(ids),
                                            0 if ids is None else len(ids), _ptr(out)))
