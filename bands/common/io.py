@@ -17,6 +17,7 @@ from fractions import Fraction
 
 import numpy as np
 
+from .resize import resize_rgb
 from .yuv import i420_bytes, i420_to_rgb, rgb_to_i420
 
 Y4M_MAGIC = b"YUV4MPEG2"
@@ -206,13 +207,17 @@ class FrameReader:
 class VideoWriter:
     """write(uint8 HxWx3) / close().  .mp4 -> PyAV libx264 crf 15 (io.py:246-305); .npy -> frame stack; .y4m -> I420 frames appended to
     the file as they come (nothing is kept in memory), the header written with the first frame and that frame's own size (no rescale, as
-    the .npy writer), write_i420(planes, h, w) for frames that already are I420 (the engines' "rgb_out_i420" results)."""
+    the .npy writer), write_i420(planes, h, w) for frames that already are I420 (the engines' "rgb_out_i420" results).
+    rescale=True (a .y4m writer's; the flow bands pass it, whose frames are `--scale` times the clip's): the video has the width and height
+    the writer was opened with, as the reference's has (io.py:297 rescales every frame to them).  write() resizes a frame of another size
+    on the host (common/resize.py: bilinear with two taps, where PyAV's reformat runs swscale's), write_i420 takes frames of that size only."""
 
-    def __init__(self, width, height, frame_rate, filename):
+    def __init__(self, width, height, frame_rate, filename, rescale=False):
         self.filename, self._frames, self._av, self._y4m = filename, None, None, None
         self.i420 = is_y4m(filename)
         if self.i420:
-            self._rate, self._size = as_rate(frame_rate), None
+            # rescale: the size is the writer's, not the first frame's
+            self._rate, self._size, self._rescale, self._started = as_rate(frame_rate), (int(height), int(width)) if rescale else None, bool(rescale), False
             self._y4m = open(filename, "wb")
         elif filename.endswith(".npy"):
             self._frames = []
@@ -239,7 +244,9 @@ class VideoWriter:
             raise RuntimeError("%s: write_i420 is a .y4m writer's" % self.filename)
         if self._size is None:
             self._size = (height, width)
-            self._y4m.write(y4m_header(width, height, self._rate))
+        if not self._started:       # the header goes out with the first frame
+            self._started = True
+            self._y4m.write(y4m_header(self._size[1], self._size[0], self._rate))
         yuv = np.ascontiguousarray(yuv, np.uint8).reshape(-1)
         if (height, width) != self._size or yuv.size != i420_bytes(height, width):
             raise ValueError("%s: a %d x %d frame of %d bytes in a %d x %d video" % ((self.filename, height, width, yuv.size) + self._size))
@@ -249,6 +256,8 @@ class VideoWriter:
 
     def write(self, rgb):
         if self._y4m is not None:
+            if self._rescale and tuple(rgb.shape[:2]) != self._size:
+                rgb = resize_rgb(rgb, *self._size)
             self.write_i420(rgb_to_i420(np.asarray(rgb, np.uint8)), rgb.shape[0], rgb.shape[1])
             return
         if self._frames is not None:

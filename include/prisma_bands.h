@@ -256,6 +256,28 @@ int pb_i420_to_rgb_dev(pb_ctx *ctx, const uint8_t *yuv, int n, int H, int W, uin
 int pb_rgb_to_i420(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
 int pb_rgb_to_i420_dev(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
 
+/* Bilinear resize of RGB frames, 8 bit, exact integers, half-pixel centres (the geometry of swscale's SWS_BILINEAR, which the reference's
+ * VideoWriter applies to every frame that is not of the video's size).  Per axis, for output index x of n_out from n_in samples:
+ *   num = (2 x + 1) n_in - n_out (may be negative);  i0 = floor(num / (2 n_out)), r = num - i0 * 2 n_out (0 <= r < 2 n_out);
+ *   w = (256 r + n_out) / (2 n_out) (integer division, 0 .. 256);  taps clamp(i0, 0, n_in - 1) and clamp(i0 + 1, 0, n_in - 1)
+ * and per channel, with the taps' four samples p00 p01 (row i0) p10 p11 (row i0 + 1):
+ *   out = ((256 - wy) ((256 - wx) p00 + wx p01) + wy ((256 - wx) p10 + wx p11) + 32768) >> 16
+ * Rounded once; an equal-size call is a byte copy.  The same two taps serve a shrink - swscale widens its filter there, this does not.  It is
+ * not swscale's fixed-point code (PARITY UNPINNED: PyAV is not in the build image); tests/resize_ref.py pins the bytes by restatement and
+ * Pillow's bilinear pins the geometry to one LSB on enlargements.  A side above 16384 is refused.
+ * pb_rgb_resize: host pointers, blocking, in chunks of "host_chunk" frames (default 8); pb_rgb_resize_dev: device pointers, asynchronous on the
+ * ctx stream.  out_i420 = 0: out is n x H x W x 3 uint8; 1: n x pb_i420_bytes(H, W) bytes, byte for byte pb_rgb_to_i420 of the resized frames,
+ * which are never written to memory.  No alignment is needed (with W % 16 == 0 and a 16-byte aligned device `out` the kernels store 16 bytes
+ * per access).  Work on any ctx.
+ *   rgb : n x sh x sw x 3 uint8
+ * Inside the flow bands: pb_set_option(ctx, "rgb_out_full", 1) makes the rgb_out of pb_flow_infer_sequence(_masks) and
+ * pb_flow_submit_sequence(_masks) hold frames of the clip's H x W instead of the band's sh x sw (pb_flow_out_size) - H x W x 3 bytes per pair
+ * and direction, or pb_i420_bytes(H, W) with "rgb_out_i420" - resized on the ctx stream from the sh x sw frame the band encodes: what a video
+ * of the clip's size (the reference's VideoWriter) holds.  flow_out, mask_out and maxdisp_out stay at sh x sw, the *_dev entry points keep
+ * sh x sw RGB, and where (sh, sw) == (H, W) the option changes no byte.  0 by default; set only while no submission is outstanding. */
+int pb_rgb_resize(pb_ctx *ctx, const uint8_t *rgb, int n, int sh, int sw, int H, int W, uint8_t *out, int out_i420);
+int pb_rgb_resize_dev(pb_ctx *ctx, const uint8_t *rgb, int n, int sh, int sw, int H, int W, uint8_t *out, int out_i420);
+
 /* Network input size for an H x W frame: keep-aspect lower-bound resize to 518, each side a
  * multiple of 14 (bands/d_anything/util/transform.py:100-166). */
 int pb_depth_net_size(int H, int W, int *net_h, int *net_w);
@@ -417,7 +439,8 @@ int pb_set_profiling(pb_ctx *ctx, int enabled);
  * 12 128x96 (convolutions with N <= 96) (prisma_amd/csrc/gemm.h; the other round-1 variants were measured slower and
  * removed); "tile_n96" (process-wide) = 0: convolutions with 64 < N <= 96 stay on the 128x128 tile, 1: auto gives them
  * the 128x96 tile (same bytes), 2 (default): ... and the packed-channel K axis where the weights carry one (RAFT encoder
- * stage 2: another summation order); "host_chunk", "op_splitk": see INTEGRATION.md; "frames_i420", "rgb_out_i420" (0 | 1): see pb_i420_bytes. */
+ * stage 2: another summation order); "host_chunk", "op_splitk": see INTEGRATION.md; "frames_i420", "rgb_out_i420" (0 | 1): see pb_i420_bytes;
+ * "rgb_out_full" (0 | 1): see pb_rgb_resize. */
 int pb_set_option(pb_ctx *ctx, const char *key, int value);
 int pb_get_kernel_stats(pb_ctx *ctx, pb_kernel_stat *out, int cap);
 

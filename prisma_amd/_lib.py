@@ -87,6 +87,8 @@ SYMBOLS = {
     "pb_i420_to_rgb_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_rgb_to_i420": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_rgb_to_i420_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_rgb_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
+    "pb_rgb_resize_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "pb_depth_net_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "pb_depth_get_stage": (C.c_int64, [_P, C.c_char_p, _P, C.c_int64, C.POINTER(C.c_int64)]),
     "pb_mask_infer_batch": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P]),

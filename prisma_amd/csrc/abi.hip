@@ -481,8 +481,11 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     cp = std::max(1, c->raft->chunk_pairs(cp, H, W, scale, dirs));
     const size_t px = (size_t)sh * sw * dirs, np = (size_t)pairs;      // px: result pixels of a pair, all directions
     // "frames_i420" / "rgb_out_i420": I420 frames in, I420 frames of the output size out (dirs of them per pair), converted on the ctx stream
-    const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out;
-    const size_t fpx = yin ? (size_t)i420_frame_bytes(H, W) : (size_t)H * W * 3, rpx = yout ? (size_t)i420_frame_bytes(sh, sw) * dirs : px * 3;
+    // "rgb_out_full": ... of the clip's H x W, resized on the ctx stream from the sh x sw frames the band encodes (nothing to do at scale 1)
+    const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out, full = c->rgb_out_full != 0 && rgb_out && (sh != H || sw != W);
+    const int rh = full ? H : sh, rw = full ? W : sw;                  // the size of an rgb_out frame
+    const size_t fpx = yin ? (size_t)i420_frame_bytes(H, W) : (size_t)H * W * 3,
+                 rpx = (yout ? (size_t)i420_frame_bytes(rh, rw) : (size_t)rh * rw * 3) * dirs;
     const bool pin_in = pb_is_pinned(frames, (size_t)F * fpx), pin_f = pb_is_pinned(flow_out, np * px * 8), pin_r = pb_is_pinned(rgb_out, np * rpx),
                pin_k = pb_is_pinned(mask_out, np * px), pin_m = !maxdisp_out || pb_is_pinned(maxdisp_out, np * dirs * 4);
     if (submit) PB_CHECK(pin_in && (!flow_out || pin_f) && (!rgb_out || pin_r) && (!mask_out || pin_k) && pin_m, PB_ERR_ARG,
@@ -493,7 +496,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
                                 {maxdisp_out, (size_t)dirs * 4, true, pin_m, true},
                                 {mask_out, mask_out ? px : 0, true, pin_k}};
     if (yin) PB_TRY(c->yuv_grow(0, (size_t)(cp + 1) * H * W * 3));
-    if (yout) PB_TRY(c->yuv_grow(1, (size_t)cp * px * 3));
+    if (yout || full) PB_TRY(c->yuv_grow(1, (size_t)cp * px * 3));
     TimerSpan span(c->raft->timer);
     const ChunkPipe::Lane *l = c->pipe.lane;
     return run_chunks(c, pairs, cp, 1, lanes, 5, submit, [&](int slot, int, int m) {
@@ -502,9 +505,10 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
             PB_TRY(launch_i420_to_rgb(c->stream, in, m + 1, H, W, (uint8_t *)c->yuv[0]));
             in = (const uint8_t *)c->yuv[0];
         }
-        uint8_t *enc = (uint8_t *)(rgb_out ? (yout ? c->yuv[1] : l[2].d[slot]) : nullptr);
+        uint8_t *enc = (uint8_t *)(rgb_out ? (yout || full ? c->yuv[1] : l[2].d[slot]) : nullptr);
         PB_TRY(c->raft->infer(in, m + 1, H, W, scale, iters, backward, (float *)(flow_out ? l[1].d[slot] : nullptr), enc, (float *)l[3].d[slot],
                               (uint8_t *)(mask_out ? l[4].d[slot] : nullptr), alpha1, alpha2));
+        if (full) return launch_rgb_resize(c->stream, enc, m * dirs, sh, sw, H, W, (uint8_t *)l[2].d[slot], yout);
         return yout ? launch_rgb_to_i420(c->stream, enc, m * dirs, sh, sw, (uint8_t *)l[2].d[slot]) : 0;
     });
 }
@@ -714,10 +718,10 @@ int pb_set_option(pb_ctx *c, const char *key, int value) {
     else if (!strcmp(key, "conv_tile")) (c->band ? c->band->conv_tile : c->conv_tile) = value;
     else if (!strcmp(key, "host_chunk")) c->host_chunk = value;
     else if (!strcmp(key, "op_splitk")) c->op_splitk = value;
-    else if (!strcmp(key, "frames_i420") || !strcmp(key, "rgb_out_i420")) {
+    else if (!strcmp(key, "frames_i420") || !strcmp(key, "rgb_out_i420") || !strcmp(key, "rgb_out_full")) {
         PB_CHECK(value == 0 || value == 1, PB_ERR_ARG, "option '%s' is 0 or 1, not %d", key, value);
         PB_CHECK(c->pending.empty(), PB_ERR_STATE, "option '%s': a submission of this ctx is still outstanding (pb_wait first)", key);
-        (key[0] == 'f' ? c->frames_i420 : c->rgb_out_i420) = value;
+        (key[0] == 'f' ? c->frames_i420 : key[8] == 'i' ? c->rgb_out_i420 : c->rgb_out_full) = value;
     }
     else if (!strcmp(key, "tile_n96")) pb_gemm_set_n96(value);         // process-wide (gemm.h): A/B of the 128 x 96 tile inside one test process
     else PB_CHECK(false, PB_ERR_ARG, "unknown option '%s'", key);
@@ -934,5 +938,26 @@ static int yuv_host_pipeline(pb_ctx *c, const uint8_t *in, int n, int H, int W, 
 
 int pb_i420_to_rgb(pb_ctx *c, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out) { return yuv_host_pipeline(c, yuv, n, H, W, rgb_out, true); }
 int pb_rgb_to_i420(pb_ctx *c, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out) { return yuv_host_pipeline(c, rgb, n, H, W, yuv_out, false); }
+
+// ---- bilinear RGB resize on its own (resize.hip): what "rgb_out_full" runs behind the flow bands, for callers that hold frames, and the tests ----
+int pb_rgb_resize_dev(pb_ctx *c, const uint8_t *rgb, int n, int sh, int sw, int H, int W, uint8_t *out, int out_i420) {
+    PB_CHECK(c && rgb && out && n > 0 && sh > 0 && sw > 0 && H > 0 && W > 0, PB_ERR_ARG, "rgb_resize: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    return launch_rgb_resize(c->stream, rgb, n, sh, sw, H, W, out, out_i420 != 0);
+}
+
+// Host-pointer variant: run_chunks over chunks of "host_chunk" (default 8) frames; lanes: the frames in, the resized frames out.
+int pb_rgb_resize(pb_ctx *c, const uint8_t *rgb, int n, int sh, int sw, int H, int W, uint8_t *out, int out_i420) {
+    PB_CHECK(c && rgb && out && n > 0 && sh > 0 && sw > 0 && H > 0 && W > 0, PB_ERR_ARG, "rgb_resize: bad arguments");
+    PB_CHECK(c->pending.empty(), PB_ERR_STATE, "rgb_resize: a submission of this ctx is still outstanding (pb_wait first)");
+    PB_HIP(hipSetDevice(c->device));
+    const size_t fi = (size_t)sh * sw * 3, fo = out_i420 ? (size_t)i420_frame_bytes(H, W) : (size_t)H * W * 3;
+    const int cap = std::min(n, c->host_chunk > 0 ? c->host_chunk : 8);
+    const ChunkLane lanes[2] = {{(void *)rgb, fi, false, pb_is_pinned(rgb, n * fi)}, {out, fo, true, pb_is_pinned(out, n * fo)}};
+    const ChunkPipe::Lane *l = c->pipe.lane;
+    return run_chunks(c, n, cap, 0, lanes, 2, false, [&](int slot, int, int m) {
+        return launch_rgb_resize(c->stream, (const uint8_t *)l[0].d[slot], m, sh, sw, H, W, (uint8_t *)l[1].d[slot], out_i420 != 0);
+    });
+}
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "engine.h"
 #include "mask_engine.h"
 #include "raft_engine.h"
+#include "resize.h"
 #include "yuv.h"
 
 void pb_cubic_taps(int src, int dst, int *idx, float *wt);   // engine.hip
@@ -152,7 +153,8 @@ struct pb_ctx {
     // I420.  The conversions run on the ctx stream between the copies and the band, through one RGB buffer per direction (yuv[0]: the frames the
     // band reads - for the mask band the I420 frames instead, its pipeline keeps whole-batch RGB buffers of its own; yuv[1]: what it encodes).
     // Work on one stream runs in order, so chunks and submissions share them; they grow only while the stream is idle.
-    int frames_i420 = 0, rgb_out_i420 = 0;
+    // pb_set_option("rgb_out_full"): the flow bands' rgb_out holds frames of the clip's size, resized (resize.hip) out of yuv[1] as well.
+    int frames_i420 = 0, rgb_out_i420 = 0, rgb_out_full = 0;
     void *yuv[2] = {};
     size_t yuv_cap[2] = {};
     int yuv_grow(int k, size_t need) {

@@ -9,3 +9,26 @@ int64_t i420_frame_bytes(int H, int W);
 // 16-byte aligned the kernels move 16 bytes per access.
 int launch_i420_to_rgb(hipStream_t s, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb);
 int launch_rgb_to_i420(hipStream_t s, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv);
+
+// ---- what the kernels of yuv.hip and resize.hip share -------------------------------------------------------------------------------------------
+struct I420Frame {  // plane geometry of one I420 frame
+    int H, W, ch, cw;
+    size_t luma, chroma, bytes;
+    __host__ __device__ I420Frame(int h, int w) : H(h), W(w), ch((h + 1) / 2), cw((w + 1) / 2) {
+        luma = (size_t)H * W;
+        chroma = (size_t)ch * cw;
+        bytes = luma + 2 * chroma;
+    }
+};
+
+// The empty asm keeps the `>> 8` of its argument and the clamp apart.  Left together, hipcc 7 fuses pairs of them into v_ashr_pk_u8_i32 (shift,
+// saturate to u8, pack two) and ORs the result into the output word as if its bits 16 .. 31 were zero; on the MI355X they were not, and the two
+// bytes above such a pair came out as 255 wherever one of the pair's values had been negative (tests/test_gpu_yuv.py, 16 x 64).
+__device__ __forceinline__ unsigned clip8(int v) {
+    asm volatile("" : "+v"(v));
+    return (unsigned)min(max(v, 0), 255);
+}
+
+__device__ __forceinline__ unsigned luma_of(int r, int g, int b) { return (unsigned)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16); }
+__device__ __forceinline__ unsigned cb_of(int r, int g, int b) { return (unsigned)(((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128); }
+__device__ __forceinline__ unsigned cr_of(int r, int g, int b) { return (unsigned)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128); }

@@ -14,18 +14,6 @@
 
 namespace {
 
-// The empty asm keeps the `>> 8` of its argument and the clamp apart.  Left together, hipcc 7 fuses pairs of them into v_ashr_pk_u8_i32 (shift,
-// saturate to u8, pack two) and ORs the result into the output word as if its bits 16 .. 31 were zero; on the MI355X they were not, and the two
-// bytes above such a pair came out as 255 wherever one of the pair's values had been negative (tests/test_gpu_yuv.py, 16 x 64).
-__device__ __forceinline__ unsigned clip8(int v) {
-    asm volatile("" : "+v"(v));
-    return (unsigned)min(max(v, 0), 255);
-}
-
-__device__ __forceinline__ unsigned luma_of(int r, int g, int b) { return (unsigned)(((66 * r + 129 * g + 25 * b + 128) >> 8) + 16); }
-__device__ __forceinline__ unsigned cb_of(int r, int g, int b) { return (unsigned)(((-38 * r - 74 * g + 112 * b + 128) >> 8) + 128); }
-__device__ __forceinline__ unsigned cr_of(int r, int g, int b) { return (unsigned)(((112 * r - 94 * g - 18 * b + 128) >> 8) + 128); }
-
 // one pixel's three output bytes, each in a word of its own
 __device__ __forceinline__ void rgb_of(unsigned y, unsigned cb, unsigned cr, unsigned &r, unsigned &g, unsigned &b) {
     const int c = 298 * ((int)y - 16) + 128, d = (int)cb - 128, e = (int)cr - 128;
@@ -36,15 +24,7 @@ __device__ __forceinline__ void rgb_of(unsigned y, unsigned cb, unsigned cr, uns
 
 __device__ __forceinline__ unsigned byte_of(const unsigned *w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 255u; }
 
-struct Frame {      // plane geometry of one I420 frame
-    int H, W, ch, cw;
-    size_t luma, chroma, bytes;
-    __host__ __device__ Frame(int h, int w) : H(h), W(w), ch((h + 1) / 2), cw((w + 1) / 2) {
-        luma = (size_t)H * W;
-        chroma = (size_t)ch * cw;
-        bytes = luma + 2 * chroma;
-    }
-};
+using Frame = I420Frame;
 
 // ---- 16-byte paths: W % 16 == 0, lane = (frame, block row by, group of 8 blocks gx) ------------------------------------------------------------
 __global__ __launch_bounds__(256) void i420_to_rgb_kernel(const uint8_t *__restrict__ yuv, int H, int W, int64_t lanes, uint8_t *__restrict__ rgb) {

@@ -99,6 +99,7 @@ class _Ctx:
         self.ctx = C.c_void_p()
         self._host = {}                 # host_empty(): address -> (weak reference to the array, bytes)
         self._formats = ["rgb", "rgb"]  # frame_format, rgb_format
+        self._rgb_full = False
 
     def close(self):
         """pb_destroy: waits for the submissions still outstanding, then frees everything the context owns - the host_empty() arrays
@@ -282,6 +283,24 @@ class _Ctx:
     def rgb_to_i420_dev(self, rgb_ptr: int, n: int, H: int, W: int, yuv_ptr: int):
         check(self.lib.pb_rgb_to_i420_dev(self.ctx, C.c_void_p(rgb_ptr), n, H, W, C.c_void_p(yuv_ptr)))
 
+    # bilinear RGB resize (pb_rgb_resize: 8 bit, exact integers, half-pixel centres; tests/resize_ref.py restates it)
+    def rgb_resize(self, rgb: np.ndarray, H: int, W: int, i420: bool = False, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """RGB uint8 [n, sh, sw, 3] (or one frame [sh, sw, 3]) -> RGB uint8 [n, H, W, 3] ([H, W, 3]), or with i420 I420 frames
+        [n, i420_bytes(H, W)] ([i420_bytes]) - the bytes of rgb_to_i420 on the resized frames; `out`: the caller's own (page-locked) array"""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert rgb.ndim in (3, 4) and rgb.shape[-1] == 3, rgb.shape
+        sh, sw = rgb.shape[-3:-1]
+        H, W = int(H), int(W)
+        shape = rgb.shape[:-3] + ((i420_bytes(H, W),) if i420 else (H, W, 3))
+        res = np.empty(shape, np.uint8) if out is None else out
+        assert res.shape == shape and res.dtype == np.uint8 and res.flags.c_contiguous
+        check(self.lib.pb_rgb_resize(self.ctx, _ptr(rgb), rgb.size // (sh * sw * 3), sh, sw, H, W, _ptr(res), int(bool(i420))))
+        return res
+
+    def rgb_resize_dev(self, rgb_ptr: int, n: int, sh: int, sw: int, H: int, W: int, out_ptr: int, i420: bool = False):
+        """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_rgb_resize_dev): sync() waits"""
+        check(self.lib.pb_rgb_resize_dev(self.ctx, C.c_void_p(rgb_ptr), n, sh, sw, H, W, C.c_void_p(out_ptr), int(bool(i420))))
+
     # what the band's host-pointer and submit calls take as `frames` and give as their encoded `rgb` (the mask band: its id images):
     # "rgb" (the default) or "i420" - pb_set_option "frames_i420" / "rgb_out_i420".  With frame_format = "i420" those calls take
     # [n, i420_bytes(H, W)] arrays and need `size=(H, W)`; with rgb_format = "i420" their rgb arrays are [..., i420_bytes(h, w)] of the output size.
@@ -300,6 +319,17 @@ class _Ctx:
     @rgb_format.setter
     def rgb_format(self, fmt: str):
         self._set_format(1, "rgb_out_i420", fmt)
+
+    # flow bands: their `rgb` results have the clip's H x W instead of the band's sh x sw (pb_set_option "rgb_out_full": resized on the GPU, what
+    # a video of the clip's size holds); flow, masks and max displacements stay at sh x sw
+    @property
+    def rgb_full(self) -> bool:
+        return self._rgb_full
+
+    @rgb_full.setter
+    def rgb_full(self, on: bool):
+        self.set_option("rgb_out_full", int(bool(on)))
+        self._rgb_full = bool(on)
 
     def _set_format(self, which: int, key: str, fmt: str):
         if fmt not in FORMATS:
@@ -321,6 +351,10 @@ class _Ctx:
     def rgb_shape(self, h: int, w: int) -> tuple:
         """trailing shape of one encoded result frame in the context's rgb_format"""
         return (i420_bytes(h, w),) if self.rgb_format == "i420" else (h, w, 3)
+
+    def _flow_rgb_shape(self, H: int, W: int, sh: int, sw: int) -> tuple:
+        """trailing shape of one encoded frame of a flow call: the band's sh x sw, or with rgb_full the clip's H x W"""
+        return self.rgb_shape(H, W) if self.rgb_full else self.rgb_shape(sh, sw)
 
     def set_option(self, key: str, value: int):
         check(self.lib.pb_set_option(self.ctx, key.encode(), int(value)))
@@ -1313,13 +1347,14 @@ class FlowRaft(_Ctx):
                        out_rgb: Optional[np.ndarray] = None, size=None):
         """frames uint8 [F,H,W,3] -> (flow f32 [F-1,dirs,sh,sw,2] | None, rgb u8 [F-1,dirs,sh,sw,3] | None, maxdisp [F-1,dirs]).
         out_flow / out_rgb: caller-owned result arrays (page-locked ones are written by the copy engines directly).
-        frame_format / rgb_format "i420": frames [F, i420_bytes(H, W)] with size=(H, W) / rgb [F-1, dirs, i420_bytes(sh, sw)]."""
+        frame_format / rgb_format "i420": frames [F, i420_bytes(H, W)] with size=(H, W) / rgb [F-1, dirs, i420_bytes(sh, sw)].
+        rgb_full: the rgb frames have the clip's size - [F-1, dirs, H, W, 3] / [F-1, dirs, i420_bytes(H, W)] (also of the three calls below)."""
         frames = np.ascontiguousarray(frames, np.uint8)
         F, H, W = self._frames_in(frames, size)
         assert F >= 2
         sh, sw = flow_out_size(H, W, scale)
         d = 2 if backward else 1
-        rshape = (F - 1, d) + self.rgb_shape(sh, sw)
+        rshape = (F - 1, d) + self._flow_rgb_shape(H, W, sh, sw)
         flow = (out_flow if out_flow is not None else np.empty((F - 1, d, sh, sw, 2), np.float32)) if want_flow else None
         rgb = (out_rgb if out_rgb is not None else np.empty(rshape, np.uint8)) if want_rgb else None
         assert flow is None or (flow.dtype == np.float32 and flow.shape == (F - 1, d, sh, sw, 2) and flow.flags.c_contiguous)
@@ -1337,7 +1372,7 @@ class FlowRaft(_Ctx):
         assert F >= 2 and frames.dtype == np.uint8 and frames.flags.c_contiguous
         sh, sw = flow_out_size(H, W, scale)
         d = 2 if backward else 1
-        for a, dt, shp in ((out_flow, np.float32, (F - 1, d, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, d) + self.rgb_shape(sh, sw)), (out_max, np.float32, (F - 1, d))):
+        for a, dt, shp in ((out_flow, np.float32, (F - 1, d, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, d) + self._flow_rgb_shape(H, W, sh, sw)), (out_max, np.float32, (F - 1, d))):
             assert a is None or (a.dtype == dt and a.shape == shp and a.flags.c_contiguous)
         check(self.lib.pb_flow_submit_sequence(self.ctx, _ptr(frames), F, H, W, C.c_float(scale), iters, int(backward), _ptr(out_flow), _ptr(out_rgb), _ptr(out_max)))
         self._hold((out_flow, out_rgb, out_max), frames, out_flow, out_rgb, out_max)
@@ -1352,7 +1387,7 @@ class FlowRaft(_Ctx):
         F, H, W = self._frames_in(frames, size)
         assert F >= 2
         sh, sw = flow_out_size(H, W, scale)
-        rshape = (F - 1, 2) + self.rgb_shape(sh, sw)
+        rshape = (F - 1, 2) + self._flow_rgb_shape(H, W, sh, sw)
         flow = (out_flow if out_flow is not None else np.empty((F - 1, 2, sh, sw, 2), np.float32)) if want_flow else None
         rgb = (out_rgb if out_rgb is not None else np.empty(rshape, np.uint8)) if want_rgb else None
         mx = np.empty((F - 1, 2), np.float32)
@@ -1374,7 +1409,7 @@ class FlowRaft(_Ctx):
         assert F >= 2 and frames.dtype == np.uint8 and frames.flags.c_contiguous
         assert out_mask is not None, "submit_sequence_masks: out_mask is required"
         sh, sw = flow_out_size(H, W, scale)
-        for a, dt, shp in ((out_flow, np.float32, (F - 1, 2, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, 2) + self.rgb_shape(sh, sw)), (out_max, np.float32, (F - 1, 2)),
+        for a, dt, shp in ((out_flow, np.float32, (F - 1, 2, sh, sw, 2)), (out_rgb, np.uint8, (F - 1, 2) + self._flow_rgb_shape(H, W, sh, sw)), (out_max, np.float32, (F - 1, 2)),
                            (out_mask, np.uint8, (F - 1, 2, sh, sw))):
             assert a is None or (a.dtype == dt and a.shape == shp and a.flags.c_contiguous)
         check(self.lib.pb_flow_submit_sequence_masks(self.ctx, _ptr(frames), F, H, W, C.c_float(scale), iters, C.c_float(alpha_1), C.c_float(alpha_2),
