@@ -185,13 +185,14 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
     PB_HIP(hipSetDevice(device_id));
     pb_ctx *c = new pb_ctx();
     c->device = device_id;
+    const CreateEnv env = create_env();         // the create-time switches, read once for this context
     if (!strcmp(band, "depth_anything")) {
         if (!cfg || cfg_bytes != sizeof(pb_depth_cfg) || !weights || n_weights <= 0) {
             delete c;
             PB_CHECK(false, PB_ERR_ARG, "depth_anything: needs a pb_depth_cfg (%zu bytes, got %zu) and weights",
                      sizeof(pb_depth_cfg), cfg_bytes);
         }
-        c->depth = new DepthEngine(device_id, *(const pb_depth_cfg *)cfg);
+        c->depth = new DepthEngine(device_id, *(const pb_depth_cfg *)cfg, env);
         int r = c->depth->load(weights, n_weights);
         if (r) {
             delete c->depth;
@@ -210,12 +211,9 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
             delete c;
             PB_CHECK(false, PB_ERR_ARG, "%s: precision %d unknown", band, prec);
         }
-        c->raft = gm ? new GmflowEngine(device_id) : new RaftEngine(device_id);      // GmflowEngine overrides load / infer
+        c->raft = gm ? new GmflowEngine(device_id, env) : new RaftEngine(device_id, env);      // GmflowEngine overrides load / infer
         c->raft->split_w_ = prec == PB_PREC_SPLIT;
-        {
-            const char *mx = getenv("PB_MX");
-            c->raft->mx_ = !gm && c->raft->split_w_ && !(mx && mx[0] == '0');
-        }
+        c->raft->mx_ = !gm && c->raft->split_w_ && env.mx;
         int r = c->raft->load(weights, n_weights);
         if (r) {
             delete c->raft;
@@ -229,7 +227,7 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
             PB_CHECK(false, PB_ERR_ARG, "mask_mmdet: needs a pb_mask_cfg (%zu bytes, got %zu) and weights", sizeof(pb_mask_cfg),
                      cfg_bytes);
         }
-        c->mask = new MaskEngine(device_id, *(const pb_mask_cfg *)cfg);
+        c->mask = new MaskEngine(device_id, *(const pb_mask_cfg *)cfg, env);
         int r = c->mask->load(weights, n_weights);
         if (r) {
             delete c->mask;
@@ -473,7 +471,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     const int dirs = backward ? 2 : 1, pairs = F - 1;
     // (default 32 pairs since round 6 - was 16: a chunk's launches are the same kernels on fewer rows, and 16-pair chunks cost the bench clip more in
     // launch tails and re-encoded halo frames than their hidden copies gave; profiles/r06j_pcie_entry_points.txt)
-    static const int env_cp = pb_env_int("PB_FLOW_HOST_PAIRS", 32);
+    const int env_cp = launch_env().flow_host_pairs;
     int cp = c->host_chunk > 0 ? c->host_chunk : (env_cp > 0 ? env_cp : 32);
     if (pairs <= cp + cp / 4) cp = pairs;                       // a short tail is not worth a chunk of its own
     // ... and no chunk larger than one infer() call accepts at this size (flow_chunk.h: 4K frames); a single pair that does not fit goes

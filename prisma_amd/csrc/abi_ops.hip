@@ -1374,9 +1374,10 @@ int pb_op_gemm_bench(pb_ctx *c, int M, int N, int K, int tile, int epi, int iter
         if (epi == 12) { g.cKW = 5; g.cPad = 0; g.cPadX = 2; g.cKH = 1; }
         else { g.cKW = 3; g.cPad = 1; g.cKH = 3; g.cTapInner = epi == 11; }
     }
-    g.ablate = pb_env_int("PB_GEMM_ABL", 0);       // timing-only epilogue ablations (wrong results): this tool op only, never an engine launch
+    const BenchEnv benv = bench_env();
+    g.ablate = benv.gemm_abl;                      // PB_GEMM_ABL: timing-only epilogue ablations (wrong results): this tool op only, never an engine launch
     for (int i = 0; i < 2; ++i) PB_TRY(launch_gemm(c->stream, amode, e, tile, g));
-    if (const char *dump = getenv("PB_GEMM_DBG")) {      // per-block stamps of one launch -> binary file
+    if (!benv.gemm_dbg.empty()) {                        // PB_GEMM_DBG=<file>: per-block stamps of one launch -> binary file
         const int nblk = (int)((Mp / 256) * (Np / 256));
         DevMem d;
         PB_TRY(d.alloc((size_t)nblk * 64));
@@ -1385,7 +1386,7 @@ int pb_op_gemm_bench(pb_ctx *c, int M, int N, int K, int tile, int epi, int iter
         PB_HIP(hipStreamSynchronize(c->stream));
         std::vector<long long> h((size_t)nblk * 8);
         PB_HIP(hipMemcpy(h.data(), d.p, h.size() * 8, hipMemcpyDeviceToHost));
-        if (FILE *f = fopen(dump, "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
+        if (FILE *f = fopen(benv.gemm_dbg.c_str(), "wb")) { fwrite(h.data(), 8, h.size(), f); fclose(f); }
         g.dbg = nullptr;
     }
     return time_launches(c->stream, iters, ms_out, [&] { return launch_gemm(c->stream, amode, e, tile, g); });

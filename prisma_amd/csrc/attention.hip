@@ -24,8 +24,7 @@
 // Timing-only ablations of the same loop: MFMAs + ds_reads alone 0.60 ms, + LDS-DMA 0.71 ms, + softmax VALU 0.875 ms;
 // VALU alone 0.52 ms; barriers, LDS read latency (PF), occupancy 2 / 3 / 4 waves per SIMD and NQB = 2 all within 2 %.
 #include "common.h"
-
-#include <stdlib.h>
+#include "launch_env.h"
 
 namespace {
 
@@ -305,9 +304,7 @@ __global__ __launch_bounds__(64 * NW, OCC) void attnq_kernel(const AttnArgs p) {
 
 int launch_attention(hipStream_t stream, const f16 *q, const f16 *k, const f16 *vt, f16 *o, int B, int heads,
                      int ntp, int ntok, int ldo, int variant, int o8_off, float o8_scale) {
-    static int env_variant = -1;
-    if (env_variant < 0) { const char *e = getenv("PB_ATTN_VARIANT"); env_variant = e ? atoi(e) : 0; }
-    if (variant <= 0) variant = env_variant;
+    if (variant <= 0) variant = launch_env().attn_variant;
     // a small batch does not fill the chip with 8-wave workgroups (one 720p frame: 16 heads x 10 blocks of 256 rows = 160): the 4-wave
     // geometry (128 rows per workgroup, same per-wave arithmetic - bit-identical output) puts twice as many on it
     if (variant == 0 && (int64_t)((ntok + 255) / 256) * ((B * heads + 7) / 8) * 8 < 384) variant = 2;

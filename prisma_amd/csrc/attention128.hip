@@ -253,11 +253,8 @@ int launch_r(hipStream_t s, const f16 *Q, const f16 *K, const f16 *Vt, const int
              int64_t q_bstride, int64_t k_bstride, int64_t v_bstride, int kxor, int nreg) {
     using G = AttnGeom<SPLIT, SPV, NVB>;
     auto kern = attn128_kernel<SPLIT, SPV, NVB, RMODE>;
-    static bool attr_set = false;
-    if (!attr_set) {
-        PB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, G::NBUF * G::BUF + G::REG_MAX));
-        attr_set = true;
-    }
+    static PbLdsLimit lds;
+    if (int rc = pb_lds_limit(lds, (const void *)kern, G::NBUF * G::BUF + G::REG_MAX)) return rc;
     const int smem_bytes = G::NBUF * G::BUF + (RMODE == 1 ? (L + 31) / 32 * 32 : 0);
     hipLaunchKernelGGL(kern, dim3((L + AQ - 1) / AQ, B), dim3(256), smem_bytes, s, Q, K, Vt, region, O, L, ldq, ldv, q_bstride, k_bstride, v_bstride, kxor, nreg);
     PB_HIP(hipGetLastError());

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <atomic>
 #include <string>
 
 typedef _Float16 f16;
@@ -40,11 +41,16 @@ void pb_set_error(const char *fmt, ...);
     } while (0)
 
 static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-// integer tuning knob from the environment (read where an engine is constructed; the default is the shipped value)
-static inline int pb_env_int(const char *name, int dflt) {
-    const char *e = getenv(name);
-    return e && *e ? atoi(e) : dflt;
-}
+
+// ---- device facts (host; gemm.hip) -----------------------------------------------------------
+// CU count of the current device, cached per device id; 256 where the query fails
+int pb_device_cus();
+// Raises a kernel's dynamic-LDS limit once per (device, kernel).  A launcher keeps one `static PbLdsLimit` per kernel (constant-initialised:
+// no guard) and calls this before every launch: one atomic load once the bit of the current device is set.  Threads that meet at a first
+// launch may each set the attribute - the same value - before one of them publishes the bit.  `cus`, where a launcher sizes its grid by
+// the CU count, receives pb_device_cus() from the same device query.
+struct PbLdsLimit { std::atomic<uint64_t> devices{0}; };
+int pb_lds_limit(PbLdsLimit &done, const void *kernel, int bytes, int *cus = nullptr);
 
 // ---- device helpers --------------------------------------------------------------------------
 #if defined(__HIPCC__)

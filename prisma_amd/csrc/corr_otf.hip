@@ -195,8 +195,8 @@ int launch_corr_lookup_otf(hipStream_t s, const f16 *fmap_src, const f16 *const 
     OtfArgs g;
     g.src = fmap_src; g.dirs = dirs;
     for (int l = 0; l < 4; ++l) { g.tgt[l] = fmap_tgt[l]; g.h[l] = h[l]; g.w[l] = w[l]; }
-    static bool attr = false;
-    if (!attr) { PB_HIP(hipFuncSetAttribute((const void *)corr_lookup_otf_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, OTF_SMEM)); attr = true; }
+    static PbLdsLimit lds;
+    if (int rc = pb_lds_limit(lds, (const void *)corr_lookup_otf_kernel, OTF_SMEM)) return rc;
     const int nd = (int)(rows / P);
     PB_CHECK(nd <= 65535, -1, "corr_lookup_otf: %d pair-directions", nd);
     hipLaunchKernelGGL(corr_lookup_otf_kernel, dim3((unsigned)(((w8 + 7) / 8) * ((h[0] + 7) / 8)), (unsigned)nd), dim3(256), OTF_SMEM, s, g, flow, P, w8, out,

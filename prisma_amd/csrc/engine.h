@@ -9,7 +9,7 @@
 
 class DepthEngine : public EngineBase {
   public:
-    DepthEngine(int device, const pb_depth_cfg &cfg);
+    DepthEngine(int device, const pb_depth_cfg &cfg, const CreateEnv &env = create_env());
     int load(const pb_tensor *w, int n);
     int infer(const uint8_t *frames_dev, int n, int H, int W, float *depth_out, uint8_t *rgb_out, float *mn,
               float *mx, int flip);

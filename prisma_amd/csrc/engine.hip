@@ -20,7 +20,7 @@ enum { F_GEMM_RESID = 6, F_GEMM_QKV = 7 };      // (the depth band's use of Engi
 inline int cp64(int c) { return (int)round_up(c, 64); }
 }  // namespace
 
-DepthEngine::DepthEngine(int dev, const pb_depth_cfg &cfg) : EngineBase(dev, kFam), cfg_(cfg) {}
+DepthEngine::DepthEngine(int dev, const pb_depth_cfg &cfg, const CreateEnv &env) : EngineBase(dev, env, kFam), cfg_(cfg) {}
 
 PackSpec DepthEngine::spec(int sa, int sw, int mx2) const {
     PackSpec s;
@@ -37,27 +37,23 @@ int DepthEngine::pack_vit(const float *wt, int N, int K, PackedW &out, const flo
 
 int DepthEngine::load(const pb_tensor *w, int n) {
     for (int i = 0; i < n; ++i) PB_CHECK(w[i].dtype == PB_F32 && w[i].data && w[i].name, PB_ERR_ARG, "weight %d: only host float32 tensors", i);
-    int r0 = begin_load(w, n, "PB_CU_MASK_DEPTH");
+    int r0 = begin_load(w, n, true);
     if (r0) return r0;
     const int D = cfg_.embed_dim, Hd = 4 * D, F = cfg_.features;
-    if (const char *e = getenv("PB_TAPIN")) head_tapin_ = e[0] != '0';
+    if (env.tapin >= 0) head_tapin_ = env.tapin != 0;       // PB_TAPIN
     PB_CHECK(cfg_.precision == PB_PREC_F16 || cfg_.precision == PB_PREC_SPLIT, PB_ERR_ARG, "precision %d unknown", cfg_.precision);
     if (cfg_.precision == PB_PREC_SPLIT) {
-        vit_sw_ = 1; head_sa_ = 1; head_sw_ = 1;
-        // experiment switches (tools/precision_budget.py rows): PB_SPLIT=<vit_w><head_a><head_w>, e.g. 110
-        if (const char *e = getenv("PB_SPLIT")) {
-            if (strlen(e) == 3) { vit_sw_ = e[0] == '1'; head_sa_ = e[1] == '1'; head_sw_ = e[2] == '1'; }
-        }
+        // all 1 unless the experiment switch (tools/precision_budget.py rows) PB_SPLIT=<vit_w><head_a><head_w>, e.g. 110, says otherwise
+        vit_sw_ = env.split_vit_w; head_sa_ = env.split_head_a; head_sw_ = env.split_head_w;
         hs_ = head_sa_ ? 2 : 1;
-        const char *mx = getenv("PB_MX");
-        vit_mx_ = vit_sw_ && D % 128 == 0 && !(mx && mx[0] == '0');
+        vit_mx_ = vit_sw_ && D % 128 == 0 && env.mx;
         // Which ViT linears keep their weight residual (bit 0 qkv, 1 proj, 2 fc1, 3 fc2).  tools/precision_budget_vit_layers.py (ViT-L 360x640,
         // everything else as the split mode runs it; max / range, L2): all four 3.9e-4 / 2.2e-4; without fc1's 4.2e-4 / 2.6e-4, without
         // qkv's 4.8e-4 / 2.9e-4, without fc2's 5.3e-4 / 3.3e-4, without proj's 5.9e-4 / 3.8e-4, none 7.9e-4 / 5.0e-4: the two layers that
         // read LayerNorm outputs are the cheap ones to drop - 58 % of the ViT linears' FLOPs run one pass instead of 1.5, and the LayerNorm
         // kernels stop writing e4m3 copies - for ~5.1e-4 / 3.2e-4 in quadrature.  Default 10 = proj + fc2; PB_VIT_RES=15 is round 2's mode.
-        vit_res_ = vit_mx_ ? pb_env_int("PB_VIT_RES", 10) & 15 : 15;
-        head_mx_ = head_sa_ && head_sw_ && !(mx && (mx[0] == '0' || mx[1] == '0'));      // PB_MX=10: MX in the ViT only
+        vit_res_ = vit_mx_ ? env.vit_res & 15 : 15;
+        head_mx_ = head_sa_ && head_sw_ && env.mx_head;      // PB_MX=10: MX in the ViT only
     }
     PB_CHECK(D % 128 == 0 && D <= 1024 && D / cfg_.heads == 64, PB_ERR_ARG, "embed_dim %d / heads %d unsupported", D,
              cfg_.heads);
@@ -72,7 +68,7 @@ int DepthEngine::load(const pb_tensor *w, int n) {
     };
 #define NEED(var, name, numel) const float *var = need(name, numel); if (!var) return PB_ERR_ARG
 #define UP(dst, name, numel) { NEED(_p, name, numel); int _r = upload_f32(_p, numel, &dst); if (_r) return _r; }
-    if ((cfg_.max_batch <= 1 || pb_env_int("PB_SPLITK_ALWAYS", 0)) && pb_env_int("PB_SPLITK", 8) > 1) {      // split-K workspace (engine.h kSkFloats)
+    if ((cfg_.max_batch <= 1 || env.splitk_always) && launch_env().splitk > 1) {      // split-K workspace (engine.h kSkFloats)
         void *w = nullptr;
         PB_HIP(hipMalloc(&w, (size_t)kSkFloats * 4));
         owned_.push_back(w);
@@ -164,7 +160,7 @@ int DepthEngine::load(const pb_tensor *w, int n) {
     if ((r = pack_conv(Hh + "resize_layers.3", oc[3], oc[3], 3, true, rs3_))) return r;
     if ((r = pack_conv(Hh + "scratch.output_conv1", F / 2, F, 3, true, oc1_))) return r;
     if ((r = pack_conv(Hh + "scratch.output_conv2.0", 32, F / 2, 3, true, oc2_))) return r;
-    head_tail_ = pb_env_int("PB_HEAD_TAIL", 1) && !cfg_.metric;
+    head_tail_ = env.head_tail && !cfg_.metric;
     if (head_tail_) {
         const int ci = F / 2, cip = cp64(ci);
         const float *wt = need(Hh + "scratch.output_conv2.0.weight", (int64_t)32 * ci * 9);

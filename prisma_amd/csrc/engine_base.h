@@ -10,17 +10,17 @@
 #include "common.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "launch_env.h"
 #include "pack_layout.h"
 
-// The ctx stream of a band engine.  `mask_env` names an environment variable with a CU mask as comma-separated 32-bit hex words (bit i of the
-// concatenation = CU i of the queue's mask; on gfx950 the driver deals the bits round-robin over the 8 XCDs, so 0f0f0f0f,... keeps XCDs 0-3):
-// an experiment switch for running two bands on disjoint parts of the chip (tools/overlap_bench.py --cu-masks).  Unset = the whole device.
-static inline hipError_t pb_create_stream(hipStream_t *s, const char *mask_env) {
-    const char *e = mask_env ? getenv(mask_env) : nullptr;
-    if (e && *e) {
+// The ctx stream of a band engine.  `se.cu_mask` (PB_CU_MASK_DEPTH / PB_CU_MASK_FLOW, launch_env.h) is a CU mask as comma-separated 32-bit hex
+// words (bit i of the concatenation = CU i of the queue's mask; on gfx950 the driver deals the bits round-robin over the 8 XCDs, so 0f0f0f0f,...
+// keeps XCDs 0-3): an experiment switch for running two bands on disjoint parts of the chip (tools/overlap_bench.py --cu-masks).  Empty = the whole device.
+static inline hipError_t pb_create_stream(hipStream_t *s, const StreamEnv &se) {
+    if (!se.cu_mask.empty()) {
         uint32_t words[8];
         int n = 0;
-        for (const char *p = e; *p && n < 8;) {
+        for (const char *p = se.cu_mask.c_str(); *p && n < 8;) {
             char *end = nullptr;
             words[n++] = (uint32_t)strtoul(p, &end, 16);
             if (!end || end == p) break;
@@ -28,15 +28,11 @@ static inline hipError_t pb_create_stream(hipStream_t *s, const char *mask_env) 
         }
         if (n > 0) return hipExtStreamCreateWithCUMask(s, (uint32_t)n, words);
     }
-    // <mask_env>_PRIO = -1 / 1: a higher- / lower-priority queue (hipStreamCreateWithPriority; 0 or unset = default).  Experiment switch: with two
+    // se.prio (<mask>_PRIO) = -1 / 1: a higher- / lower-priority queue (hipStreamCreateWithPriority; 0 = default).  Experiment switch: with two
     // bands at once the band with the large persistent GEMMs gets more than half of the chip (tools/overlap_bench.py 2way-fprio / 2way-dprio)
-    if (mask_env) {
-        const std::string pe = std::string(mask_env) + "_PRIO";
-        const char *p = getenv(pe.c_str());
-        if (p && *p && atoi(p) != 0) {
-            int lo = 0, hi = 0;
-            if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) return hipStreamCreateWithPriority(s, hipStreamNonBlocking, atoi(p) < 0 ? hi : lo);
-        }
+    if (se.prio != 0) {
+        int lo = 0, hi = 0;
+        if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess) return hipStreamCreateWithPriority(s, hipStreamNonBlocking, se.prio < 0 ? hi : lo);
     }
     return hipStreamCreateWithFlags(s, hipStreamNonBlocking);
 }
@@ -111,14 +107,16 @@ struct KernelTimer {
 
 class EngineBase {
   public:
+    // env: the create-time switches (launch_env.h) - pb_create reads them once per context, the op-level helpers at every call;
     // fam_names: the F_COUNT family names stats() reports (default: the convolutional bands' table, engine_base.hip)
-    explicit EngineBase(int device, const char *const *fam_names = nullptr);
+    explicit EngineBase(int device, const CreateEnv &env = create_env(), const char *const *fam_names = nullptr);
     virtual ~EngineBase();
     int stats(pb_kernel_stat *out, int cap);
     // the stage `name` of the last infer call as fp32 in out[cap] (floats): returns the element count and the dimensions in shape, or a
     // negative pb error ("unknown stage", "stage buffer too small") that leaves the registry as it was
     int64_t get_stage(const char *name, float *out, int64_t cap, int64_t shape[4]);
 
+    const CreateEnv env;
     hipStream_t stream = nullptr;
     int device = 0;
     bool debug = false;
@@ -134,10 +132,10 @@ class EngineBase {
     // 448, so the copy of |x| > 448 / 2^kLo8Pa clamps and that element's correction term degrades to the single-pass error.  Round 3:
     // 2^0 (saturation at 448; was 2^3 = 56) - a correction term needs a few significant bits of a NORMAL e4m3 (|x| >= 2^-6) and what
     // lies below contributes |x| 2^-12 |w| at most (tools/precision_budget.py --scales; tests/test_gpu_outliers.py)
-    const int kLo8Pa = pb_env_int("PB_LO8_POW", 0);
+    const int kLo8Pa = env.lo8_pow;               // PB_LO8_POW
     int pack_mx2_ = 0;           // while set, pack() lays weights out as [w_hi fp16 | w_lo e4m3] per tap (PackedW::mx2): the layer's input
                                  // map carries an fp8 copy after its fp16 part ([a16 (Ctot) | a8 (Ctot bytes)], scaled by 2^kMx2Pa)
-    const int kMx2Pa = pb_env_int("PB_A8_POW", 0);      // [a16 | a8] maps: a8 = e4m3(a 2^kMx2Pa); 2^0 since round 3 (was 2^4: |a| > 28 clamped)
+    const int kMx2Pa = env.a8_pow;      // PB_A8_POW.  [a16 | a8] maps: a8 = e4m3(a 2^kMx2Pa); 2^0 since round 3 (was 2^4: |a| > 28 clamped)
     int pack_tapin_ = 0;         // while set, pack() stores convolution weights (taps > 1) in slice-major K order (gemm.h cTapInner)
     const f16 *zero_page() const { return zero_; }
 
@@ -146,8 +144,9 @@ class EngineBase {
     // and 7 are the band's own: the depth band counts its residual / qkv GEMMs there (engine.hip)
     enum { F_GEMM = 0, F_CONV = 1, F_ATTN = 2, F_LN = 3, F_ELT = 4, F_PP = 5, F_CONV128 = 6, F_CONV64 = 7, F_COUNT = 8 };
 
-    // create the ctx stream (cu_mask_env: pb_create_stream), index the float32 tensors by name, allocate the zero page
-    int begin_load(const pb_tensor *w, int n, const char *cu_mask_env = "PB_CU_MASK_FLOW");
+    // create the ctx stream (pb_create_stream; depth_stream: env.stream_depth instead of env.stream_flow), index the float32 tensors by name,
+    // allocate the zero page
+    int begin_load(const pb_tensor *w, int n, bool depth_stream = false);
     const pb_tensor *find(const std::string &name) const;
     int upload_f32(const float *src, size_t n, float **dst);
     // src: host fp32 [N, K] in GEMM order -> device fp16 [round_up(N, 256), out.K] in the layout `spec` asks for (pack_layout.h pack_rows)

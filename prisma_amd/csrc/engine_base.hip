@@ -44,7 +44,7 @@ int KernelTimer::collect(const char *const *fam_names, int nfam, pb_kernel_stat 
     return n;
 }
 
-EngineBase::EngineBase(int device, const char *const *fam_names) : device(device), fam_names_(fam_names ? fam_names : kFam) {}
+EngineBase::EngineBase(int device, const CreateEnv &env, const char *const *fam_names) : env(env), device(device), fam_names_(fam_names ? fam_names : kFam) {}
 
 EngineBase::~EngineBase() {
     hipSetDevice(device);
@@ -139,9 +139,9 @@ int64_t EngineBase::get_stage(const char *name, float *out, int64_t cap, int64_t
     return total;
 }
 
-int EngineBase::begin_load(const pb_tensor *w, int n, const char *cu_mask_env) {
+int EngineBase::begin_load(const pb_tensor *w, int n, bool depth_stream) {
     PB_HIP(hipSetDevice(device));
-    PB_HIP(pb_create_stream(&stream, cu_mask_env));
+    PB_HIP(pb_create_stream(&stream, depth_stream ? env.stream_depth : env.stream_flow));
     cur_ = stream;
     for (int i = 0; i < n; ++i) {
         PB_CHECK(w[i].data && w[i].name, PB_ERR_ARG, "weight %d: null", i);
@@ -247,8 +247,7 @@ int EngineBase::pack_conv(const std::string &name, bool has_bias, const float *s
     if (r) return r;
     // RAFT's encoder stage 2: 96 -> 96 channels carried as 128.  The per-tap layout walks 9 x (2 + 2) K tiles of which a quarter multiply padding
     // channels; the packed-channel copy (conv_walk.h conv_cw3_word: 14 + 14 tiles) is what the 128 x 96 tile reads (PB_CW3=0: not built)
-    static const int cw3 = pb_env_int("PB_CW3", 1);
-    if (cw3 && out.mx3 && !out.tapin && kh * kw > 1 && ci % 16 == 0 && ci < cip && co > 64 && co <= 96) {
+    if (launch_env().cw3 && out.mx3 && !out.tapin && kh * kw > 1 && ci % 16 == 0 && ci < cip && co > 64 && co <= 96) {
         const int taps = kh * kw, nk16 = cw3_tiles16(taps, ci), nk8 = cw3_tiles8(taps, ci), pw = out.mx_pw;
         const int64_t Kc = (int64_t)(nk16 + nk8) * 64, Np = round_up(co, 256);
         std::vector<f16> h((size_t)Np * Kc, (f16)0.f);

@@ -20,9 +20,10 @@
 #pragma once
 #include "gemm.h"
 
-#include <stdlib.h>
-
+#include <array>
 #include <type_traits>
+
+#include "launch_env.h"
 
 namespace {
 
@@ -2056,39 +2057,31 @@ template <int AMODE, int EPI, bool MX, bool BUFP>
 int launch_g8_impl(hipStream_t stream, const GemmArgs &a) {
     constexpr int SMEM = 131072 + (AMODE == A_CONV ? KTAB_BYTES : 0);
     auto kern = gemm8_kernel<AMODE, EPI, 0, BUFP, MX>;
-    static char name[96];
-    if (!name[0]) snprintf(name, sizeof(name), "gemm8_kernel<%d, %d, 0, %s, %s>", AMODE, EPI, BUFP ? "true" : "false", MX ? "true" : "false");
-    pb_gemm_set_last_kernel(name);
-    static bool attr_set = false;
-    if (!attr_set) {
-        PB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        attr_set = true;
-    }
+    static const std::array<char, 96> name = [] {
+        std::array<char, 96> n{};
+        snprintf(n.data(), n.size(), "gemm8_kernel<%d, %d, 0, %s, %s>", AMODE, EPI, BUFP ? "true" : "false", MX ? "true" : "false");
+        return n;
+    }();
+    pb_gemm_set_last_kernel(name.data());
+    static PbLdsLimit lds;
+    int ncu = 0;
+    if (int rc = pb_lds_limit(lds, (const void *)kern, SMEM, &ncu)) return rc;
     const int tilesM = (a.M + 255) / 256, tilesN = (a.N + 255) / 256;
     // persistent workgroups: one per CU walks the tiles (gemm8_kernel header); PB_GEMM_PERSIST=0 launches one workgroup per tile,
     // PB_GEMM_PREFETCH=0 keeps the persistent loop but issues every tile's prologue after the previous epilogue (A/B switches)
-    static int ncu = 0, persist = 0, prefetch = 1;
-    if (!ncu) {
-        int dev = 0;
-        PB_HIP(hipGetDevice(&dev));
-        PB_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));
-        // default ON since the end of round 4.  History: on the first straight-line epilogues the per-tile stamps had a one-tile workgroup as
-        // fast or faster (profiles/r04f_gemm8_phase_cycles.log: fc1 45.1k against 46.9k cycles per tile, proj 77.7k against 81.6k - what a
-        // persistent workgroup saves in front of the K loop it pays inside the epilogue, whose own loads wait behind the prefetched DMAs on the
-        // one in-order vmcnt counter) and the bench saw no difference; on the final tree the bench does (r04w, alternating on one box:
-        // 120.55 -> 121.17 frames/s; proj + fc2 28.2 -> 27.6 ms, the update block's convolutions 35.5 -> 34.9, fc1 19.5 -> 19.4) although a
-        // tile's own stamps are still ~3 % longer: launch ramp and tail, which the stamps do not see, shrink.  PB_GEMM_PERSIST=0: one workgroup per tile.
-        persist = pb_env_int("PB_GEMM_PERSIST", 1);
-        prefetch = pb_env_int("PB_GEMM_PREFETCH", 1);
-    }
+    // default ON since the end of round 4.  History: on the first straight-line epilogues the per-tile stamps had a one-tile workgroup as
+    // fast or faster (profiles/r04f_gemm8_phase_cycles.log: fc1 45.1k against 46.9k cycles per tile, proj 77.7k against 81.6k - what a
+    // persistent workgroup saves in front of the K loop it pays inside the epilogue, whose own loads wait behind the prefetched DMAs on the
+    // one in-order vmcnt counter) and the bench saw no difference; on the final tree the bench does (r04w, alternating on one box:
+    // 120.55 -> 121.17 frames/s; proj + fc2 28.2 -> 27.6 ms, the update block's convolutions 35.5 -> 34.9, fc1 19.5 -> 19.4) although a
+    // tile's own stamps are still ~3 % longer: launch ramp and tail, which the stamps do not see, shrink.  PB_GEMM_PERSIST=0: one workgroup per tile.
+    const LaunchEnv &env = launch_env();
     GemmArgs b = a;
     b.ntiles = tilesM * tilesN;
-    b.prefetch = prefetch;
+    b.prefetch = env.gemm_prefetch;
     // b.ablate: timing-only switch of the microbenchmark op (pb_op_gemm_bench reads PB_GEMM_ABL); engine launches leave it 0
-    static int ratomic = -1;
-    if (ratomic < 0) ratomic = pb_env_int("PB_RESID_ATOMIC", 0);
-    b.resid_atomic = EPI == EPI_RESID ? ratomic : 0;
-    const int grid = persist && b.ntiles > ncu ? ncu : b.ntiles;
+    b.resid_atomic = EPI == EPI_RESID ? env.resid_atomic : 0;
+    const int grid = env.gemm_persist && b.ntiles > ncu ? ncu : b.ntiles;
     hipLaunchKernelGGL(kern, dim3(grid), dim3(512), SMEM, stream, b);
     PB_HIP(hipGetLastError());
     return 0;
@@ -2097,9 +2090,7 @@ int launch_g8_impl(hipStream_t stream, const GemmArgs &a) {
 // The buffer-path variants need every DMA offset to fit an unsigned 32-bit byte count: 1 = the whole A operand does,
 // 2 = (conv) any two consecutive images do and a BM-row tile never spans more than two, 0 = neither (flat path).
 inline int buffer_mode(int amode, const GemmArgs &a, int BM) {
-    static int env = -1;
-    if (env < 0) { const char *e = getenv("PB_GEMM_BUFFER"); env = e ? atoi(e) : 1; }
-    if (!env) return 0;
+    if (!launch_env().gemm_buffer) return 0;
     const int64_t lim = (1LL << 32) - (1 << 20);
     if ((int64_t)((a.N + 255) / 256 * 256) * a.K * 2 >= lim) return 0;
     if (amode == A_DENSE) return (int64_t)a.M * a.lda * 2 < lim ? 1 : 0;
@@ -2132,16 +2123,15 @@ int launch_t(hipStream_t stream, const GemmArgs &a) {
         if (b.bufmode) return launch_t<BM, BN, WM, WN, AMODE, EPI, MX, true, NS>(stream, b);
     }
     auto kern = gemm_kernel<BM, BN, WM, WN, AMODE, EPI, BUFP, NS, MX>;
-    static char name[112];
-    if (!name[0])
-        snprintf(name, sizeof(name), "gemm_kernel<%d, %d, %d, %d, %d, %d, %s, %d, %s>", BM, BN, WM, WN, AMODE, EPI, BUFP ? "true" : "false", NS,
+    static const std::array<char, 112> name = [] {
+        std::array<char, 112> n{};
+        snprintf(n.data(), n.size(), "gemm_kernel<%d, %d, %d, %d, %d, %d, %s, %d, %s>", BM, BN, WM, WN, AMODE, EPI, BUFP ? "true" : "false", NS,
                  MX ? "true" : "false");
-    pb_gemm_set_last_kernel(name);
-    static bool attr_set = false;
-    if (!attr_set) {
-        PB_HIP(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM));
-        attr_set = true;
-    }
+        return n;
+    }();
+    pb_gemm_set_last_kernel(name.data());
+    static PbLdsLimit lds;
+    if (int rc = pb_lds_limit(lds, (const void *)kern, SMEM)) return rc;
     const int tilesM = (a.M + BM - 1) / BM, tilesN = (a.N + BN - 1) / BN;
     // split-K launches (gemm.h splitk; launch_gemm sets it for the 128 x 128 tile only) carry `splitk` workgroups per tile
     if (BM == 128 && BN == 128 && NS == 2 && a.splitk > 1) {

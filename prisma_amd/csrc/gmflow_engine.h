@@ -17,7 +17,7 @@ void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP, int splits = 2);
 
 class GmflowEngine : public RaftEngine {
   public:
-    explicit GmflowEngine(int device) : RaftEngine(device) {}
+    explicit GmflowEngine(int device, const CreateEnv &env = create_env()) : RaftEngine(device, env) {}
     int load(const pb_tensor *w, int n) override;
     // same contract as RaftEngine::infer; `iters` is ignored (GMFlow is not iterative)
     int infer(const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward, float *flow_out, uint8_t *rgb_out,

@@ -10,7 +10,7 @@
 
 class MaskEngine : public EngineBase {
   public:
-    MaskEngine(int device, const pb_mask_cfg &cfg) : EngineBase(device), cfg_(cfg) {}
+    MaskEngine(int device, const pb_mask_cfg &cfg, const CreateEnv &env = create_env()) : EngineBase(device, env), cfg_(cfg) {}
     ~MaskEngine() override;
     int load(const pb_tensor *w, int n);
     // frames: device uint8 [n, H, W, 3] RGB.  mask_out: device uint8 [n, H, W, 3] (the band's "mask ids" image).

@@ -102,7 +102,7 @@ int MaskEngine::load(const pb_tensor *w, int n) {
     // round 3: PB_PREC_SPLIT splits the activations too - every feature map is [hi (C) | lo (C)] fp16 pairs per pixel, the weights are packed
     // per tap as [w_hi | w_hi | w_lo] (engine_base.h pack sa) and every GEMM / convolution runs a_hi w_hi + a_lo w_hi + a_hi w_lo into one fp32
     // accumulator.  PB_MASK_SA=0 keeps single-fp16 activations (the round-2 schedule) for A/B.
-    sa_ = split_w_ && pb_env_int("PB_MASK_SA", 1) ? 1 : 0;
+    sa_ = split_w_ && env.mask_sa ? 1 : 0;
     int r0 = begin_load(w, n);
     if (r0) return r0;
     for (int l = 0; l < 5; ++l) {

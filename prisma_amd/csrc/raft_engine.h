@@ -9,7 +9,7 @@
 
 class RaftEngine : public EngineBase {
   public:
-    explicit RaftEngine(int device) : EngineBase(device) {}
+    explicit RaftEngine(int device, const CreateEnv &env = create_env()) : EngineBase(device, env) {}
     virtual int load(const pb_tensor *w, int n);
     // frames: device uint8 [F, H, W, 3].  Outputs are device pointers (any may be null):
     //   flow_out [F-1, dirs, sh, sw, 2] fp32, rgb_out [F-1, dirs, sh, sw, 3] u8, maxdisp [F-1, dirs]

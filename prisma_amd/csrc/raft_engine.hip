@@ -113,7 +113,7 @@ int RaftEngine::load(const pb_tensor *w, int n) {
     int r0 = begin_load(w, n);
     if (r0) return r0;
     int r;
-    pack_tapin_ = getenv("PB_TAPIN") && getenv("PB_TAPIN")[0] == '2';
+    pack_tapin_ = env.tapin == 2;
     for (int e = 0; e < 2; ++e) {
         const std::string en = e == 0 ? "fnet" : "cnet";
         Enc &E = e == 0 ? fnet_ : cnet_;
@@ -127,13 +127,12 @@ int RaftEngine::load(const pb_tensor *w, int n) {
     // variant excluded the context hoist below); round 4 fixed both - 31 pairs 1080p x 0.75: flow band 150.4 -> 142.2 ms on one box - and the
     // parity figures do not move (720p x 8 pairs 4.1e-4 ... 5.4e-4 max, 3.4e-4 ... 3.5e-4 L2 against 4.1e-4 ... 6.6e-4 / 3.4e-4 with two fp16
     // passes; heavy-tailed weights 5.8e-4 against 6.3e-4): the e4m3 rounding only ever enters a residual term.  PB_MX_UPD=0: two fp16 passes.
-    pack_mx2_ = mx_ && !(getenv("PB_MX_UPD") && getenv("PB_MX_UPD")[0] == '0');
+    pack_mx2_ = mx_ && env.mx_upd;
     upd8_ = pack_mx2_;
     // slice-major K order (gemm.h cTapInner) for the 3x3 / 1x5 / 5x1 convolutions over the 128 ... 384-channel maps of the update block:
     // tap-major order overflows the XCD L2 there.  PB_TAPIN=0 turns it off, 2 also applies it to the encoders (A/B runs).
-    const char *tin = getenv("PB_TAPIN");
     const int tapin_all = pack_tapin_;
-    pack_tapin_ = !(tin && tin[0] == '0');
+    pack_tapin_ = env.tapin != 0;
     if ((r = pack_conv(u + "encoder.convc1", true, nullptr, nullptr, convc1_))) return r;
     if ((r = pack_conv(u + "encoder.convc2", true, nullptr, nullptr, convc2_))) return r;
     if ((r = pack_conv(u + "encoder.convf2", true, nullptr, nullptr, convf2_))) return r;
@@ -149,8 +148,7 @@ int RaftEngine::load(const pb_tensor *w, int n) {
                 for (int tp = 0; tp < 49; ++tp) g[(size_t)o * 98 + tp * 2 + c] = wt[((size_t)o * 2 + c) * 49 + tp];
         if ((r = pack(g.data(), 128, 98, 128, convf1_, (const float *)ib->second->data))) return r;
         {
-            const char *e = getenv("PB_CONVF1_DIRECT");
-            f1_direct_ = !(e && e[0] == '0');
+            f1_direct_ = env.convf1_direct;
             f1_passes_ = split_w_ ? 2 : 1;
             std::vector<f16> hw((size_t)convf1_packed_halfs(f1_passes_));
             convf1_pack(wt, f1_passes_, hw.data());
@@ -168,10 +166,7 @@ int RaftEngine::load(const pb_tensor *w, int n) {
     // epilogue's skip tensors (add1, add2) before the gate's activation.  The buffers hold [h | motion | inp] so that the two varying
     // parts are adjacent.  (First version: fp32 share as the accumulators' starting value - its 256 KB per tile were a prologue burst that
     // ate half of what the smaller K saved; as an fp32 read in the GRU epilogues it cost every EPI_STD kernel its register allocation.)
-    {
-        const char *e = getenv("PB_GRU_HOIST");
-        hoist_ = !(e && e[0] == '0');
-    }
+    hoist_ = env.gru_hoist;
     for (int half = 0; half < 2; ++half) {
         // z and r gates share their input: one GEMM with N = 256 ([z | r]); q separately
         const std::string sfx = std::to_string(half + 1);
@@ -358,8 +353,7 @@ int RaftEngine::run_encoder(const Enc &E, bool inorm, int F, const f16 **x_out) 
     // value, and a 64-channel pixel's hi part is one of its two 128-byte lines (the lo8 bytes sit in the other one): half the pass's traffic,
     // -1.2 ms per step, RAFT parity unchanged (worst 720p pair 6.0e-4 either way).  flow_gmflow (fp16 residual planes) keeps hi + lo: its
     // 216x300 vector moves from 2.2e-4 to 3.8e-4 without them.
-    static const bool stats_lo_env = getenv("PB_IN_STATS_LO") && getenv("PB_IN_STATS_LO")[0] == '1';
-    const bool stats_lo = stats_lo_env || !mx_;
+    const bool stats_lo = launch_env().in_stats_lo || !mx_;
     auto stats = [&](const f16 *t, float *st, int HW, int C) -> int {
         tic(F_ELT, 0, 0);
         int rr = launch_in_stats(stream, t, F, HW, C, es * C, stp_, st, stats_lo ? lo(C) : 0, l8);
@@ -485,8 +479,7 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
                 a.out = pyr_[l] + (int64_t)n * P_ * pld_[l]; a.ldo = pld_[l]; a.zero = zero_;
                 // K = 256 against P x pld fp16 outputs: this launch is bound by writing the volume, not by the matrix pipe (bytes: A + W + out)
                 tic(F_GEMM, 2.0 * P_ * (double)lh_[l] * lw_[l] * 256, 2.0 * ((double)P_ * 256 + (double)pld_[l] * 256 + (double)P_ * pld_[l]));
-                static const bool generic = getenv("PB_VOLUME") && getenv("PB_VOLUME")[0] == '0';     // A/B: the generic GEMM kernels
-                if (generic) {
+                if (!launch_env().volume) {        // PB_VOLUME=0, A/B: the generic GEMM kernels
                     r = launch_gemm(stream, A_DENSE, EPI_STD, TILE_AUTO, a);
                     if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = pb_gemm_last_kernel();
                 } else {        // volume.hip: A-stationary, persistent along the targets; same accumulation order, same bits

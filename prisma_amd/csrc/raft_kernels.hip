@@ -916,8 +916,8 @@ void convf1_pack(const float *w, int passes, f16 *dst) {
 int launch_convf1(hipStream_t s, const float *flow, const f16 *wpk, const float *bias, f16 *out, int64_t rows, int P, int h8, int w8, int ldo,
                   int o8_off, float o8_scale, int passes) {
     const int smem = passes * 128 * F1_LD * 2;
-    static bool attr = false;
-    if (!attr) { PB_HIP(hipFuncSetAttribute((const void *)convf1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 128 * F1_LD * 2)); attr = true; }
+    static PbLdsLimit lds;
+    if (int rc = pb_lds_limit(lds, (const void *)convf1_kernel, 2 * 128 * F1_LD * 2)) return rc;
     const int64_t ntiles = (rows + 31) / 32;
     const int grid = (int)std::min<int64_t>((ntiles + 3) / 4, 512);
     hipLaunchKernelGGL(convf1_kernel, dim3(grid), dim3(256), smem, s, flow, wpk, bias, out, rows, P, h8, w8, ldo, o8_off, o8_scale, passes);

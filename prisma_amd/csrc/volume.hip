@@ -31,6 +31,7 @@
 // k-step over the whole tile (12.15), one 8-wave workgroup per CU sharing the target tiles (half the DMA bytes: 13.4 ms, matrix work
 // alone 8.6 - the barrier spans twice the waves).
 #include "common.h"
+#include "launch_env.h"
 #include "raft_kernels.h"
 #include "../../include/prisma_bands.h"
 
@@ -221,28 +222,24 @@ __global__ __launch_bounds__(VNT, 2) void corr_volume_kernel(const f16 *__restri
 
 int launch_corr_volume(hipStream_t s, const f16 *A, int M, const f16 *W, int N, int w_rows, f16 *out, int64_t ldo) {
     PB_CHECK(A && W && out && M > 0 && N > 0 && N % 8 == 0 && ldo >= N && w_rows >= N && ldo < (1 << 24), PB_ERR_ARG, "corr_volume: bad arguments");
-    static bool once = false;
     const int smem = VSTAGES * VSTAGE_BYTES;
-    static int abl = 0;                                         // PB_VOL_ABL (-DPB_DIAG builds only; wrong results): 1 no stores, 2 no fragment reads / MFMAs, 4 no DMA
-    if (!once) {
-        PB_HIP(hipFuncSetAttribute((const void *)corr_volume_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
 #ifdef PB_DIAG
-        abl = pb_env_int("PB_VOL_ABL", 0);
-        PB_HIP(hipFuncSetAttribute((const void *)corr_volume_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        PB_HIP(hipFuncSetAttribute((const void *)corr_volume_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        PB_HIP(hipFuncSetAttribute((const void *)corr_volume_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        PB_HIP(hipFuncSetAttribute((const void *)corr_volume_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
-        PB_HIP(hipFuncSetAttribute((const void *)corr_volume_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, smem));
+    const int abl = launch_env().vol_abl;                       // PB_VOL_ABL (wrong results): 1 no stores, 2 no fragment reads / MFMAs, 4 no DMA
+#else
+    const int abl = 0;
 #endif
-        once = true;
-    }
     const int tilesM = (M + VBM - 1) / VBM, tilesN = (N + VBN - 1) / VBN;
     // ~2000 workgroups (4 rounds of 2 per CU) unless the level is small; a workgroup's A load (64 KB) is amortised over its tiles
     int groups = (2048 + tilesM - 1) / tilesM;
     groups = groups < 1 ? 1 : (groups > tilesN ? tilesN : groups);
     const int tpw = (tilesN + groups - 1) / groups;
     groups = (tilesN + tpw - 1) / tpw;
-#define PB_VOL_LAUNCH(X) hipLaunchKernelGGL(corr_volume_kernel<X>, dim3(tilesM * groups), dim3(VNT), smem, s, A, M, W, N, w_rows, out, ldo, tpw)
+#define PB_VOL_LAUNCH(X)                                                                                                  \
+    {                                                                                                                     \
+        static PbLdsLimit lds;                                                                                            \
+        if (int rc = pb_lds_limit(lds, (const void *)corr_volume_kernel<X>, smem)) return rc;                             \
+        hipLaunchKernelGGL(corr_volume_kernel<X>, dim3(tilesM * groups), dim3(VNT), smem, s, A, M, W, N, w_rows, out, ldo, tpw); \
+    }
     switch (abl) {
 #ifdef PB_DIAG
         case 1: PB_VOL_LAUNCH(1); break;
