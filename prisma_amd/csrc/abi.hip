@@ -9,6 +9,7 @@
 
 #include "abi_ctx.h"
 #include "gmflow_engine.h"
+#include "raft_engine.h"
 
 static thread_local char g_err[1024] = "";
 
@@ -211,16 +212,16 @@ int pb_create(pb_ctx **out, int device_id, const char *band, const pb_tensor *we
             delete c;
             PB_CHECK(false, PB_ERR_ARG, "%s: precision %d unknown", band, prec);
         }
-        c->raft = gm ? new GmflowEngine(device_id, env) : new RaftEngine(device_id, env);      // GmflowEngine overrides load / infer
-        c->raft->split_w_ = prec == PB_PREC_SPLIT;
-        c->raft->mx_ = !gm && c->raft->split_w_ && env.mx;
-        int r = c->raft->load(weights, n_weights);
+        c->flow = gm ? (FlowEngine *)new GmflowEngine(device_id, env) : new RaftEngine(device_id, env);
+        c->flow->split_w_ = prec == PB_PREC_SPLIT;
+        c->flow->mx_ = !gm && c->flow->split_w_ && env.mx;
+        int r = c->flow->load(weights, n_weights);
         if (r) {
-            delete c->raft;
+            delete c->flow;
             delete c;
             return r;
         }
-        c->band = c->raft;
+        c->band = c->flow;
     } else if (!strcmp(band, "mask_mmdet")) {
         if (!cfg || cfg_bytes != sizeof(pb_mask_cfg) || !weights || n_weights <= 0) {
             delete c;
@@ -339,7 +340,7 @@ void pb_destroy(pb_ctx *c) {
     // pb_host_alloc blocks: the submissions that wrote into them were waited for above and the copy streams are drained and gone
     for (void *p : c->host_blocks) hipHostFree(p);
     if (c->depth) delete c->depth;
-    if (c->raft) delete c->raft;
+    if (c->flow) delete c->flow;
     if (c->mask) delete c->mask;
     if (c->own_stream) {
         hipStreamSynchronize(c->stream);
@@ -449,14 +450,14 @@ int pb_set_profiling(pb_ctx *c, int enabled) {
 
 int pb_flow_out_size(int H, int W, float scale, int *sh, int *sw) {
     PB_CHECK(H > 0 && W > 0 && scale > 0.f && sh && sw, PB_ERR_ARG, "flow_out_size: bad arguments");
-    RaftEngine::out_size(H, W, scale, sh, sw);
+    FlowEngine::out_size(H, W, scale, sh, sw);
     return 0;
 }
 
 int pb_flow_infer_sequence_dev(pb_ctx *c, const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward,
                                float *flow_out, uint8_t *rgb_out, float *maxdisp_out) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
-    return c->raft->infer(frames, F, H, W, scale, iters, backward, flow_out, rgb_out, maxdisp_out);
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow_raft band");
+    return c->flow->infer(frames, F, H, W, scale, iters, backward, flow_out, rgb_out, maxdisp_out);
 }
 
 // Host-pointer variants (reference loop bands/flow_raft.py:98-113: a decoded frame pair per iteration; :63-64 the consistency masks of --mask):
@@ -467,7 +468,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
                               float *flow_out, uint8_t *rgb_out, float *maxdisp_out, uint8_t *mask_out, float alpha1, float alpha2, bool submit = false) {
     PB_HIP(hipSetDevice(c->device));
     int sh, sw;
-    RaftEngine::out_size(H, W, scale, &sh, &sw);
+    FlowEngine::out_size(H, W, scale, &sh, &sw);
     const int dirs = backward ? 2 : 1, pairs = F - 1;
     // (default 32 pairs since round 6 - was 16: a chunk's launches are the same kernels on fewer rows, and 16-pair chunks cost the bench clip more in
     // launch tails and re-encoded halo frames than their hidden copies gave; profiles/r06j_pcie_entry_points.txt)
@@ -476,7 +477,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     if (pairs <= cp + cp / 4) cp = pairs;                       // a short tail is not worth a chunk of its own
     // ... and no chunk larger than one infer() call accepts at this size (flow_chunk.h: 4K frames); a single pair that does not fit goes
     // through as it is and the engine refuses it
-    cp = std::max(1, c->raft->chunk_pairs(cp, H, W, scale, dirs));
+    cp = std::max(1, c->flow->chunk_pairs(cp, H, W, scale, dirs));
     const size_t px = (size_t)sh * sw * dirs, np = (size_t)pairs;      // px: result pixels of a pair, all directions
     // "frames_i420" / "rgb_out_i420": I420 frames in, I420 frames of the output size out (dirs of them per pair), converted on the ctx stream
     // "rgb_out_full": ... of the clip's H x W, resized on the ctx stream from the sh x sw frames the band encodes (nothing to do at scale 1)
@@ -495,7 +496,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
                                 {mask_out, mask_out ? px : 0, true, pin_k}};
     if (yin) PB_TRY(c->yuv_grow(0, (size_t)(cp + 1) * H * W * 3));
     if (yout || full) PB_TRY(c->yuv_grow(1, (size_t)cp * px * 3));
-    TimerSpan span(c->raft->timer);
+    TimerSpan span(c->flow->timer);
     const ChunkPipe::Lane *l = c->pipe.lane;
     return run_chunks(c, pairs, cp, 1, lanes, 5, submit, [&](int slot, int, int m) {
         const uint8_t *in = (const uint8_t *)l[0].d[slot];
@@ -504,7 +505,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
             in = (const uint8_t *)c->yuv[0];
         }
         uint8_t *enc = (uint8_t *)(rgb_out ? (yout || full ? c->yuv[1] : l[2].d[slot]) : nullptr);
-        PB_TRY(c->raft->infer(in, m + 1, H, W, scale, iters, backward, (float *)(flow_out ? l[1].d[slot] : nullptr), enc, (float *)l[3].d[slot],
+        PB_TRY(c->flow->infer(in, m + 1, H, W, scale, iters, backward, (float *)(flow_out ? l[1].d[slot] : nullptr), enc, (float *)l[3].d[slot],
                               (uint8_t *)(mask_out ? l[4].d[slot] : nullptr), alpha1, alpha2));
         if (full) return launch_rgb_resize(c->stream, enc, m * dirs, sh, sw, H, W, (uint8_t *)l[2].d[slot], yout);
         return yout ? launch_rgb_to_i420(c->stream, enc, m * dirs, sh, sw, (uint8_t *)l[2].d[slot]) : 0;
@@ -513,14 +514,14 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
 
 int pb_flow_submit_sequence(pb_ctx *c, const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward,
                             float *flow_out, uint8_t *rgb_out, float *maxdisp_out) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow_raft band");
     PB_CHECK(frames && F >= 2 && H > 0 && W > 0, PB_ERR_ARG, "flow submit: bad arguments");
     return flow_host_pipeline(c, frames, F, H, W, scale, iters, backward, flow_out, rgb_out, maxdisp_out, nullptr, 0.05f, 0.5f, true);
 }
 
 int pb_flow_infer_sequence(pb_ctx *c, const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward,
                            float *flow_out, uint8_t *rgb_out, float *maxdisp_out) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow_raft band");
     PB_CHECK(frames && F >= 2 && H > 0 && W > 0, PB_ERR_ARG, "flow infer: bad arguments");
     return flow_host_pipeline(c, frames, F, H, W, scale, iters, backward, flow_out, rgb_out, maxdisp_out, nullptr, 0.05f, 0.5f);
 }
@@ -528,21 +529,21 @@ int pb_flow_infer_sequence(pb_ctx *c, const uint8_t *frames, int F, int H, int W
 int pb_flow_infer_sequence_masks_dev(pb_ctx *c, const uint8_t *frames, int F, int H, int W, float scale, int iters,
                                      float alpha1, float alpha2, float *flow_out, uint8_t *rgb_out, float *maxdisp_out,
                                      uint8_t *mask_out) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow_raft band");
     PB_CHECK(mask_out, PB_ERR_ARG, "flow masks: mask_out is NULL");
-    return c->raft->infer(frames, F, H, W, scale, iters, 1, flow_out, rgb_out, maxdisp_out, mask_out, alpha1, alpha2);
+    return c->flow->infer(frames, F, H, W, scale, iters, 1, flow_out, rgb_out, maxdisp_out, mask_out, alpha1, alpha2);
 }
 
 int pb_flow_infer_sequence_masks(pb_ctx *c, const uint8_t *frames, int F, int H, int W, float scale, int iters, float alpha1,
                                  float alpha2, float *flow_out, uint8_t *rgb_out, float *maxdisp_out, uint8_t *mask_out) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow_raft band");
     PB_CHECK(frames && F >= 2 && H > 0 && W > 0 && mask_out, PB_ERR_ARG, "flow masks: bad arguments");
     return flow_host_pipeline(c, frames, F, H, W, scale, iters, 1, flow_out, rgb_out, maxdisp_out, mask_out, alpha1, alpha2);
 }
 
 int pb_flow_submit_sequence_masks(pb_ctx *c, const uint8_t *frames, int F, int H, int W, float scale, int iters, float alpha1,
                                   float alpha2, float *flow_out, uint8_t *rgb_out, float *maxdisp_out, uint8_t *mask_out) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow_raft band");
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow_raft band");
     PB_CHECK(frames && F >= 2 && H > 0 && W > 0 && mask_out, PB_ERR_ARG, "flow masks submit: bad arguments");
     return flow_host_pipeline(c, frames, F, H, W, scale, iters, 1, flow_out, rgb_out, maxdisp_out, mask_out, alpha1, alpha2, true);
 }
@@ -674,40 +675,41 @@ int64_t pb_mask_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, 
 }
 
 int pb_flow_set_inference_size(pb_ctx *c, int h, int w) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow band");
-    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->raft);
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow band");
+    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->flow);
     PB_CHECK(g, PB_ERR_STATE, "--inference_size is a flow_gmflow option");
     return g->set_inference_size(h, w);
 }
 
 int pb_flow_set_matching(pb_ctx *c, int corr_radius, int prop_radius) {
-    PB_CHECK(c && c->raft, PB_ERR_STATE, "ctx has no flow band");
-    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->raft);
+    PB_CHECK(c && c->flow, PB_ERR_STATE, "ctx has no flow band");
+    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->flow);
     PB_CHECK(g, PB_ERR_STATE, "--corr_radius_list / --prop_radius_list are flow_gmflow options");
     return g->set_matching(corr_radius, prop_radius);
 }
 
 int pb_flow_num_scales(pb_ctx *c) {
-    PB_CHECK(c && c->raft, PB_ERR_ARG, "ctx has no flow band");
-    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->raft);
+    PB_CHECK(c && c->flow, PB_ERR_ARG, "ctx has no flow band");
+    GmflowEngine *g = dynamic_cast<GmflowEngine *>(c->flow);
     PB_CHECK(g, PB_ERR_ARG, "num_scales is a flow_gmflow property");
     return g->num_scales();
 }
 
 int pb_flow_set_alternate_corr(pb_ctx *c, int on) {
-    PB_CHECK(c && c->raft, PB_ERR_ARG, "ctx has no flow band");
-    PB_CHECK(!dynamic_cast<GmflowEngine *>(c->raft), PB_ERR_ARG, "--alternate_corr is a flow_raft option");
-    c->raft->set_alternate_corr(on);
+    PB_CHECK(c && c->flow, PB_ERR_ARG, "ctx has no flow band");
+    RaftEngine *e = dynamic_cast<RaftEngine *>(c->flow);
+    PB_CHECK(e, PB_ERR_ARG, "--alternate_corr is a flow_raft option");
+    e->set_alternate_corr(on);
     return 0;
 }
 
 int64_t pb_flow_arena_bytes(pb_ctx *c) {
-    PB_CHECK(c && c->raft, PB_ERR_ARG, "ctx has no flow band");
-    return c->raft->plan_bytes();
+    PB_CHECK(c && c->flow, PB_ERR_ARG, "ctx has no flow band");
+    return c->flow->plan_bytes();
 }
 
 int64_t pb_flow_get_stage(pb_ctx *c, const char *name, float *out, int64_t cap, int64_t shape_out[4]) {
-    return band_stage(c, c ? c->raft : nullptr, "flow ", name, out, cap, shape_out);
+    return band_stage(c, c ? c->flow : nullptr, "flow ", name, out, cap, shape_out);
 }
 
 int pb_set_option(pb_ctx *c, const char *key, int value) {

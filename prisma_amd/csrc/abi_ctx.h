@@ -7,7 +7,7 @@
 
 #include "engine.h"
 #include "mask_engine.h"
-#include "raft_engine.h"
+#include "flow_engine.h"
 #include "resize.h"
 #include "yuv.h"
 
@@ -124,7 +124,7 @@ struct MaskPipe {
 struct pb_ctx {
     int device = 0;
     DepthEngine *depth = nullptr;
-    RaftEngine *raft = nullptr;
+    FlowEngine *flow = nullptr;
     MaskEngine *mask = nullptr;
     EngineBase *band = nullptr;     // whichever of the three was created: what every band has (timer, debug, tiles, stats)
     hipStream_t stream = nullptr;   // == depth->stream when a band is loaded

@@ -138,8 +138,8 @@ class SplitOpEngine : public EngineBase {
 };
 
 // ---- the flow_raft band's own kernels one by one (pb_op_raft_*) -----------------------------------------------------------------------
-// Every entry point calls the launcher RaftEngine::infer calls, with the engine's arguments; host maps are built by build_map above, weights
-// go through EngineBase::pack / pack_conv / convf1_pack.  Output buffers are preset to 0xFF bytes (an fp16 / fp32 / e4m3 NaN) with guard
+// Every entry point calls the launcher RaftEngine::infer calls (FlowEngine's encoder and tail included), with the engine's arguments; host maps
+// are built by build_map above, weights go through EngineBase::pack / pack_conv / convf1_pack.  Output buffers are preset to 0xFF bytes (an fp16 / fp32 / e4m3 NaN) with guard
 // rows behind the last row, so a test can tell what the kernel did NOT write.
 class RaftOpEngine : public SplitOpEngine {
   public:

@@ -303,7 +303,7 @@ int DepthEngine::prepare(int B, int H, int W) {
     if (B <= pB_ && H == pH_ && W == pW_) return 0;
     B = std::max(B, (pH_ == H && pW_ == W) ? pB_ : 0);
     PB_HIP(hipStreamSynchronize(stream));
-    pB_ = 0; pH_ = 0; pW_ = 0;          // (a failure below must not leave the old plan's key on a half-written plan: raft_engine.hip prepare)
+    pB_ = 0; pH_ = 0; pW_ = 0;          // (a failure below must not leave the old plan's key on a half-written plan: flow_engine.h PlanKey)
     int r = pb_depth_net_size(H, W, &nh_, &nw_);
     if (r) return r;
     if (cfg_.metric) { nh_ = 392; nw_ = 518; }      // DepthAnythingCore.prep: img_size [392, 518], aspect ratio not kept
@@ -322,9 +322,7 @@ int DepthEngine::prepare(int B, int H, int W) {
              "batch %d too large for %dx%d frames (32-bit tensor offsets); lower max_batch", B, H, W);
     const int64_t rows = round_up((int64_t)B * ntp_, 256);
     const size_t slack = 32768;
-    for (int pass = 0; pass < 2; ++pass) {
-        planning_ = pass == 0;
-        arena_off_ = 0;
+    r = plan_arena("depth", [&]() -> int {
         xi_ = (int *)carve((size_t)nw_ * 16); xw_ = (float *)carve((size_t)nw_ * 16);
         yi_ = (int *)carve((size_t)nh_ * 16); yw_ = (float *)carve((size_t)nh_ * 16);
         pos_ = (float *)carve((size_t)ntok_ * D * 4);
@@ -356,9 +354,9 @@ int DepthEngine::prepare(int B, int H, int W) {
         netd_ = (float *)carve((size_t)HB * nh_ * nw_ * 4);
         full_ = (float *)carve((size_t)HB * H * W * 4);
         mm_ = (unsigned *)carve((size_t)HB * 8);
-        if (cfg_.metric && (r = plan_metric(HB, H, W))) return r;
-        if (pass == 0 && (r = commit_arena("depth"))) return r;
-    }
+        return cfg_.metric ? plan_metric(HB, H, W) : 0;
+    });
+    if (r) return r;
     std::vector<int> xi, yi;
     std::vector<float> xw, yw, pos;
     if (cfg_.metric) {
@@ -395,12 +393,9 @@ int DepthEngine::gemm(int amode, int epi, GemmArgs &a, const PackedW &w, int til
     const int taps = w.taps > 0 ? w.taps : 1;
     const double a_elems = amode == A_CONV ? (double)(a.M / ((int64_t)a.cOH * a.cOW)) * a.cH * a.cW * (w.Kreal / taps) : (double)a.M * w.Kreal;
     const double bytes = 2.0 * (a_elems + (double)a.N * w.Kreal) + (epi == EPI_HEAD ? 4.0 * a.M : 2.0 * (double)a.M * a.N);
-    tic(amode == A_CONV ? F_CONV : (epi == EPI_RESID ? F_GEMM_RESID : (epi == EPI_QKV ? F_GEMM_QKV : F_GEMM)), flops, bytes, w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
     if (tile == TILE_AUTO) tile = amode == A_CONV ? conv_tile : dense_tile;
-    int r = launch_gemm(stream, amode, epi, tile, a);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-    toc();
-    return r;
+    return timed_gemm(amode == A_CONV ? F_CONV : (epi == EPI_RESID ? F_GEMM_RESID : (epi == EPI_QKV ? F_GEMM_QKV : F_GEMM)), flops, bytes,
+                      [&] { return launch_gemm(stream, amode, epi, tile, a); }, w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
 }
 
 int DepthEngine::conv3(const f16 *in, int inC, int n, int H, int W, const PackedW &w, f16 *out, f16 *out2,
@@ -428,9 +423,7 @@ int DepthEngine::vit(int n) {
         a.A = patchA_; a.lda = 640; a.M = n * P_;
         a.resid = X_; a.ldr = D; a.pos = pos_; a.ppi = P_; a.ntp = ntp_; a.D = D;
         if ((r = gemm(A_DENSE, EPI_PATCH, a, patch_, TILE_128))) return r;
-        tic(F_ELT, 0, 0);
-        r = launch_cls_rows(stream, X_, cls_, pos_, n, ntp_, D);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_cls_rows(stream, X_, cls_, pos_, n, ntp_, D); });
         if (r) return r;
     }
     if (debug && (r = snapshot_tokens("tokens", n))) return r;
@@ -444,9 +437,7 @@ int DepthEngine::vit(int n) {
     const float o8s = (float)(1 << kMx2Pa);
     for (int i = 0; i < cfg_.depth; ++i) {
         const Block &b = blocks_[i];
-        tic(F_LN, 0, ln_bytes);
-        r = launch_layernorm(stream, X_, b.ln1g, b.ln1b, Y_, n, ntp_, ntok_, D, 1e-6f, 0, ldY, 0, o8Y, o8s);
-        toc();
+        r = timed(F_LN, 0, ln_bytes, [&] { return launch_layernorm(stream, X_, b.ln1g, b.ln1b, Y_, n, ntp_, ntok_, D, 1e-6f, 0, ldY, 0, o8Y, o8s); });
         if (r) return r;
         {
             GemmArgs a;
@@ -454,18 +445,16 @@ int DepthEngine::vit(int n) {
             a.q = Q_; a.k = K_; a.vt = Vt_; a.ntp = ntp_; a.heads = cfg_.heads; a.D = D; a.qscale = PB_QSCALE;
             if ((r = gemm(A_DENSE, EPI_QKV, a, b.qkv))) return r;
         }
-        tic(F_ATTN, 4.0 * n * cfg_.heads * (double)ntok_ * ntok_ * 64.0, (double)n * ntok_ * D * 2.0 * 4.0);
-        r = launch_attention(stream, Q_, K_, Vt_, AO_, n, cfg_.heads, ntp_, ntok_, ldA, 0, o8A, o8s);
-        toc();
+        r = timed(F_ATTN, 4.0 * n * cfg_.heads * (double)ntok_ * ntok_ * 64.0, (double)n * ntok_ * D * 2.0 * 4.0, [&] {
+            return launch_attention(stream, Q_, K_, Vt_, AO_, n, cfg_.heads, ntp_, ntok_, ldA, 0, o8A, o8s);
+        });
         if (r) return r;
         {
             GemmArgs a;
             a.A = AO_; a.lda = ldA; a.M = M; a.resid = X_; a.ldr = D; a.gamma = b.ls1;
             if ((r = gemm(A_DENSE, EPI_RESID, a, b.proj))) return r;
         }
-        tic(F_LN, 0, ln_bytes);
-        r = launch_layernorm(stream, X_, b.ln2g, b.ln2b, Y_, n, ntp_, ntok_, D, 1e-6f, 0, ldY, 0, o8Y, o8s);
-        toc();
+        r = timed(F_LN, 0, ln_bytes, [&] { return launch_layernorm(stream, X_, b.ln2g, b.ln2b, Y_, n, ntp_, ntok_, D, 1e-6f, 0, ldY, 0, o8Y, o8s); });
         if (r) return r;
         {
             GemmArgs a;
@@ -481,10 +470,8 @@ int DepthEngine::vit(int n) {
         if (debug && (r = snapshot_tokens("block" + std::to_string(i), n))) return r;
         const int tap = i - (cfg_.depth - 4);
         if (tap >= 0) {
-            tic(F_LN, 0, ln_bytes);
-            r = launch_layernorm(stream, X_, normg_, normb_, feat_[tap], n, ntp_, ntok_, D, 1e-6f, 1, hs_ * D, head_sa_ ? D : 0, 0, 16.f,
-                                 head_mx_ ? kLo8Pa : -1);
-            toc();
+            r = timed(F_LN, 0, ln_bytes, [&] { return launch_layernorm(stream, X_, normg_, normb_, feat_[tap], n, ntp_, ntok_, D, 1e-6f, 1, hs_ * D, head_sa_ ? D : 0, 0, 16.f,
+                                 head_mx_ ? kLo8Pa : -1); });
             if (r) return r;
             stages_["feat" + std::to_string(tap)] = Stage::f16_rows(feat_[tap], n, P_, D, hs_ * D);
         }
@@ -503,9 +490,9 @@ int DepthEngine::head(int f0, int n) {
         stages_[name] = Stage::f16_nhwc(p, n, c, h, w, (split ? hs : 1) * ld);      // split maps: the hi part
     };
     auto bil = [&](const f16 *x, f16 *y, int h, int w, int oh, int ow, int c, int ld) -> int {
-        tic(F_ELT, 0, (double)n * ((double)h * w + (double)oh * ow) * c * 2.0 * hs);
-        int rr = launch_bilinear_nhwc(stream, x, y, n, h, w, oh, ow, c, hs * ld, 1, lo(ld), head_mx_ ? kLo8Pa : -1);
-        toc();
+        int rr = timed(F_ELT, 0, (double)n * ((double)h * w + (double)oh * ow) * c * 2.0 * hs, [&] {
+            return launch_bilinear_nhwc(stream, x, y, n, h, w, oh, ow, c, hs * ld, 1, lo(ld), head_mx_ ? kLo8Pa : -1);
+        });
         return rr;
     };
     // reassemble: 1x1 projection of each tap, then x4 / x2 transposed convs, identity, 3x3 stride 2
@@ -559,9 +546,9 @@ int DepthEngine::head(int f0, int n) {
         a.A = o1_; a.lda = hs * F2p; a.M = n * h1 * w1; a.out = z_; a.ldo = hs * Zp; a.lo_off = lo(Zp); a.N = 288;
         // (K = F / 2 is two to four K tiles: the launch is its epilogue - 1.5 ms per 16 frames on the 128 x 128 tile, 1.75 on the ping-pong kernel)
         if ((r = gemm(A_DENSE, EPI_STD, a, wz_))) return r;
-        tic(F_ELT, 0, (double)n * ((double)h1 * w1 * 288 * (head_sa_ ? 3.0 : 2.0) + (double)nh_ * nw_ * 4.0));
-        r = launch_dpt_tail(stream, z_, n, h1, w1, hs * Zp, lo(Zp), head_mx_ ? kLo8Pa : -1, oc2_.bias, w2_, b2_, netd_, nh_, nw_);
-        toc();
+        r = timed(F_ELT, 0, (double)n * ((double)h1 * w1 * 288 * (head_sa_ ? 3.0 : 2.0) + (double)nh_ * nw_ * 4.0), [&] {
+            return launch_dpt_tail(stream, z_, n, h1, w1, hs * Zp, lo(Zp), head_mx_ ? kLo8Pa : -1, oc2_.bias, w2_, b2_, netd_, nh_, nw_);
+        });
         if (r) return r;
         stages_["net_depth"] = Stage::f32_rows(netd_, n, nh_, nw_);
         return 0;
@@ -573,9 +560,7 @@ int DepthEngine::head(int f0, int n) {
         a.cH = nh_; a.cW = nw_; a.cC = F2p; a.cKW = 3; a.cStride = 1; a.cPad = 1; a.cOH = nh_; a.cOW = nw_;
         a.M = n * nh_ * nw_; a.N = 32; a.out = act32_; a.ldo = 32; a.act = ACT_RELU;
         if ((r = gemm(A_CONV, EPI_STD, a, oc2_))) return r;
-        tic(F_ELT, 0, (double)a.M * 68);
-        r = launch_dot32_relu(stream, act32_, 32, w2_, b2_, netd_, a.M);
-        toc();
+        r = timed(F_ELT, 0, (double)a.M * 68, [&] { return launch_dot32_relu(stream, act32_, 32, w2_, b2_, netd_, a.M); });
         if (r) return r;
         nhwc("output_conv2_0", act32_, 32, nh_, nw_, 32, false);
     } else {   // output_conv2: 3x3 -> ReLU -> 1x1 -> ReLU fused in one implicit-GEMM launch
@@ -594,9 +579,9 @@ int DepthEngine::run_chunk(const uint8_t *frames, int n, float *depth_out, uint8
                            int flip) {
     int r;
     stages_.clear();
-    tic(F_PP, 0, (double)n * ((double)pH_ * pW_ * 3 + (double)nh_ * nw_ * 3 * 2));
-    r = launch_preprocess(stream, frames, n, pH_, pW_, nh_, nw_, xi_, xw_, yi_, yw_, patchA_, 640, nullptr);
-    toc();
+    r = timed(F_PP, 0, (double)n * ((double)pH_ * pW_ * 3 + (double)nh_ * nw_ * 3 * 2), [&] {
+        return launch_preprocess(stream, frames, n, pH_, pW_, nh_, nw_, xi_, xw_, yi_, yw_, patchA_, 640, nullptr);
+    });
     if (r) return r;
     if ((r = vit(n))) return r;
     // the DPT head and the tail in balanced chunks of at most hB_ frames (32-bit offsets of the high-resolution split maps)
@@ -619,25 +604,22 @@ int DepthEngine::tail(int n, float *depth_out, uint8_t *rgb_out, float *mn, floa
     float *full = depth_out ? depth_out : full_;
     if (cfg_.metric) {      // ZoeDepth head -> Pillow resize to the frame -> per-frame min / max -> heat encode
         if ((r = metric_head(n))) return r;
-        tic(F_PP, 0, (double)n * ((double)nh_ * nw_ * 4 + (double)pH_ * pW_ * 8));
-        r = launch_pil_resize(stream, md_, ptmp_, full, n, nh_, nw_, pH_, pW_, pxb_, pxk_, pxks_, pyb_, pyk_, pyks_);
-        if (!r) r = launch_init_minmax(stream, mm_, n);
-        if (!r) r = launch_minmax_only(stream, full, n, (int64_t)pH_ * pW_, mm_);
-        toc();
+        r = timed(F_PP, 0, (double)n * ((double)nh_ * nw_ * 4 + (double)pH_ * pW_ * 8), [&] {
+            int rc = launch_pil_resize(stream, md_, ptmp_, full, n, nh_, nw_, pH_, pW_, pxb_, pxk_, pxks_, pyb_, pyk_, pyks_);
+            if (!rc) rc = launch_init_minmax(stream, mm_, n);
+            if (!rc) rc = launch_minmax_only(stream, full, n, (int64_t)pH_ * pW_, mm_);
+            return rc;
+        });
         if (r) return r;
-        tic(F_PP, 0, (double)n * (double)pH_ * pW_ * 7);
-        r = launch_heat_encode(stream, full, n, pH_, pW_, mm_, flip, rgb_out, mn, mx);
-        toc();
+        r = timed(F_PP, 0, (double)n * (double)pH_ * pW_ * 7, [&] { return launch_heat_encode(stream, full, n, pH_, pW_, mm_, flip, rgb_out, mn, mx); });
         return r;
     }
-    tic(F_PP, 0, (double)n * ((double)nh_ * nw_ * 4 + (double)pH_ * pW_ * 4));
-    if ((r = launch_init_minmax(stream, mm_, n))) return r;
-    r = launch_depth_resize_minmax(stream, netd_, n, nh_, nw_, full, pH_, pW_, mm_);
-    toc();
+    r = timed(F_PP, 0, (double)n * ((double)nh_ * nw_ * 4 + (double)pH_ * pW_ * 4), [&] {
+        const int rc = launch_init_minmax(stream, mm_, n);
+        return rc ? rc : launch_depth_resize_minmax(stream, netd_, n, nh_, nw_, full, pH_, pW_, mm_);
+    });
     if (r) return r;
-    tic(F_PP, 0, (double)n * (double)pH_ * pW_ * 7);
-    r = launch_heat_encode(stream, full, n, pH_, pW_, mm_, flip, rgb_out, mn, mx);
-    toc();
+    r = timed(F_PP, 0, (double)n * (double)pH_ * pW_ * 7, [&] { return launch_heat_encode(stream, full, n, pH_, pW_, mm_, flip, rgb_out, mn, mx); });
     return r;
 }
 

@@ -1,7 +1,9 @@
 // Shared plumbing of the band engines (depth_anything, flow_raft, flow_gmflow, mask_mmdet): the ctx stream, the named-weight map, the upload
-// of packed GEMM weights (pack_layout.h has the layouts) with folded BatchNorm, a two-pass arena, per-family kernel timing, the
-// implicit-GEMM / dense GEMM launch helpers, and the debug-stage registry behind pb_*_get_stage.
+// of packed GEMM weights (pack_layout.h has the layouts) with folded BatchNorm, the two-pass arena planner (plan_arena), the timed launch
+// (timed / timed_gemm: per-family and per-kernel timing around a launch), the implicit-GEMM / dense GEMM launch helpers, and the debug-stage
+// registry behind pb_*_get_stage.  The two flow bands share more than this: flow_engine.h.
 #pragma once
+#include <functional>
 #include <map>
 #include <string>
 #include <vector>
@@ -165,13 +167,33 @@ class EngineBase {
     // Convolutions set a.cC (and a.cLd, unless the map is exactly its parts) of ONE part before the call, and check a.cC == w.Cseg
     void set_weights(GemmArgs &a, const PackedW &w, bool is_conv) const;
 
+    // The two-pass arena of a prepare(): `carves` assigns every buffer of the plan with carve() and returns 0 or a pb error.  It runs twice -
+    // first planning (carve returns null and only adds up the sizes), then, with the arena grown to the planned size and zeroed, for real -
+    // so a buffer's offset is decided by the order and the sizes of the carve calls alone.  `what` names the arena in the allocation error.
+    int plan_arena(const char *what, const std::function<int()> &carves);
     void *carve(size_t bytes);
-    // grow the arena to the planned size (after the planning pass) and zero it
-    int commit_arena(const char *what);
 
-    // helpers launch on cur_ (the ctx stream unless a derived engine forks work onto side streams)
-    void tic(int fam, double flops, double bytes, double passes = 1.0);
-    void toc();
+    // One timed launch: `launch` issues the kernel(s) of one timer record and returns their status; with the timer on, the record opens on
+    // cur_ before the call and closes on cur_ after it (cur_: the ctx stream unless a derived engine forks work onto side streams), counted
+    // in family `fam` with the algorithmic flops / bytes and `passes` MFMA passes over the flops.  `name`: the kernel symbol stats() reports
+    // instead of the family's name.  A failed launch leaves its record without a name.
+    template <class Launch> int timed(int fam, double flops, double bytes, Launch &&launch, const char *name = nullptr, double passes = 1.0) {
+        if (!timer.enabled) return launch();
+        const size_t rec = tic(fam, flops, bytes, passes);
+        const int r = launch();
+        if (!r) timer.recs[rec].name = name;
+        toc(rec);
+        return r;
+    }
+    // ... of launch_gemm (or a launcher that records its choice the same way): named by the kernel symbol the launch picked (gemm.h)
+    template <class Launch> int timed_gemm(int fam, double flops, double bytes, Launch &&launch, double passes = 1.0) {
+        if (!timer.enabled) return launch();
+        const size_t rec = tic(fam, flops, bytes, passes);
+        const int r = launch();
+        if (!r) timer.recs[rec].name = pb_gemm_last_kernel();
+        toc(rec);
+        return r;
+    }
     // fusion hooks of one conv() call: a second (ReLU'd) copy of the output, and the SepConvGRU epilogues (gemm.h ACT_GRU_*)
     struct ConvFuse { f16 *out2 = nullptr; float *gru_h = nullptr; const f16 *gru_z = nullptr; f16 *gru_rh = nullptr; int gru_ld = 384;
                       const f16 *add2 = nullptr; };       // add2: a second skip tensor (same row stride as the output), added next to add1
@@ -194,14 +216,17 @@ class EngineBase {
     std::map<std::string, const pb_tensor *> tmap_;
     std::vector<void *> owned_;                 // permanent device allocations (weights), freed by the destructor
     f16 *zero_ = nullptr;
-    char *arena_ = nullptr;
-    size_t arena_bytes_ = 0, arena_off_ = 0;
-    size_t plan_bytes_ = 0;                     // what the last commit_arena's plan carved (arena_bytes_ never shrinks)
-    bool planning_ = false;
+    size_t plan_bytes_ = 0;                     // what the last plan_arena carved (the arena itself never shrinks)
     hipStream_t cur_ = nullptr;
-    std::vector<size_t> open_;                  // tic / toc nesting across streams
 
   private:
+    // grow the arena to the planned size (after the planning pass) and zero it
+    int commit_arena(const char *what);
+    char *arena_ = nullptr;
+    size_t arena_bytes_ = 0, arena_off_ = 0;
+    bool planning_{false};
+    size_t tic(int fam, double flops, double bytes, double passes);     // opens a record on cur_, returns its index
+    void toc(size_t rec);
     int upload_rows(const std::vector<f16> &rows, f16 **dst);
     std::map<std::string, DevMem> snaps_;
 };

@@ -55,18 +55,13 @@ EngineBase::~EngineBase() {
     if (stream) hipStreamDestroy(stream);
 }
 
-void EngineBase::tic(int fam, double flops, double bytes, double passes) {
-    if (!timer.enabled) return;
+size_t EngineBase::tic(int fam, double flops, double bytes, double passes) {
     KernelTimer::Rec r{fam, timer.get(), timer.get(), flops, bytes, flops * passes, nullptr};
     hipEventRecord(r.a, cur_);
     timer.recs.push_back(r);
-    open_.push_back(timer.recs.size() - 1);
+    return timer.recs.size() - 1;
 }
-void EngineBase::toc() {
-    if (!timer.enabled) return;
-    hipEventRecord(timer.recs[open_.back()].b, cur_);
-    open_.pop_back();
-}
+void EngineBase::toc(size_t rec) { hipEventRecord(timer.recs[rec].b, cur_); }
 
 int EngineBase::stats(pb_kernel_stat *out, int cap) {
     if (hipStreamSynchronize(stream) != hipSuccess) return -2;
@@ -314,6 +309,17 @@ void *EngineBase::carve(size_t bytes) {
     return planning_ ? nullptr : (void *)(arena_ + off);
 }
 
+int EngineBase::plan_arena(const char *what, const std::function<int()> &carves) {
+    for (int pass = 0; pass < 2; ++pass) {
+        planning_ = pass == 0;
+        arena_off_ = 0;
+        int r = carves();
+        if (!r && pass == 0) r = commit_arena(what);
+        if (r) return r;
+    }
+    return 0;
+}
+
 int EngineBase::commit_arena(const char *what) {
     plan_bytes_ = arena_off_;
     if (arena_off_ > arena_bytes_) {
@@ -349,12 +355,11 @@ int EngineBase::conv(const f16 *in, int cC, int cLd, int n, int H, int W, int kh
     // algorithmic bytes: the input map once, the weights once, the output once (fp16)
     // one family per kernel symbol launch_gemm picks: 256 x 256 ping-pong, 256 x 64 (N <= 64), 128 x 128
     const double nr = w.Nreal ? w.Nreal : a.N;       // (padding rows of the weights are not the layer's work)
-    tic(wide ? F_CONV : (conv_tile == TILE_AUTO && a.N <= 64 ? F_CONV64 : F_CONV128), 2.0 * a.M * nr * w.Kreal, 2.0 * ((double)n * H * W * cC + nr * w.Kreal + (double)a.M * nr), w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
-    // 64 -> 64 channels at half resolution: the halo-tiled direct kernel (halo_conv.hip) instead of the implicit GEMM
-    int r = kh == 3 && kw == 3 && conv_tile == TILE_AUTO && conv3x3_c64_supported(a) ? launch_conv3x3_c64(cur_, a) : launch_gemm(cur_, A_CONV, EPI_STD, conv_tile, a);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-    toc();
-    return r;
+    return timed_gemm(wide ? F_CONV : (conv_tile == TILE_AUTO && a.N <= 64 ? F_CONV64 : F_CONV128), 2.0 * a.M * nr * w.Kreal,
+                      2.0 * ((double)n * H * W * cC + nr * w.Kreal + (double)a.M * nr), [&] {
+        // 64 -> 64 channels at half resolution: the halo-tiled direct kernel (halo_conv.hip) instead of the implicit GEMM
+        return kh == 3 && kw == 3 && conv_tile == TILE_AUTO && conv3x3_c64_supported(a) ? launch_conv3x3_c64(cur_, a) : launch_gemm(cur_, A_CONV, EPI_STD, conv_tile, a);
+    }, w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
 }
 
 int EngineBase::dense(const f16 *A, int lda, int64_t M, const PackedW &w, f16 *out, int ldo, int act, const f16 *add1, int o8_off, int a_pa,
@@ -367,9 +372,6 @@ int EngineBase::dense(const f16 *A, int lda, int64_t M, const PackedW &w, f16 *o
     if (o8_off) { a.o8_off = o8_off; a.o8_scale = (float)(1 << kMx2Pa); }
     if (w.mx2 && a_pa >= 0) a.mx_scale_a = 127 - a_pa;
     a.sk_ws = sk_ws_; a.sk_cap = sk_cap_;
-    tic(F_GEMM, 2.0 * M * (double)a.N * w.Kreal, 2.0 * ((double)M * w.Kreal + (double)a.N * w.Kreal + (double)M * a.N), w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
-    int r = launch_gemm(cur_, A_DENSE, EPI_STD, dense_tile, a);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-    toc();
-    return r;
+    return timed_gemm(F_GEMM, 2.0 * M * (double)a.N * w.Kreal, 2.0 * ((double)M * w.Kreal + (double)a.N * w.Kreal + (double)M * a.N),
+                      [&] { return launch_gemm(cur_, A_DENSE, EPI_STD, dense_tile, a); }, w.mx3 ? 2.0 : (w.mx2 ? 1.5 : 1.0 + w.sa + w.sw));
 }

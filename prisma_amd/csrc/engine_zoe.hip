@@ -132,10 +132,7 @@ int DepthEngine::metric_head(int n) {
         return gemm(A_DENSE, EPI_F32, a, w);
     };
     auto softplus = [&](float *x, int64_t rows, int cols, int ld) -> int {
-        tic(F_ELT, 0, (double)rows * cols * 8);
-        int rr = launch_softplus(stream, x, rows, cols, ld);
-        toc();
-        return rr;
+        return timed(F_ELT, 0, (double)rows * cols * 8, [&] { return launch_softplus(stream, x, rows, cols, ld); });
     };
     // the two bin buffers ping-pong, so intermediate levels are only kept (copied) for parity dumps
     auto keep_bins = [&](const std::string &name, const float *src, int hh, int ww) -> int {
@@ -161,32 +158,27 @@ int DepthEngine::metric_head(int n) {
         const int64_t R = (int64_t)n * H * W;
         if ((r = dense16(xb, Fp, R, zproj_[i].a, zh_, 128, ACT_RELU))) return r;
         if ((r = dense16(zh_, 128, R, zproj_[i].b, zemb_[ce ^ 1], 128, ACT_NONE))) return r;
-        tic(F_ELT, 0, (double)R * 128 * 6);
-        r = launch_bilerp_add(stream, zemb_[ce ^ 1], zemb_[ce], zxa_, n, h, w, H, W, 128, 128, 128, 128);
-        toc();
+        r = timed(F_ELT, 0, (double)R * 128 * 6, [&] { return launch_bilerp_add(stream, zemb_[ce ^ 1], zemb_[ce], zxa_, n, h, w, H, W, 128, 128, 128, 128); });
         if (r) return r;
         if ((r = dense16(zxa_, 128, R, zattr_[i].a, zh_, 128, ACT_RELU))) return r;
         const int ldA = zattr_[i].b.N;
         if ((r = dense32(zh_, 128, R, zattr_[i].b, zA_, ldA))) return r;
         if ((r = softplus(zA_, R, na[i], ldA))) return r;
-        tic(F_ELT, 0, (double)R * 64 * 8);
-        r = launch_attractor(stream, zA_, ldA, na[i], zbins_[cb], h, w, zbins_[cb ^ 1], n, H, W, 300.f);   // inv_attractor's defaults apply
-        toc();
+        // inv_attractor's defaults apply
+        r = timed(F_ELT, 0, (double)R * 64 * 8, [&] {
+            return launch_attractor(stream, zA_, ldA, na[i], zbins_[cb], h, w, zbins_[cb ^ 1], n, H, W, 300.f);
+        });
         if (r) return r;
         cb ^= 1; ce ^= 1; h = H; w = W;
         if ((r = keep_bins("bins" + std::to_string(i), zbins_[cb], h, w))) return r;
     }
     // ---- conditional log-binomial over [out_conv activation | rel depth | embedding] (zoedepth_v1.py:192-205) ----
     const int64_t RF = (int64_t)n * nh_ * nw_;
-    tic(F_ELT, 0, (double)RF * (192 * 2 + 128 * 8));
-    r = launch_zoe_cat(stream, act32_, 32, netd_, zemb_[ce], 128, h, w, zcat_, n, nh_, nw_);
-    toc();
+    r = timed(F_ELT, 0, (double)RF * (192 * 2 + 128 * 8), [&] { return launch_zoe_cat(stream, act32_, 32, netd_, zemb_[ce], 128, h, w, zcat_, n, nh_, nw_); });
     if (r) return r;
     if ((r = dense16(zcat_, 192, RF, zclb_.a, zmid_, 128, ACT_GELU))) return r;
     if ((r = dense32(zmid_, 128, RF, zclb_.b, zpt_, 8))) return r;
-    tic(F_ELT, 0, (double)RF * (8 * 4 + 64 * 16));
-    r = launch_logbinom_depth(stream, zpt_, 8, zbins_[cb], h, w, md_, n, nh_, nw_, 0.0212f, 50.f);
-    toc();
+    r = timed(F_ELT, 0, (double)RF * (8 * 4 + 64 * 16), [&] { return launch_logbinom_depth(stream, zpt_, 8, zbins_[cb], h, w, md_, n, nh_, nw_, 0.0212f, 50.f); });
     if (r) return r;
     stages_["metric_net"] = Stage::f32_rows(md_, n, nh_, nw_);
     return 0;

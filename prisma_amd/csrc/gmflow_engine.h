@@ -1,10 +1,12 @@
 // flow_gmflow band engine: GMFlow at the band's defaults (bands/flow_gmflow.py:223-255: feature_channels 128, 1 scale,
 // 1 head, swin attention with 2 x 2 windows, global matching, global propagation, 6 transformer blocks, ffn x 4, padding_factor 16), and
 // with set_matching the two inference-time radii of the same checkpoint (local matching, local-window propagation: gmflow_local.hip).
-// Shares RaftEngine's frame prep, instance-norm encoder, convex upsampling, flow encode and consistency-mask kernels.
+// Frame prep, the instance-norm encoder and the tail of a call (convex upsampling, flow encode, consistency masks) are FlowEngine's.
 #pragma once
+#include <vector>
+
+#include "flow_engine.h"
 #include "gmflow_kernels.h"
-#include "raft_engine.h"
 
 // Host tables of prepare_g (gmflow_engine.hip; pb_op_gm_tables hands the same two functions to the tests): the per-window sine position
 // embedding tiled over the 2 x 2 windows, token-major [h8 * w8, 128], and the shifted-window region ids in window order [4][Lw]
@@ -15,11 +17,11 @@ void shift_regions(int h8, int w8, std::vector<int8_t> &reg, int splits = 2);
 // propagation V^T (round_up(P, 32))
 void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP, int splits = 2);
 
-class GmflowEngine : public RaftEngine {
+class GmflowEngine : public FlowEngine {
   public:
-    explicit GmflowEngine(int device, const CreateEnv &env = create_env()) : RaftEngine(device, env) {}
+    explicit GmflowEngine(int device, const CreateEnv &env = create_env()) : FlowEngine(device, env) {}
     int load(const pb_tensor *w, int n) override;
-    // same contract as RaftEngine::infer; `iters` is ignored (GMFlow is not iterative)
+    // `iters` is ignored (GMFlow is not iterative)
     int infer(const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward, float *flow_out, uint8_t *rgb_out,
               float *maxdisp, uint8_t *mask_out = nullptr, float alpha1 = 0.05f, float alpha2 = 0.5f) override;
     // It registers its own stages only, all fp32 rows [n, rows, cols]: "feat" [F, P, 128], "block0" / "tfeat" [2 pairs, P, 128] (token stream after
@@ -40,6 +42,7 @@ class GmflowEngine : public RaftEngine {
     // 1, or 2 for the refinement model (gmflow_with_refine: num_scales 2, upsample_factor 4, padding_factor 32, attn_splits_list 2 8) - decided
     // by the weights in load(): 'backbone.trident_conv.weight' and an 'upsampler.2.weight' of 144 rows
     int num_scales() const { return scales_; }
+    // two scales: the fine scale's token rows and batch elements bound the pairs of a call
     int chunk_pairs(int wanted, int H, int W, float scale, int dirs) const override;
 
   private:
@@ -57,6 +60,7 @@ class GmflowEngine : public RaftEngine {
     int blocks(const GmGeom &g, int NPs, const int8_t *region, const char *blk0);
     int fine_scale(int B, int dirs);
 
+    Enc backbone_;                  // CNNEncoder: FlowEngine's encoder without conv biases
     Layer layers_[6];
     PackedW ffq_, ffk_, up0_, up2_;
     GmGeom g_{};
@@ -70,16 +74,14 @@ class GmflowEngine : public RaftEngine {
     float *feat4_ = nullptr, *pos4_ = nullptr, *warp_ = nullptr, *flowu_ = nullptr, *flowm4_ = nullptr, *flowf_ = nullptr, *flowp4_ = nullptr,
           *tfeat8_ = nullptr, *blk08_ = nullptr;
     int8_t *region4_ = nullptr;
-    int gF_ = 0, gH_ = 0, gW_ = 0, gD_ = 0;
     int isz_h_ = 0, isz_w_ = 0;
     int corr_r_ = -1, prop_r_ = -1;
-    float *gupi_ = nullptr;           // flow at the inference size, before the resize back
-    float gS_ = 0.f;
+    int options_ = 0;                 // the plan key's word: counts the changes set_inference_size / set_matching made, so the next call re-plans
+    float *upi_ = nullptr;            // flow at the inference size, before the resize back
     int ldvP_ = 0;
     float *feat_ = nullptr, *pos_ = nullptr, *X_ = nullptr, *Y1_ = nullptr, *Yq_ = nullptr, *Ow_ = nullptr, *M_ = nullptr, *Om_ = nullptr,
-          *flowm_ = nullptr, *flowp_ = nullptr, *gmask_ = nullptr, *gup_ = nullptr, *blk0_ = nullptr;
+          *flowm_ = nullptr, *flowp_ = nullptr, *blk0_ = nullptr;
     f16 *Xs_ = nullptr, *Qw_ = nullptr, *Kw_ = nullptr, *Kcw_ = nullptr, *Vtw_ = nullptr, *Vtcw_ = nullptr, *Os_ = nullptr, *cat_ = nullptr,
         *Hs_ = nullptr, *gridvt_ = nullptr, *Vtf_ = nullptr, *qs_ = nullptr, *ks_ = nullptr, *umap_ = nullptr, *u1_ = nullptr;
     int8_t *region_ = nullptr;
-    unsigned *gmaxd_ = nullptr;
 };

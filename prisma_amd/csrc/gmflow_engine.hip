@@ -17,6 +17,7 @@
 //   * PB_PREC_SPLIT: every MFMA operand is a hi + lo fp16 pair (GEMMs: three K segments; attention: three passes for S and for P V) -
 //     this network's two softmax stages amplify operand rounding several times more than RAFT does.
 #include "gmflow_engine.h"
+#include "flow_chunk.h"
 
 #include <math.h>
 #include <string.h>
@@ -54,8 +55,8 @@ int GmflowEngine::load(const pb_tensor *w, int n) {
         scales_ = tri ? 2 : 1;
         enc_s3_ = tri ? 1 : 2;
     }
-    if ((r = pack_encoder("backbone", false, false, fnet_))) return r;
-    if ((r = pack_conv("backbone.conv2", true, nullptr, nullptr, fnet_.out, 1))) return r;
+    if ((r = pack_encoder("backbone", false, false, backbone_))) return r;
+    if ((r = pack_conv("backbone.conv2", true, nullptr, nullptr, backbone_.out, 1))) return r;
     if (scales_ == 2 && (r = pack_conv("backbone.trident_conv", false, nullptr, nullptr, trident_, 1))) return r;
     auto lin = [&](const std::string &name, int N, int K, PackedW &out, bool bias) -> int {
         const pb_tensor *t = find(name + ".weight");
@@ -137,9 +138,9 @@ void gm_geometry(int h8, int w8, GmGeom &g, int &ldvP, int splits) {
 }
 
 int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
-    if (F <= gF_ && H == gH_ && W == gW_ && scale == gS_ && dirs <= gD_) return 0;
+    if (plan_.covers(F, H, W, scale, dirs, options_)) return 0;
     PB_HIP(hipStreamSynchronize(stream));
-    gF_ = 0; gH_ = 0; gW_ = 0; gD_ = 0;       // (a failure below must not leave the old plan's key on a half-written geometry: raft_engine.hip prepare)
+    plan_.clear();
     geometry(H, W, scale, scales_ == 2 ? 32 : 16);        // InputPadder(padding_factor): 16 = 8 x the 2 x 2 split, 32 = 4 x the fine scale's 8 x 8 split
     if (isz_h_ > 0) {                 // --inference_size: the network's size is given, nothing is padded (sh_, sw_ stay the output size)
         padl_ = padt_ = 0;
@@ -164,9 +165,7 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
         R = std::max(R, B * 2 * P4_); VtW = std::max(VtW, B * 2 * 64 * g4_.ldv); Pm = P4_;
     }
     const size_t slack = 1 << 16;
-    for (int pass = 0; pass < 2; ++pass) {
-        planning_ = pass == 0;
-        arena_off_ = 0;
+    int r = plan_arena("flow_gmflow", [&]() -> int {
         carve_encoder(F);
         feat_ = (float *)carve((size_t)F * P_ * 128 * 4);
         pos_ = (float *)carve((size_t)P_ * 128 * 4);
@@ -196,15 +195,13 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
         Vtf_ = (f16 *)carve((size_t)B * 64 * ldvP_ * 2 + slack);
         qs_ = (f16 *)carve((size_t)R * 256 * 2 + slack); ks_ = (f16 *)carve((size_t)R * 256 * 2 + slack);
         umap_ = (f16 *)carve((size_t)B * Pm * 384 * 2 + slack); u1_ = (f16 *)carve((size_t)round_up(B * Pm, 256) * 512 * 2 + slack);
-        gmask_ = (float *)carve((size_t)B * P_ * 576 * 4);                // (two scales: P4 x 144 logits, the same bytes)
-        gup_ = (float *)carve((size_t)B * sh_ * sw_ * 2 * 4);
-        gupi_ = isz_h_ > 0 ? (float *)carve((size_t)B * Hp_ * Wp_ * 2 * 4) : nullptr;
-        gmaxd_ = (unsigned *)carve((size_t)B * 4);
-        if (pass == 0) {
-            const int rc = commit_arena("flow_gmflow");
-            if (rc) return rc;
-        }
-    }
+        mask_ = (float *)carve((size_t)B * P_ * 576 * 4);                 // (two scales: P4 x 144 logits, the same bytes)
+        up_ = (float *)carve((size_t)B * sh_ * sw_ * 2 * 4);
+        upi_ = isz_h_ > 0 ? (float *)carve((size_t)B * Hp_ * Wp_ * 2 * 4) : nullptr;
+        maxd_ = (unsigned *)carve((size_t)B * 4);
+        return 0;
+    });
+    if (r) return r;
     std::vector<float> pos;
     std::vector<int8_t> reg;
     sine_positions(h8_, w8_, pos);
@@ -219,10 +216,9 @@ int GmflowEngine::prepare_g(int F, int H, int W, float scale, int dirs) {
         PB_HIP(hipMemcpyAsync(pos4_, pos4.data(), pos4.size() * 4, hipMemcpyHostToDevice, stream));
         PB_HIP(hipMemcpyAsync(region4_, reg4.data(), reg4.size(), hipMemcpyHostToDevice, stream));
     }
-    int r = launch_gm_grid_vt(stream, gridvt_, P_, w8_, ldvP_);
-    if (r) return r;
+    if ((r = launch_gm_grid_vt(stream, gridvt_, P_, w8_, ldvP_))) return r;
     if ((r = upload_resize_tables(H, W, scale))) return r;         // synchronises: the host vectors above stay alive until then
-    gF_ = F; gH_ = H; gW_ = W; gS_ = scale; gD_ = dirs;
+    plan_.set(F, H, W, scale, dirs, options_);
     return 0;
 }
 
@@ -231,11 +227,8 @@ int GmflowEngine::gemm32(const f16 *A, int lda, int64_t M, const PackedW &w, flo
     a.A = A; a.lda = lda; a.N = w.N; a.M = (int)M;
     set_weights(a, w, false);
     a.out32 = out; a.ldo = ldo; a.scale = 1.f;
-    tic(F_GEMM, 2.0 * M * (double)w.N * w.Kreal, 2.0 * ((double)M * w.Kreal + (double)w.N * w.Kreal) + 4.0 * M * w.N, 1.0 + w.sa + w.sw);
-    int r = launch_gemm(cur_, A_DENSE, EPI_F32, TILE_AUTO, a);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-    toc();
-    return r;
+    return timed_gemm(F_GEMM, 2.0 * M * (double)w.N * w.Kreal, 2.0 * ((double)M * w.Kreal + (double)w.N * w.Kreal) + 4.0 * M * w.N, [&] { return launch_gemm(cur_, A_DENSE, EPI_F32, TILE_AUTO, a); },
+                      1.0 + w.sa + w.sw);
 }
 
 int GmflowEngine::gemm16(const f16 *A, int lda, int64_t M, const PackedW &w, f16 *out, int ldo, int act, int lo_off) {
@@ -243,11 +236,8 @@ int GmflowEngine::gemm16(const f16 *A, int lda, int64_t M, const PackedW &w, f16
     a.A = A; a.lda = lda; a.N = w.N; a.M = (int)M;
     set_weights(a, w, false);
     a.out = out; a.ldo = ldo; a.act = act; a.lo_off = lo_off;
-    tic(F_GEMM, 2.0 * M * (double)w.N * w.Kreal, 2.0 * ((double)M * w.Kreal + (double)w.N * w.Kreal + (double)M * w.N), 1.0 + w.sa + w.sw);
-    int r = launch_gemm(cur_, A_DENSE, EPI_STD, TILE_AUTO, a);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-    toc();
-    return r;
+    return timed_gemm(F_GEMM, 2.0 * M * (double)w.N * w.Kreal, 2.0 * ((double)M * w.Kreal + (double)w.N * w.Kreal + (double)M * w.N), [&] { return launch_gemm(cur_, A_DENSE, EPI_STD, TILE_AUTO, a); },
+                      1.0 + w.sa + w.sw);
 }
 
 // 3 x 3 convolution of a split map [n, H, W, 256] (128 channels) with fp32 output [n * OH * OW, 128]: the implicit GEMM with the fp32 epilogue
@@ -261,20 +251,14 @@ int GmflowEngine::conv32(const f16 *in, int n, int H, int W, int stride, const P
     PB_CHECK(!w.sw || w.Cseg == 128, PB_ERR_STATE, "conv32: weights packed for %d channels", w.Cseg);
     set_weights(a, w, true);
     PB_CHECK(w.K == 9 * a.cC, PB_ERR_STATE, "conv32: packed K %d != 9*%d", w.K, a.cC);
-    tic(F_CONV128, 2.0 * a.M * (double)a.N * w.Kreal, 2.0 * ((double)n * H * W * 128 + (double)a.N * w.Kreal) + 4.0 * a.M * a.N, 1.0 + w.sa + w.sw);
-    int r = launch_gemm(cur_, A_CONV, EPI_F32, TILE_128, a);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-    toc();
-    return r;
+    return timed_gemm(F_CONV128, 2.0 * a.M * (double)a.N * w.Kreal, 2.0 * ((double)n * H * W * 128 + (double)a.N * w.Kreal) + 4.0 * a.M * a.N, [&] { return launch_gemm(cur_, A_CONV, EPI_F32, TILE_128, a); },
+                      1.0 + w.sa + w.sw);
 }
 
 int GmflowEngine::attention(const Attn128Args &a, double keys_per_query) {
     // S and P V: 2 x 2 x (128 + vcols) flops per (query, key); three MFMA passes each in split mode
     const double qk = 2.0 * a.B * (double)a.L * keys_per_query * 128.0, pv = 2.0 * a.B * (double)a.L * keys_per_query * a.vcols;
-    tic(F_ATTN, qk + pv, 0, ((a.split ? 3.0 : 1.0) * qk + (a.split && !a.pv_single ? 3.0 : 1.0) * pv) / (qk + pv));
-    int r = launch_attention128x(cur_, a);
-    toc();
-    return r;
+    return timed(F_ATTN, qk + pv, 0, [&] { return launch_attention128x(cur_, a); }, nullptr, ((a.split ? 3.0 : 1.0) * qk + (a.split && !a.pv_single ? 3.0 : 1.0) * pv) / (qk + pv));
 }
 
 int GmflowEngine::set_inference_size(int h, int w) {
@@ -283,7 +267,7 @@ int GmflowEngine::set_inference_size(int h, int w) {
                  "flow_gmflow (two scales): --inference_size %d %d must be multiples of 32, at least 64 (4 x the fine scale's 8 x 8 window split)", h, w);
     PB_CHECK((h == 0 && w == 0) || (h >= 32 && w >= 32 && h % 16 == 0 && w % 16 == 0), PB_ERR_ARG,
              "flow_gmflow: --inference_size %d %d must be multiples of 16 (8 x the 2 x 2 window split; the reference fails in its window split otherwise)", h, w);
-    if (h != isz_h_ || w != isz_w_) { isz_h_ = h; isz_w_ = w; gF_ = 0; }      // re-plan on the next call
+    if (h != isz_h_ || w != isz_w_) { isz_h_ = h; isz_w_ = w; ++options_; }      // re-plan on the next call
     return 0;
 }
 
@@ -300,16 +284,15 @@ int GmflowEngine::set_matching(int corr_radius, int prop_radius) {
              "flow_gmflow: --corr_radius_list %d must be -1 (global matching) or 1 .. 4", corr_radius);
     PB_CHECK(prop_radius == -1 || (prop_radius >= 1 && prop_radius <= 2), PB_ERR_ARG,
              "flow_gmflow: --prop_radius_list %d must be -1 (global propagation) or 1 .. 2", prop_radius);
-    if (corr_radius != corr_r_ || prop_radius != prop_r_) { corr_r_ = corr_radius; prop_r_ = prop_radius; gF_ = 0; }      // re-plan on the next call
+    if (corr_radius != corr_r_ || prop_radius != prop_r_) { corr_r_ = corr_radius; prop_r_ = prop_radius; ++options_; }      // re-plan on the next call
     return 0;
 }
 
 // two scales: a (pair, direction) carries 2 x P4 token rows of ~14 KB through the fine scale's blocks - chunks of at most 2^20 rows (~14 GB)
 int GmflowEngine::chunk_pairs(int wanted, int H, int W, float scale, int dirs) const {
-    if (scales_ != 2) return RaftEngine::chunk_pairs(wanted, H, W, scale, dirs);
-    int sh, sw;
-    out_size(H, W, scale, &sh, &sw);
-    const int64_t P4 = isz_h_ > 0 ? (int64_t)(isz_h_ / 4) * (isz_w_ / 4) : (int64_t)((sh + 31) / 32 * 8) * ((sw + 31) / 32 * 8);
+    if (scales_ != 2) return wanted;
+    const FlowGeometry g = flow_geometry(H, W, scale, 32);
+    const int64_t P4 = isz_h_ > 0 ? (int64_t)(isz_h_ / 4) * (isz_w_ / 4) : (int64_t)(g.Hp / 4) * (g.Wp / 4);
     const int64_t fit = std::min<int64_t>((INT64_C(1) << 20) / ((int64_t)dirs * 2 * P4), 511 / dirs);       // ... and of 511 batch elements (fine_scale)
     return (int)std::max<int64_t>(1, std::min<int64_t>(wanted, fit));
 }
@@ -331,9 +314,7 @@ int GmflowEngine::blocks(const GmGeom &g, int NPs, const int8_t *region, const c
         jobs.j[2] = GmPackJob{Y1_, 640, 256, Vtw_, 1};
         jobs.j[3] = GmPackJob{Y1_, 640, 384, Kcw_, 0};
         jobs.j[4] = GmPackJob{Y1_, 640, 512, Vtcw_, 1};
-        tic(F_ELT, 0, 0);
-        r = launch_gm_pack(stream, jobs, g, Bw, shifted);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_gm_pack(stream, jobs, g, Bw, shifted); });
         if (r) return r;
         Attn128Args a;
         a.Q = Qw_; a.K = Kw_; a.Vt = Vtw_; a.region = shifted ? region : nullptr; a.nreg = nw; a.O = Ow_;
@@ -344,39 +325,27 @@ int GmflowEngine::blocks(const GmGeom &g, int NPs, const int8_t *region, const c
         // features (EXPERIMENTS.md 6.12), so the coarse scale has to be several times closer than the one-scale model needs to be.
         a.pv_single = scales_ == 2 ? 0 : 1;
         if ((r = attention(a, g.Lw))) return r;
-        tic(F_ELT, 0, 0);
-        r = launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R); });
         if (r) return r;
         if ((r = gemm32(Os_, 256, R, L.merge_s, M_, 128))) return r;
-        tic(F_LN, 0, 0);
-        r = launch_gm_ln(stream, M_, L.ln1s_g, L.ln1s_b, X_, Xs_, R, g, 1, shifted, 0);
-        toc();
+        r = timed(F_LN, 0, 0, [&] { return launch_gm_ln(stream, M_, L.ln1s_g, L.ln1s_b, X_, Xs_, R, g, 1, shifted, 0); });
         if (r) return r;
         // cross attention + FFN: queries from the updated stream, keys / values from the partner frame's ENTERING stream (Kcw_, Vtcw_)
         if ((r = gemm32(Xs_, 256, R, L.q_c, Yq_, 128))) return r;
         jobs.n = 1;
         jobs.j[0] = GmPackJob{Yq_, 128, 0, Qw_, 0};
-        tic(F_ELT, 0, 0);
-        r = launch_gm_pack(stream, jobs, g, Bw, shifted);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_gm_pack(stream, jobs, g, Bw, shifted); });
         if (r) return r;
         a.K = Kcw_; a.Vt = Vtcw_; a.kxor = nw;            // the same window of the pair's other frame
         if ((r = attention(a, g.Lw))) return r;
-        tic(F_ELT, 0, 0);
-        r = launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_gm_split_rows(stream, Ow_, 128, 128, Os_, R); });
         if (r) return r;
         if ((r = gemm32(Os_, 256, R, L.merge_c, M_, 128))) return r;
-        tic(F_LN, 0, 0);
-        r = launch_gm_ln(stream, M_, L.ln1c_g, L.ln1c_b, X_, cat_, R, g, 1, shifted, 1);
-        toc();
+        r = timed(F_LN, 0, 0, [&] { return launch_gm_ln(stream, M_, L.ln1c_g, L.ln1c_b, X_, cat_, R, g, 1, shifted, 1); });
         if (r) return r;
         if ((r = gemm16(cat_, 512, R, L.mlp0, Hs_, 2048, ACT_GELU, 1024))) return r;
         if ((r = gemm32(Hs_, 2048, R, L.mlp2, M_, 128))) return r;
-        tic(F_LN, 0, 0);
-        r = launch_gm_ln(stream, M_, L.ln2c_g, L.ln2c_b, X_, Xs_, R, g, 0, 0, 0);
-        toc();
+        r = timed(F_LN, 0, 0, [&] { return launch_gm_ln(stream, M_, L.ln2c_g, L.ln2c_b, X_, Xs_, R, g, 0, 0, 0); });
         if (r) return r;
         if (debug && li == 0) {
             PB_HIP(hipMemcpyAsync(blk0_, X_, (size_t)R * 128 * 4, hipMemcpyDeviceToDevice, stream));
@@ -404,19 +373,15 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     const int corr_r = fine ? -1 : corr_r_, prop_r = fine ? -1 : prop_r_;       // two scales: the coarse scale is always global
 
     // ---- frame prep (resize, replicate pad to /16 - two scales: /32 -, ImageNet normalisation) and the backbone, once per frame ----
-    tic(F_PP, 0, (double)F * H * W * 3);
-    r = launch_raft_prep(stream, frames, F, H, W, sh_, sw_, Hp_, Wp_, padl_, padt_, scale != 1.f, xi_, xc_, yi_, yc_, img_, nullptr, 1,
-                         split_w_ ? 64 : 0, -1, 1, isz_h_ > 0);
-    toc();
-    if (r) return r;
+    if ((r = prep_frames(frames, F, H, W, scale, -1, 1, isz_h_ > 0))) return r;
     const f16 *x = nullptr;
-    if ((r = run_encoder(fnet_, true, F, &x))) return r;
+    if ((r = run_encoder(backbone_, true, F, &x))) return r;
     if (!fine) {
-        if ((r = gemm32(x, es * 128, (int64_t)F * P, fnet_.out, feat_, 128))) return r;
+        if ((r = gemm32(x, es * 128, (int64_t)F * P, backbone_.out, feat_, 128))) return r;
     } else {
         // the backbone ends at 1/4 (layer3 at stride 1, conv2 1 x 1) and ONE 3 x 3 weight gives both scales (trident_conv.py:64-72): stride 1
         // the 1/4 features, stride 2 the 1/8 features
-        if ((r = gemm16(x, es * 128, (int64_t)F * P4_, fnet_.out, c2_, 256, ACT_NONE, split_w_ ? 128 : 0))) return r;
+        if ((r = gemm16(x, es * 128, (int64_t)F * P4_, backbone_.out, c2_, 256, ACT_NONE, split_w_ ? 128 : 0))) return r;
         if ((r = conv32(c2_, F, h4_, w4_, 1, trident_, feat4_))) return r;
         if ((r = conv32(c2_, F, h4_, w4_, 2, trident_, feat_))) return r;
         stages_["feat4"] = Stage::f32_rows(feat4_, F, P4_, 128);
@@ -424,9 +389,7 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     stages_["feat"] = Stage::f32_rows(feat_, F, P, 128);
 
     // ---- tokens + per-window sine positions; the six transformer blocks ----
-    tic(F_ELT, 0, 0);
-    r = launch_gm_tokens(stream, feat_, pos_, X_, Xs_, NP, P);
-    toc();
+    r = timed(F_ELT, 0, 0, [&] { return launch_gm_tokens(stream, feat_, pos_, X_, Xs_, NP, P); });
     if (r) return r;
     if ((r = blocks(g_, NP, region_, "block0"))) return r;
     stages_["tfeat"] = Stage::f32_rows(X_, (int64_t)NP * 2, P, 128);
@@ -451,16 +414,12 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
         if (dirs == 2) { m.K = Xs_; m.q_bstride = m.k_bstride = img; m.kxor = 1; }
         else { m.K = Xs_ + img; m.q_bstride = m.k_bstride = 2 * img; }
         if ((r = attention(m, P))) return r;
-        tic(F_ELT, 0, 0);
-        r = launch_gm_match_flow(stream, Om_, flowm_, Vtf_, B, P, w8_, ldvP_);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_gm_match_flow(stream, Om_, flowm_, Vtf_, B, P, w8_, ldvP_); });
         if (r) return r;
     } else {
         const double nc = (2.0 * corr_r + 1) * (2.0 * corr_r + 1);
-        tic(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4);
-        r = launch_gm_local_match(stream, X_, flowm_, prop_r < 0 ? Vtf_ : nullptr, B, h8_, w8_, img_step, corr_r, ldvP_);
-        if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_match_kernel";
-        toc();
+        r = timed(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4, [&] { return launch_gm_local_match(stream, X_, flowm_, prop_r < 0 ? Vtf_ : nullptr, B, h8_, w8_, img_step, corr_r, ldvP_); },
+                  "gm_local_match_kernel");
         if (r) return r;
     }
     stages_["flow_match"] = Stage::f32_rows(flowm_, B, P, 2);
@@ -469,14 +428,10 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     // matched flow ----
     if ((r = gemm32(Xs_, 256, R, ffq_, Yq_, 128))) return r;
     if (prop_r < 0) {
-        tic(F_ELT, 0, 0);
-        r = launch_gm_split_rows(stream, Yq_, 128, 128, qs_, R);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_gm_split_rows(stream, Yq_, 128, 128, qs_, R); });
         if (r) return r;
         if ((r = gemm32(qs_, 256, R, ffk_, M_, 128))) return r;         // the key is k_proj of the PROJECTED query, as in the reference (:363-364)
-        tic(F_ELT, 0, 0);
-        r = launch_gm_split_rows(stream, M_, 128, 128, ks_, R);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_gm_split_rows(stream, M_, 128, 128, ks_, R); });
         if (r) return r;
         Attn128Args pa;
         pa.Q = qs_; pa.K = ks_; pa.O = Om_; pa.B = B; pa.L = P; pa.ldv = ldvP_; pa.split = split; pa.vcols = 32; pa.ldq = 256;
@@ -486,19 +441,15 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
     } else {
         if ((r = gemm32(Xs_, 256, R, ffk_, M_, 128))) return r;         // the local form projects the key from the feature itself (:389), not from the query
         const double nc = (2.0 * prop_r + 1) * (2.0 * prop_r + 1);
-        tic(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4);
-        r = launch_gm_local_prop(stream, Yq_, M_, flowm_, Om_, B, h8_, w8_, img_step, prop_r);
-        if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_prop_kernel";
-        toc();
+        r = timed(F_ATTN, 2.0 * B * (double)P * nc * 128.0, 2.0 * (double)B * P * 128 * 4, [&] { return launch_gm_local_prop(stream, Yq_, M_, flowm_, Om_, B, h8_, w8_, img_step, prop_r); },
+                  "gm_local_prop_kernel");
         if (r) return r;
     }
 
     // ---- convex upsampling (gmflow.py:74-92), unpad, encode ----
-    tic(F_ELT, 0, 0);
     // (two scales: launched for the coarse flow it leaves in flowp_; the B P x 768 bytes of umap_ it also writes - 29 MB at 1080p x 0.75 with
     // both directions, microseconds - are overwritten by the fine scale's launch.  The kernel is the one-scale model's, left as it is.)
-    r = launch_gm_upsampler_in(stream, Om_, X_, flowp_, umap_, B, P, img_step);
-    toc();
+    r = timed(F_ELT, 0, 0, [&] { return launch_gm_upsampler_in(stream, Om_, X_, flowp_, umap_, B, P, img_step); });
     if (r) return r;
     stages_["flow_prop"] = Stage::f32_rows(flowp_, B, P, 2);
     int hu = h8_, wu = w8_, Pu = P, factor = 8;            // the grid the upsampler runs on
@@ -508,25 +459,8 @@ int GmflowEngine::infer(const uint8_t *frames, int F, int H, int W, float scale,
         hu = h4_; wu = w4_; Pu = P4_; factor = 4; flow_lo = flowp4_;
     }
     if ((r = conv(umap_, 192, 384, B, hu, wu, 3, 3, 1, up0_, u1_, 512, ACT_RELU, 0, nullptr, nullptr, split_w_ ? 256 : 0))) return r;
-    if ((r = gemm32(u1_, 512, (int64_t)B * Pu, up2_, gmask_, 9 * factor * factor))) return r;
-    float *up = flow_out ? flow_out : gup_;
-    tic(F_PP, 0, (double)B * sh_ * sw_ * 8);
-    if (isz_h_ > 0) {                 // convex upsampling at the inference size, then the bilinear resize back to the scaled frame
-        r = launch_upsample(stream, flow_lo, gmask_, B, hu, wu, 0, 0, Hp_, Wp_, gupi_, gmaxd_, factor);
-        if (!r) r = launch_flow_resize_back(stream, gupi_, B, Hp_, Wp_, sh_, sw_, up, gmaxd_);
-    } else {
-        r = launch_upsample(stream, flow_lo, gmask_, B, hu, wu, padl_, padt_, sh_, sw_, up, gmaxd_, factor);
-    }
-    toc();
-    if (r) return r;
-    tic(F_PP, 0, (double)B * sh_ * sw_ * 11);
-    r = launch_flow_encode(stream, up, B, sh_, sw_, gmaxd_, rgb_out, maxdisp);
-    toc();
-    if (r || !mask_out) return r;
-    tic(F_PP, 0, (double)B * sh_ * sw_ * 17);
-    r = launch_fwdbwd_mask(stream, up, NP, sh_, sw_, alpha1, alpha2, mask_out);
-    toc();
-    return r;
+    if ((r = gemm32(u1_, 512, (int64_t)B * Pu, up2_, mask_, 9 * factor * factor))) return r;
+    return flow_tail(flow_lo, B, NP, hu, wu, factor, flow_out, rgb_out, maxdisp, mask_out, alpha1, alpha2, upi_);
 }
 
 // The fine scale of the two-scale model (gmflow.py:112-165, scale_idx = 1) from the coarse flow in flowp_ [B, P, 2] and the 1/4 features in
@@ -537,29 +471,20 @@ int GmflowEngine::fine_scale(int B, int dirs) {
     int r;
     const int64_t R4 = (int64_t)B * 2 * P4_;
     PB_CHECK(B * 128 <= 65535, PB_ERR_ARG, "flow_gmflow (two scales): %d (pair, direction) elements in one call; the window kernels take 511 (128 windows each)", B);
-    tic(F_ELT, 0, (double)B * P4_ * 128 * 8);
-    r = launch_gm_warp(stream, flowp_, feat4_, flowu_, warp_, B, dirs, h8_, w8_);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_warp_kernel";
-    toc();
+    r = timed(F_ELT, 0, (double)B * P4_ * 128 * 8, [&] { return launch_gm_warp(stream, flowp_, feat4_, flowu_, warp_, B, dirs, h8_, w8_); }, "gm_warp_kernel");
     if (r) return r;
     stages_["flow_up"] = Stage::f32_rows(flowu_, B, P4_, 2);
     stages_["warp"] = Stage::f32_rows(warp_, B, P4_, 128);
-    tic(F_ELT, 0, 0);
-    r = launch_gm_tokens(stream, feat4_, pos4_, X_, Xs_, B, P4_, warp_, dirs);
-    toc();
+    r = timed(F_ELT, 0, 0, [&] { return launch_gm_tokens(stream, feat4_, pos4_, X_, Xs_, B, P4_, warp_, dirs); });
     if (r) return r;
     if ((r = blocks(g4_, B, region4_, "block0_4"))) return r;
     stages_["tfeat4"] = Stage::f32_rows(X_, (int64_t)B * 2, P4_, 128);
     // local matching of (source, warped target): images 2 b and 2 b + 1 of the stream; the residual adds to the enlarged flow (:145)
     const double nc = (2.0 * corr_r4_ + 1) * (2.0 * corr_r4_ + 1);
-    tic(F_ATTN, 2.0 * B * (double)P4_ * nc * 128.0, 2.0 * (double)B * P4_ * 128 * 4);
-    r = launch_gm_local_match(stream, X_, flowm4_, nullptr, B, h4_, w4_, 2, corr_r4_, 0);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_match_kernel";
-    toc();
+    r = timed(F_ATTN, 2.0 * B * (double)P4_ * nc * 128.0, 2.0 * (double)B * P4_ * 128 * 4, [&] { return launch_gm_local_match(stream, X_, flowm4_, nullptr, B, h4_, w4_, 2, corr_r4_, 0); },
+              "gm_local_match_kernel");
     if (r) return r;
-    tic(F_ELT, 0, 0);
-    r = launch_gm_flow_add(stream, flowu_, flowm4_, flowf_, (int64_t)B * P4_);
-    toc();
+    r = timed(F_ELT, 0, 0, [&] { return launch_gm_flow_add(stream, flowu_, flowm4_, flowf_, (int64_t)B * P4_); });
     if (r) return r;
     stages_["flow_match4"] = Stage::f32_rows(flowf_, B, P4_, 2);
     // the two projections run over the whole stream in one launch each, as at the coarse scale; gm_local_prop reads the source images only
@@ -568,14 +493,10 @@ int GmflowEngine::fine_scale(int B, int dirs) {
     if ((r = gemm32(Xs_, 256, R4, ffq_, Yq_, 128))) return r;
     if ((r = gemm32(Xs_, 256, R4, ffk_, M_, 128))) return r;
     const double np = (2.0 * prop_r4_ + 1) * (2.0 * prop_r4_ + 1);
-    tic(F_ATTN, 2.0 * B * (double)P4_ * np * 128.0, 2.0 * (double)B * P4_ * 128 * 4);
-    r = launch_gm_local_prop(stream, Yq_, M_, flowf_, Om_, B, h4_, w4_, 2, prop_r4_);
-    if (timer.enabled && !r) timer.recs[open_.back()].name = "gm_local_prop_kernel";
-    toc();
+    r = timed(F_ATTN, 2.0 * B * (double)P4_ * np * 128.0, 2.0 * (double)B * P4_ * 128 * 4, [&] { return launch_gm_local_prop(stream, Yq_, M_, flowf_, Om_, B, h4_, w4_, 2, prop_r4_); },
+              "gm_local_prop_kernel");
     if (r) return r;
-    tic(F_ELT, 0, 0);
-    r = launch_gm_upsampler_in(stream, Om_, X_, flowp4_, umap_, B, P4_, 2);
-    toc();
+    r = timed(F_ELT, 0, 0, [&] { return launch_gm_upsampler_in(stream, Om_, X_, flowp4_, umap_, B, P4_, 2); });
     if (r) return r;
     stages_["flow_prop4"] = Stage::f32_rows(flowp4_, B, P4_, 2);
     return 0;

@@ -190,7 +190,7 @@ int MaskEngine::prepare(int n, int H, int W) {
     const int B = std::min(n, cfg_.max_batch);
     if (B <= pB_ && H == pH_ && W == pW_) return 0;
     PB_HIP(hipStreamSynchronize(stream));
-    pB_ = 0; pH_ = 0; pW_ = 0;          // (a failure below must not leave the old plan's key on a half-written plan: raft_engine.hip prepare)
+    pB_ = 0; pH_ = 0; pW_ = 0;          // (a failure below must not leave the old plan's key on a half-written plan: flow_engine.h PlanKey)
     {   // the post-processing scratch is sized by the mask-feature resolution: drop it when the geometry changes
         void **post[] = {(void **)&pk_, (void **)&bits_, (void **)&plog_, (void **)&pstat_, (void **)&inter_, (void **)&sig_,
                          (void **)&nmsf_, (void **)&pidx_, (void **)&nmsi_, (void **)&use_};
@@ -212,9 +212,7 @@ int MaskEngine::prepare(int n, int H, int W) {
     const size_t slack = 1 << 20;
     const int sp = 1 + sa_;                                 // fp16 parts per element of a feature map
     auto rows = [&](int i) { return (size_t)round_up((int64_t)B * lh_[i] * lw_[i], 256) * sp; };
-    for (int pass = 0; pass < 2; ++pass) {
-        planning_ = pass == 0;
-        arena_off_ = 0;
+    int r = plan_arena("mask", [&]() -> int {
         xt_ = (int *)carve((size_t)nw_ * 16); yt_ = (int *)carve((size_t)nh_ * 16);
         img_ = (f16 *)carve((size_t)B * Hp_ * Wp_ * 8 * sp + slack);
         chw_ = debug ? (float *)carve((size_t)B * 3 * Hp_ * Wp_ * 4) : nullptr;
@@ -248,11 +246,9 @@ int MaskEngine::prepare(int n, int H, int W) {
         cl_ = (float *)carve((size_t)B * pts_ * Cp * 4 + slack);
         cs_ = (float *)carve((size_t)B * pts_ * Cp * 4 + slack);
         gst_ = (float *)carve((size_t)B * gn_chunks(lh_[0] * lw_[0]) * 512 * 2 * 4); gaff_ = (float *)carve((size_t)B * 512 * 2 * 4);
-        if (pass == 0) {
-            const int rc = commit_arena("mask");
-            if (rc) return rc;
-        }
-    }
+        return 0;
+    });
+    if (r) return r;
     std::vector<int> xt, yt;
     linear_taps_u8(W, nw_, false, xt);
     linear_taps_u8(H, nh_, true, yt);
@@ -271,11 +267,7 @@ int MaskEngine::conv_f32(const f16 *in, int cC, int cLd, int n, int H, int W, co
     a.out32 = out; a.ldo = ldo; a.scale = 1.f;
     set_weights(a, w, true);
     PB_CHECK(w.K == 9 * a.cC, PB_ERR_STATE, "conv_f32: packed K %d != 9*%d", w.K, a.cC);
-    tic(F_CONV, 2.0 * a.M * (double)a.N * w.Kreal, 0);
-    int r = launch_gemm(cur_, A_CONV, EPI_F32, TILE_128, a);
-    if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-    toc();
-    return r;
+    return timed_gemm(F_CONV, 2.0 * a.M * (double)a.N * w.Kreal, 0, [&] { return launch_gemm(cur_, A_CONV, EPI_F32, TILE_128, a); });
 }
 
 int MaskEngine::conv_gn_relu(const f16 *in, int cC, int cLd, int n, int H, int W, int k, const ConvGN &c, f16 *tmp, f16 *out,
@@ -284,12 +276,11 @@ int MaskEngine::conv_gn_relu(const f16 *in, int cC, int cLd, int n, int H, int W
     int r = k == 1 ? dense(in, L(cLd), (int64_t)n * H * W, c.w, tmp, L(N), ACT_NONE, nullptr, 0, -1, lo(N))
                    : conv(in, cC, L(cLd), n, H, W, k, k, 1, c.w, tmp, L(N), ACT_NONE, 0, nullptr, nullptr, lo(N));
     if (r) return r;
-    tic(F_ELT, 0, (double)n * H * W * N * 6 * (1 + sa_));
     // dup (split only): rows [hi | hi | lo] instead of [hi | lo]
-    r = launch_gn_relu(cur_, tmp, out, n, H * W, c.gn.C, L(N), dup && sa_ ? 3 * ldo : L(ldo), 32, c.gn.g, c.gn.b, gst_cur_, gaff_cur_, lo(N),
-                       dup && sa_ ? 2 * ldo : lo(ldo), dup && sa_ ? ldo : 0);
-    toc();
-    return r;
+    return timed(F_ELT, 0, (double)n * H * W * N * 6 * (1 + sa_), [&] {
+        return launch_gn_relu(cur_, tmp, out, n, H * W, c.gn.C, L(N), dup && sa_ ? 3 * ldo : L(ldo), 32, c.gn.g, c.gn.b, gst_cur_, gaff_cur_, lo(N),
+                              dup && sa_ ? 2 * ldo : lo(ldo), dup && sa_ ? ldo : 0);
+    });
 }
 
 int MaskEngine::backbone(int n) {
@@ -303,15 +294,10 @@ int MaskEngine::backbone(int n) {
         a.cOH = a.cH; a.cOW = a.cW; a.M = n * a.cH * a.cW;
         a.out = stem_out_; a.ldo = L(64); a.lo_off = lo(64); a.act = ACT_RELU;
         a.ps_h = a.cH; a.ps_w = a.cW; a.ps_s = 2; a.ps_co = 64;
-        tic(F_CONV, 2.0 * n * H2 * W2 * 64.0 * 147, 0);
-        r = launch_gemm(cur_, A_CONV, EPI_PIXSHUF, TILE_AUTO, a);
-        if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-        toc();
+        r = timed_gemm(F_CONV, 2.0 * n * H2 * W2 * 64.0 * 147, 0, [&] { return launch_gemm(cur_, A_CONV, EPI_PIXSHUF, TILE_AUTO, a); });
         if (r) return r;
     }
-    tic(F_ELT, 0, 0);
-    r = launch_maxpool3x3s2(stream, stem_out_, pool_, n, H2, W2, 64, sa_);
-    toc();
+    r = timed(F_ELT, 0, 0, [&] { return launch_maxpool3x3s2(stream, stem_out_, pool_, n, H2, W2, 64, sa_); });
     if (r) return r;
     const f16 *x = pool_;
     int hi = lh_[0], wi = lw_[0];
@@ -344,16 +330,12 @@ int MaskEngine::neck(int n) {
     for (int i = 0; i < 4; ++i)
         if ((r = dense(c_[i], L(256 << i), (int64_t)n * lh_[i] * lw_[i], lat_[i], latb_[i], L(256), ACT_NONE, nullptr, 0, -1, lo(256)))) return r;
     for (int i = 3; i > 0; --i) {
-        tic(F_ELT, 0, 0);
-        r = launch_nearest_add(stream, latb_[i - 1], latb_[i], n, lh_[i - 1], lw_[i - 1], lh_[i], lw_[i], 256, sa_);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_nearest_add(stream, latb_[i - 1], latb_[i], n, lh_[i - 1], lw_[i - 1], lh_[i], lw_[i], 256, sa_); });
         if (r) return r;
     }
     for (int i = 0; i < 4; ++i)
         if ((r = conv(latb_[i], 256, L(256), n, lh_[i], lw_[i], 3, 3, 1, fpnc_[i], p_[i], L(256), ACT_NONE, 0, nullptr, nullptr, lo(256)))) return r;
-    tic(F_ELT, 0, 0);
-    r = launch_subsample2(stream, p_[3], p_[4], n, lh_[3], lw_[3], L(256));         // whole rows: both parts of a split map
-    toc();
+    r = timed(F_ELT, 0, 0, [&] { return launch_subsample2(stream, p_[3], p_[4], n, lh_[3], lw_[3], L(256)); });         // whole rows: both parts of a split map
     for (int i = 0; i < 5; ++i) stages_["p" + std::to_string(i + 2)] = Stage::f16_nhwc(p_[i], n, 256, lh_[i], lw_[i], L(256), lo(256));
     return r;
 }
@@ -367,18 +349,14 @@ int MaskEngine::head(int n) {
         const f16 *x = p_[i];
         int cC = 256, h = lh_[i], w = lw_[i];
         if (i == 3) {
-            tic(F_ELT, 0, 0);
-            r = launch_coord_concat(stream, p_[3], p5cc_, n, h, w, 256, L(256), lo(256));
-            toc();
+            r = timed(F_ELT, 0, 0, [&] { return launch_coord_concat(stream, p_[3], p5cc_, n, h, w, 256, L(256), lo(256)); });
             if (r) return r;
             x = p5cc_; cC = 320;
         }
         for (int j = 0; j < i; ++j) {
             if ((r = conv_gn_relu(x, cC, cC, n, h, w, 3, mfc_[i][j], mt_[0], mg_[0], mfc))) return r;
             const bool last = j == i - 1;
-            tic(F_ELT, 0, 0);
-            r = launch_bilinear(stream, mg_[0], last ? macc_ : mg_[1], n, h, w, 2 * h, 2 * w, mfc, L(mfc), L(mfc), last ? 1 : 0, lo(mfc), lo(mfc));
-            toc();
+            r = timed(F_ELT, 0, 0, [&] { return launch_bilinear(stream, mg_[0], last ? macc_ : mg_[1], n, h, w, 2 * h, 2 * w, mfc, L(mfc), L(mfc), last ? 1 : 0, lo(mfc), lo(mfc)); });
             if (r) return r;
             x = mg_[1]; cC = mfc; h *= 2; w *= 2;
         }
@@ -400,16 +378,14 @@ int MaskEngine::head_level(int n, int lvl) {
     int fh = lh_[lvl], fw = lw_[lvl];
     if (lvl == 0 || lvl == 4) {
         const int th = lvl == 0 ? lh_[1] : lh_[3], tw = lvl == 0 ? lw_[1] : lw_[3];
-        tic(F_ELT, 0, 0);
-        r = launch_bilinear(cur_, src, rs, n, fh, fw, th, tw, 256, L(256), L(256), 0, lo(256), lo(256));
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_bilinear(cur_, src, rs, n, fh, fw, th, tw, 256, L(256), L(256), 0, lo(256), lo(256)); });
         if (r) return r;
         src = rs; fh = th; fw = tw;
     }
-    tic(F_ELT, 0, 0);
-    r = launch_coord_concat(cur_, src, fcc, n, fh, fw, 256, L(256), lo(256));
-    if (!r) r = launch_bilinear(cur_, fcc, grid, n, fh, fw, g, g, 320, L(320), L(320), 0, lo(320), lo(320));
-    toc();
+    r = timed(F_ELT, 0, 0, [&] {
+        const int rc = launch_coord_concat(cur_, src, fcc, n, fh, fw, 256, L(256), lo(256));
+        return rc ? rc : launch_bilinear(cur_, fcc, grid, n, fh, fw, g, g, 320, L(320), L(320), 0, lo(320), lo(320));
+    });
     if (r) return r;
     const f16 *x = grid;
     int cC = 320, cLd = 320;
@@ -428,9 +404,7 @@ int MaskEngine::head_level(int n, int lvl) {
     }
     float *cl = cl_ + (int64_t)n * goff_[lvl] * Cp;
     if ((r = conv_f32(x, fc, fc, n, g, g, conv_cls_, cl, Cp))) return r;
-    tic(F_PP, 0, (double)n * g * g * Cp * 8);
-    r = launch_cls_points_nms(cur_, cl, cs_, n, pts_, goff_[lvl], g, Cp);
-    toc();
+    r = timed(F_PP, 0, (double)n * g * g * Cp * 8, [&] { return launch_cls_points_nms(cur_, cl, cs_, n, pts_, goff_[lvl], g, Cp); });
     if (r) return r;
     stages_["kernel_pred" + std::to_string(lvl)] = Stage::f32_nhwc(kp, n, 256, g, g, 256);
     stages_["cls_logit" + std::to_string(lvl)] = Stage::f32_nhwc(cl, n, cfg_.num_classes, g, g, Cp);
@@ -521,9 +495,7 @@ int MaskEngine::post_chunk(int n, int first, float confidence, const std::vector
     }
     if (total) {
         PB_HIP(hipMemcpyAsync(pidx_, rows.data(), total * 4, hipMemcpyHostToDevice, stream));
-        tic(F_PP, 0, (double)total * 256 * 6);
-        r = launch_gather_rows_f16(stream, kp_, pidx_, pk_, (int)total, (int)total, 256, sa_);
-        toc();
+        r = timed(F_PP, 0, (double)total * 256 * 6, [&] { return launch_gather_rows_f16(stream, kp_, pidx_, pk_, (int)total, (int)total, 256, sa_); });
         if (r) return r;
     }
     for (int b = 0; b < n; ++b) {
@@ -535,14 +507,9 @@ int MaskEngine::post_chunk(int n, int first, float confidence, const std::vector
         a.A = pk_ + f.off * L(256); a.lda = L(256); a.M = K; a.W = mf_ + (int64_t)b * HW4 * (sa_ ? 768 : 256); a.K = sa_ ? 768 : 256; a.N = HW4;
         if (sa_) a.kwrap = 8;
         a.out32 = plog_ + f.off * HW4; a.ldo = HW4; a.scale = 1.f; a.zero = zero_;
-        tic(F_GEMM, 2.0 * K * (double)HW4 * 256, 0, sa_ ? 3.0 : 1.0);
-        r = launch_gemm(stream, A_DENSE, EPI_F32, TILE_AUTO, a);
-        if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-        toc();
+        r = timed_gemm(F_GEMM, 2.0 * K * (double)HW4 * 256, 0, [&] { return launch_gemm(stream, A_DENSE, EPI_F32, TILE_AUTO, a); }, sa_ ? 3.0 : 1.0);
         if (r) return r;
-        tic(F_PP, 0, (double)K * HW4 * 4);
-        r = launch_mask_stats(stream, plog_ + f.off * HW4, K, HW4, HW4, cfg_.mask_thr, pstat_ + f.off * 2);
-        toc();
+        r = timed(F_PP, 0, (double)K * HW4 * 4, [&] { return launch_mask_stats(stream, plog_ + f.off * HW4, K, HW4, HW4, cfg_.mask_thr, pstat_ + f.off * 2); });
         if (r) return r;
         f.st.resize((size_t)K * 2);
         PB_HIP(hipMemcpyAsync(f.st.data(), pstat_ + f.off * 2, (size_t)K * 8, hipMemcpyDeviceToHost, stream));
@@ -575,11 +542,12 @@ int MaskEngine::post_chunk(int n, int first, float confidence, const std::vector
         PB_HIP(hipMemcpyAsync(ni, li[b].data(), 1024 * 4, hipMemcpyHostToDevice, stream));
         PB_HIP(hipMemcpyAsync(nf, lf[b].data(), 1024 * 4, hipMemcpyHostToDevice, stream));
         // binary masks as bit rows; pairwise intersections by popcount (matrix_nms.py:66-67), then the decay
-        tic(F_PP, 0, (double)n2 * HW4 * 4 + (double)n2 * n2 * (HW4 / 8));
-        r = launch_bitpack_rows(stream, plog_, HW4, ni, n2, HW4, cfg_.mask_thr, bits);
-        if (!r) r = launch_mask_intersections(stream, bits, n2, HW4 / 64, inter, 512);
-        if (!r) r = launch_matrix_nms(stream, inter, 512, nf, ni + 512, nf + 512, n2, cfg_.sigma, nf + 1536, nf + 1024);
-        toc();
+        r = timed(F_PP, 0, (double)n2 * HW4 * 4 + (double)n2 * n2 * (HW4 / 8), [&] {
+            int rc = launch_bitpack_rows(stream, plog_, HW4, ni, n2, HW4, cfg_.mask_thr, bits);
+            if (!rc) rc = launch_mask_intersections(stream, bits, n2, HW4 / 64, inter, 512);
+            if (!rc) rc = launch_matrix_nms(stream, inter, 512, nf, ni + 512, nf + 512, n2, cfg_.sigma, nf + 1536, nf + 1024);
+            return rc;
+        });
         if (r) return r;
         f.ns.resize(n2);
         PB_HIP(hipMemcpyAsync(f.ns.data(), nf + 1024, (size_t)n2 * 4, hipMemcpyDeviceToHost, stream));
@@ -613,9 +581,7 @@ int MaskEngine::post_chunk(int n, int first, float confidence, const std::vector
         float *sig = sig_ + (size_t)b * cfg_.max_per_img * HW4;
         PB_HIP(hipMemcpyAsync(ni, frow[b].data(), (size_t)n3 * 4, hipMemcpyHostToDevice, stream));
         PB_HIP(hipMemcpyAsync(us, use[b].data(), (size_t)n3, hipMemcpyHostToDevice, stream));
-        tic(F_PP, 0, (double)n3 * HW4 * 8);
-        r = launch_sigmoid_rows(stream, plog_, HW4, ni, n3, HW4, sig);
-        toc();
+        r = timed(F_PP, 0, (double)n3 * HW4 * 8, [&] { return launch_sigmoid_rows(stream, plog_, HW4, ni, n3, HW4, sig); });
         if (r) return r;
         uint8_t *inst = nullptr;
         if (debug) {        // parity dumps only: one frame at a time through a shared buffer
@@ -628,9 +594,9 @@ int MaskEngine::post_chunk(int n, int first, float confidence, const std::vector
             }
             inst = inst_;
         }
-        tic(F_PP, 0, (double)opix * (3 + 64.0 * n3));
-        r = launch_band_accumulate(stream, sig, n3, fh, fw, nh_, nw_, pH_, pW_, cfg_.mask_thr, us, mask_out + (int64_t)(first + b) * opix * 3, inst);
-        toc();
+        r = timed(F_PP, 0, (double)opix * (3 + 64.0 * n3), [&] {
+            return launch_band_accumulate(stream, sig, n3, fh, fw, nh_, nw_, pH_, pW_, cfg_.mask_thr, us, mask_out + (int64_t)(first + b) * opix * 3, inst);
+        });
         if (r) return r;
         if (debug) {
             res.masks.resize((size_t)n3 * opix);
@@ -645,9 +611,9 @@ int MaskEngine::post_chunk(int n, int first, float confidence, const std::vector
 int MaskEngine::run_chunk(const uint8_t *frames, int n, int first, float confidence, const std::vector<uint8_t> &keep_class,
                           uint8_t *mask_out) {
     int r;
-    tic(F_PP, 0, (double)n * ((double)pH_ * pW_ * 3 + (double)Hp_ * Wp_ * 8));
-    r = launch_mask_prep(stream, frames, n, pH_, pW_, nh_, nw_, Hp_, Wp_, xt_, yt_, img_, chw_, sa_);
-    toc();
+    r = timed(F_PP, 0, (double)n * ((double)pH_ * pW_ * 3 + (double)Hp_ * Wp_ * 8), [&] {
+        return launch_mask_prep(stream, frames, n, pH_, pW_, nh_, nw_, Hp_, Wp_, xt_, yt_, img_, chw_, sa_);
+    });
     if (r) return r;
     if (chw_) stages_["input"] = Stage::f32_nchw(chw_, n, 3, Hp_, Wp_);
     if ((r = backbone(n)) || (r = neck(n))) return r;
@@ -684,7 +650,6 @@ int MaskEngine::infer(const uint8_t *frames, int n, int H, int W, float confiden
     if (r) return r;
     cur_ = stream; gst_cur_ = gst_; gaff_cur_ = gaff_;
     timer.reset();
-    open_.clear();
     stages_.clear();
     results_.assign(n, Instances());
     auto cb = std::move(chunk_begin), ce = std::move(chunk_end);       // hooks are per call
@@ -727,9 +692,8 @@ int MaskEngine::sdf_green(uint8_t *masks, int n, int H, int W) {
         sdf_px_ = px;
     }
     PB_CHECK(n <= 4096, PB_ERR_ARG, "sdf_green: %d frames per call (at most 4096)", n);
-    tic(F_PP, 0, (double)px * 14.0);
-    const int r = launch_sdf_green(stream, masks, n, H, W, sdf_g_, sdf_g_ + px, (int *)(sdf_g_ + round_up(2 * sdf_px_, 16)), sdf_tab_,
-                                   sdf_tab_ + sdf_ncap_ + 1, sdf_ncap_);
-    toc();
-    return r;
+    return timed(F_PP, 0, (double)px * 14.0, [&] {
+        return launch_sdf_green(stream, masks, n, H, W, sdf_g_, sdf_g_ + px, (int *)(sdf_g_ + round_up(2 * sdf_px_, 16)), sdf_tab_, sdf_tab_ + sdf_ncap_ + 1,
+                                sdf_ncap_);
+    });
 }

@@ -18,95 +18,9 @@
 
 #include <algorithm>
 
-namespace {
-inline int cp64(int c) { return (int)round_up(c, 64); }
-
-void cubic_taps_u8(int src, int dst, double scale, std::vector<int> &idx, std::vector<int> &co) {
-    // OpenCV 8-bit INTER_CUBIC: float32 coefficients (A = -0.75) -> saturate_cast<short>(c * 2048)
-    idx.resize((size_t)dst * 4);
-    co.resize((size_t)dst * 4);
-    const double inv = 1.0 / scale;
-    const float A = -0.75f;
-    for (int d = 0; d < dst; ++d) {
-        float fx = (float)((d + 0.5) * inv - 0.5);
-        const int sx = (int)floorf(fx);
-        fx -= (float)sx;
-        float c[4];
-        c[0] = ((A * (fx + 1.f) - 5.f * A) * (fx + 1.f) + 8.f * A) * (fx + 1.f) - 4.f * A;
-        c[1] = ((A + 2.f) * fx - (A + 3.f)) * fx * fx + 1.f;
-        c[2] = ((A + 2.f) * (1.f - fx) - (A + 3.f)) * (1.f - fx) * (1.f - fx) + 1.f;
-        c[3] = 1.f - c[0] - c[1] - c[2];
-        for (int t = 0; t < 4; ++t) {
-            idx[(size_t)d * 4 + t] = std::min(std::max(sx - 1 + t, 0), src - 1);
-            co[(size_t)d * 4 + t] = (int)nearbyint((double)c[t] * 2048.0);
-        }
-    }
-}
-}  // namespace
-
 int RaftEngine::chunk_pairs(int wanted, int H, int W, float scale, int dirs) const {
     if (!hoist_) return wanted;
-    int sh, sw;
-    out_size(H, W, scale, &sh, &sw);
-    const int64_t P = (int64_t)((sh + 7) / 8) * ((sw + 7) / 8);       // geometry(): the scaled frame padded to multiples of 8
-    return flow_chunk_pairs(wanted, dirs, P, upd8_ ? 576 : 384);
-}
-
-void RaftEngine::out_size(int H, int W, float scale, int *sh, int *sw) {
-    *sh = (int)nearbyint((double)H * scale);
-    *sw = (int)nearbyint((double)W * scale);
-}
-
-// BasicEncoder weights (extractor.py:118-192) up to the last residual block: stem, layer1-3, downsample paths.  bnf: eval BatchNorm folded
-// into the convolutions (cnet); conv_bias: the 3x3 / 7x7 convolutions carry biases (RAFT yes, GMFlow's CNNEncoder no - its 1x1 downsample
-// convolutions do, backbone.py:22-25)
-int RaftEngine::pack_encoder(const std::string &en, bool bnf, bool conv_bias, Enc &E) {
-    int r;
-    const int dims[3] = {64, 96, 128};
-    std::vector<float> sc, sf;
-    {   // stem 7x7 / stride 2 (extractor.py:124,171): on the 4 x 4 space-to-depth image (64 channels = (dy, dx, c), raft_prep) it is a
-        // 3x3 / stride 1 convolution whose 4 x 64 output channels are the 2 x 2 output pixels of a block - an implicit GEMM on the
-        // ping-pong kernel with the pixel-shuffle epilogue instead of an im2col round trip (2.8 GB per 32 frames at 1080p x 0.75).
-        // W2[(sy, sx, o)][(ty, tx)][(dy, dx, c)] = w[o][c][ky][kx],  ky = 4 (ty - 1) + dy - 2 sy + 3 (same in x), zero outside 0..6
-        auto iw = tmap_.find(en + ".conv1.weight"), ib = tmap_.find(en + ".conv1.bias");
-        PB_CHECK(iw != tmap_.end() && (ib != tmap_.end() || !conv_bias), PB_ERR_ARG, "missing %s.conv1", en.c_str());
-        if (bnf && (r = fold_bn(en + ".norm1", 64, sc, sf))) return r;
-        const float *wt = (const float *)iw->second->data, *bs = conv_bias ? (const float *)ib->second->data : nullptr;
-        std::vector<float> g((size_t)256 * 576, 0.f), bb(256);
-        for (int sy = 0; sy < 2; ++sy)
-            for (int sx = 0; sx < 2; ++sx)
-                for (int o = 0; o < 64; ++o) {
-                    const float s = bnf ? sc[o] : 1.f;
-                    const int n = (sy * 2 + sx) * 64 + o;
-                    bb[n] = (bs ? bs[o] : 0.f) * s + (bnf ? sf[o] : 0.f);
-                    for (int ty = 0; ty < 3; ++ty)
-                        for (int tx = 0; tx < 3; ++tx)
-                            for (int dy = 0; dy < 4; ++dy)
-                                for (int dx = 0; dx < 4; ++dx) {
-                                    const int ky = 4 * (ty - 1) + dy - 2 * sy + 3, kx = 4 * (tx - 1) + dx - 2 * sx + 3;
-                                    if (ky < 0 || ky > 6 || kx < 0 || kx > 6) continue;
-                                    for (int c = 0; c < 3; ++c)
-                                        g[(size_t)n * 576 + (ty * 3 + tx) * 64 + (dy * 4 + dx) * 4 + c] = wt[((size_t)o * 3 + c) * 49 + ky * 7 + kx] * s;
-                                }
-                }
-        if ((r = pack(g.data(), 256, 576, 576, E.stem, bb.data(), 9, 1))) return r;
-        E.stem.Kreal = 147;
-    }
-    for (int li = 0; li < 3; ++li)
-        for (int bi = 0; bi < 2; ++bi) {
-            const std::string p = en + ".layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-            for (int c = 0; c < 2; ++c) {
-                if (bnf && (r = fold_bn(p + ".norm" + std::to_string(c + 1), dims[li], sc, sf))) return r;
-                if ((r = pack_conv(p + ".conv" + std::to_string(c + 1), conv_bias, bnf ? sc.data() : nullptr, bnf ? sf.data() : nullptr,
-                                   E.l[li][bi][c], 1)))
-                    return r;
-            }
-            if (bi == 0 && li > 0) {
-                if (bnf && (r = fold_bn(p + ".norm3", dims[li], sc, sf))) return r;
-                if ((r = pack_conv(p + ".downsample.0", true, bnf ? sc.data() : nullptr, bnf ? sf.data() : nullptr, E.ds[li], 1))) return r;
-            }
-        }
-    return 0;
+    return flow_chunk_pairs(wanted, dirs, flow_geometry(H, W, scale, 8).P, upd8_ ? 576 : 384);
 }
 
 int RaftEngine::load(const pb_tensor *w, int n) {
@@ -238,15 +152,11 @@ int RaftEngine::load(const pb_tensor *w, int n) {
 }
 
 int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
-    if (F <= pF_ && H == pH_ && W == pW_ && scale == pS_ && dirs <= pD_ && alt_corr_ == pA_) return 0;
+    if (plan_.covers(F, H, W, scale, dirs, alt_corr_)) return 0;
     PB_HIP(hipStreamSynchronize(stream));
-    // from here on the plan's members are being rewritten: a failure below (a frame too small, an allocation) must not leave the OLD plan's key
-    // behind, or the next call with the old size would skip this function and run on the half-written geometry (round 6: found by
-    // tests/test_gpu_raft.py::test_pipeline_error_exit_leaves_no_copy_in_flight - wrong flows after a refused 40 x 40 call)
-    pF_ = 0; pH_ = 0; pW_ = 0; pD_ = 0;
+    plan_.clear();
     geometry(H, W, scale, 8);
     PB_CHECK(h8_ >= 16 && w8_ >= 16, PB_ERR_ARG, "flow_raft: %dx%d is too small (the 4-level pyramid needs >= 128 px)", sh_, sw_);
-    P8_ = (P_ + 7) / 8 * 8;       // row stride of the level-0 volume (the GEMM epilogue writes 8-column groups)
     {
         CorrGeo g;
         corr_pyramid_geometry(h8_, w8_, g);
@@ -254,9 +164,7 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
     }
     const int64_t ND = (int64_t)(F - 1) * dirs;
     const size_t slack = 1 << 20;
-    for (int pass = 0; pass < 2; ++pass) {
-        planning_ = pass == 0;
-        arena_off_ = 0;
+    int r = plan_arena("flow", [&]() -> int {
         carve_encoder(F);
         fmap_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2 + slack);
         ctx_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2);
@@ -284,141 +192,10 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
         m0_ = (f16 *)carve((size_t)rows * 256 * 2);
         up_ = (float *)carve((size_t)ND * sh_ * sw_ * 2 * 4);
         maxd_ = (unsigned *)carve((size_t)ND * 4);
-        if (pass == 0) {
-            const int rc = commit_arena("flow");
-            if (rc) return rc;
-        }
-    }
-    int rt = upload_resize_tables(H, W, scale);
-    if (rt) return rt;
-    pF_ = F; pH_ = H; pW_ = W; pS_ = scale; pD_ = dirs; pA_ = alt_corr_;
-    return 0;
-}
-
-// scaled size, InputPadder('sintel', padding_factor = factor) amounts (bands/common/flow.py:43-55) and the 1/8 grid
-void RaftEngine::geometry(int H, int W, float scale, int factor) {
-    out_size(H, W, scale, &sh_, &sw_);
-    const int ph = (((sh_ / factor) + 1) * factor - sh_) % factor, pw = (((sw_ / factor) + 1) * factor - sw_) % factor;
-    padl_ = pw / 2; padt_ = ph / 2;
-    Hp_ = sh_ + ph; Wp_ = sw_ + pw;
-    h8_ = Hp_ / 8; w8_ = Wp_ / 8; P_ = h8_ * w8_;
-}
-
-// arena buffers of frame prep and run_encoder (call between the planning / carving passes of a prepare)
-void RaftEngine::carve_encoder(int F) {
-    const int h2 = Hp_ / 2, w2 = Wp_ / 2, h4 = Hp_ / 4, w4 = Wp_ / 4;
-    xi_ = (int *)carve((size_t)sw_ * 16); xc_ = (int *)carve((size_t)sw_ * 16);
-    yi_ = (int *)carve((size_t)sh_ * 16); yc_ = (int *)carve((size_t)sh_ * 16);
-    // split-fp16 mode: the encoders' maps (image included) are [hi | lo] per pixel (es = 2)
-    const size_t es = split_w_ ? 2 : 1;
-    img_ = (f16 *)carve((size_t)F * Hp_ * Wp_ * 8 * es);
-    for (auto &b : r1_) b = (f16 *)carve((size_t)round_up((int64_t)F * h2 * w2, 256) * 64 * 2 * es);
-    for (auto &b : r2_) b = (f16 *)carve((size_t)round_up((int64_t)F * h4 * w4, 256) * 128 * 2 * es);
-    for (auto &b : r3_) b = (f16 *)carve((size_t)round_up((int64_t)F * (enc_s3_ == 1 ? h4 * w4 : P_), 256) * 128 * 2 * es);
-    for (auto &b : st_) b = (float *)carve((size_t)F * 256 * 2 * 4);
-    stp_ = (float *)carve((size_t)in_stats_chunks(h2 * w2) * F * 256 * 2 * 4);     // per-chunk partial sums of the largest map
-}
-
-int RaftEngine::upload_resize_tables(int H, int W, float scale) {
-    if (scale != 1.f) {
-        std::vector<int> xi, xc, yi, yc;
-        cubic_taps_u8(W, sw_, scale, xi, xc);
-        cubic_taps_u8(H, sh_, scale, yi, yc);
-        PB_HIP(hipMemcpyAsync(xi_, xi.data(), xi.size() * 4, hipMemcpyHostToDevice, stream));
-        PB_HIP(hipMemcpyAsync(xc_, xc.data(), xc.size() * 4, hipMemcpyHostToDevice, stream));
-        PB_HIP(hipMemcpyAsync(yi_, yi.data(), yi.size() * 4, hipMemcpyHostToDevice, stream));
-        PB_HIP(hipMemcpyAsync(yc_, yc.data(), yc.size() * 4, hipMemcpyHostToDevice, stream));
-    }
-    PB_HIP(hipStreamSynchronize(stream));
-    return 0;
-}
-
-// BasicEncoder.forward (extractor.py:171-192) without its last 1x1 convolution, on the F prepared frames in img_: stem, three stages of two
-// residual blocks.  inorm: InstanceNorm with run-time statistics (fnet; GMFlow's backbone) - otherwise the folded BatchNorm path (cnet).
-// *x_out = the last block's output map [F, h8, w8, 128] (split-fp16 layout in PB_PREC_SPLIT); with enc_s3_ = 1 [F, Hp / 4, Wp / 4, 128].
-int RaftEngine::run_encoder(const Enc &E, bool inorm, int F, const f16 **x_out) {
-    int r = 0;
-    const int h2 = Hp_ / 2, w2 = Wp_ / 2;
-    const int es = split_w_ ? 2 : 1;                         // encoder maps are [hi | lo] in split-fp16 mode
-    auto lo = [&](int c) { return split_w_ ? c : 0; };
-    const int l8 = split_w_ && mx_ ? kLo8Pa : -1;            // the residual parts of the encoder maps are e4m3 ([hi | hi8 | lo8])
-    auto norm_relu = [&](const f16 *t, float *st, f16 *y, int HW, int C, const f16 *b, const float *sb) -> int {
-        tic(F_ELT, 0, 0);
-        int rr = launch_in_apply(stream, t, st, b, sb, y, F, HW, C, es * C, lo(C), l8);
-        toc();
-        return rr;
-    };
-    // On the e4m3-residual maps (flow_raft) the instance-norm statistics are taken from the hi parts alone (PB_IN_STATS_LO=1: from hi + lo8
-    // as before): the fp16 rounding residuals are symmetric around zero, so over a channel's pixels they move the mean by ~2^-12 / sqrt(n) of a
-    // value, and a 64-channel pixel's hi part is one of its two 128-byte lines (the lo8 bytes sit in the other one): half the pass's traffic,
-    // -1.2 ms per step, RAFT parity unchanged (worst 720p pair 6.0e-4 either way).  flow_gmflow (fp16 residual planes) keeps hi + lo: its
-    // 216x300 vector moves from 2.2e-4 to 3.8e-4 without them.
-    const bool stats_lo = launch_env().in_stats_lo || !mx_;
-    auto stats = [&](const f16 *t, float *st, int HW, int C) -> int {
-        tic(F_ELT, 0, 0);
-        int rr = launch_in_stats(stream, t, F, HW, C, es * C, stp_, st, stats_lo ? lo(C) : 0, l8);
-        toc();
-        return rr;
-    };
-    // stem (BasicEncoder.forward, extractor.py:171-192)
-    {
-        GemmArgs a;
-        a.A = img_; a.N = 256;
-        a.cH = Hp_ / 4; a.cW = Wp_ / 4; a.cC = 64; a.cLd = es * 64; a.cKW = 3; a.cStride = 1; a.cPad = 1; a.cPadX = 1;
-        set_weights(a, E.stem, true);
-        a.cOH = a.cH; a.cOW = a.cW; a.M = F * a.cH * a.cW;
-        a.out = r1_[5]; a.ldo = es * 64; a.lo_off = lo(64); a.act = inorm ? ACT_NONE : ACT_RELU;
-        if (l8 >= 0) { a.lo8 = 1; a.lo8_pa = l8; }
-        a.ps_h = a.cH; a.ps_w = a.cW; a.ps_s = 2; a.ps_co = 64;
-        tic(F_CONV, 2.0 * F * h2 * w2 * 64.0 * 147, 0, E.stem.mx3 ? 2.0 : 1.0 + E.stem.sa + E.stem.sw);
-        r = launch_gemm(stream, A_CONV, EPI_PIXSHUF, TILE_AUTO, a);
-        if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-        toc();
-        if (r) return r;
-    }
-    const f16 *x = r1_[5];
-    if (inorm) {
-        if ((r = stats(r1_[5], st_[0], h2 * w2, 64))) return r;
-        if ((r = norm_relu(r1_[5], st_[0], r1_[6], h2 * w2, 64, nullptr, nullptr))) return r;
-        x = r1_[6];
-    }
-    int H_ = h2, W_ = w2, C_ = 64;
-    for (int li = 0; li < 3; ++li) {
-        const int stride = li == 0 ? 1 : (li == 2 ? enc_s3_ : 2);
-        const int Cn = li == 0 ? 64 : 128;               // 96 is carried as 128 (zero padded channels)
-        f16 **R = li == 0 ? r1_ : (li == 1 ? r2_ : r3_);
-        for (int bi = 0; bi < 2; ++bi) {                  // ResidualBlock.forward (extractor.py:46-56)
-            const int s = bi == 0 ? stride : 1;
-            const bool ds = bi == 0 && li > 0;            // the block changes stride or channel count: 1 x 1 convolution + norm on the skip path
-            const int OH = (H_ - 1) / s + 1, OW = (W_ - 1) / s + 1;
-            const int Cin = bi == 0 ? C_ : Cn;
-            f16 *t1 = R[0], *t2 = R[1], *t3 = R[2], *outb = R[3 + bi];
-            if (inorm) {
-                if ((r = conv(x, Cin, es * Cin, F, H_, W_, 3, 3, s, E.l[li][bi][0], t1, es * Cn, ACT_NONE, 0, nullptr, nullptr, lo(Cn)))) return r;
-                if ((r = stats(t1, st_[0], OH * OW, Cn))) return r;
-                if ((r = norm_relu(t1, st_[0], t1, OH * OW, Cn, nullptr, nullptr))) return r;
-                if ((r = conv(t1, Cn, es * Cn, F, OH, OW, 3, 3, 1, E.l[li][bi][1], t2, es * Cn, ACT_NONE, 0, nullptr, nullptr, lo(Cn)))) return r;
-                if ((r = stats(t2, st_[1], OH * OW, Cn))) return r;
-                if (ds) {
-                    if ((r = conv(x, Cin, es * Cin, F, H_, W_, 1, 1, s, E.ds[li], t3, es * Cn, ACT_NONE, 0, nullptr, nullptr, lo(Cn)))) return r;
-                    if ((r = stats(t3, st_[2], OH * OW, Cn))) return r;
-                    if ((r = norm_relu(t2, st_[1], outb, OH * OW, Cn, t3, st_[2]))) return r;
-                } else {
-                    if ((r = norm_relu(t2, st_[1], outb, OH * OW, Cn, x, nullptr))) return r;
-                }
-            } else {
-                if ((r = conv(x, Cin, es * Cin, F, H_, W_, 3, 3, s, E.l[li][bi][0], t1, es * Cn, ACT_RELU, 0, nullptr, nullptr, lo(Cn)))) return r;
-                const f16 *xs = x;
-                if (ds) {
-                    if ((r = conv(x, Cin, es * Cin, F, H_, W_, 1, 1, s, E.ds[li], t3, es * Cn, ACT_NONE, 0, nullptr, nullptr, lo(Cn)))) return r;
-                    xs = t3;
-                }
-                if ((r = conv(t1, Cn, es * Cn, F, OH, OW, 3, 3, 1, E.l[li][bi][1], outb, es * Cn, ACT_RELU, 1, xs, nullptr, lo(Cn)))) return r;
-            }
-            x = outb; H_ = OH; W_ = OW; C_ = Cn;
-        }
-    }
-    *x_out = x;
+        return 0;
+    });
+    if (r || (r = upload_resize_tables(H, W, scale))) return r;
+    plan_.set(F, H, W, scale, dirs, alt_corr_);
     return 0;
 }
 
@@ -436,15 +213,11 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
     const int64_t rows = (int64_t)ND * P_;
 
     // ---- frame prep + stem im2col (shared by fnet and cnet) ----
-    tic(F_PP, 0, (double)F * H * W * 3);
     const int Lhx = upd8_ ? 576 : 384, L256 = upd8_ ? 384 : 256, L128 = upd8_ ? 192 : 128;    // pixel strides of the update block's maps
     const float s8 = (float)(1 << kMx2Pa);
     const int es = split_w_ ? 2 : 1;                         // encoder maps are [hi | lo] in split-fp16 mode
-    auto lo = [&](int c) { return split_w_ ? c : 0; };
-    const int l8 = split_w_ && mx_ ? kLo8Pa : -1;            // the residual parts of the encoder maps are e4m3 ([hi | hi8 | lo8])
-    r = launch_raft_prep(stream, frames, F, H, W, sh_, sw_, Hp_, Wp_, padl_, padt_, scale != 1.f, xi_, xc_, yi_, yc_, img_, nullptr, 1, lo(64), l8);
-    toc();
-    if (r) return r;
+    // (the residual parts of the encoder maps are e4m3 where the mode has them: [hi | hi8 | lo8])
+    if ((r = prep_frames(frames, F, H, W, scale, split_w_ && mx_ ? kLo8Pa : -1))) return r;
 
     // ---- the two encoders ----
     for (int e = 0; e < 2; ++e) {
@@ -462,10 +235,11 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
     // corr.py:22-27 pools the volume over the target dims; pooling is linear, so level l is the correlation of fmap1 with the
     // l-times avg-pooled target features: three small pooling passes over [F, P, 256] instead of three over the 4 P^2-byte volume
     for (int l = 0; l < 4; ++l) {
-        tic(F_ELT, 0, 0);
-        if (l > 0) r = launch_avgpool2_nhwc(stream, l == 1 ? fmap_ : fpool_[l - 1], fpool_[l], F, lh_[l - 1], lw_[l - 1], 256);
-        if (!r && !alt_corr_) r = launch_corr_tile(stream, l == 0 ? fmap_ : fpool_[l], ftile_[l], F, lh_[l], lw_[l], lwp_[l], pld_[l]);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] {
+            int rc = l > 0 ? launch_avgpool2_nhwc(stream, l == 1 ? fmap_ : fpool_[l - 1], fpool_[l], F, lh_[l - 1], lw_[l - 1], 256) : 0;
+            if (!rc && !alt_corr_) rc = launch_corr_tile(stream, l == 0 ? fmap_ : fpool_[l], ftile_[l], F, lh_[l], lw_[l], lwp_[l], pld_[l]);
+            return rc;
+        });
         if (r) return r;
     }
     for (int i = 0; i < F - 1; ++i)
@@ -478,21 +252,17 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
                 a.K = 256; a.N = pld_[l];
                 a.out = pyr_[l] + (int64_t)n * P_ * pld_[l]; a.ldo = pld_[l]; a.zero = zero_;
                 // K = 256 against P x pld fp16 outputs: this launch is bound by writing the volume, not by the matrix pipe (bytes: A + W + out)
-                tic(F_GEMM, 2.0 * P_ * (double)lh_[l] * lw_[l] * 256, 2.0 * ((double)P_ * 256 + (double)pld_[l] * 256 + (double)P_ * pld_[l]));
-                if (!launch_env().volume) {        // PB_VOLUME=0, A/B: the generic GEMM kernels
-                    r = launch_gemm(stream, A_DENSE, EPI_STD, TILE_AUTO, a);
-                    if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-                } else {        // volume.hip: A-stationary, persistent along the targets; same accumulation order, same bits
-                    r = launch_corr_volume(stream, a.A, a.M, a.W, a.N, a.N, a.out, a.ldo);
-                    if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = "corr_volume_kernel";
-                }
-                toc();
+                const double flops = 2.0 * P_ * (double)lh_[l] * lw_[l] * 256, bytes = 2.0 * ((double)P_ * 256 + (double)pld_[l] * 256 + (double)P_ * pld_[l]);
+                if (!launch_env().volume)          // PB_VOLUME=0, A/B: the generic GEMM kernels
+                    r = timed_gemm(F_GEMM, flops, bytes, [&] { return launch_gemm(stream, A_DENSE, EPI_STD, TILE_AUTO, a); });
+                else            // volume.hip: A-stationary, persistent along the targets; same accumulation order, same bits
+                    r = timed(F_GEMM, flops, bytes, [&] { return launch_corr_volume(stream, a.A, a.M, a.W, a.N, a.N, a.out, a.ldo); }, "corr_volume_kernel");
                 if (r) return r;
             }
-            tic(F_ELT, 0, 0);
-            r = launch_init_state(stream, ctx_ + (int64_t)(i + d) * P_ * 256, h32_ + (int64_t)n * P_ * 128,
-                                  hx_ + (int64_t)n * P_ * Lhx, hx2_ + (int64_t)n * P_ * Lhx, flow_ + (int64_t)n * P_ * 2, P_, Lhx, upd8_ ? 768 : 0, s8, hoist_ ? 256 : 128);
-            toc();
+            r = timed(F_ELT, 0, 0, [&] {
+                return launch_init_state(stream, ctx_ + (int64_t)(i + d) * P_ * 256, h32_ + (int64_t)n * P_ * 128, hx_ + (int64_t)n * P_ * Lhx,
+                                         hx2_ + (int64_t)n * P_ * Lhx, flow_ + (int64_t)n * P_ * 2, P_, Lhx, upd8_ ? 768 : 0, s8, hoist_ ? 256 : 128);
+            });
             if (r) return r;
         }
 
@@ -518,14 +288,12 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
     for (int it = 0; it < iters; ++it) {
         if (alt_corr_) {       // --alternate_corr (corr.py:63-91): the window entries are computed from fmap_ and the pooled maps, 100 per row and level
             const f16 *const tg[4] = {fmap_, fpool_[1], fpool_[2], fpool_[3]};
-            tic(F_GEMM, 2.0 * rows * 4.0 * 100.0 * 256.0, 0);
-            r = launch_corr_lookup_otf(stream, fmap_, tg, lh_, lw_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8, dirs);
-            if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = "corr_lookup_otf_kernel";
+            r = timed(F_GEMM, 2.0 * rows * 4.0 * 100.0 * 256.0, 0, [&] {
+                return launch_corr_lookup_otf(stream, fmap_, tg, lh_, lw_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8, dirs);
+            }, "corr_lookup_otf_kernel");
         } else {
-            tic(F_ELT, 0, 0);
-            r = launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, lhp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8);
+            r = timed(F_ELT, 0, 0, [&] { return launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, lhp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8); });
         }
-        toc();
         if (r) return r;
         if (debug && it == 0 && (r = snapshot("corr0", corr_, (size_t)ND * P_ * Lhx * 2, Stage::f16_nhwc(nullptr, ND, 324, h8_, w8_, Lhx)))) return r;
         // BasicMotionEncoder.  With upd8_ every map is [a16 (C) | a8 (C bytes)] per pixel (pixel stride 1.5 C halfs): the conv epilogues
@@ -533,15 +301,12 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         if ((r = conv(corr_, 384, Lhx, ND, h8_, w8_, 1, 1, 1, convc1_, c1_, L256, ACT_RELU, 0, nullptr, nullptr, 0, 0, upd8_ ? 512 : 0))) return r;
         if ((r = conv(c1_, 256, L256, ND, h8_, w8_, 3, 3, 1, convc2_, corflo_, L256, ACT_RELU, 0, nullptr, nullptr, 0, 0, upd8_ ? 512 : 0))) return r;
         if (f1_direct_) {
-            tic(F_CONV, 2.0 * rows * 128.0 * 98.0, 8.0 * rows + 256.0 * rows, (double)f1_passes_);
-            r = launch_convf1(stream, flow_, f1w_, convf1_.bias, f1_, rows, P_, h8_, w8_, L128, upd8_ ? 256 : 0, (float)(1 << kMx2Pa), f1_passes_);
-            if (timer.enabled && !r) timer.recs[open_.back()].name = "convf1_kernel";
-            toc();
+            r = timed(F_CONV, 2.0 * rows * 128.0 * 98.0, 8.0 * rows + 256.0 * rows, [&] {
+                return launch_convf1(stream, flow_, f1w_, convf1_.bias, f1_, rows, P_, h8_, w8_, L128, upd8_ ? 256 : 0, (float)(1 << kMx2Pa), f1_passes_);
+            }, "convf1_kernel", (double)f1_passes_);
             if (r) return r;
         } else {
-            tic(F_ELT, 0, 0);
-            r = launch_im2col7_flow(stream, flow_, ND, h8_, w8_, fa_, 128, L128, upd8_);
-            toc();
+            r = timed(F_ELT, 0, 0, [&] { return launch_im2col7_flow(stream, flow_, ND, h8_, w8_, fa_, 128, L128, upd8_); });
             if (r) return r;
             if ((r = dense(fa_, L128, rows, convf1_, f1_, L128, ACT_RELU, nullptr, upd8_ ? 256 : 0, 0))) return r;     // flow is in pixels: its fp8 copy is unscaled
         }
@@ -550,9 +315,7 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         // written to both by the producing conv (its ReLU'd second output), r * h and the state update by the GRU epilogues
         ConvFuse dup; dup.out2 = hx2_ + mot;
         if ((r = conv(corflo_, 256, L256, ND, h8_, w8_, 3, 3, 1, convm_, hx_ + mot, Lhx, ACT_RELU, 0, nullptr, &dup, 0, 0, upd8_ ? 768 - mot : 0))) return r;
-        tic(F_ELT, 0, 0);
-        r = launch_put_flow(stream, flow_, hx_, hx2_, rows, Lhx, upd8_ ? 768 : 0, s8, mot + 126);
-        toc();
+        r = timed(F_ELT, 0, 0, [&] { return launch_put_flow(stream, flow_, hx_, hx2_, rows, Lhx, upd8_ ? 768 : 0, s8, mot + 126); });
         if (r) return r;
         // SepConvGRU: (1 x 5) then (5 x 1)
         for (int half = 0; half < 2; ++half) {
@@ -568,10 +331,8 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         }
         // FlowHead -> delta_flow (fp32), coords1 += delta (the h slice's fp8 copy sits 384 halfs after it)
         if ((r = conv(hx_, 128, Lhx, ND, h8_, w8_, 3, 3, 1, fh1_, fh_, 256, ACT_RELU, 0, nullptr, nullptr, 0, upd8_ ? 384 : 0))) return r;
-        tic(F_CONV, 2.0 * rows * 2.0 * fh2_.Kreal, 0);
-        r = launch_flow_head2(stream, fh_, fh2_.w, fh2_.bias, flow_, ND, h8_, w8_, fh2_.sw);
-        if (timer.enabled && !r) timer.recs[open_.back()].name = fh2_.sw ? "flow_head2_kernel<true>" : "flow_head2_kernel<false>";
-        toc();
+        r = timed(F_CONV, 2.0 * rows * 2.0 * fh2_.Kreal, 0, [&] { return launch_flow_head2(stream, fh_, fh2_.w, fh2_.bias, flow_, ND, h8_, w8_, fh2_.sw); },
+                  fh2_.sw ? "flow_head2_kernel<true>" : "flow_head2_kernel<false>");
         if (r) return r;
         if (debug && it == 0 && (r = snapshot("flow_it0", flow_, (size_t)ND * P_ * 2 * 4, Stage::f32_rows(nullptr, ND, P_, 2)))) return r;
     }
@@ -584,23 +345,8 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         a.A = m0_; a.lda = 256; a.N = 576; a.M = (int)rows;
         set_weights(a, mk2_, false);
         a.out32 = mask_; a.ldo = 576; a.scale = 0.25f;
-        tic(F_GEMM, 2.0 * rows * 576.0 * 256, 0, 1.0 + mk2_.sw);
-        r = launch_gemm(stream, A_DENSE, EPI_F32, TILE_AUTO, a);
-        if (timer.enabled && !r && !open_.empty()) timer.recs[open_.back()].name = pb_gemm_last_kernel();
-        toc();
+        r = timed_gemm(F_GEMM, 2.0 * rows * 576.0 * 256, 0, [&] { return launch_gemm(stream, A_DENSE, EPI_F32, TILE_AUTO, a); }, 1.0 + mk2_.sw);
         if (r) return r;
     }
-    float *up = flow_out ? flow_out : up_;
-    tic(F_PP, 0, (double)ND * sh_ * sw_ * 8);
-    r = launch_upsample(stream, flow_, mask_, ND, h8_, w8_, padl_, padt_, sh_, sw_, up, maxd_);
-    toc();
-    if (r) return r;
-    tic(F_PP, 0, (double)ND * sh_ * sw_ * 11);
-    r = launch_flow_encode(stream, up, ND, sh_, sw_, maxd_, rgb_out, maxdisp);
-    toc();
-    if (r || !mask_out) return r;
-    tic(F_PP, 0, (double)ND * sh_ * sw_ * 17);
-    r = launch_fwdbwd_mask(stream, up, F - 1, sh_, sw_, alpha1, alpha2, mask_out);
-    toc();
-    return r;
+    return flow_tail(flow_, ND, F - 1, h8_, w8_, 8, flow_out, rgb_out, maxdisp, mask_out, alpha1, alpha2);
 }

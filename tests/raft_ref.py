@@ -487,7 +487,7 @@ def upsample_margin_case(flow, mask, w8: int):
 
 
 def pad_geometry(h: int, w: int):
-    """InputPadder('sintel') as RaftEngine::geometry: (pad_l, pad_t, h8, w8)"""
+    """InputPadder('sintel') as flow_geometry (flow_chunk.h) with factor 8: (pad_l, pad_t, h8, w8)"""
     ph, pw = (((h // 8) + 1) * 8 - h) % 8, (((w // 8) + 1) * 8 - w) % 8
     return pw // 2, ph // 2, (h + ph) // 8, (w + pw) // 8
 

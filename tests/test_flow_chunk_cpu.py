@@ -1,6 +1,6 @@
-"""CPU: how many pairs a host-pointer flow call hands to one RaftEngine::infer (prisma_amd/csrc/flow_chunk.h - the text abi.hip compiles) built
-with g++ and held against a brute-force loop over cp; and the flow_raft band's --alternate_corr plumbing with a recording stand-in for the
-engine."""
+"""CPU: the host-compilable pieces of the flow engines (prisma_amd/csrc/flow_chunk.h - the text the engines and abi.hip compile) built with g++:
+how many pairs a host-pointer flow call hands to one FlowEngine::infer, held against a brute-force loop over cp, and the padded geometry of a
+call, held against a brute-force padder; and the flow_raft band's --alternate_corr plumbing with a recording stand-in for the engine."""
 import os
 import subprocess
 import sys
@@ -12,8 +12,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = r"""
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include "flow_chunk.h"
 int main(int argc, char **argv) {
+    if (argc > 1 && !strcmp(argv[1], "geo")) {          // geo H W scale factor ...: one line of sh sw Hp Wp padl padt h8 w8 P per case
+        for (int i = 2; i + 3 < argc; i += 4) {
+            const FlowGeometry g = flow_geometry(atoi(argv[i]), atoi(argv[i + 1]), (float)atof(argv[i + 2]), atoi(argv[i + 3]));
+            printf("%d %d %d %d %d %d %d %d %d\n", g.sh, g.sw, g.Hp, g.Wp, g.padl, g.padt, g.h8, g.w8, g.P);
+        }
+        return 0;
+    }
     for (int i = 1; i + 3 < argc; i += 4)
         printf("%d\n", flow_chunk_pairs(atoi(argv[i]), atoi(argv[i + 1]), atoll(argv[i + 2]), atoll(argv[i + 3])));
     return 0;
@@ -39,9 +47,47 @@ def brute(wanted, dirs, P, Lhx):
     return best
 
 
-def grid(h, w, scale):
-    sh, sw = round(h * scale), round(w * scale)
-    return -(-sh // 8) * -(-sw // 8)
+GEO = ("sh", "sw", "Hp", "Wp", "padl", "padt", "h8", "w8", "P")
+
+
+def geometry(exe, cases):
+    """flow_geometry of every (H, W, scale, factor), as dicts over GEO"""
+    out = subprocess.run([exe, "geo"] + [repr(v) for c in cases for v in c], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert len(out) == len(cases)
+    return [dict(zip(GEO, map(int, line.split()))) for line in out]
+
+
+def grid(exe, h, w, scale):
+    """tokens of RAFT's 1/8 grid (padding factor 8) as the compiled flow_geometry gives them"""
+    return geometry(exe, [(h, w, scale, 8)])[0]["P"]
+
+
+def pad_brute(size, factor):
+    """InputPadder: the smallest multiple of factor that is at least size; the smaller half of the padding goes left / top"""
+    m = size
+    while m % factor:
+        m += 1
+    return m, (m - size) // 2
+
+
+# (H, W, scale, factor) and the scaled size it gives: the two ragged sizes of the GPU tests at RAFT's factor, the bench's 810 x 1440 at every
+# factor, and a size that is a multiple of 32 already (plain and through a scale)
+GEO_CASES = [((125, 157, 1.0, 8), (125, 157)), ((131, 181, 1.0, 8), (131, 181)), ((1080, 1920, 0.75, 8), (810, 1440)),
+             ((1080, 1920, 0.75, 16), (810, 1440)), ((1080, 1920, 0.75, 32), (810, 1440)), ((96, 128, 1.0, 8), (96, 128)),
+             ((96, 128, 1.0, 16), (96, 128)), ((96, 128, 1.0, 32), (96, 128)), ((192, 256, 0.5, 32), (96, 128))]
+
+
+def test_flow_geometry_against_brute_force_padder(exe):
+    got = geometry(exe, [c for c, _ in GEO_CASES])
+    for (case, (sh, sw)), g in zip(GEO_CASES, got):
+        factor = case[3]
+        Hp, padt = pad_brute(sh, factor)
+        Wp, padl = pad_brute(sw, factor)
+        want = dict(sh=sh, sw=sw, Hp=Hp, Wp=Wp, padl=padl, padt=padt, h8=Hp // 8, w8=Wp // 8, P=(Hp // 8) * (Wp // 8))
+        assert g == want, (case, g, want)
+    # the ragged grids the GPU tests run on, and no padding where the size is a multiple of the factor already
+    assert (got[0]["h8"], got[0]["w8"]) == (16, 20) and (got[1]["h8"], got[1]["w8"]) == (17, 23)
+    assert all(g["Hp"] == 96 and g["Wp"] == 128 and g["padl"] == 0 and g["padt"] == 0 for g in got[5:])
 
 
 def test_chunk_pairs_against_brute_force(exe):
@@ -60,11 +106,11 @@ def test_chunk_pairs_against_brute_force(exe):
 def test_chunk_pairs_named_cases(exe):
     run = lambda *a: int(subprocess.run([exe] + [str(v) for v in a], check=True, capture_output=True, text=True).stdout)
     # a chunk that fits is left alone: the band's 16 pairs (and the pipeline's 32) at 1080p x 0.75, both directions
-    P = grid(1080, 1920, 0.75)
+    P = grid(exe, 1080, 1920, 0.75)
     assert P == 102 * 180
     assert run(16, 2, P, 576) == 16 and run(32, 2, P, 576) == 32 and run(31, 1, P, 576) == 31
     # 2160p x 1.0, both directions: 2 x 129600 x 576 halfs per pair -> 14 pairs at most (15 would be 2.24e9 >= 2^31)
-    P4 = grid(2160, 3840, 1.0)
+    P4 = grid(exe, 2160, 3840, 1.0)
     assert P4 == 270 * 480
     assert run(16, 2, P4, 576) == 14 and run(32, 2, P4, 576) == 14 and run(32, 1, P4, 576) == 28 and run(8, 2, P4, 576) == 8
     assert 14 * 2 * P4 * 576 < 2 ** 31 <= 15 * 2 * P4 * 576

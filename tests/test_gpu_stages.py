@@ -110,7 +110,7 @@ def test_debug_only_stages_disappear_without_the_debug_bit(depth_w, raft_w):
     assert net.stage("flow_lo").shape[0] == 2
     net.close()
 
-    # flow_gmflow shares RaftEngine's registry and registers its own names only
+    # flow_gmflow shares EngineBase's registry and registers its own names only
     net = engine.FlowGMFlow(synth.gmflow_weights(seed=2468), device=0, precision=1)
     net.set_profiling(timing=False, debug_stages=True)
     fr = synth.frame_pair_sequence(2, 120, 168, seed=33)
