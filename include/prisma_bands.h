@@ -440,7 +440,8 @@ int pb_set_profiling(pb_ctx *ctx, int enabled);
  * removed); "tile_n96" (process-wide) = 0: convolutions with 64 < N <= 96 stay on the 128x128 tile, 1: auto gives them
  * the 128x96 tile (same bytes), 2 (default): ... and the packed-channel K axis where the weights carry one (RAFT encoder
  * stage 2: another summation order); "host_chunk", "op_splitk": see INTEGRATION.md; "frames_i420", "rgb_out_i420" (0 | 1): see pb_i420_bytes;
- * "rgb_out_full" (0 | 1): see pb_rgb_resize. */
+ * "rgb_out_full" (0 | 1): see pb_rgb_resize; "corr_layout" (0 | 1, flow_raft): 1 (default) = the correlation volume
+ * source-blocked, read by corr_lookup_blocked_kernel, 0 = row-major and corr_lookup_kernel - same bytes out (prisma_amd/csrc/corr_layout.h). */
 int pb_set_option(pb_ctx *ctx, const char *key, int value);
 int pb_get_kernel_stats(pb_ctx *ctx, pb_kernel_stat *out, int cap);
 
@@ -455,6 +456,11 @@ int pb_op_gemm_bench(pb_ctx *ctx, int M, int N, int K, int tile, int epi, int it
  * features): out[m, n] = fp16(sum_k fp16(A[m, k]) fp16(W[n, k])), A [M, 256], W [N, 256] fp32 on the host, N % 8 == 0, ldo >= N.
  * `out` holds (M + guard_rows) x ldo floats; everything the kernel must not touch - columns N..ldo-1 and the guard rows - is preset to NaN. */
 int pb_op_corr_volume(pb_ctx *ctx, const float *A, int M, const float *W, int N, int ldo, int guard_rows, float *out);
+/* The same kernel storing flow_raft's source-blocked volume layout (prisma_amd/csrc/corr_layout.h; ldo % 64 == 0): `out` holds the raw halfs,
+ * round_up(M, 8) rows of ldo entries and guard_halfs behind them, preset to 0x7e7e.  pb_op_corr_layout_index (no GPU needed): out[p * pld + c] =
+ * the offset in halfs of entry c of source row p < P in layout 0 (row-major) / 1 (blocked) - corr_layout.h's function, the one the kernels use. */
+int pb_op_corr_volume_blocked(pb_ctx *ctx, const float *A, int M, const float *W, int N, int ldo, int guard_halfs, void *out);
+int pb_op_corr_layout_index(int layout, int P, int pld, int64_t *out);
 /* LayerNorm over the last dim, eps 1e-6 (vision_transformer.py:95). */
 /* times `iters` launches of the fused attention kernel on random Q, K, V (variant 0 = default); ms per launch */
 int pb_op_attention_bench(pb_ctx *ctx, int B, int heads, int N, int variant, int iters, double *ms_out);
@@ -536,7 +542,7 @@ int pb_op_conv_head(pb_ctx *ctx, const float *x, const float *w, const float *bi
  * grid - the function RaftEngine::prepare plans with.
  * lookup: avg-pool x3, tile x4, the all-pairs volume x4 per pair, then the 9 x 9 x 4 lookup.  fmap1 [n, h8 w8, 256], fmap2 [n, h8, w8, 256],
  *   flow [n h8 w8, 2]; out: (rows + guard) x (o8 ? 576 : 384) halfs (o8: the e4m3 copy at byte 768 of a row); levels (or NULL): the four volume
- *   levels de-tiled, [n h8 w8, h_l, w_l] floats one after the other.
+ *   levels de-tiled, [n h8 w8, h_l, w_l] floats one after the other.  The volume between the kernels is stored as the ctx's "corr_layout" option says.
  * convf1: flow [n, h8, w8, 2], w [128, 2, 7, 7], bias [128]; passes 1 / 2 (w_hi, + w_lo); out: (rows + guard) x (o8 ? 192 : 128) halfs (e4m3
  *   copy at byte 256); gemm_path: im2col + GEMM (PB_CONVF1_DIRECT=0) instead of the direct kernel.
  * flow_head2: x [n, H, W, 256], w [2, 256, 3, 3], bias [2]; flow [n H W + guard, 2] is read (rows < n H W) and written in place.

@@ -124,6 +124,8 @@ SYMBOLS = {
     "pb_op_gemm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "pb_op_gemm_bench": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "pb_op_corr_volume": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_op_corr_volume_blocked": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_op_corr_layout_index": (C.c_int, [C.c_int, C.c_int, C.c_int, _P]),
     "pb_op_attention_bench": (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]),
     "pb_op_layernorm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "pb_op_attention": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int]),

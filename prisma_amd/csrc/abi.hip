@@ -723,6 +723,12 @@ int pb_set_option(pb_ctx *c, const char *key, int value) {
         PB_CHECK(c->pending.empty(), PB_ERR_STATE, "option '%s': a submission of this ctx is still outstanding (pb_wait first)", key);
         (key[0] == 'f' ? c->frames_i420 : key[8] == 'i' ? c->rgb_out_i420 : c->rgb_out_full) = value;
     }
+    else if (!strcmp(key, "corr_layout")) {        // corr_layout.h: 1 = source-blocked volume (default), 0 = row-major; the next flow_raft call re-plans
+        PB_CHECK(value == 0 || value == 1, PB_ERR_ARG, "option '%s' is 0 or 1, not %d", key, value);
+        PB_CHECK(c->pending.empty(), PB_ERR_STATE, "option '%s': a submission of this ctx is still outstanding (pb_wait first)", key);
+        c->corr_layout = value;
+        if (RaftEngine *e = dynamic_cast<RaftEngine *>(c->flow)) e->set_corr_layout(value);
+    }
     else if (!strcmp(key, "tile_n96")) pb_gemm_set_n96(value);         // process-wide (gemm.h): A/B of the 128 x 96 tile inside one test process
     else PB_CHECK(false, PB_ERR_ARG, "unknown option '%s'", key);
     return 0;

@@ -133,6 +133,7 @@ struct pb_ctx {
     int gemm_tile = TILE_AUTO, conv_tile = TILE_AUTO;
     int op_splitk = 0;              // pb_set_option("op_splitk", 1): pb_op_gemm / pb_op_conv2d lend launch_gemm a split-K workspace (gemm.h splitk; op-level tests)
     int host_chunk = 0;             // pb_set_option("host_chunk"): frames (depth) / frame pairs (flow) per chunk of the host-pointer pipelines, 0 = default
+    int corr_layout = 1;            // pb_set_option("corr_layout"): flow_raft's volume layout (corr_layout.h) - the band's engine and pb_op_raft_lookup follow it
     ChunkPipe pipe;                 // depth / flow bands (a ctx has one band)
     MaskPipe mpipe;
     std::deque<hipEvent_t> pending;     // completion events of pb_*_submit_* calls not yet waited for (pb_wait pops the oldest)

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "abi_ctx.h"
+#include "corr_layout.h"
 #include "gmflow_engine.h"
 #include "mask_kernels.h"
 #include "zoe_kernels.h"
@@ -168,12 +169,14 @@ class RaftOpEngine : public SplitOpEngine {
         return 0;
     }
 
-    int lookup(const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows, void *out, float *levels) {
+    // layout (corr_layout.h): how the volume between the two kernels is stored - the ctx's "corr_layout" option, as RaftEngine follows it
+    int lookup(const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows, void *out, float *levels,
+               int layout) {
         PB_CHECK(h8 >= 16 && w8 >= 16, PB_ERR_ARG, "op_raft_lookup: a %d x %d grid is too small (the 4-level pyramid needs >= 16 x 16)", h8, w8);
         CorrGeo g;
         corr_pyramid_geometry(h8, w8, g);
         const int P = h8 * w8;
-        const int64_t rows = (int64_t)n * P;
+        const int64_t rows = (int64_t)n * P, Pv = corr_layout_rows(layout, P);      // Pv: volume rows a pair-direction is carved for
         const size_t slack = 1 << 20;                       // what RaftEngine::prepare leaves behind fmap_ and every pyramid buffer
         const int ldo = o8 ? 576 : 384;
         DevMem f1, f2, dflow, dout, fpool[4], ftile[4], pyr[4];
@@ -183,7 +186,7 @@ class RaftOpEngine : public SplitOpEngine {
         PB_TRY(preset(dout, (size_t)(rows + guard_rows) * ldo * 2));
         const f16 *lv[4];
         for (int l = 0; l < 4; ++l) {
-            PB_TRY(pyr[l].alloc((size_t)rows * g.ld[l] * 2 + slack));
+            PB_TRY(pyr[l].alloc((size_t)n * Pv * g.ld[l] * 2 + slack));
             if (l) PB_TRY(fpool[l].alloc((size_t)round_up((int64_t)n * g.h[l] * g.w[l], 256) * 256 * 2 + slack));
             PB_TRY(ftile[l].alloc((size_t)(n * (int64_t)g.ld[l] + 256) * 256 * 2 + slack));
             lv[l] = pyr[l].as<f16>();
@@ -195,20 +198,23 @@ class RaftOpEngine : public SplitOpEngine {
         for (int i = 0; i < n; ++i)
             for (int l = 0; l < 4; ++l)
                 PB_TRY(launch_corr_volume(stream, f1.as<f16>() + (int64_t)i * P * 256, P, ftile[l].as<f16>() + (int64_t)i * g.ld[l] * 256, g.ld[l], g.ld[l],
-                                          pyr[l].as<f16>() + (int64_t)i * P * g.ld[l], g.ld[l]));
+                                          pyr[l].as<f16>() + (int64_t)i * Pv * g.ld[l], g.ld[l], layout));
         PB_TRY(launch_corr_lookup(stream, lv, g.h, g.w, g.wp, g.hp, g.ld, dflow.as<float>(), P, w8, dout.as<f16>(), rows, ldo, o8 ? 768 : 0,
-                                  (float)(1 << kMx2Pa)));
+                                  (float)(1 << kMx2Pa), layout));
         PB_TRY(finish(out, dout, (size_t)(rows + guard_rows) * ldo * 2));
-        if (levels) {                                       // the four levels, de-tiled: [n P, h_l, w_l] one after the other
+        if (levels) {                                       // the four levels, de-blocked and de-tiled: [n P, h_l, w_l] one after the other
             float *dst = levels;
             for (int l = 0; l < 4; ++l) {
-                std::vector<f16> h((size_t)rows * g.ld[l]);
+                std::vector<f16> h((size_t)n * Pv * g.ld[l]);
                 PB_HIP(hipMemcpy(h.data(), pyr[l].p, h.size() * 2, hipMemcpyDeviceToHost));
                 const int wt = g.wp[l] >> 3;
-                for (int64_t r = 0; r < rows; ++r)
+                for (int64_t r = 0; r < rows; ++r) {
+                    const f16 *hn = h.data() + (size_t)(r / P) * Pv * g.ld[l];
+                    const int p = (int)(r % P);
                     for (int y = 0; y < g.h[l]; ++y)
                         for (int x = 0; x < g.w[l]; ++x)
-                            *dst++ = (float)h[(size_t)r * g.ld[l] + ((y >> 3) * wt + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7)];
+                            *dst++ = (float)hn[corr_layout_index(layout, p, ((y >> 3) * wt + (x >> 3)) * 64 + (y & 7) * 8 + (x & 7), g.ld[l])];
+                }
             }
         }
         return 0;
@@ -1352,6 +1358,35 @@ int pb_op_corr_volume(pb_ctx *c, const float *A, int M, const float *W, int N, i
     return 0;
 }
 
+// the kernel storing the blocked layout (corr_layout.h): raw halfs of round_up(M, 8) rows of ldo entries + guard_halfs behind them, preset to 0x7e7e
+int pb_op_corr_volume_blocked(pb_ctx *c, const float *A, int M, const float *W, int N, int ldo, int guard_halfs, void *out) {
+    PB_CHECK(c && A && W && out && M > 0 && N > 0 && N % 8 == 0 && ldo >= N && ldo % 64 == 0 && guard_halfs >= 0, PB_ERR_ARG, "op_corr_volume_blocked: bad arguments");
+    PB_HIP(hipSetDevice(c->device));
+    const int64_t Np = round_up(N, 64);
+    const size_t halfs = (size_t)corr_layout_rows(CORR_BLOCKED, M) * ldo + guard_halfs;
+    DevMem a32, w32, a16, w16, o16;
+    PB_TRY(a32.alloc((size_t)M * 256 * 4)); PB_TRY(w32.alloc((size_t)N * 256 * 4));
+    PB_TRY(a16.alloc((size_t)M * 256 * 2)); PB_TRY(w16.alloc((size_t)Np * 256 * 2));
+    PB_TRY(o16.alloc(halfs * 2));
+    PB_HIP(hipMemcpy(a32.p, A, (size_t)M * 256 * 4, hipMemcpyHostToDevice));
+    PB_HIP(hipMemcpy(w32.p, W, (size_t)N * 256 * 4, hipMemcpyHostToDevice));
+    PB_HIP(hipMemsetAsync(w16.p, 0, (size_t)Np * 256 * 2, c->stream));
+    PB_HIP(hipMemsetAsync(o16.p, 0x7e, halfs * 2, c->stream));
+    PB_TRY(launch_f32_to_f16(c->stream, a32.as<float>(), a16.as<f16>(), M, 256, 256));
+    PB_TRY(launch_f32_to_f16(c->stream, w32.as<float>(), w16.as<f16>(), N, 256, 256));
+    PB_TRY(launch_corr_volume(c->stream, a16.as<f16>(), M, w16.as<f16>(), N, (int)Np, o16.as<f16>(), ldo, CORR_BLOCKED));
+    PB_HIP(hipStreamSynchronize(c->stream));
+    PB_HIP(hipMemcpy(out, o16.p, halfs * 2, hipMemcpyDeviceToHost));
+    return 0;
+}
+// corr_layout.h's index function for the tests (needs no GPU): out[p * pld + c] = where entry c of source row p sits, p < P
+int pb_op_corr_layout_index(int layout, int P, int pld, int64_t *out) {
+    PB_CHECK(out && P > 0 && pld > 0 && pld % 64 == 0 && (layout == CORR_ROWMAJOR || layout == CORR_BLOCKED), PB_ERR_ARG, "op_corr_layout_index: bad arguments");
+    for (int p = 0; p < P; ++p)
+        for (int cc = 0; cc < pld; ++cc) out[(size_t)p * pld + cc] = corr_layout_index(layout, p, cc, pld);
+    return 0;
+}
+
 int pb_op_gemm_bench(pb_ctx *c, int M, int N, int K, int tile, int epi, int iters, double *ms_out) {
     PB_CHECK(c && M > 0 && N > 0 && K > 0 && K % 64 == 0 && N % 8 == 0 && iters > 0 && ms_out, PB_ERR_ARG, "gemm_bench: bad arguments");
     PB_HIP(hipSetDevice(c->device));
@@ -1717,7 +1752,7 @@ int pb_op_raft_lookup(pb_ctx *c, const float *fmap1, const float *fmap2, const f
                       float *levels) {
     PB_CHECK(c && fmap1 && fmap2 && flow && out && n > 0 && guard_rows >= 0, PB_ERR_ARG, "op_raft_lookup: bad arguments");
     RAFT_OP_ENGINE(e);
-    return e.lookup(fmap1, fmap2, flow, n, h8, w8, o8, guard_rows, out, levels);
+    return e.lookup(fmap1, fmap2, flow, n, h8, w8, o8, guard_rows, out, levels, launch_env().volume ? c->corr_layout : CORR_ROWMAJOR);
 }
 int pb_op_raft_lookup_otf(pb_ctx *c, const float *fmap1, const float *fmap2, const float *flow, int n, int h8, int w8, int o8, int guard_rows, void *out) {
     PB_CHECK(c && fmap1 && fmap2 && flow && out && n > 0 && guard_rows >= 0, PB_ERR_ARG, "op_raft_lookup_otf: bad arguments");

@@ -12,6 +12,9 @@ class RaftEngine : public FlowEngine {
     // --alternate_corr (raft.py:103-106): the lookup computes its window entries from the feature maps (corr_otf.hip) and prepare() carves no
     // correlation volume.  The plan key's word: the next call re-plans.
     void set_alternate_corr(int on) { alt_corr_ = on ? 1 : 0; }
+    // pb_set_option "corr_layout" (corr_layout.h): 1 = the volume source-blocked and corr_lookup_blocked_kernel (default), 0 = row-major and
+    // corr_lookup_kernel.  Same bytes out either way; part of the plan key's word (a blocked level holds round_up(P, 8) rows per pair-direction).
+    void set_corr_layout(int blocked) { corr_layout_ = blocked ? 1 : 0; }
     // the hoisted GRU share's 32-bit plane offset bounds the pairs of a call (flow_chunk.h)
     int chunk_pairs(int wanted, int H, int W, float scale, int dirs) const override;
 
@@ -30,9 +33,13 @@ class RaftEngine : public FlowEngine {
 
     // plan
     int alt_corr_ = 0;
+    int corr_layout_ = 1;
+    // the layout the volume is stored in: blocked only where volume.hip writes it (PB_VOLUME=0's generic GEMM writes row-major)
+    int vol_layout() const;
+    int plan_word() const { return alt_corr_ | (vol_layout() << 1); }
     int lh_[4] = {0, 0, 0, 0}, lw_[4] = {0, 0, 0, 0};
     f16 *fmap_ = nullptr, *ctx_ = nullptr;
-    f16 *pyr_[4] = {};                                // correlation volume levels: fp16 [pairs * P, pld_] in 8 x 8 target tiles
+    f16 *pyr_[4] = {};                                // correlation volume levels: fp16 [pairs][corr_layout_rows(P)][pld_] in 8 x 8 target tiles (corr_layout.h)
     f16 *ftile_[4] = {};                              // target features / 16 in tile order (B operand of the volume GEMM)
     int lwp_[4] = {}, lhp_[4] = {};                   // padded width / height of a level's tiled layout (multiples of 8)
     f16 *fpool_[4] = {};                              // avg-pooled target features of levels 1..3

@@ -12,6 +12,7 @@
 //     run-time statistics and stays a separate pass.
 #include "raft_engine.h"
 #include "flow_chunk.h"
+#include "corr_layout.h"
 
 #include <math.h>
 #include <string.h>
@@ -151,8 +152,10 @@ int RaftEngine::load(const pb_tensor *w, int n) {
     return 0;
 }
 
+int RaftEngine::vol_layout() const { return corr_layout_ && !alt_corr_ && launch_env().volume ? CORR_BLOCKED : CORR_ROWMAJOR; }
+
 int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
-    if (plan_.covers(F, H, W, scale, dirs, alt_corr_)) return 0;
+    if (plan_.covers(F, H, W, scale, dirs, plan_word())) return 0;
     PB_HIP(hipStreamSynchronize(stream));
     plan_.clear();
     geometry(H, W, scale, 8);
@@ -169,9 +172,10 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
         fmap_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2 + slack);
         ctx_ = (f16 *)carve((size_t)round_up((int64_t)F * P_, 256) * 256 * 2);
         for (int l = 0; l < 4; ++l) {
-            // level l of the volume: fp16, one row per source pixel of pld_[l] entries (raft_kernels.hip corr_pyramid_geometry).  alt_corr_:
-            // no volume and no tiled B operand - corr_otf.hip reads fmap_ and the pooled maps
-            pyr_[l] = alt_corr_ ? nullptr : (f16 *)carve((size_t)ND * P_ * pld_[l] * 2 + slack);
+            // level l of the volume: fp16, one row per source pixel of pld_[l] entries (raft_kernels.hip corr_pyramid_geometry), a
+            // pair-direction's rows rounded up to whole groups of 8 in the blocked layout (corr_layout.h).  alt_corr_: no volume and no tiled B
+            // operand - corr_otf.hip reads fmap_ and the pooled maps
+            pyr_[l] = alt_corr_ ? nullptr : (f16 *)carve((size_t)ND * corr_layout_rows(vol_layout(), P_) * pld_[l] * 2 + slack);
             fpool_[l] = l == 0 ? nullptr : (f16 *)carve((size_t)round_up((int64_t)F * lh_[l] * lw_[l], 256) * 256 * 2 + slack);
             ftile_[l] = alt_corr_ ? nullptr : (f16 *)carve((size_t)(F * (int64_t)pld_[l] + 256) * 256 * 2 + slack);
         }
@@ -195,7 +199,7 @@ int RaftEngine::prepare(int F, int H, int W, float scale, int dirs) {
         return 0;
     });
     if (r || (r = upload_resize_tables(H, W, scale))) return r;
-    plan_.set(F, H, W, scale, dirs, alt_corr_);
+    plan_.set(F, H, W, scale, dirs, plan_word());
     return 0;
 }
 
@@ -242,29 +246,28 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
         });
         if (r) return r;
     }
-    for (int i = 0; i < F - 1; ++i)
+    const int layout = vol_layout();
+    for (int i = 0; i < F - 1 && !alt_corr_; ++i)
         for (int d = 0; d < dirs; ++d) {
             const int n = i * dirs + d;
-            for (int l = 0; l < 4 && !alt_corr_; ++l) {
+            for (int l = 0; l < 4; ++l) {
                 GemmArgs a;
                 a.A = fmap_ + (int64_t)(i + d) * P_ * 256; a.lda = 256; a.M = P_;
                 a.W = ftile_[l] + (int64_t)(i + 1 - d) * pld_[l] * 256;
                 a.K = 256; a.N = pld_[l];
-                a.out = pyr_[l] + (int64_t)n * P_ * pld_[l]; a.ldo = pld_[l]; a.zero = zero_;
+                a.out = pyr_[l] + (int64_t)n * corr_layout_rows(layout, P_) * pld_[l]; a.ldo = pld_[l]; a.zero = zero_;
                 // K = 256 against P x pld fp16 outputs: this launch is bound by writing the volume, not by the matrix pipe (bytes: A + W + out)
                 const double flops = 2.0 * P_ * (double)lh_[l] * lw_[l] * 256, bytes = 2.0 * ((double)P_ * 256 + (double)pld_[l] * 256 + (double)P_ * pld_[l]);
                 if (!launch_env().volume)          // PB_VOLUME=0, A/B: the generic GEMM kernels
                     r = timed_gemm(F_GEMM, flops, bytes, [&] { return launch_gemm(stream, A_DENSE, EPI_STD, TILE_AUTO, a); });
                 else            // volume.hip: A-stationary, persistent along the targets; same accumulation order, same bits
-                    r = timed(F_GEMM, flops, bytes, [&] { return launch_corr_volume(stream, a.A, a.M, a.W, a.N, a.N, a.out, a.ldo); }, "corr_volume_kernel");
+                    r = timed(F_GEMM, flops, bytes, [&] { return launch_corr_volume(stream, a.A, a.M, a.W, a.N, a.N, a.out, a.ldo, layout); }, "corr_volume_kernel");
                 if (r) return r;
             }
-            r = timed(F_ELT, 0, 0, [&] {
-                return launch_init_state(stream, ctx_ + (int64_t)(i + d) * P_ * 256, h32_ + (int64_t)n * P_ * 128, hx_ + (int64_t)n * P_ * Lhx,
-                                         hx2_ + (int64_t)n * P_ * Lhx, flow_ + (int64_t)n * P_ * 2, P_, Lhx, upd8_ ? 768 : 0, s8, hoist_ ? 256 : 128);
-            });
-            if (r) return r;
         }
+    // the recurrent state of every pair-direction in one launch: pair-direction n = i * dirs + d starts from the context features of frame i + d
+    r = timed(F_ELT, 0, 0, [&] { return launch_init_state(stream, ctx_, h32_, hx_, hx2_, flow_, rows, Lhx, upd8_ ? 768 : 0, s8, hoist_ ? 256 : 128, P_, dirs); });
+    if (r) return r;
 
     if (debug && (r = snapshot("net0", h32_, (size_t)ND * P_ * 128 * 4, Stage::f32_rows(nullptr, ND, P_, 128)))) return r;
 
@@ -292,7 +295,7 @@ int RaftEngine::infer(const uint8_t *frames, int F, int H, int W, float scale, i
                 return launch_corr_lookup_otf(stream, fmap_, tg, lh_, lw_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8, dirs);
             }, "corr_lookup_otf_kernel");
         } else {
-            r = timed(F_ELT, 0, 0, [&] { return launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, lhp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8); });
+            r = timed(F_ELT, 0, 0, [&] { return launch_corr_lookup(stream, pyr_, lh_, lw_, lwp_, lhp_, pld_, flow_, P_, w8_, corr_, rows, Lhx, upd8_ ? 768 : 0, s8, layout); });
         }
         if (r) return r;
         if (debug && it == 0 && (r = snapshot("corr0", corr_, (size_t)ND * P_ * Lhx * 2, Stage::f16_nhwc(nullptr, ND, 324, h8_, w8_, Lhx)))) return r;

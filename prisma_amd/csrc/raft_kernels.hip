@@ -3,6 +3,7 @@
 // bands/raft/corr.py:12-50 (pyramid + 9x9 lookup), bands/raft/update.py:33-60 (GRU gating),
 // bands/raft/raft.py:73-84 (convex upsample), bands/common/encode.py:98-126 (process_flow).
 #include "raft_kernels.h"
+#include "corr_layout.h"
 
 #include <algorithm>
 
@@ -322,15 +323,21 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const f16 *__restrict__ a
 }
 
 // cnet output [rows][256] fp16 -> net = tanh(c[:128]) (fp32 master + fp16 copy in HX[:, 0:128]),
-// inp = relu(c[128:]) in HX[:, 128:256]; flow = 0.
+// inp = relu(c[128:]) in HX[:, 128:256]; flow = 0.  dirs 1 / 2: one launch over all pair-directions of a call - row block n = i * dirs + d
+// (P rows) reads the context features of frame i + d; dirs 0: row r reads row r of c.
 __global__ __launch_bounds__(256) void init_state_kernel(const f16 *__restrict__ c, float *__restrict__ h32,
                                                           f16 *__restrict__ hx, f16 *__restrict__ hx2, float *__restrict__ flow, int64_t rows,
-                                                          int ld, int o8_off, float o8_scale, int inp_off) {
+                                                          int ld, int o8_off, float o8_scale, int inp_off, int P, int dirs) {
     const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows * 32) return;
     const int c8 = (int)(i % 32);
     const int64_t r = i / 32;
-    const f16x8 v = *(const f16x8 *)(c + r * 256 + c8 * 8);
+    int64_t cr = r;
+    if (dirs) {
+        const int n = (int)(r / P);
+        cr = (int64_t)(n / dirs + n % dirs) * P + (r - (int64_t)n * P);
+    }
+    const f16x8 v = *(const f16x8 *)(c + cr * 256 + c8 * 8);
     f16x8 o;
     if (c8 < 16) {
 #pragma unroll
@@ -416,6 +423,42 @@ __device__ __forceinline__ const f16 *sel4(const f16 *const (&a)[4], int l) {
     return (const f16 *)(((unsigned long long)hi << 32) | lo);
 }      // hp8: padded target rows of the level (CorrGeo::hp)
 
+// The arithmetic of the lookup, shared by corr_lookup_kernel and corr_lookup_blocked_kernel so that both give the same bits.
+// Sample k of source pixel p on level l: x samples k = 0..8 around column p % w8, y samples k = 9..17 around row p / w8 (the same expression for
+// both; dim = the level's width / height); ci = floor, ca = fraction.
+__device__ __forceinline__ void lookup_sample(int p, int w8, float fx, float fy, int k, int l, int dim, int &ci, float &ca) {
+    const float inv = 1.f / (float)(1 << l);
+    const bool isx = k < 9;
+    const float c = (float)(isx ? p % w8 : p / w8) + (isx ? fx : fy);
+    // reproduce grid_sample's round trip: normalise then un-normalise (align_corners=True)
+    const float v = ((2.f * (c * inv + (float)(isx ? k - 4 : k - 13)) / (float)(dim - 1) - 1.f) + 1.f) * 0.5f * (float)(dim - 1);
+    const float f = floorf(v);
+    // far out-of-range samples are all zero anyway: clamp so that the integer arithmetic of the callers cannot overflow
+    ci = (int)fminf(fmaxf(f, -65536.f), 65536.f);
+    ca = v - f;
+}
+// One of the nine samples of a window column: wp = the LDS window (rows of 24 halfs) at the column, yo the sample's row in it
+// v00 (1 - ax)(1 - ay) + v01 ax (1 - ay) + v10 (1 - ax) ay + v11 ax ay, with the roundings corr_lookup_kernel has always had, written out so
+// that they no longer depend on how the compiler contracts the expression in one kernel or the other: three fused multiply-adds over
+// products rounded to fp32, and the fp16 result rounded from the fp32 sum - except for a window column's LAST sample (j = 8, `last`), whose
+// final multiply-add the compiler had fused with the conversion (v_fma_mixlo_f16: one rounding, from the exact sum).  Both are kept, bit for
+// bit; the empty asm keeps the other eight from being fused the same way.
+__device__ __forceinline__ f16 lookup_blend(const f16 *wp, int yo, float ax, float ay, bool last) {
+    const float v00 = (float)wp[yo * 24], v01 = (float)wp[yo * 24 + 1];
+    const float v10 = (float)wp[yo * 24 + 24], v11 = (float)wp[yo * 24 + 25];
+    float s = __builtin_fmaf(v00 * (1.f - ax), 1.f - ay, (v01 * ax) * (1.f - ay));
+    s = __builtin_fmaf(v10 * (1.f - ax), ay, s);
+    const float a11 = v11 * ax;
+    if (last) {
+        unsigned o;
+        asm("v_fma_mixlo_f16 %0, %1, %2, %3" : "=v"(o) : "v"(ay), "v"(a11), "v"(s));
+        return __builtin_bit_cast(f16, (unsigned short)o);
+    }
+    float r = __builtin_fmaf(a11, ay, s);
+    asm("" : "+v"(r));
+    return (f16)r;
+}
+
 // CorrBlock.__call__ (corr.py:29-50): 9 x 9 bilinear window on each of the 4 levels around coords / 2^l, zero outside.
 // A block covers 7 pixels, i.e. 28 (pixel, level) windows:
 //   1. the 9 + 9 sample coordinates of every window, once (the reference's normalise / un-normalise round trip costs a
@@ -449,18 +492,12 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(PyrPtrs py, const floa
             const int k = idc % 18, pl = idc / 18, l = pl & 3, pr = pl >> 2;
             const int64_t r = r0 + pr < rows ? r0 + pr : rows - 1;
             const int p = (int)((unsigned)r % (unsigned)P);           // rows < 2^31 (launcher check): a 32-bit remainder, not the 64-bit library one
-            const float inv = 1.f / (float)(1 << l);
-            const bool isx = k < 9;
-            // x samples k = 0..8 around column p % w8, y samples k = 9..17 around row p / w8; the same expression for both
-            const float c = (float)(isx ? p % w8 : p / w8) + (isx ? fl[u][0] : fl[u][1]);
-            const int dim = isx ? sel4(py.w, l) : sel4(py.h, l);
-            // reproduce grid_sample's round trip: normalise then un-normalise (align_corners=True)
-            const float v = ((2.f * (c * inv + (float)(isx ? k - 4 : k - 13)) / (float)(dim - 1) - 1.f) + 1.f) * 0.5f * (float)(dim - 1);
-            const float f = floorf(v);
+            int cif;
+            float caf;
+            lookup_sample(p, w8, fl[u][0], fl[u][1], k, l, k < 9 ? sel4(py.w, l) : sel4(py.h, l), cif, caf);
             if (idx < 28 * 18) {
-                // far out-of-range samples are all zero anyway: clamp so that the integer arithmetic below cannot overflow
-                ci[idx] = (int)fminf(fmaxf(f, -65536.f), 65536.f);
-                ca[idx] = v - f;
+                ci[idx] = cif;
+                ca[idx] = caf;
             }
         }
     }
@@ -509,9 +546,7 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(PyrPtrs py, const floa
             int yo = ci[cb + 9 + j] - yb;
             const float ay = ca[cb + 9 + j];
             yo = yo < 0 ? 0 : (yo > 9 ? 9 : yo);
-            const float v00 = (float)wp[yo * 24], v01 = (float)wp[yo * 24 + 1];
-            const float v10 = (float)wp[yo * 24 + 24], v11 = (float)wp[yo * 24 + 25];
-            dst[j] = (f16)(v00 * (1.f - ax) * (1.f - ay) + v01 * ax * (1.f - ay) + v10 * (1.f - ax) * ay + v11 * ax * ay);
+            dst[j] = lookup_blend(wp, yo, ax, ay, j == 8);
         }
     }
     __syncthreads();
@@ -522,6 +557,117 @@ __global__ __launch_bounds__(256) void corr_lookup_kernel(PyrPtrs py, const floa
             const f16x4 o = *(const f16x4 *)(tile + pr * 324 + c4 * 4);
             *(f16x4 *)(out + r * ldo + c4 * 4) = o;
             if (o8_off)      // fp8 copy after the row's fp16 part: the A operand of convc1's MX segment (gemm.h nk16)
+                *(int *)((char *)(out + r * ldo) + o8_off + c4 * 4) = pb_fp8x4((float)o[0] * o8_scale, (float)o[1] * o8_scale, (float)o[2] * o8_scale, (float)o[3] * o8_scale);
+        }
+    }
+}
+
+// The same lookup from the source-blocked volume (corr_layout.h CORR_BLOCKED): a block owns ONE group of 8 source rows - blockIdx.x = pair-direction
+// x groups per pair-direction + (p >> 3), which is also the group's index inside every level buffer - and all four levels, 32 windows:
+//   1. coordinates as above (lookup_sample);
+//   2. loads by whole target tile: wave l takes level l, lane (q, yy) = (pixel of the group, row of the tile) fetches the 16 bytes of row yy of
+//      its pixel's copy of tile (tr, tc) of the window's 3 x 3 tiles, at tile * 1 KB + q * 128 + yy * 16 inside the group.  Where the eight
+//      pixels want the same tile (coherent flow) one wave instruction reads up to 1 KB in a run; where they do not, every pixel addresses its
+//      own tile.  Only what corr_lookup_kernel reads is read: the window's 11 rows (a third tile row when the first row sits at offset 6, 7 of
+//      its tile), a third tile column when the last column + 1 reaches it; every other lane - rows outside the window, tiles outside the
+//      level, pixels past P - reads the level's first 16 bytes and stores zeros or nothing.  All nine loads are issued before the first LDS
+//      store, and as non-temporal ones: a launch reads every volume byte it needs exactly once;
+//   3. the blend (lookup_blend) by (window column, three of the nine samples) - 864 items over 256 threads;  4. 8 x 324 results as 8-byte vectors.
+// Build output: 26 688 bytes of LDS, 52 VGPRs, 6 waves per SIMD = six blocks of 8 rows per CU (the LDS is the limit).  corr_lookup_kernel:
+// 23 360 bytes, 33 VGPRs, 7 waves per SIMD by the compiler's count = seven blocks of 7 rows: 48 against 49 source rows in flight per CU.
+__global__ __launch_bounds__(256) void corr_lookup_blocked_kernel(PyrPtrs py, const float *__restrict__ flow, int P, int w8, int nb8,
+                                                                   f16 *__restrict__ out, int ldo, int o8_off, float o8_scale) {
+    __shared__ __attribute__((aligned(16))) f16 win[32 * 11 * 24];
+    __shared__ __attribute__((aligned(8))) f16 tile[8 * 324];
+    __shared__ int ci[32 * 18];
+    __shared__ float ca[32 * 18];
+    const int t = threadIdx.x;
+    const int g = blockIdx.x, n = g / nb8, p0 = (g - n * nb8) * 8;
+    const int64_t r0 = (int64_t)n * P + p0;
+    const int nv = P - p0 < 8 ? P - p0 : 8;                   // pixels of the group that exist (the last group of a pair-direction may be partial)
+    {
+        f32x2 fl[3];
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int idx = t + 256 * u, idc = idx < 32 * 18 ? idx : 0;
+            const int pr = (idc / 18) >> 2;
+            fl[u] = *(const f32x2 *)(flow + (r0 + (pr < nv ? pr : nv - 1)) * 2);
+        }
+#pragma unroll
+        for (int u = 0; u < 3; ++u) {
+            const int idx = t + 256 * u, idc = idx < 32 * 18 ? idx : 0;
+            const int k = idc % 18, pl = idc / 18, l = pl & 3, pr = pl >> 2;
+            int cif;
+            float caf;
+            lookup_sample(p0 + (pr < nv ? pr : nv - 1), w8, fl[u][0], fl[u][1], k, l, k < 9 ? sel4(py.w, l) : sel4(py.h, l), cif, caf);
+            if (idx < 32 * 18) {
+                ci[idx] = cif;
+                ca[idx] = caf;
+            }
+        }
+    }
+    __syncthreads();
+    {
+        const int l = __builtin_amdgcn_readfirstlane(t >> 6), q = (t & 63) >> 3, yy = t & 7;
+        const int pl = q * 4 + l;
+        const int hp8 = sel4(py.hp8, l), wt = sel4(py.wp, l) >> 3;
+        const int x0 = ci[pl * 18], y0 = ci[pl * 18 + 9];
+        const bool third = ci[pl * 18 + 8] + 1 - (x0 & ~7) >= 16;
+        const f16 *lv0 = sel4(py.lv, l), *grp = lv0 + corr_blocked_tile(g, 0, sel4(py.ld, l) >> 6);
+        f16x8 wv[9];
+        int wdst[9];
+#pragma unroll
+        for (int u = 0; u < 9; ++u) {
+            const int tr = u / 3, tc = u % 3;
+            const int wr = tr * 8 + yy - (y0 & 7);             // window row of this lane's tile row: target row y0 + wr = ((y0 >> 3) + tr) * 8 + yy
+            const int y = y0 + wr, tx = (x0 >> 3) + tc;
+            const bool slot = (unsigned)wr < 11u;
+            const bool ok = slot && q < nv && (tc < 2 || third) && (unsigned)y < (unsigned)hp8 && (unsigned)tx < (unsigned)wt;
+            // (a lane with nothing to fetch reads the LEVEL's first 16 bytes, one line for the whole launch: the group's own first bytes cost a
+            // 64-byte fetch per block and level that the window may not need - 26 MB per launch at 31 pairs of 1440 x 816, measured)
+            const f16 *src = ok ? grp + ((int)corr_blocked_tile(0, (y >> 3) * wt + tx, 0) + q * 64 + yy * 8) : lv0;
+            const f16x8 ld = __builtin_nontemporal_load((const __attribute__((address_space(1))) f16x8 *)(unsigned long long)src);
+            const f16x8 z = {(f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f, (f16)0.f};
+            wv[u] = ok ? ld : z;
+            wdst[u] = slot ? (pl * 11 + wr) * 24 + tc * 8 : -1;
+        }
+#pragma unroll
+        for (int u = 0; u < 9; ++u)
+            if (wdst[u] >= 0) *(f16x8 *)(win + wdst[u]) = wv[u];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int v = t + 256 * u;
+        if (v < 3 * 288) {
+            const int jg = v / 288, rem = v - jg * 288;
+            const int li = rem % 36, pr = rem / 36;
+            const int l = li / 9, wi = li - l * 9;
+            const int pl = pr * 4 + l, cb = pl * 18;
+            const int xb = ci[cb] & ~7, yb = ci[cb + 9];
+            int xo = ci[cb + wi] - xb;
+            const float ax = ca[cb + wi];
+            xo = xo < 0 ? 0 : (xo > 22 ? 22 : xo);              // always in range (spread of the 9 floors <= 9); defensive
+            const f16 *wp = win + pl * 11 * 24 + xo;
+            f16 *dst = tile + pr * 324 + l * 81 + wi * 9;
+#pragma unroll
+            for (int jj = 0; jj < 3; ++jj) {
+                const int j = jg * 3 + jj;
+                int yo = ci[cb + 9 + j] - yb;
+                const float ay = ca[cb + 9 + j];
+                yo = yo < 0 ? 0 : (yo > 9 ? 9 : yo);
+                dst[j] = lookup_blend(wp, yo, ax, ay, j == 8);
+            }
+        }
+    }
+    __syncthreads();
+    for (int v = t; v < 8 * 81; v += 256) {
+        const int pr = v / 81, c4 = v - pr * 81;
+        const int64_t r = r0 + pr;
+        if (pr < nv) {
+            const f16x4 o = *(const f16x4 *)(tile + pr * 324 + c4 * 4);
+            *(f16x4 *)(out + r * ldo + c4 * 4) = o;
+            if (o8_off)      // fp8 copy after the row's fp16 part, as corr_lookup_kernel's
                 *(int *)((char *)(out + r * ldo) + o8_off + c4 * 4) = pb_fp8x4((float)o[0] * o8_scale, (float)o[1] * o8_scale, (float)o[2] * o8_scale, (float)o[3] * o8_scale);
         }
     }
@@ -786,8 +932,10 @@ int launch_in_apply(hipStream_t s, const f16 *a, const float *sa, const f16 *b, 
     hipLaunchKernelGGL(in_apply_kernel, dim3(nblk((int64_t)B * HW * (C / 8))), dim3(256), 0, s, a, sa, b, sb, out, B, HW, C / 8, ldc, lo_off, lo8_pa);
     LAUNCH_CHECK();
 }
-int launch_init_state(hipStream_t s, const f16 *c, float *h32, f16 *hx, f16 *hx2, float *flow, int64_t rows, int ld, int o8_off, float o8_scale, int inp_off) {
-    hipLaunchKernelGGL(init_state_kernel, dim3(nblk(rows * 32)), dim3(256), 0, s, c, h32, hx, hx2, flow, rows, ld, o8_off, o8_scale, inp_off);
+int launch_init_state(hipStream_t s, const f16 *c, float *h32, f16 *hx, f16 *hx2, float *flow, int64_t rows, int ld, int o8_off, float o8_scale, int inp_off,
+                      int P, int dirs) {
+    PB_CHECK(dirs == 0 || (P > 0 && rows % P == 0 && dirs <= 2), -1, "init_state: %lld rows in blocks of %d, %d directions", (long long)rows, P, dirs);
+    hipLaunchKernelGGL(init_state_kernel, dim3(nblk(rows * 32)), dim3(256), 0, s, c, h32, hx, hx2, flow, rows, ld, o8_off, o8_scale, inp_off, P, dirs);
     LAUNCH_CHECK();
 }
 int launch_avgpool2_nhwc(hipStream_t s, const f16 *x, f16 *y, int n, int H, int W, int C) {
@@ -813,13 +961,20 @@ void corr_pyramid_geometry(int h8, int w8, CorrGeo &g) {
     }
 }
 int launch_corr_lookup(hipStream_t s, const f16 *const lv[4], const int h[4], const int w[4], const int wp[4], const int hp[4], const int ld[4],
-                       const float *flow, int P, int w8, f16 *out, int64_t rows, int ldo, int o8_off, float o8_scale) {
+                       const float *flow, int P, int w8, f16 *out, int64_t rows, int ldo, int o8_off, float o8_scale, int layout) {
     PyrPtrs py;
     // hp8 is the level's padded height, not ld / wp: where the stride's rounding to 256 adds a tile row's worth of entries (e.g. a 129 x 17 or a
     // 56 x 184 grid) rows hp .. ld / wp - 1 would pass the kernel's range test and address the next source pixel's volume row
     for (int i = 0; i < 4; ++i) { py.lv[i] = lv[i]; py.h[i] = h[i]; py.w[i] = w[i]; py.wp[i] = wp[i]; py.ld[i] = ld[i]; py.hp8[i] = hp[i]; }
     PB_CHECK(rows < (1LL << 31), -1, "corr_lookup: %lld rows", (long long)rows);
-    hipLaunchKernelGGL(corr_lookup_kernel, dim3((unsigned)((rows + 6) / 7)), dim3(256), 0, s, py, flow, P, w8, out, rows, ldo, o8_off, o8_scale);
+    if (layout == CORR_BLOCKED) {
+        PB_CHECK(P > 0 && rows % P == 0, -1, "corr_lookup: %lld rows are no whole pair-directions of %d", (long long)rows, P);
+        for (int i = 0; i < 4; ++i) PB_CHECK(ld[i] % 64 == 0 && ld[i] >= hp[i] * wp[i], -1, "corr_lookup: level %d stride %d", i, ld[i]);
+        const int nb8 = (P + 7) / 8;
+        hipLaunchKernelGGL(corr_lookup_blocked_kernel, dim3((unsigned)(rows / P * nb8)), dim3(256), 0, s, py, flow, P, w8, nb8, out, ldo, o8_off, o8_scale);
+    } else {
+        hipLaunchKernelGGL(corr_lookup_kernel, dim3((unsigned)((rows + 6) / 7)), dim3(256), 0, s, py, flow, P, w8, out, rows, ldo, o8_off, o8_scale);
+    }
     LAUNCH_CHECK();
 }
 // BasicMotionEncoder.convf1 (update.py:88: 7 x 7, 2 -> 128, ReLU) as a direct kernel on the fp32 flow field.  As an im2col GEMM it cost a 130 MB

@@ -33,6 +33,7 @@
 #include "common.h"
 #include "launch_env.h"
 #include "raft_kernels.h"
+#include "corr_layout.h"
 #include "../../include/prisma_bands.h"
 
 #define LAUNCH_CHECK() do { PB_HIP(hipGetLastError()); return 0; } while (0)
@@ -54,7 +55,7 @@ constexpr int VBM = 128, VBN = 64, VNT = 256, VSTAGES = 4, VSTAGE_BYTES = 2 * VB
 
 template <int ABL>
 __global__ __launch_bounds__(VNT, 2) void corr_volume_kernel(const f16 *__restrict__ A, int M, const f16 *__restrict__ W, int N, int w_rows,
-                                                             f16 *__restrict__ out, int64_t ldo, int tiles_per_wg) {
+                                                             f16 *__restrict__ out, int64_t ldo, int layout, int tiles_per_wg) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -143,12 +144,17 @@ __global__ __launch_bounds__(VNT, 2) void corr_volume_kernel(const f16 *__restri
     f16x2 pk[16];
     int pk_n = -1;                                              // first column of the tile held in pk, -1: none
     const int rows_w = (M - m0) < 32 ? (M - m0 < 0 ? 0 : M - m0) : 32;
-    const int ldb = (int)ldo * 2;                               // row stride in bytes (launch_corr_volume checks 32 rows fit 31 bits)
+    // Byte strides of the stores (corr_layout.h): rs between the rows of a group of 8, gs between groups, ts between column tiles.  Row-major:
+    // a row is ldo halfs; blocked: the 8 rows' 128 bytes of a tile are 1 KB contiguous, a group holds ldo / 64 such tiles.  A wave's rows are
+    // four whole groups either way (m0 is a multiple of 32), and the register -> row map below puts (r & 3) + 4 lh inside group r >> 2.
+    const int ldb = (int)ldo * 2;                               // row-major row stride in bytes (launch_corr_volume checks 32 rows fit 31 bits)
+    const int rs = layout == CORR_BLOCKED ? 128 : ldb, gs = layout == CORR_BLOCKED ? (int)corr_blocked_tile(1, 0, (int)(ldo >> 6)) * 2 : 8 * ldb;
+    const int ts = layout == CORR_BLOCKED ? 1024 : VBN * 2;
     // (built from readfirstlane'd halves: left to itself the compiler keeps the descriptor in VGPRs and wraps every store in a waterfall loop)
-    const uint64_t ob = (uint64_t)(out + (int64_t)m0 * ldo);
+    const uint64_t ob = (uint64_t)((char *)out + (int64_t)(m0 >> 3) * gs);
     const uint64_t ob_u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(ob >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)ob);
-    const __amdgpu_buffer_rsrc_t rsO = make_rsrc((const void *)ob_u, (unsigned)__builtin_amdgcn_readfirstlane(rows_w * ldb));
-    const int vo_lane = 4 * lh * ldb + 4 * li;
+    const __amdgpu_buffer_rsrc_t rsO = make_rsrc((const void *)ob_u, (unsigned)__builtin_amdgcn_readfirstlane(layout == CORR_BLOCKED ? ((rows_w + 7) >> 3) * gs : rows_w * ldb));
+    const int vo_lane = 4 * lh * rs + 4 * li;
     // Lanes without a tile to store (none yet, columns past N) carry an offset outside the resource: the store is dropped by the range check.
     // The row of a store travels in the SCALAR offset, which the compiler's builtin documents as excluded from bounds checking: the last
     // row tile (fewer than 32 valid rows) therefore marks its rows past M in the lane offset as well.  (Measured: gfx950 drops such stores
@@ -162,12 +168,12 @@ __global__ __launch_bounds__(VNT, 2) void corr_volume_kernel(const f16 *__restri
         if (rows_full) {
 #pragma unroll
             for (int r = 0; r < 16; ++r)
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pk[r]), rsO, vo_st, ((r & 3) + 8 * (r >> 2)) * ldb, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pk[r]), rsO, vo_st, (r & 3) * rs + (r >> 2) * gs, 0);
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = (r & 3) + 8 * (r >> 2);
-                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pk[r]), rsO, row + 4 * lh < rows_w ? vo_st : VO_NONE, row * ldb, 0);
+                __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pk[r]), rsO, row + 4 * lh < rows_w ? vo_st : VO_NONE, (r & 3) * rs + (r >> 2) * gs, 0);
             }
         }
     };
@@ -202,7 +208,7 @@ __global__ __launch_bounds__(VNT, 2) void corr_volume_kernel(const f16 *__restri
             for (int ks = 0; ks < 4; ++ks) { PB_VOL_MM(qb, 12, ks) }
         }
         pk_n = (nt0 + j) * VBN + 2 * li;
-        vo_st = pk_n < N ? vo_lane + (nt0 + j) * (VBN * 2) : VO_NONE;
+        vo_st = pk_n < N ? vo_lane + (nt0 + j) * ts : VO_NONE;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             pk[r] = f16x2{(f16)acc[0][r], (f16)acc[1][r]};
@@ -220,8 +226,10 @@ __global__ __launch_bounds__(VNT, 2) void corr_volume_kernel(const f16 *__restri
 
 }  // namespace
 
-int launch_corr_volume(hipStream_t s, const f16 *A, int M, const f16 *W, int N, int w_rows, f16 *out, int64_t ldo) {
+int launch_corr_volume(hipStream_t s, const f16 *A, int M, const f16 *W, int N, int w_rows, f16 *out, int64_t ldo, int layout) {
     PB_CHECK(A && W && out && M > 0 && N > 0 && N % 8 == 0 && ldo >= N && w_rows >= N && ldo < (1 << 24), PB_ERR_ARG, "corr_volume: bad arguments");
+    PB_CHECK(layout == CORR_ROWMAJOR || (layout == CORR_BLOCKED && ldo % 64 == 0), PB_ERR_ARG, "corr_volume: layout %d with a row of %lld entries", layout,
+             (long long)ldo);
     const int smem = VSTAGES * VSTAGE_BYTES;
 #ifdef PB_DIAG
     const int abl = launch_env().vol_abl;                       // PB_VOL_ABL (wrong results): 1 no stores, 2 no fragment reads / MFMAs, 4 no DMA
@@ -238,7 +246,7 @@ int launch_corr_volume(hipStream_t s, const f16 *A, int M, const f16 *W, int N, 
     {                                                                                                                     \
         static PbLdsLimit lds;                                                                                            \
         if (int rc = pb_lds_limit(lds, (const void *)corr_volume_kernel<X>, smem)) return rc;                             \
-        hipLaunchKernelGGL(corr_volume_kernel<X>, dim3(tilesM * groups), dim3(VNT), smem, s, A, M, W, N, w_rows, out, ldo, tpw); \
+        hipLaunchKernelGGL(corr_volume_kernel<X>, dim3(tilesM * groups), dim3(VNT), smem, s, A, M, W, N, w_rows, out, ldo, layout, tpw); \
     }
     switch (abl) {
 #ifdef PB_DIAG

@@ -409,6 +409,14 @@ def raft_geometry(h8: int, w8: int) -> List[dict]:
     return [dict(h=geo[l * 5], w=geo[l * 5 + 1], wp=geo[l * 5 + 2], hp=geo[l * 5 + 3], ld=geo[l * 5 + 4]) for l in range(4)]
 
 
+def corr_layout_index(layout: int, P: int, pld: int) -> np.ndarray:
+    """[P, pld] int64: where entry c of source row p sits in a level of flow_raft's correlation volume, layout 0 row-major / 1 source-blocked
+    (csrc/corr_layout.h, the function the kernels compile; needs no GPU)"""
+    out = np.empty((P, pld), np.int64)
+    check(_lib.load().pb_op_corr_layout_index(layout, P, pld, _ptr(out)))
+    return out
+
+
 def gm_geometry(h8: int, w8: int, splits: int = 2) -> dict:
     """the flow_gmflow band's window geometry of an h8 x w8 token grid (csrc gm_geometry): P, window wh x ww = Lw tokens, V^T row strides;
     splits = 8: the two-scale model's 1/4 grid"""
@@ -456,6 +464,16 @@ class Ops(_Ctx):
         ldo = ldo or N
         out = np.empty((M + guard_rows, ldo), np.float32)
         check(self.lib.pb_op_corr_volume(self.ctx, _ptr(A), M, _ptr(W), N, ldo, guard_rows, _ptr(out)))
+        return out
+
+    def corr_volume_blocked(self, A, W, ldo: int = 0, guard_halfs: int = 4096) -> np.ndarray:
+        """the same kernel storing the source-blocked layout (csrc/corr_layout.h): the raw fp16 buffer, round_up(M, 8) * ldo + guard_halfs
+        entries, 0x7e7e (a NaN) wherever the kernel did not write."""
+        A, W = _f32(A), _f32(W)
+        M, N = A.shape[0], W.shape[0]
+        ldo = ldo or N
+        out = np.empty(-(-M // 8) * 8 * ldo + guard_halfs, np.float16)
+        check(self.lib.pb_op_corr_volume_blocked(self.ctx, _ptr(A), M, _ptr(W), N, ldo, guard_halfs, _ptr(out)))
         return out
 
     def gemm_bench(self, M: int, N: int, K: int, tile: int = 0, epi: int = 0, iters: int = 20) -> float:
