@@ -44,10 +44,10 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
     # to the I420 conversion (engine rgb_full).  The mask videos and the trailing zero frame are small and rare: they are converted, and
     # resized, on the host (VideoWriter.write)
     yin, yout = src.i420, is_y4m(args.output)
-    fmt = frame_formats(model, yin, yout, h, w)
+    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None))
     model.rgb_full = yout and (sh, sw) != (h, w)
     rh, rw = (h, w) if model.rgb_full else (sh, sw)      # the size of the engine's rgb frames
-    frame = ((i420_bytes(h, w),), np.uint8) if yin else (src[0].shape, np.uint8)
+    frame = ((src.frame_bytes,), np.uint8) if yin else (src[0].shape, np.uint8)       # a .y4m's planes, in the clip's own layout
 
     def step(_s, frames):
         mask = None

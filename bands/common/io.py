@@ -9,8 +9,12 @@ frame stacks ([n,H,W,3] uint8) and .png work everywhere.
 .y4m (YUV4MPEG2) is the video container that needs no library: one text header line, then `FRAME\n` + the raw I420 planes per frame.
 It streams in both directions, ffmpeg / mpv / every encoder read and write it (`ffmpeg -i in.mp4 in.y4m` before a run,
 `ffmpeg -i depth_anything.y4m -crf 15 depth_anything.mp4` after it), and its frames are what the engines take and give with the
-"frames_i420" / "rgb_out_i420" options (include/prisma_bands.h) - half the bytes of RGB through PCIe and the page-locked rings.  8 bit,
-4:2:0, progressive, limited range only; the colour arithmetic is common/yuv.py's.
+"frames_i420" / "rgb_out_i420" options (include/prisma_bands.h) - half the bytes of RGB through PCIe and the page-locked rings.
+
+A clip is read in whatever planar layout it has (Y4M_TAGS: 4:2:0, 4:2:2, 4:4:4 or mono, 8 to 16 bit, limited or full range) - `ffmpeg -i in.mov
+in.y4m` does not convert pixel formats - and its planes go to the engine as they are (pb_set_frame_format).  A header does not name the matrix:
+PRISMA_Y4M_MATRIX=bt601 (the default) | bt709 does; it is not guessed from the frame size.  Chroma siting is not acted on, interlaced clips,
+4:1:1 and alpha layouts are refused, and so is XCOLORRANGE=FULL in a header without a `C` tag (a header that names no layout is 8-bit 4:2:0, limited).  What is written is always 8 bit, 4:2:0, limited range, BT.601.  The colour arithmetic is common/yuv.py's.
 """
 import os
 from fractions import Fraction
@@ -18,10 +22,23 @@ from fractions import Fraction
 import numpy as np
 
 from .resize import resize_rgb
-from .yuv import i420_bytes, i420_to_rgb, rgb_to_i420
+from .yuv import Format, i420_bytes, rgb_to_i420, yuv_bytes, yuv_to_rgb
 
 Y4M_MAGIC = b"YUV4MPEG2"
 Y4M_CHROMA = ("C420", "C420jpeg", "C420mpeg2", "C420paldv")      # 8-bit 4:2:0; the siting they name is not acted on (nearest / block mean)
+Y4M_DEPTHS = (9, 10, 12, 14, 16)
+# every `C` tag a clip may carry -> (chroma layout, bits per sample)
+Y4M_TAGS = dict([(t, (420, 8)) for t in Y4M_CHROMA] + [("C422", (422, 8)), ("C444", (444, 8)), ("Cmono", (400, 8))]
+                + [("C%dp%d" % (c, d), (c, d)) for c in (420, 422, 444) for d in Y4M_DEPTHS] + [("Cmono%d" % d, (400, d)) for d in Y4M_DEPTHS])
+Y4M_MATRICES = ("bt601", "bt709")
+
+
+def y4m_matrix():
+    """the matrix .y4m clips are decoded with: PRISMA_Y4M_MATRIX, "bt601" when unset (a header does not carry it)"""
+    m = os.environ.get("PRISMA_Y4M_MATRIX", "") or "bt601"
+    if m not in Y4M_MATRICES:
+        raise RuntimeError("PRISMA_Y4M_MATRIX=%s: one of %s" % (m, ", ".join(Y4M_MATRICES)))
+    return m
 
 
 def create_folder(path):
@@ -79,7 +96,9 @@ def as_rate(rate):
 
 
 class Y4MFile:
-    """The container side of a .y4m: header, frame index, raw planes.  .width / .height / .rate (Fraction) / len(); read_i420(i, out)."""
+    """The container side of a .y4m: header, frame index, raw planes.  .width / .height / .rate (Fraction) / .format (common/yuv.py Format: the
+    layout of the `C` tag - 4:2:0, 8 bit without one -, the range of XCOLORRANGE, the matrix of PRISMA_Y4M_MATRIX) / .frame_bytes / len();
+    read_i420(i, out) copies a frame's planes as they are in the file, whatever the layout."""
 
     def __init__(self, path):
         self.path = path
@@ -91,6 +110,8 @@ class Y4MFile:
             raise RuntimeError("%s: not a YUV4MPEG2 file (no `YUV4MPEG2 ...` header line)" % path)
         self.width = self.height = 0
         self.rate = Fraction(24)
+        layout, full, ctag, xtag = (420, 8), False, None, None
+        matrix = y4m_matrix()
         try:
             for tok in head[:end].decode("ascii").split()[1:]:
                 k, v = tok[0], tok[1:]
@@ -103,16 +124,39 @@ class Y4MFile:
                     self.rate = Fraction(int(num), int(den))
                 elif k == "I" and tok != "Ip":
                     raise RuntimeError("%s: %s: interlaced material is not supported (progressive `Ip` only)" % (path, tok))
-                elif k == "C" and tok not in Y4M_CHROMA:
-                    raise RuntimeError("%s: %s: only 8-bit 4:2:0 is supported (%s)" % (path, tok, ", ".join(Y4M_CHROMA)))
-                elif k == "X" and tok.upper().startswith("XCOLORRANGE=") and tok.upper() != "XCOLORRANGE=LIMITED":
-                    raise RuntimeError("%s: %s: only limited range is supported (XCOLORRANGE=LIMITED)" % (path, tok))
+                elif k == "C":
+                    if tok not in Y4M_TAGS:
+                        raise RuntimeError("%s: %s: not a layout this reader has (%s)" % (path, tok, ", ".join(Y4M_TAGS)))
+                    layout, ctag = Y4M_TAGS[tok], tok
+                elif k == "X" and tok.upper().startswith("XCOLORRANGE="):
+                    if tok.upper() not in ("XCOLORRANGE=LIMITED", "XCOLORRANGE=FULL"):
+                        raise RuntimeError("%s: %s: XCOLORRANGE is LIMITED or FULL" % (path, tok))
+                    full, xtag = tok.upper() == "XCOLORRANGE=FULL", tok
         except (ValueError, ZeroDivisionError) as e:
             raise RuntimeError("%s: malformed YUV4MPEG2 header %r" % (path, head[:end])) from e
         if self.width < 1 or self.height < 1:
             raise RuntimeError("%s: the YUV4MPEG2 header carries no W / H" % path)
-        self.frame_bytes = fb = i420_bytes(self.height, self.width)
+        if full and ctag is None:
+            # XCOLORRANGE is ffmpeg's extension, and ffmpeg always writes the `C` tag next to it: a header that names no layout is the plain
+            # 8-bit 4:2:0 stream of the format's first writers, which this reader has always taken as limited range and refused otherwise
+            raise RuntimeError("%s: %s without a `C` tag: a header that names no layout is read as 8-bit 4:2:0, limited range only; full range is "
+                               "read from a clip whose header names its layout (%s)" % (path, xtag, ", ".join(Y4M_TAGS)))
+        self.format = Format(layout[0], layout[1], full, matrix)
+        self.frame_bytes = fb = yuv_bytes(self.format, self.height, self.width)
         first = end + 1
+        try:
+            self._index(first, size, fb)
+        except RuntimeError as e:
+            # the commonest cause of frames that do not fit their `C` tag: a tool relabelled the header and left 8-bit 4:2:0 planes behind it
+            plain = i420_bytes(self.height, self.width)
+            n, rest = divmod(size - first, 6 + plain)
+            if fb != plain and n and rest == 0 and all(os.pread(self._fd, 6, first + i * (6 + plain)) == b"FRAME\n" for i in range(n)):
+                raise RuntimeError("%s: %s: the header says frames of %d bytes, the file holds %d frames of %d bytes each - the size of 8-bit 4:2:0 "
+                                   "frames (%s)" % (path, ctag, fb, n, plain, e)) from e
+            raise
+
+    def _index(self, first, size, fb):
+        path = self.path
         # every frame line the bare `FRAME\n`: frame i is found by arithmetic (each supposed line is looked at once); otherwise one scan
         n, rest = divmod(size - first, 6 + fb)
         if rest == 0 and all(os.pread(self._fd, 6, first + i * (6 + fb)) == b"FRAME\n" for i in range(n)):
@@ -165,8 +209,9 @@ class Y4MFile:
 class FrameReader:
     """len() / [i] -> uint8 HxWx3 RGB; fps.  decord for .mp4 (reference), numpy memmap for .npy, Y4MFile for .y4m.
     .rate is what a VideoWriter of the band's output takes: the exact Fraction of a .y4m source, else fps.
-    .i420: the source holds I420 frames (.y4m) - then .width / .height are known without a decode, read_i420(i, out) copies frame i's
-    planes into the caller's buffer of i420_bytes(height, width) bytes, and [i] converts them on the host (common/yuv.py)."""
+    .i420: the source holds planar YUV frames (.y4m) - then .width / .height are known without a decode, .format is their layout (common/yuv.py
+    Format; I420 for the usual clip) and .frame_bytes their size, read_i420(i, out) copies frame i's planes as they are into the caller's
+    buffer of frame_bytes bytes, and [i] converts them on the host (common/yuv.py), whatever the layout."""
 
     def __init__(self, path):
         self.fps = 24.0
@@ -174,10 +219,11 @@ class FrameReader:
         if is_y4m(path):
             self._y4m = Y4MFile(path)
             self.i420, self.width, self.height = True, self._y4m.width, self._y4m.height
+            self.format, self.frame_bytes = self._y4m.format, self._y4m.frame_bytes
             self.fps = self._y4m.rate.numerator / self._y4m.rate.denominator
             self.read_i420 = self._y4m.read_i420
             self._n = len(self._y4m)
-            self._get = lambda i: i420_to_rgb(self._y4m.read_i420(i, np.empty(self._y4m.frame_bytes, np.uint8)), self.height, self.width)
+            self._get = lambda i: yuv_to_rgb(self.format, self._y4m.read_i420(i, np.empty(self.frame_bytes, np.uint8)), self.height, self.width)
         elif path.endswith(".npy"):
             self._a = np.load(path, mmap_mode="r")
             assert self._a.ndim == 4 and self._a.shape[-1] == 3 and self._a.dtype == np.uint8

@@ -9,8 +9,9 @@ ring of page-locked slots, the main thread submits chunk k + 1 before it waits f
 in flight: one's copies run under the other's kernels), and the results land in a second ring whose slots the sink thread gives back when
 the chunk has been written.  Both forms hand the same bytes to `write_chunk` and `dump`.
 
-A source of I420 frames (a .y4m: FrameReader.i420) is read without a conversion: `i420=True` makes a frame its packed planes - read_i420
-straight into the stacked array or the ring slot - for an engine whose frame_format is "i420"."""
+A source of planar YUV frames (a .y4m: FrameReader.i420) is read without a conversion: `i420=True` makes a frame its packed planes, in whatever
+layout the clip has (FrameReader.format, .frame_bytes) - read_i420 straight into the stacked array or the ring slot - for an engine whose
+frame_format is that layout (frame_formats)."""
 import collections
 import os
 import queue
@@ -65,17 +66,19 @@ class Stream:
 
     def __init__(self, host, frame, results, submit, collect, wait=None, i420=False):
         self.host, self.frame, self.results, self.submit, self.collect = host, frame, dict(results), submit, collect
-        self.i420 = i420            # frame = ((i420_bytes,), uint8): the decode thread fills a slot's rows with src.read_i420
+        self.i420 = i420            # frame = ((src.frame_bytes,), uint8): the decode thread fills a slot's rows with src.read_i420
         self.wait = wait if wait is not None else host.wait
 
 
-def frame_formats(model, yin, yout, h, w):
-    """Tells a band's engine what the loop will hand it (`yin`: the source is a .y4m, its frames are I420 planes) and wants back (`yout`: the
-    output is a .y4m): engine.frame_format / rgb_format.  -> the extra keyword arguments of the engine's calls: the frame size, which I420
-    arrays do not carry.  With neither, nothing is touched and nothing is passed: the calls are what they were before .y4m."""
+def frame_formats(model, yin, yout, h, w, layout=None):
+    """Tells a band's engine what the loop will hand it (`yin`: the source is a .y4m, its frames are planes of `layout`, the reader's .format -
+    I420 without one) and wants back (`yout`: the output is a .y4m): engine.frame_format / rgb_format.  -> the extra keyword arguments of the
+    engine's calls: the frame size, which plane arrays do not carry.  With neither, nothing is touched and nothing is passed: the calls are what
+    they were before .y4m."""
     if not (yin or yout) and getattr(model, "frame_format", "rgb") == "rgb" and getattr(model, "rgb_format", "rgb") == "rgb":
         return {}
-    model.frame_format, model.rgb_format = "i420" if yin else "rgb", "i420" if yout else "rgb"
+    plain = layout is None or tuple(layout) == (420, 8, False, "bt601")
+    model.frame_format, model.rgb_format = ("i420" if plain else tuple(layout)) if yin else "rgb", "i420" if yout else "rgb"
     return {"size": (h, w)} if yin or yout else {}
 
 
@@ -85,9 +88,9 @@ def i420_bytes(h, w):
 
 def chunks(src, first, last, chunk, halo=0, i420=False):
     """(start, frames) for start in range(first, last, chunk): frames = src[start : min(last, start + chunk) + halo] as one array, read up to two
-    chunks ahead on one worker thread.  halo = 1 for pairs: chunk k's last frame is chunk k+1's first.  i420: [frames, i420_bytes] planes."""
+    chunks ahead on one worker thread.  halo = 1 for pairs: chunk k's last frame is chunk k+1's first.  i420: [frames, src.frame_bytes] planes."""
     def load_i420(s):
-        a = np.empty((min(last, s + chunk) + halo - s, i420_bytes(src.height, src.width)), np.uint8)
+        a = np.empty((min(last, s + chunk) + halo - s, getattr(src, "frame_bytes", None) or i420_bytes(src.height, src.width)), np.uint8)
         for j in range(len(a)):
             src.read_i420(s + j, a[j])
         return a

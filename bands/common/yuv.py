@@ -3,7 +3,12 @@ FrameReader's `[i]`, a VideoWriter's `write(rgb)`, the flow bands' mask videos. 
 (against swscale PARITY UNPINNED, an LSB or two); tests/yuv_ref.py pins it.
 
 A frame is H W bytes of Y, then ceil(H / 2) ceil(W / 2) bytes of Cb, then as many of Cr.  A chroma sample is computed from the rounded
-mean of its 2 x 2 block (indices clamped to the frame) and read back by the block's four pixels (nearest)."""
+mean of its 2 x 2 block (indices clamped to the frame) and read back by the block's four pixels (nearest).
+
+Clips come in other layouts too - 4:2:2, 4:4:4, mono, 9 - 16 bit, full range, BT.709: yuv_to_rgb at the end of this file decodes any of them
+(prisma_amd/csrc/yuv_formats.hip on the host).  What is written stays I420."""
+import collections
+
 import numpy as np
 
 
@@ -39,4 +44,65 @@ def i420_to_rgb(yuv, h, w):
     rgb[..., 0] = np.clip((c + 409 * e) >> 8, 0, 255)
     rgb[..., 1] = np.clip((c - 100 * d - 208 * e) >> 8, 0, 255)
     rgb[..., 2] = np.clip((c + 516 * d) >> 8, 0, 255)
+    return rgb
+
+
+# ---- every planar layout a .y4m can have, to RGB (the way in only) ----------------------------------------------------------------------------
+# prisma_amd/csrc/yuv_formats.hip in numpy (include/prisma_bands.h pb_yuv_fmt has the rule; tests/yuv_fmt_ref.py pins both): chroma 400 / 420 /
+# 422 / 444, depth 8 .. 16 (a byte per sample at 8, else a 16-bit little-endian word, read whole), limited or full range, "bt601" or "bt709".
+# A format is any 4-tuple (chroma, depth, full_range, matrix) - the engine's YuvFormat is one; this module needs no engine.
+Format = collections.namedtuple("Format", "chroma depth full_range matrix")
+I420 = Format(420, 8, False, "bt601")
+_SHIFTS = {400: None, 420: (1, 1), 422: (1, 0), 444: (0, 0)}      # (sx, sy) of the chroma planes
+_MATRICES = {"bt601": (299, 114, 1000), "bt709": (2126, 722, 10000)}      # Kr, Kb as numerator, numerator, denominator
+
+
+def _plane_shapes(fmt, h, w):
+    """((ch, cw) of a chroma plane or None, bytes per sample)"""
+    chroma, depth = int(fmt[0]), int(fmt[1])
+    if chroma not in _SHIFTS or not 8 <= depth <= 16 or fmt[3] not in _MATRICES:
+        raise ValueError("no such YUV format: %r" % (tuple(fmt),))
+    s = _SHIFTS[chroma]
+    return (None if s is None else (-(-h >> s[1]), -(-w >> s[0]))), 1 if depth == 8 else 2
+
+
+def yuv_bytes(fmt, h, w):
+    c, bps = _plane_shapes(fmt, h, w)
+    return (h * w + (0 if c is None else 2 * c[0] * c[1])) * bps
+
+
+def yuv_coeffs(fmt):
+    """(cy, crv, cgu, cgv, cbu, yoff, coff): exact rationals rounded half up, floor((2 p + q) / (2 q)), in Python's integers"""
+    _plane_shapes(fmt, 1, 1)
+    d, full = int(fmt[1]), bool(fmt[2])
+    kr, kb, den = _MATRICES[fmt[3]]
+    kg = den - kr - kb
+    top = (1 << d) - 1
+    yn, yd, cd = (255 << d, top, top) if full else (255 * 256, 219, 224)      # 2^d sy = yn / yd, 2^d sc = yn / cd
+    rhu = lambda p, q: (2 * p + q) // (2 * q)      # noqa: E731
+    return (rhu(yn, yd), rhu(yn * 2 * (den - kr), cd * den), rhu(yn * 2 * kb * (den - kb), cd * den * kg),
+            rhu(yn * 2 * kr * (den - kr), cd * den * kg), rhu(yn * 2 * (den - kb), cd * den), 0 if full else 16 << (d - 8), 1 << (d - 1))
+
+
+def yuv_to_rgb(fmt, yuv, h, w):
+    """uint8 [yuv_bytes(fmt, H, W)] -> uint8 [H, W, 3]"""
+    c, bps = _plane_shapes(fmt, h, w)
+    cy, crv, cgu, cgv, cbu, yoff, coff = yuv_coeffs(fmt)
+    d = int(fmt[1])
+    yuv = np.ascontiguousarray(yuv, np.uint8).reshape(-1)
+    if yuv.size != yuv_bytes(fmt, h, w):
+        raise ValueError("a %d x %d frame of %r is %d bytes, not %d" % (h, w, tuple(fmt), yuv_bytes(fmt, h, w), yuv.size))
+    v = (yuv if bps == 1 else yuv.view("<u2")).astype(np.int32)
+    lum = cy * (v[:h * w].reshape(h, w) - yoff) + (1 << (d - 1))
+    if c is None:
+        dd = ee = np.zeros((h, w), np.int32)
+    else:
+        sx, sy = _SHIFTS[int(fmt[0])]
+        n = c[0] * c[1]
+        up = lambda p: np.repeat(np.repeat(p.reshape(c) - coff, 1 << sy, axis=0), 1 << sx, axis=1)[:h, :w]      # noqa: E731 - nearest
+        dd, ee = up(v[h * w:h * w + n]), up(v[h * w + n:])
+    rgb = np.empty((h, w, 3), np.uint8)
+    rgb[..., 0] = np.clip((lum + crv * ee) >> d, 0, 255)
+    rgb[..., 1] = np.clip((lum - cgu * dd - cgv * ee) >> d, 0, 255)
+    rgb[..., 2] = np.clip((lum + cbu * dd) >> d, 0, 255)
     return rgb

@@ -149,8 +149,8 @@ def process_video(a):
         init_model(device=rk.device)
     first, last = rk.frames(n)
     want_depth = bool(a.npy or a.subpath)
-    fmt = frame_formats(model, yin, yout, h, w)
-    frame = ((i420_bytes(h, w),), np.uint8) if yin else (src[0].shape, np.uint8)
+    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None))
+    frame = ((src.frame_bytes,), np.uint8) if yin else (src[0].shape, np.uint8)       # a .y4m's planes, in the clip's own layout
 
     def step(_s, frames):
         depth, rgb, mn, mx = model.infer_batch(frames, want_depth=want_depth, want_rgb=True, flip=_flip(), **fmt)

@@ -96,8 +96,8 @@ def process_video(args):
     # a .y4m on either side: its I420 frames go to / come from the engine as they are - but the COLMAP dump needs the id images' red channel, so
     # with --subpath they come back as RGB and the video's frames are converted on the host
     yin, yout = src.i420, is_y4m(args.output) and not args.subpath
-    fmt = frame_formats(model, yin, yout, h, w)
-    frame = ((i420_bytes(h, w),), np.uint8) if yin else (src[0].shape, np.uint8)
+    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None))
+    frame = ((src.frame_bytes,), np.uint8) if yin else (src[0].shape, np.uint8)       # a .y4m's planes, in the clip's own layout
 
     def step(_s, frames):            # the SDF, if asked for, is already in G: set_sdf
         masks = model.infer_batch(frames, args.confidence, keep_ids(), **fmt)

@@ -108,7 +108,7 @@ int pb_version(void);
 /* ABI guard: bumped whenever a public struct's layout or an entry point's signature changes.  A binding compares
  * pb_abi_version() with the PB_ABI_VERSION it was written against and pb_struct_size(which) with its own sizeof before the first
  * call (prisma_amd/_lib.py load(); integration/depth_anything_stub.py) - a stale binding fails at load, not by reading shifted
- * fields.  which: 0 pb_tensor, 1 pb_depth_cfg, 2 pb_flow_cfg, 3 pb_mask_cfg, 4 pb_kernel_stat, 5 pb_comm_id; -1 for others. */
+ * fields.  which: 0 pb_tensor, 1 pb_depth_cfg, 2 pb_flow_cfg, 3 pb_mask_cfg, 4 pb_kernel_stat, 5 pb_comm_id, 6 pb_yuv_fmt; -1 for others. */
 #define PB_ABI_VERSION 3
 int pb_abi_version(void);
 int pb_struct_size(int which);
@@ -255,6 +255,46 @@ int pb_i420_to_rgb(pb_ctx *ctx, const uint8_t *yuv, int n, int H, int W, uint8_t
 int pb_i420_to_rgb_dev(pb_ctx *ctx, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out);
 int pb_rgb_to_i420(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
 int pb_rgb_to_i420_dev(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
+
+/* Every planar layout a `.y4m` clip can have, to RGB (the way in only: what the bands write stays 8 bit, 4:2:0, limited range, BT.601; chroma
+ * siting is not acted on; the matrix is the caller's to name - it is not guessed from the frame size).  One rule, exact integers:
+ *   chroma      400 (mono: no chroma planes), 420, 422 or 444;  (sx, sy) = (1, 1) for 420, (1, 0) for 422, (0, 0) for 444
+ *   depth d     8 .. 16: one byte per sample at d = 8, else a 16-bit little-endian word, read whole and not masked
+ *   full_range  0: limited (yoff = 16 << (d - 8)), 1: full (yoff = 0);  coff = half = 1 << (d - 1)
+ *   matrix      PB_YUV_BT601: Kr = 299 / 1000, Kb = 114 / 1000;  PB_YUV_BT709: Kr = 2126 / 10000, Kb = 722 / 10000;  Kg = 1 - Kr - Kb
+ * A frame is H x W samples of Y, then ceil(H / 2^sy) x ceil(W / 2^sx) of Cb, then as many of Cr; frames are packed.  Per pixel (x, y), with the
+ * chroma samples plane[y >> sy][x >> sx] (nearest) and D = E = 0 for 400:
+ *   C = Y - yoff, D = Cb - coff, E = Cr - coff
+ *   R = clip8((cy C + crv E + half) >> d)     G = clip8((cy C - cgu D - cgv E + half) >> d)     B = clip8((cy C + cbu D + half) >> d)
+ * `>>` an arithmetic shift on int32 (every intermediate is inside int32; below 2^27 for samples within d bits), clip8 a clamp to 0 .. 255.  The coefficients are exact rationals rounded
+ * half up, rhu(p / q) = floor((2 p + q) / (2 q)), no floating point anywhere:
+ *   limited: sy = 255 / (219 2^(d - 8)), sc = 255 / (224 2^(d - 8));   full: sy = sc = 255 / (2^d - 1)
+ *   cy = rhu(2^d sy)   crv = rhu(2^d sc 2 (1 - Kr))   cgu = rhu(2^d sc 2 Kb (1 - Kb) / Kg)   cgv = rhu(2^d sc 2 Kr (1 - Kr) / Kg)   cbu = rhu(2^d sc 2 (1 - Kb))
+ * - (298, 409, 100, 208, 516) for BT.601 limited at every d, so {420, 8, 0, PB_YUV_BT601} is pb_i420_to_rgb byte for byte (and runs its kernel);
+ * (298, 459, 55, 136, 541) for BT.709 limited.  For samples within d bits the result is within 1.5 of the real-valued conversion: 0.5 for the final floor, and
+ * 0.5 (|C| + |D| + |E|) / 2^d <= 1 for the rounding of the coefficients.
+ * pb_yuv_bytes: bytes of one frame, 0 for a format outside the above or a size that is not positive; pb_yuv_coeffs: out = cy, crv, cgu, cgv, cbu,
+ * yoff, coff.  Neither needs a GPU.  pb_yuv_to_rgb: host pointers, blocking, in chunks of "host_chunk" frames (default 8) as pb_i420_to_rgb;
+ * pb_yuv_to_rgb_dev: device pointers, asynchronous on the ctx stream, pb_sync() waits.  No alignment is needed (with W % 16 == 0 and 16-byte
+ * aligned device pointers a lane moves 16 bytes per access).  Work on any ctx.
+ *   yuv : n x pb_yuv_bytes(fmt, H, W) bytes      rgb : n x H x W x 3 uint8
+ * Inside the bands: pb_set_frame_format(ctx, fmt) makes the host-pointer and submit entry points of the ctx (those "frames_i420" names above) take
+ * `frames` as n (F) x pb_yuv_bytes(fmt, H, W) bytes, converted on the ctx stream into the RGB buffer the band reads; page-locked caller buffers
+ * stay directly addressed.  fmt = NULL: RGB again.  pb_set_option(ctx, "frames_i420", 1) is pb_set_frame_format with {420, 8, 0, PB_YUV_BT601},
+ * 0 is NULL.  Refused while a submission is outstanding, and for a format outside the above - the ctx is then left as it was.  The *_dev band
+ * entry points keep RGB. */
+enum { PB_YUV_BT601 = 0, PB_YUV_BT709 = 1 };
+typedef struct {
+    int32_t chroma;           /* 400 / 420 / 422 / 444 */
+    int32_t depth;            /* 8 .. 16 bits per sample */
+    int32_t full_range;       /* 0 limited, 1 full */
+    int32_t matrix;           /* PB_YUV_BT601 / PB_YUV_BT709 */
+} pb_yuv_fmt;
+int64_t pb_yuv_bytes(const pb_yuv_fmt *fmt, int H, int W);
+int pb_yuv_coeffs(const pb_yuv_fmt *fmt, int32_t out[7]);
+int pb_yuv_to_rgb(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out);
+int pb_yuv_to_rgb_dev(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out);
+int pb_set_frame_format(pb_ctx *ctx, const pb_yuv_fmt *fmt);
 
 /* Bilinear resize of RGB frames, 8 bit, exact integers, half-pixel centres (the geometry of swscale's SWS_BILINEAR, which the reference's
  * VideoWriter applies to every frame that is not of the video's size).  Per axis, for output index x of n_out from n_in samples:

@@ -5,6 +5,7 @@ missing or was built without its kernels this module raises at import of the sym
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -51,6 +52,25 @@ class pb_kernel_stat(C.Structure):
                 ("launches", C.c_int32)]
 
 
+class pb_yuv_fmt(C.Structure):
+    _fields_ = [("chroma", C.c_int32), ("depth", C.c_int32), ("full_range", C.c_int32), ("matrix", C.c_int32)]
+
+
+YUV_MATRICES = ("bt601", "bt709")       # pb_yuv_fmt.matrix: PB_YUV_BT601, PB_YUV_BT709
+
+
+class YuvFormat(collections.namedtuple("YuvFormat", "chroma depth full_range matrix")):
+    """A planar YUV layout (include/prisma_bands.h pb_yuv_fmt): chroma 400 / 420 / 422 / 444, depth 8 .. 16, full_range, matrix "bt601" / "bt709"."""
+    __slots__ = ()
+
+    def c(self) -> pb_yuv_fmt:
+        m = YUV_MATRICES.index(self.matrix) if self.matrix in YUV_MATRICES else -1       # a name the library does not know: it refuses -1
+        return pb_yuv_fmt(int(self.chroma), int(self.depth), int(bool(self.full_range)), m)
+
+
+I420 = YuvFormat(420, 8, False, "bt601")       # what "frames_i420" means
+
+
 # every symbol include/prisma_bands.h declares: (restype, argtypes)
 _P = C.c_void_p
 _F = C.POINTER(C.c_float)
@@ -87,6 +107,11 @@ SYMBOLS = {
     "pb_i420_to_rgb_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_rgb_to_i420": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_rgb_to_i420_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_yuv_bytes": (C.c_int64, [C.POINTER(pb_yuv_fmt), C.c_int, C.c_int]),
+    "pb_yuv_coeffs": (C.c_int, [C.POINTER(pb_yuv_fmt), C.POINTER(C.c_int32)]),
+    "pb_yuv_to_rgb": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_yuv_to_rgb_dev": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_set_frame_format": (C.c_int, [_P, C.POINTER(pb_yuv_fmt)]),
     "pb_rgb_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "pb_rgb_resize_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "pb_depth_net_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -228,7 +253,7 @@ def load():
     if lib.pb_abi_version() != ABI_VERSION:
         raise PrismaBandsError(f"{LIB_PATH}: ABI version {lib.pb_abi_version()}, this binding expects {ABI_VERSION} - rebuild the library "
                                "(make -C prisma_amd/csrc) or update prisma_amd/_lib.py")
-    for which, st in enumerate((pb_tensor, pb_depth_cfg, pb_flow_cfg, pb_mask_cfg, pb_kernel_stat)):
+    for which, st in ((0, pb_tensor), (1, pb_depth_cfg), (2, pb_flow_cfg), (3, pb_mask_cfg), (4, pb_kernel_stat), (6, pb_yuv_fmt)):
         if lib.pb_struct_size(which) != C.sizeof(st):
             raise PrismaBandsError(f"{LIB_PATH}: sizeof({st.__name__}) is {lib.pb_struct_size(which)} in the library, {C.sizeof(st)} in the binding")
     _lib = lib

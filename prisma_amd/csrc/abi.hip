@@ -164,6 +164,7 @@ int pb_struct_size(int which) {
         case 3: return (int)sizeof(pb_mask_cfg);
         case 4: return (int)sizeof(pb_kernel_stat);
         case 5: return (int)sizeof(pb_comm_id);
+        case 6: return (int)sizeof(pb_yuv_fmt);
         default: return -1;
     }
 }
@@ -374,7 +375,7 @@ static int depth_host_pipeline(pb_ctx *c, const uint8_t *frames, int n, int H, i
     const int cap = std::min(n, c->host_chunk > 0 ? std::min(c->host_chunk, mb) : mb);
     // "frames_i420" / "rgb_out_i420": the lane carries I420 frames, converted on the ctx stream into / out of the RGB buffer the band works on
     const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out;
-    const size_t fin = yin ? (size_t)i420_frame_bytes(H, W) : px * 3, fout = yout ? (size_t)i420_frame_bytes(H, W) : px * 3;
+    const size_t fin = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : px * 3, fout = yout ? (size_t)i420_frame_bytes(H, W) : px * 3;
     const bool pin_in = pb_is_pinned(frames, (size_t)n * fin), pin_d = pb_is_pinned(depth_out, (size_t)n * px * 4),
                pin_r = pb_is_pinned(rgb_out, (size_t)n * fout);
     const bool pin_mm = (!min_out || pb_is_pinned(min_out, (size_t)n * 4)) && (!max_out || pb_is_pinned(max_out, (size_t)n * 4));
@@ -392,7 +393,7 @@ static int depth_host_pipeline(pb_ctx *c, const uint8_t *frames, int n, int H, i
         float *mn = (float *)l[3].d[slot];
         const uint8_t *in = (const uint8_t *)l[0].d[slot];
         if (yin) {
-            PB_TRY(launch_i420_to_rgb(c->stream, in, m, H, W, (uint8_t *)c->yuv[0]));
+            PB_TRY(launch_yuv_to_rgb(c->stream, c->frame_fmt, in, m, H, W, (uint8_t *)c->yuv[0]));
             in = (const uint8_t *)c->yuv[0];
         }
         uint8_t *enc = (uint8_t *)(rgb_out ? (yout ? c->yuv[1] : l[2].d[slot]) : nullptr);
@@ -483,7 +484,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     // "rgb_out_full": ... of the clip's H x W, resized on the ctx stream from the sh x sw frames the band encodes (nothing to do at scale 1)
     const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out, full = c->rgb_out_full != 0 && rgb_out && (sh != H || sw != W);
     const int rh = full ? H : sh, rw = full ? W : sw;                  // the size of an rgb_out frame
-    const size_t fpx = yin ? (size_t)i420_frame_bytes(H, W) : (size_t)H * W * 3,
+    const size_t fpx = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : (size_t)H * W * 3,
                  rpx = (yout ? (size_t)i420_frame_bytes(rh, rw) : (size_t)rh * rw * 3) * dirs;
     const bool pin_in = pb_is_pinned(frames, (size_t)F * fpx), pin_f = pb_is_pinned(flow_out, np * px * 8), pin_r = pb_is_pinned(rgb_out, np * rpx),
                pin_k = pb_is_pinned(mask_out, np * px), pin_m = !maxdisp_out || pb_is_pinned(maxdisp_out, np * dirs * 4);
@@ -501,7 +502,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     return run_chunks(c, pairs, cp, 1, lanes, 5, submit, [&](int slot, int, int m) {
         const uint8_t *in = (const uint8_t *)l[0].d[slot];
         if (yin) {
-            PB_TRY(launch_i420_to_rgb(c->stream, in, m + 1, H, W, (uint8_t *)c->yuv[0]));
+            PB_TRY(launch_yuv_to_rgb(c->stream, c->frame_fmt, in, m + 1, H, W, (uint8_t *)c->yuv[0]));
             in = (const uint8_t *)c->yuv[0];
         }
         uint8_t *enc = (uint8_t *)(rgb_out ? (yout || full ? c->yuv[1] : l[2].d[slot]) : nullptr);
@@ -588,10 +589,10 @@ int pb_mask_infer_batch(pb_ctx *c, const uint8_t *frames, int n, int H, int W, f
     // "frames_i420" / "rgb_out_i420": the copies move I420 frames (fi / fo bytes each) into / out of whole-batch I420 buffers (ctx yuv[0] / yuv[1]);
     // the chunk's frames are converted into d_in once its copy has arrived, its id images out of d_out before they leave - both on the ctx stream
     const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0;
-    const size_t fi = yin ? (size_t)i420_frame_bytes(H, W) : fb, fo = yout ? (size_t)i420_frame_bytes(H, W) : fb;
+    const size_t fi = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : fb, fo = yout ? (size_t)i420_frame_bytes(H, W) : fb;
     const bool pin_in = pb_is_pinned(frames, n * fi), pin_out = pb_is_pinned(mask_out, n * fo);
     MaskPipe &mp = c->mpipe;
-    PB_TRY(mp.ensure(bytes, !pin_in, !pin_out, chunks));
+    PB_TRY(mp.ensure(bytes, n * fi, !pin_in, !pin_out, chunks));        // h_in by the frames' own size: up to 6 bytes per pixel, not RGB's 3
     if (yin) PB_TRY(c->yuv_grow(0, n * fi));
     if (yout) PB_TRY(c->yuv_grow(1, n * fo));
     PipeDrain drain{mp.s_in, c->stream, mp.s_out};              // no exit, error or not, leaves a copy into caller memory in flight
@@ -605,9 +606,10 @@ int pb_mask_infer_batch(pb_ctx *c, const uint8_t *frames, int n, int H, int W, f
     }
     hipStream_t st = c->stream;
     char *dst = pin_out ? (char *)mask_out : (char *)mp.h_out;
-    c->mask->chunk_begin = [&mp, st, cf, yin, up, fi, fb, H, W](int first, int m) -> int {
+    const pb_yuv_fmt ffmt = c->frame_fmt;
+    c->mask->chunk_begin = [&mp, st, cf, yin, up, fi, fb, H, W, ffmt](int first, int m) -> int {
         PB_HIP(hipStreamWaitEvent(st, mp.ev_in[first / cf], 0));
-        if (yin) PB_TRY(launch_i420_to_rgb(st, (const uint8_t *)up + (size_t)first * fi, m, H, W, (uint8_t *)mp.d_in + (size_t)first * fb));
+        if (yin) PB_TRY(launch_yuv_to_rgb(st, ffmt, (const uint8_t *)up + (size_t)first * fi, m, H, W, (uint8_t *)mp.d_in + (size_t)first * fb));
         return 0;
     };
     c->mask->chunk_end = [&mp, st, cf, fb, fo, dst, yout, down, H, W](int first, int m) -> int {
@@ -722,6 +724,7 @@ int pb_set_option(pb_ctx *c, const char *key, int value) {
         PB_CHECK(value == 0 || value == 1, PB_ERR_ARG, "option '%s' is 0 or 1, not %d", key, value);
         PB_CHECK(c->pending.empty(), PB_ERR_STATE, "option '%s': a submission of this ctx is still outstanding (pb_wait first)", key);
         (key[0] == 'f' ? c->frames_i420 : key[8] == 'i' ? c->rgb_out_i420 : c->rgb_out_full) = value;
+        if (key[0] == 'f') c->frame_fmt = pb_yuv_fmt{420, 8, 0, PB_YUV_BT601};      // pb_set_frame_format's special case
     }
     else if (!strcmp(key, "corr_layout")) {        // corr_layout.h: 1 = source-blocked volume (default), 0 = row-major; the next flow_raft call re-plans
         PB_CHECK(value == 0 || value == 1, PB_ERR_ARG, "option '%s' is 0 or 1, not %d", key, value);
@@ -944,6 +947,52 @@ static int yuv_host_pipeline(pb_ctx *c, const uint8_t *in, int n, int H, int W, 
 
 int pb_i420_to_rgb(pb_ctx *c, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out) { return yuv_host_pipeline(c, yuv, n, H, W, rgb_out, true); }
 int pb_rgb_to_i420(pb_ctx *c, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out) { return yuv_host_pipeline(c, rgb, n, H, W, yuv_out, false); }
+
+// ---- any .y4m layout -> RGB (yuv_formats.hip): on its own, and as the frame format of a band ctx ------------------------------------------------
+int64_t pb_yuv_bytes(const pb_yuv_fmt *fmt, int H, int W) { return fmt ? yuv_frame_bytes(*fmt, H, W) : 0; }
+
+int pb_yuv_coeffs(const pb_yuv_fmt *fmt, int32_t out[7]) {
+    PB_CHECK(fmt && out, PB_ERR_ARG, "yuv_coeffs: bad arguments");
+    PB_CHECK(yuv_fmt_ok(*fmt), PB_ERR_ARG, "yuv_coeffs: no such format (chroma %d, depth %d, full_range %d, matrix %d)", fmt->chroma, fmt->depth,
+             fmt->full_range, fmt->matrix);
+    yuv_coeffs(*fmt, out);
+    return 0;
+}
+
+int pb_yuv_to_rgb_dev(pb_ctx *c, const pb_yuv_fmt *fmt, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out) {
+    PB_CHECK(c && fmt && yuv && rgb_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "yuv_to_rgb: bad arguments");
+    PB_CHECK(yuv_fmt_ok(*fmt), PB_ERR_ARG, "yuv_to_rgb: no such format (chroma %d, depth %d, full_range %d, matrix %d)", fmt->chroma, fmt->depth,
+             fmt->full_range, fmt->matrix);
+    PB_HIP(hipSetDevice(c->device));
+    return launch_yuv_to_rgb(c->stream, *fmt, yuv, n, H, W, rgb_out);
+}
+
+// Host-pointer variant: run_chunks over chunks of "host_chunk" (default 8) frames, as pb_i420_to_rgb.
+int pb_yuv_to_rgb(pb_ctx *c, const pb_yuv_fmt *fmt, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out) {
+    PB_CHECK(c && fmt && yuv && rgb_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "yuv_to_rgb: bad arguments");
+    PB_CHECK(yuv_fmt_ok(*fmt), PB_ERR_ARG, "yuv_to_rgb: no such format (chroma %d, depth %d, full_range %d, matrix %d)", fmt->chroma, fmt->depth,
+             fmt->full_range, fmt->matrix);
+    PB_CHECK(c->pending.empty(), PB_ERR_STATE, "yuv_to_rgb: a submission of this ctx is still outstanding (pb_wait first)");
+    PB_HIP(hipSetDevice(c->device));
+    const pb_yuv_fmt f = *fmt;
+    const size_t fi = (size_t)yuv_frame_bytes(f, H, W), fo = (size_t)H * W * 3;
+    const int cap = std::min(n, c->host_chunk > 0 ? c->host_chunk : 8);
+    const ChunkLane lanes[2] = {{(void *)yuv, fi, false, pb_is_pinned(yuv, n * fi)}, {rgb_out, fo, true, pb_is_pinned(rgb_out, n * fo)}};
+    const ChunkPipe::Lane *l = c->pipe.lane;
+    return run_chunks(c, n, cap, 0, lanes, 2, false, [&](int slot, int, int m) {
+        return launch_yuv_to_rgb(c->stream, f, (const uint8_t *)l[0].d[slot], m, H, W, (uint8_t *)l[1].d[slot]);
+    });
+}
+
+int pb_set_frame_format(pb_ctx *c, const pb_yuv_fmt *fmt) {
+    PB_CHECK(c, PB_ERR_ARG, "set_frame_format: null ctx");
+    PB_CHECK(!fmt || yuv_fmt_ok(*fmt), PB_ERR_ARG, "set_frame_format: no such format (chroma %d, depth %d, full_range %d, matrix %d)", fmt->chroma,
+             fmt->depth, fmt->full_range, fmt->matrix);
+    PB_CHECK(c->pending.empty(), PB_ERR_STATE, "set_frame_format: a submission of this ctx is still outstanding (pb_wait first)");
+    c->frames_i420 = fmt != nullptr;
+    if (fmt) c->frame_fmt = *fmt;
+    return 0;
+}
 
 // ---- bilinear RGB resize on its own (resize.hip): what "rgb_out_full" runs behind the flow bands, for callers that hold frames, and the tests ----
 int pb_rgb_resize_dev(pb_ctx *c, const uint8_t *rgb, int n, int sh, int sw, int H, int W, uint8_t *out, int out_i420) {

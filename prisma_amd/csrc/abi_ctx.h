@@ -76,7 +76,8 @@ struct MaskPipe {
     void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
     size_t cap_d = 0, cap_hi = 0, cap_ho = 0;
     std::vector<hipEvent_t> ev_in, ev_done;
-    int ensure(size_t bytes, bool host_in, bool host_out, int chunks) {
+    // bytes: the batch as RGB (d_in, d_out, h_out); in_bytes: the batch as the caller hands it over (h_in) - planar YUV frames may be larger than RGB
+    int ensure(size_t bytes, size_t in_bytes, bool host_in, bool host_out, int chunks) {
         if (!s_in) {
             PB_HIP(hipStreamCreateWithFlags(&s_in, hipStreamNonBlocking));
             PB_HIP(hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking));
@@ -89,11 +90,11 @@ struct MaskPipe {
             PB_HIP(hipMalloc(&d_out, bytes));
             cap_d = bytes;
         }
-        if (host_in && bytes > cap_hi) {
+        if (host_in && in_bytes > cap_hi) {
             if (h_in) PB_HIP(hipHostFree(h_in));
             h_in = nullptr; cap_hi = 0;
-            PB_HIP(hipHostMalloc(&h_in, bytes, hipHostMallocDefault));
-            cap_hi = bytes;
+            PB_HIP(hipHostMalloc(&h_in, in_bytes, hipHostMallocDefault));
+            cap_hi = in_bytes;
         }
         if (host_out && bytes > cap_ho) {
             if (h_out) PB_HIP(hipHostFree(h_out));
@@ -155,7 +156,9 @@ struct pb_ctx {
     // band reads - for the mask band the I420 frames instead, its pipeline keeps whole-batch RGB buffers of its own; yuv[1]: what it encodes).
     // Work on one stream runs in order, so chunks and submissions share them; they grow only while the stream is idle.
     // pb_set_option("rgb_out_full"): the flow bands' rgb_out holds frames of the clip's size, resized (resize.hip) out of yuv[1] as well.
+    // pb_set_frame_format: frames_i420 != 0 says the frames are planar YUV, frame_fmt which ("frames_i420" sets {420, 8, limited, BT.601}).
     int frames_i420 = 0, rgb_out_i420 = 0, rgb_out_full = 0;
+    pb_yuv_fmt frame_fmt = {420, 8, 0, PB_YUV_BT601};
     void *yuv[2] = {};
     size_t yuv_cap[2] = {};
     int yuv_grow(int k, size_t need) {

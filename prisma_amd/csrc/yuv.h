@@ -3,12 +3,22 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "prisma_bands.h"
+
 // bytes of one I420 frame: H W of Y + 2 ceil(H / 2) ceil(W / 2) of Cb and Cr (0 for a size that is not positive)
 int64_t i420_frame_bytes(int H, int W);
 // n packed I420 frames -> n packed [H, W, 3] RGB frames and back, on stream s.  No alignment is needed; with W % 16 == 0 and both pointers
 // 16-byte aligned the kernels move 16 bytes per access.
 int launch_i420_to_rgb(hipStream_t s, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb);
 int launch_rgb_to_i420(hipStream_t s, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv);
+
+// yuv_formats.hip: every planar layout of a .y4m to RGB - 4:0:0 / 4:2:0 / 4:2:2 / 4:4:4, 8 .. 16 bit, limited / full range, BT.601 / BT.709
+// (include/prisma_bands.h pb_yuv_fmt has every formula).  {420, 8, limited, BT.601} runs launch_i420_to_rgb.
+bool yuv_fmt_ok(const pb_yuv_fmt &f);
+bool yuv_fmt_is_i420(const pb_yuv_fmt &f);
+int64_t yuv_frame_bytes(const pb_yuv_fmt &f, int H, int W);       // 0 for a bad format or a size that is not positive
+void yuv_coeffs(const pb_yuv_fmt &f, int32_t out[7]);             // cy, crv, cgu, cgv, cbu, yoff, coff of a good format
+int launch_yuv_to_rgb(hipStream_t s, const pb_yuv_fmt &f, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb);
 
 // ---- what the kernels of yuv.hip and resize.hip share -------------------------------------------------------------------------------------------
 struct I420Frame {  // plane geometry of one I420 frame

@@ -11,7 +11,7 @@ from typing import Dict, List, Optional, Tuple
 import numpy as np
 
 from . import _lib
-from ._lib import check
+from ._lib import I420, YuvFormat, check
 from .synth import DEPTH_CFGS, MASK_CFGS, DepthCfg, MaskCfg
 
 
@@ -41,6 +41,19 @@ def net_size(H: int, W: int) -> Tuple[int, int]:
 def i420_bytes(H: int, W: int) -> int:
     """bytes of one I420 frame (a .y4m's): H W of Y, then ceil(H / 2) ceil(W / 2) each of Cb and Cr (pb_i420_bytes, needs no GPU)"""
     return int(_lib.load().pb_i420_bytes(int(H), int(W)))
+
+
+def yuv_bytes(fmt: YuvFormat, H: int, W: int) -> int:
+    """bytes of one planar YUV frame of layout `fmt` (a .y4m's; pb_yuv_bytes, needs no GPU): H W samples of Y, then for 4:2:0 / 4:2:2 / 4:4:4 the
+    subsampled Cb and Cr planes, a sample one byte at 8 bit and two above; 0 for a format the library does not have"""
+    return int(_lib.load().pb_yuv_bytes(C.byref(YuvFormat(*fmt).c()), int(H), int(W)))
+
+
+def yuv_coeffs(fmt: YuvFormat) -> Tuple[int, ...]:
+    """(cy, crv, cgu, cgv, cbu, yoff, coff) of the library's integer conversion of layout `fmt` (pb_yuv_coeffs, needs no GPU)"""
+    out = (C.c_int32 * 7)()
+    check(_lib.load().pb_yuv_coeffs(C.byref(YuvFormat(*fmt).c()), out))
+    return tuple(out)
 
 
 FORMATS = ("rgb", "i420")       # what `frames` / the encoded `rgb` results of a band context are: [..., H, W, 3] or [..., i420_bytes(H, W)] uint8
@@ -276,6 +289,26 @@ class _Ctx:
         check(self.lib.pb_rgb_to_i420(self.ctx, _ptr(rgb), rgb.size // (H * W * 3), H, W, _ptr(yuv)))
         return yuv
 
+    # any planar .y4m layout -> RGB (pb_yuv_to_rgb: exact integers, tests/yuv_fmt_ref.py restates them)
+    def yuv_to_rgb(self, fmt: YuvFormat, yuv: np.ndarray, H: int, W: int, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """frames of layout `fmt`, uint8 [n, yuv_bytes(fmt, H, W)] (or one frame [yuv_bytes]; a 16-bit sample is two bytes, little-endian) -> RGB
+        uint8 [n, H, W, 3] ([H, W, 3]); `out`: the caller's own (page-locked) array"""
+        fmt = YuvFormat(*fmt)
+        yuv = np.ascontiguousarray(yuv, np.uint8)
+        fb = yuv_bytes(fmt, H, W)
+        if fb <= 0:
+            raise ValueError("no such YUV format: %r" % (fmt,))
+        assert yuv.ndim in (1, 2) and yuv.shape[-1] == fb, (yuv.shape, fb)
+        shape = yuv.shape[:-1] + (H, W, 3)
+        rgb = np.empty(shape, np.uint8) if out is None else out
+        assert rgb.shape == shape and rgb.dtype == np.uint8 and rgb.flags.c_contiguous
+        check(self.lib.pb_yuv_to_rgb(self.ctx, C.byref(fmt.c()), _ptr(yuv), yuv.size // fb, H, W, _ptr(rgb)))
+        return rgb
+
+    def yuv_to_rgb_dev(self, fmt: YuvFormat, yuv_ptr: int, n: int, H: int, W: int, rgb_ptr: int):
+        """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_yuv_to_rgb_dev): sync() waits"""
+        check(self.lib.pb_yuv_to_rgb_dev(self.ctx, C.byref(YuvFormat(*fmt).c()), C.c_void_p(yuv_ptr), n, H, W, C.c_void_p(rgb_ptr)))
+
     def i420_to_rgb_dev(self, yuv_ptr: int, n: int, H: int, W: int, rgb_ptr: int):
         """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_i420_to_rgb_dev): sync() waits"""
         check(self.lib.pb_i420_to_rgb_dev(self.ctx, C.c_void_p(yuv_ptr), n, H, W, C.c_void_p(rgb_ptr)))
@@ -304,13 +337,19 @@ class _Ctx:
     # what the band's host-pointer and submit calls take as `frames` and give as their encoded `rgb` (the mask band: its id images):
     # "rgb" (the default) or "i420" - pb_set_option "frames_i420" / "rgb_out_i420".  With frame_format = "i420" those calls take
     # [n, i420_bytes(H, W)] arrays and need `size=(H, W)`; with rgb_format = "i420" their rgb arrays are [..., i420_bytes(h, w)] of the output size.
+    # frame_format also takes a YuvFormat (pb_set_frame_format): the calls then take [n, yuv_bytes(fmt, H, W)] arrays of that layout's planes.
     @property
-    def frame_format(self) -> str:
+    def frame_format(self):
         return self._formats[0]
 
     @frame_format.setter
-    def frame_format(self, fmt: str):
-        self._set_format(0, "frames_i420", fmt)
+    def frame_format(self, fmt):
+        if isinstance(fmt, str):
+            self._set_format(0, "frames_i420", fmt)
+            return
+        fmt = YuvFormat(*fmt)
+        check(self.lib.pb_set_frame_format(self.ctx, C.byref(fmt.c())))       # a refusal leaves the context and this attribute as they were
+        self._formats[0] = fmt
 
     @property
     def rgb_format(self) -> str:
@@ -339,10 +378,11 @@ class _Ctx:
 
     def _frames_in(self, frames: np.ndarray, size) -> Tuple[int, int, int]:
         """(n, H, W) of a call's `frames` in the context's frame_format, shape checked"""
-        if self.frame_format == "i420":
-            assert size is not None, "frame_format 'i420': the call needs size=(H, W)"
+        if self.frame_format != "rgb":
+            fmt = I420 if self.frame_format == "i420" else self.frame_format
+            assert size is not None, "frame_format %r: the call needs size=(H, W)" % (self.frame_format,)
             H, W = int(size[0]), int(size[1])
-            assert frames.ndim == 2 and frames.shape[1] == i420_bytes(H, W), (frames.shape, H, W)
+            assert frames.ndim == 2 and frames.dtype == np.uint8 and frames.shape[1] == yuv_bytes(fmt, H, W), (frames.shape, fmt, H, W)
             return frames.shape[0], H, W
         n, H, W, ch = frames.shape
         assert ch == 3 and (size is None or tuple(size) == (H, W))
