@@ -6,8 +6,9 @@ import numpy as np
 
 from prisma_amd import engine
 
-from .io import FrameReader, VideoWriter, is_y4m, write_flo, write_flow_png
-from .loop import Stream, frame_formats, i420_bytes, run_sharded, stream_enabled
+from .io import FrameReader, VideoWriter, is_y4m, write_flo, write_flow_png, y4m_out
+from .loop import Stream, frame_formats, run_sharded, stream_enabled
+from .yuv import yuv_bytes
 
 
 def _mask_rgb(mask):
@@ -39,12 +40,14 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
         files.update({"mask_" + d: (args.output_mask if d == "f" else mbase + "_bwd." + mext) for d in dirs})
     # rescale: a .y4m has the clip's w x h like the reference's videos (its VideoWriter rescales every frame, io.py:297), not the band's sw x sh;
     # a .npy stack has no declared size and keeps the band's, an .mp4 is rescaled by PyAV as ever
-    videos = {k: VideoWriter(width=w, height=h, frame_rate=src.rate, filename=f, rescale=True) for k, f in files.items()} if rk.main else {}
-    # a .y4m on either side: its I420 frames go to / come from the engine as they are - at --scale != 1 resized to the clip's size on the GPU, next
-    # to the I420 conversion (engine rgb_full).  The mask videos and the trailing zero frame are small and rare: they are converted, and
+    # the layout of every .y4m written: PRISMA_Y4M_OUT's (io.y4m_out), I420 when unset
+    ofmt = y4m_out(getattr(src, "format", None)) if any(is_y4m(f) for f in files.values()) else None
+    videos = {k: VideoWriter(width=w, height=h, frame_rate=src.rate, filename=f, rescale=True, fmt=ofmt) for k, f in files.items()} if rk.main else {}
+    # a .y4m on either side: its planes go to / come from the engine as they are - at --scale != 1 resized to the clip's size on the GPU, next
+    # to the conversion (engine rgb_full).  The mask videos and the trailing zero frame are small and rare: they are converted, and
     # resized, on the host (VideoWriter.write)
     yin, yout = src.i420, is_y4m(args.output)
-    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None))
+    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None), ofmt)
     model.rgb_full = yout and (sh, sw) != (h, w)
     rh, rw = (h, w) if model.rgb_full else (sh, sw)      # the size of the engine's rgb frames
     frame = ((src.frame_bytes,), np.uint8) if yin else (src[0].shape, np.uint8)       # a .y4m's planes, in the clip's own layout
@@ -63,7 +66,7 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
     # the streamed loop (common/loop.py): the same calls as submit_sequence(_masks) / wait on the loop's page-locked rings - one array per result
     # asked for, [directions, ...] per pair
     nd = 2 if both else 1
-    results = {"rgb": ((nd, i420_bytes(rh, rw)) if yout else (nd, sh, sw, 3), np.uint8), "mx": ((nd,), np.float32)}
+    results = {"rgb": ((nd, yuv_bytes(ofmt, rh, rw)) if yout else (nd, sh, sw, 3), np.uint8), "mx": ((nd,), np.float32)}
     if want_flow:
         results["flow"] = ((nd, sh, sw, 2), np.float32)
     if want_mask:
@@ -85,7 +88,7 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
         for j in range(len(c["rgb_f"])):
             for k, v in videos.items():
                 if k.startswith("rgb") and yout:
-                    v.write_i420(c[k][j], rh, rw)
+                    v.write_planes(c[k][j], rh, rw)
                 else:
                     v.write(c[k][j] if k.startswith("rgb") else _mask_rgb(c[k][j]))
 
@@ -102,8 +105,8 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
                     write_flow_png(os.path.join(args.subpath_mask + "_bwd", "%04d.png" % (s + j)), flow[j, 1], mask[j, 1])
 
     stream = Stream(model, frame, results, submit, collect, i420=yin) if stream_enabled(stream_min_chunks, -(-(last - first) // chunk)) else None
-    # what the other ranks' pairs park in the relay's spool: per video an encoded frame (I420 of the clip's size, or RGB) or a mask's bytes
-    pair_bytes = sum((i420_bytes(rh, rw) if yout else sh * sw * 3) if k.startswith("rgb") else sh * sw for k in files)
+    # what the other ranks' pairs park in the relay's spool: per video an encoded frame (planes of the clip's size, or RGB) or a mask's bytes
+    pair_bytes = sum((yuv_bytes(ofmt, rh, rw) if yout else sh * sw * 3) if k.startswith("rgb") else sh * sw for k in files)
     mx_all = run_sharded(rk, src, n - 1, chunk, 1, args.output, ((n - 1) - (last - first)) * pair_bytes,
                          step, write_chunk, dump if want_flow else None, n_scalars=1, ctx=model, stream=stream, i420=yin)
     if not rk.main:

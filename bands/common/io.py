@@ -14,7 +14,15 @@ It streams in both directions, ffmpeg / mpv / every encoder read and write it (`
 A clip is read in whatever planar layout it has (Y4M_TAGS: 4:2:0, 4:2:2, 4:4:4 or mono, 8 to 16 bit, limited or full range) - `ffmpeg -i in.mov
 in.y4m` does not convert pixel formats - and its planes go to the engine as they are (pb_set_frame_format).  A header does not name the matrix:
 PRISMA_Y4M_MATRIX=bt601 (the default) | bt709 does; it is not guessed from the frame size.  Chroma siting is not acted on, interlaced clips,
-4:1:1 and alpha layouts are refused, and so is XCOLORRANGE=FULL in a header without a `C` tag (a header that names no layout is 8-bit 4:2:0, limited).  What is written is always 8 bit, 4:2:0, limited range, BT.601.  The colour arithmetic is common/yuv.py's.
+4:1:1 and alpha layouts are refused, and so is XCOLORRANGE=FULL in a header without a `C` tag (a header that names no layout is 8-bit 4:2:0, limited).  The colour arithmetic is common/yuv.py's.
+
+What is written is 8 bit, 4:2:0, limited range, BT.601 unless PRISMA_Y4M_OUT (process.py --y4m_out) names another layout: a `C` tag of Y4M_TAGS,
+optionally followed by `,full` and / or `,bt709` (C444p12,full  Cmono,full  C422p10,bt709), or `source` for the layout of the input clip.  The
+band videos carry data in their colours - depth as a hue ramp, flow as direction and length, masks as grey - and 8-bit 4:2:0 averages and
+quantises it.  Properties of the two rules, checked over all 2^24 colours (tests/test_yuv_out_ref_cpu.py): a 4:4:4 video of 12, 14 or 16 bits, in
+either range and matrix, returns every RGB byte the band produced - C444p12,full is the lossless choice, 6 bytes per pixel; at 10 bits up to
+2.2 % of the colours come back off by 1, at 8 bits 75 - 84 % by up to 2; a grey value through Cmono,full comes back exactly - the choice for the
+mask videos, one byte per pixel.  A header has no tag for the matrix: a file written with `,bt709` is read back with PRISMA_Y4M_MATRIX=bt709.
 """
 import os
 from fractions import Fraction
@@ -22,7 +30,7 @@ from fractions import Fraction
 import numpy as np
 
 from .resize import resize_rgb
-from .yuv import Format, i420_bytes, rgb_to_i420, yuv_bytes, yuv_to_rgb
+from .yuv import I420, Format, i420_bytes, rgb_to_yuv, yuv_bytes, yuv_to_rgb
 
 Y4M_MAGIC = b"YUV4MPEG2"
 Y4M_CHROMA = ("C420", "C420jpeg", "C420mpeg2", "C420paldv")      # 8-bit 4:2:0; the siting they name is not acted on (nearest / block mean)
@@ -39,6 +47,36 @@ def y4m_matrix():
     if m not in Y4M_MATRICES:
         raise RuntimeError("PRISMA_Y4M_MATRIX=%s: one of %s" % (m, ", ".join(Y4M_MATRICES)))
     return m
+
+
+def y4m_out(source=None):
+    """the layout .y4m videos are written in: PRISMA_Y4M_OUT, I420 (8 bit, 4:2:0, limited, BT.601) when unset or empty.  `TAG[,full][,bt709]`
+    with TAG one of Y4M_TAGS, or `source`: the layout of the input clip (`source`: its common/yuv.py Format, None when the clip is no .y4m - then
+    I420) with PRISMA_Y4M_MATRIX's matrix.  A matrix comes from this variable only: PRISMA_Y4M_MATRIX alone changes nothing that is written."""
+    v = os.environ.get("PRISMA_Y4M_OUT", "")
+    if not v:
+        return I420
+    if v == "source":
+        return I420 if source is None else Format(int(source[0]), int(source[1]), bool(source[2]), y4m_matrix())
+    tag, *opts = v.split(",")
+    if tag not in Y4M_TAGS:
+        raise RuntimeError("PRISMA_Y4M_OUT=%s: %s is not a layout that is written: `source`, or one of %s, then `,full` and / or `,bt709`"
+                           % (v, tag or "(nothing)", ", ".join(Y4M_TAGS)))
+    if len(set(opts)) != len(opts) or any(o not in ("full", "bt709") for o in opts):
+        raise RuntimeError("PRISMA_Y4M_OUT=%s: after the layout come `,full` and / or `,bt709`, each at most once" % v)
+    return Format(Y4M_TAGS[tag][0], Y4M_TAGS[tag][1], "full" in opts, "bt709" if "bt709" in opts else "bt601")
+
+
+def y4m_tag(fmt):
+    """the `C` tag of a layout: what ffmpeg writes for it (C420jpeg for 8-bit 4:2:0, as this writer always has)"""
+    chroma, depth = int(fmt[0]), int(fmt[1])
+    if (chroma, depth) not in Y4M_TAGS.values():
+        raise ValueError("no .y4m tag for %r" % (tuple(fmt),))
+    if chroma == 400:
+        return "Cmono" if depth == 8 else "Cmono%d" % depth
+    if depth == 8:
+        return "C420jpeg" if chroma == 420 else "C%d" % chroma
+    return "C%dp%d" % (chroma, depth)
 
 
 def create_folder(path):
@@ -85,9 +123,11 @@ def is_y4m(path):
     return bool(path) and path.endswith(".y4m")
 
 
-def y4m_header(width, height, rate):
-    """the header line VideoWriter writes; `rate` a Fraction"""
-    return ("YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 C420jpeg XCOLORRANGE=LIMITED\n" % (width, height, rate.numerator, rate.denominator)).encode("ascii")
+def y4m_header(width, height, rate, fmt=None):
+    """the header line VideoWriter writes; `rate` a Fraction, `fmt` the layout (None: 8-bit 4:2:0, limited)"""
+    fmt = I420 if fmt is None else fmt
+    return ("YUV4MPEG2 W%d H%d F%d:%d Ip A1:1 %s XCOLORRANGE=%s\n" % (width, height, rate.numerator, rate.denominator, y4m_tag(fmt),
+                                                                      "FULL" if fmt[2] else "LIMITED")).encode("ascii")
 
 
 def as_rate(rate):
@@ -251,16 +291,19 @@ class FrameReader:
 
 
 class VideoWriter:
-    """write(uint8 HxWx3) / close().  .mp4 -> PyAV libx264 crf 15 (io.py:246-305); .npy -> frame stack; .y4m -> I420 frames appended to
-    the file as they come (nothing is kept in memory), the header written with the first frame and that frame's own size (no rescale, as
-    the .npy writer), write_i420(planes, h, w) for frames that already are I420 (the engines' "rgb_out_i420" results).
+    """write(uint8 HxWx3) / close().  .mp4 -> PyAV libx264 crf 15 (io.py:246-305); .npy -> frame stack; .y4m -> planar YUV frames of
+    layout `fmt` (common/yuv.py Format; None: I420) appended to the file as they come (nothing is kept in memory), the header written with the
+    first frame and that frame's own size (no rescale, as the .npy writer), write_planes(planes, h, w) for frames that already are in that
+    layout (the engines' rgb_format results; write_i420 is the same for an I420 writer).
     rescale=True (a .y4m writer's; the flow bands pass it, whose frames are `--scale` times the clip's): the video has the width and height
     the writer was opened with, as the reference's has (io.py:297 rescales every frame to them).  write() resizes a frame of another size
     on the host (common/resize.py: bilinear with two taps, where PyAV's reformat runs swscale's), write_i420 takes frames of that size only."""
 
-    def __init__(self, width, height, frame_rate, filename, rescale=False):
+    def __init__(self, width, height, frame_rate, filename, rescale=False, fmt=None):
         self.filename, self._frames, self._av, self._y4m = filename, None, None, None
         self.i420 = is_y4m(filename)
+        self.format = I420 if fmt is None else Format(*fmt)
+        yuv_bytes(self.format, 1, 1)        # an unknown layout is refused here
         if self.i420:
             # rescale: the size is the writer's, not the first frame's
             self._rate, self._size, self._rescale, self._started = as_rate(frame_rate), (int(height), int(width)) if rescale else None, bool(rescale), False
@@ -285,16 +328,24 @@ class VideoWriter:
             self._st.thread_type = "AUTO"
 
     def write_i420(self, yuv, height, width):
-        """one I420 frame (uint8, i420_bytes(height, width) bytes: Y, Cb, Cr planes) of a .y4m"""
+        """one I420 frame (uint8, i420_bytes(height, width) bytes: Y, Cb, Cr planes) of a .y4m whose layout is I420"""
         if self._y4m is None:
             raise RuntimeError("%s: write_i420 is a .y4m writer's" % self.filename)
+        if self.format != I420:
+            raise RuntimeError("%s: write_i420 on a writer of %r (write_planes takes its frames)" % (self.filename, tuple(self.format)))
+        self.write_planes(yuv, height, width)
+
+    def write_planes(self, yuv, height, width):
+        """one frame of the writer's layout (uint8, yuv_bytes(format, height, width) bytes: the Y plane, then Cb and Cr if the layout has them)"""
+        if self._y4m is None:
+            raise RuntimeError("%s: write_planes is a .y4m writer's" % self.filename)
         if self._size is None:
             self._size = (height, width)
         if not self._started:       # the header goes out with the first frame
             self._started = True
-            self._y4m.write(y4m_header(self._size[1], self._size[0], self._rate))
+            self._y4m.write(y4m_header(self._size[1], self._size[0], self._rate, self.format))
         yuv = np.ascontiguousarray(yuv, np.uint8).reshape(-1)
-        if (height, width) != self._size or yuv.size != i420_bytes(height, width):
+        if (height, width) != self._size or yuv.size != yuv_bytes(self.format, height, width):
             raise ValueError("%s: a %d x %d frame of %d bytes in a %d x %d video" % ((self.filename, height, width, yuv.size) + self._size))
         self._y4m.write(b"FRAME\n")
         self._y4m.write(memoryview(yuv))
@@ -304,7 +355,7 @@ class VideoWriter:
         if self._y4m is not None:
             if self._rescale and tuple(rgb.shape[:2]) != self._size:
                 rgb = resize_rgb(rgb, *self._size)
-            self.write_i420(rgb_to_i420(np.asarray(rgb, np.uint8)), rgb.shape[0], rgb.shape[1])
+            self.write_planes(rgb_to_yuv(self.format, np.asarray(rgb, np.uint8)), rgb.shape[0], rgb.shape[1])
             return
         if self._frames is not None:
             self._frames.append(np.array(rgb))      # a copy, always: the caller's frame may be a view of a ring slot that a later chunk overwrites

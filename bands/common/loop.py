@@ -70,15 +70,16 @@ class Stream:
         self.wait = wait if wait is not None else host.wait
 
 
-def frame_formats(model, yin, yout, h, w, layout=None):
+def frame_formats(model, yin, yout, h, w, layout=None, out_layout=None):
     """Tells a band's engine what the loop will hand it (`yin`: the source is a .y4m, its frames are planes of `layout`, the reader's .format -
-    I420 without one) and wants back (`yout`: the output is a .y4m): engine.frame_format / rgb_format.  -> the extra keyword arguments of the
+    I420 without one) and wants back (`yout`: the output is a .y4m, its frames planes of `out_layout`, io.y4m_out()'s - I420 without one):
+    engine.frame_format / rgb_format.  -> the extra keyword arguments of the
     engine's calls: the frame size, which plane arrays do not carry.  With neither, nothing is touched and nothing is passed: the calls are what
     they were before .y4m."""
     if not (yin or yout) and getattr(model, "frame_format", "rgb") == "rgb" and getattr(model, "rgb_format", "rgb") == "rgb":
         return {}
-    plain = layout is None or tuple(layout) == (420, 8, False, "bt601")
-    model.frame_format, model.rgb_format = ("i420" if plain else tuple(layout)) if yin else "rgb", "i420" if yout else "rgb"
+    named = lambda f: "i420" if f is None or tuple(f) == (420, 8, False, "bt601") else tuple(f)      # noqa: E731
+    model.frame_format, model.rgb_format = named(layout) if yin else "rgb", named(out_layout) if yout else "rgb"
     return {"size": (h, w)} if yin or yout else {}
 
 

@@ -6,7 +6,7 @@ A frame is H W bytes of Y, then ceil(H / 2) ceil(W / 2) bytes of Cb, then as man
 mean of its 2 x 2 block (indices clamped to the frame) and read back by the block's four pixels (nearest).
 
 Clips come in other layouts too - 4:2:2, 4:4:4, mono, 9 - 16 bit, full range, BT.709: yuv_to_rgb at the end of this file decodes any of them
-(prisma_amd/csrc/yuv_formats.hip on the host).  What is written stays I420."""
+(prisma_amd/csrc/yuv_formats.hip on the host), and rgb_to_yuv encodes to any of them (prisma_amd/csrc/yuv_out.hip on the host)."""
 import collections
 
 import numpy as np
@@ -106,3 +106,51 @@ def yuv_to_rgb(fmt, yuv, h, w):
     rgb[..., 1] = np.clip((lum - cgu * dd - cgv * ee) >> d, 0, 255)
     rgb[..., 2] = np.clip((lum + cbu * dd) >> d, 0, 255)
     return rgb
+
+
+# ---- RGB to every one of those layouts (the way out) -------------------------------------------------------------------------------------------
+# prisma_amd/csrc/yuv_out.hip in numpy (include/prisma_bands.h pb_rgb_to_yuv has the rule; tests/yuv_out_ref.py pins both), for frames that reach a
+# writer on the host: a VideoWriter's `write(rgb)`, the flow bands' consistency-mask videos.
+def yuv_fwd_coeffs(fmt):
+    """(yr, yg, yb, ur, ug, h, vg, vb, F, yoff, coff, 2^d - 1): exact rationals rounded half up in Python's integers; the G terms are remainders"""
+    _plane_shapes(fmt, 1, 1)
+    d, full = int(fmt[1]), bool(fmt[2])
+    kr, kb, den = _MATRICES[fmt[3]]
+    f = 8 if (d, full, fmt[3]) == (8, False, "bt601") else 24 - d      # the one exception: the published 8-bit integers of rgb_to_i420
+    top = (1 << d) - 1
+    yn, cn = ((top, top) if full else (219 << (d - 8), 224 << (d - 8)))      # 255 ys, 255 cs
+    yn, cn = yn << f, cn << f
+    rhu = lambda p, q: (2 * p + q) // (2 * q)      # noqa: E731
+    yr, yb = rhu(yn * kr, 255 * den), rhu(yn * kb, 255 * den)
+    h = rhu(cn, 510)
+    ur, vb = rhu(cn * kr, 510 * (den - kb)), rhu(cn * kb, 510 * (den - kr))
+    return (yr, rhu(yn, 255) - yr - yb, yb, ur, h - ur, h, h - vb, vb, f, 0 if full else 16 << (d - 8), 1 << (d - 1), top)
+
+
+def rgb_to_yuv(fmt, rgb, out=None):
+    """uint8 [H, W, 3] -> uint8 [yuv_bytes(fmt, H, W)] (`out`: the caller's buffer); a 16-bit sample is two bytes, little-endian"""
+    rgb = np.asarray(rgb, np.uint8)
+    h, w = rgb.shape[:2]
+    c, bps = _plane_shapes(fmt, h, w)
+    if out is None:
+        out = np.empty(yuv_bytes(fmt, h, w), np.uint8)
+    if out.shape != (yuv_bytes(fmt, h, w),) or out.dtype != np.uint8:
+        raise ValueError("a %d x %d frame of %r is %d bytes, not %r %s" % (h, w, tuple(fmt), yuv_bytes(fmt, h, w), out.shape, out.dtype))
+    yr, yg, yb, ur, ug, hh, vg, vb, f, yoff, coff, top = yuv_fwd_coeffs(fmt)
+    rnd = 1 << (f - 1)
+    planes = out if bps == 1 else out.view("<u2")
+    v = rgb.astype(np.int32)
+    planes[:h * w] = np.clip(((yr * v[..., 0] + yg * v[..., 1] + yb * v[..., 2] + rnd) >> f) + yoff, 0, top).reshape(-1)
+    if c is None:
+        return out
+    sx, sy = _SHIFTS[int(fmt[0])]
+    ph, pw = (c[0] << sy) - h, (c[1] << sx) - w
+    if ph or pw:
+        v = np.pad(v, ((0, ph), (0, pw), (0, 0)), mode="edge")      # indices clamped to the frame
+    m = sum(v[dy::1 << sy, dx::1 << sx] for dy in range(1 << sy) for dx in range(1 << sx))
+    m = (m + ((1 << (sx + sy)) >> 1)) >> (sx + sy)
+    r, g, b = m[..., 0], m[..., 1], m[..., 2]
+    n = c[0] * c[1]
+    planes[h * w:h * w + n] = np.clip(((hh * b - ur * r - ug * g + rnd) >> f) + coff, 0, top).reshape(-1)
+    planes[h * w + n:] = np.clip(((hh * r - vg * g - vb * b + rnd) >> f) + coff, 0, top).reshape(-1)
+    return out

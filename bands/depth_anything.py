@@ -17,10 +17,11 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, create_folder, is_y4m, open_rgb, write_ply, write_rgb  # noqa: E402
+from common.io import FrameReader, VideoWriter, create_folder, is_y4m, open_rgb, write_ply, write_rgb, y4m_out  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.cli import begin, end, synthetic_or_exit  # noqa: E402
-from common.loop import Stream, frame_formats, i420_bytes, run_sharded, stream_enabled  # noqa: E402
+from common.loop import Stream, frame_formats, run_sharded, stream_enabled  # noqa: E402
+from common.yuv import yuv_bytes  # noqa: E402
 from common.meta import is_video  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
@@ -137,8 +138,10 @@ def process_video(a):
     src = FrameReader(a.input)
     n = len(src)
     h, w = src[0].shape[:2]
-    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=a.output) if rk.main else None
-    yin, yout = src.i420, is_y4m(a.output)      # a .y4m on either side: its I420 frames go to / come from the engine as they are
+    yin, yout = src.i420, is_y4m(a.output)      # a .y4m on either side: its planes go to / come from the engine as they are
+    ofmt = y4m_out(getattr(src, "format", None)) if yout else None      # the layout written: PRISMA_Y4M_OUT's, I420 when unset
+    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=a.output, fmt=ofmt) if rk.main else None
+    out_bytes = yuv_bytes(ofmt, h, w) if yout else h * w * 3
     out_folder = os.path.dirname(a.output)
     if a.subpath:
         if data:
@@ -149,7 +152,7 @@ def process_video(a):
         init_model(device=rk.device)
     first, last = rk.frames(n)
     want_depth = bool(a.npy or a.subpath)
-    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None))
+    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None), ofmt)
     frame = ((src.frame_bytes,), np.uint8) if yin else (src[0].shape, np.uint8)       # a .y4m's planes, in the clip's own layout
 
     def step(_s, frames):
@@ -157,7 +160,7 @@ def process_video(a):
         return {"rgb": rgb}, depth, np.stack([mn, mx], 1)
 
     # the streamed loop (common/loop.py): the same call as submit_batch / wait on the loop's page-locked rings - one array per result asked for
-    results = {"rgb": ((i420_bytes(h, w),) if yout else (h, w, 3), np.uint8), "mn": ((), np.float32), "mx": ((), np.float32)}
+    results = {"rgb": ((out_bytes,) if yout else (h, w, 3), np.uint8), "mn": ((), np.float32), "mx": ((), np.float32)}
     if want_depth:
         results["depth"] = ((h, w), np.float32)
 
@@ -169,7 +172,7 @@ def process_video(a):
 
     def write_chunk(_s, c):          # rank 0 only: the video frames, chunk after chunk in order
         for f in c["rgb"]:
-            out.write_i420(f, h, w) if yout else out.write(f)
+            out.write_planes(f, h, w) if yout else out.write(f)
 
     def dump(s, depth):              # sink thread: .npy / .png dumps (reference :215-225); nothing of `depth` is kept past the return
         for j in range(len(depth)):
@@ -178,7 +181,7 @@ def process_video(a):
             write_depth_png(os.path.join(a.subpath, "{:05d}.png".format(s + j)), depth[j])
 
     stream = Stream(model, frame, results, submit, collect, i420=yin) if stream_enabled(STREAM_MIN_CHUNKS, -(-(last - first) // BATCH)) else None
-    mm = run_sharded(rk, src, n, BATCH, 0, a.output, (n - (last - first)) * h * w * 3, step, write_chunk,
+    mm = run_sharded(rk, src, n, BATCH, 0, a.output, (n - (last - first)) * out_bytes, step, write_chunk,
                      dump if a.subpath else None, n_scalars=2, ctx=model, stream=stream, i420=yin)
     if not rk.main:
         return

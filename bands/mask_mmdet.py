@@ -18,10 +18,11 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, create_folder, is_y4m, open_rgb, write_rgb  # noqa: E402
+from common.io import FrameReader, VideoWriter, create_folder, is_y4m, open_rgb, write_rgb, y4m_out  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.cli import begin, end, synthetic_or_exit  # noqa: E402
-from common.loop import Stream, frame_formats, i420_bytes, run_sharded, stream_enabled  # noqa: E402
+from common.loop import Stream, frame_formats, run_sharded, stream_enabled  # noqa: E402
+from common.yuv import yuv_bytes  # noqa: E402
 from common.meta import is_video  # noqa: E402
 from prisma_amd import engine, shard, synth  # noqa: E402
 
@@ -91,12 +92,14 @@ def process_video(args):
         args.subpath = os.path.join(os.path.dirname(args.output), args.subpath)
         create_folder(args.subpath)
     first, last = rk.frames(n)
-    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=args.output) if rk.main else None
+    ofmt = y4m_out(getattr(src, "format", None)) if is_y4m(args.output) else None      # the layout written: PRISMA_Y4M_OUT's, I420 when unset
+    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=args.output, fmt=ofmt) if rk.main else None
     set_sdf(args.sdf)
-    # a .y4m on either side: its I420 frames go to / come from the engine as they are - but the COLMAP dump needs the id images' red channel, so
+    # a .y4m on either side: its planes go to / come from the engine as they are - but the COLMAP dump needs the id images' red channel, so
     # with --subpath they come back as RGB and the video's frames are converted on the host
     yin, yout = src.i420, is_y4m(args.output) and not args.subpath
-    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None))
+    fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None), ofmt)
+    out_bytes = yuv_bytes(ofmt, h, w) if yout else h * w * 3
     frame = ((src.frame_bytes,), np.uint8) if yin else (src[0].shape, np.uint8)       # a .y4m's planes, in the clip's own layout
 
     def step(_s, frames):            # the SDF, if asked for, is already in G: set_sdf
@@ -114,14 +117,14 @@ def process_video(args):
 
     def write_chunk(_s, c):          # rank 0 only: the video frames, chunk after chunk in order
         for f in c["mask"]:
-            out.write_i420(f, h, w) if yout else out.write(f)
+            out.write_planes(f, h, w) if yout else out.write(f)
 
     def dump(s, masks):              # sink thread: the COLMAP frames
         for j in range(len(masks)):
             write_rgb(os.path.join(args.subpath, "{:05d}.png".format(s + j)), _colmap(masks[j]))
 
-    stream = Stream(model, frame, {"mask": ((i420_bytes(h, w),) if yout else (h, w, 3), np.uint8)}, submit, collect, wait=lambda: None, i420=yin) if stream_enabled(STREAM_MIN_CHUNKS, -(-(last - first) // BATCH)) else None
-    run_sharded(rk, src, n, BATCH, 0, args.output, (n - (last - first)) * h * w * 3, step, write_chunk, dump if args.subpath else None,
+    stream = Stream(model, frame, {"mask": ((out_bytes,) if yout else (h, w, 3), np.uint8)}, submit, collect, wait=lambda: None, i420=yin) if stream_enabled(STREAM_MIN_CHUNKS, -(-(last - first) // BATCH)) else None
+    run_sharded(rk, src, n, BATCH, 0, args.output, (n - (last - first)) * out_bytes, step, write_chunk, dump if args.subpath else None,
                 stream=stream, i420=yin)
     if not rk.main:
         return

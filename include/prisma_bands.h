@@ -256,7 +256,7 @@ int pb_i420_to_rgb_dev(pb_ctx *ctx, const uint8_t *yuv, int n, int H, int W, uin
 int pb_rgb_to_i420(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
 int pb_rgb_to_i420_dev(pb_ctx *ctx, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
 
-/* Every planar layout a `.y4m` clip can have, to RGB (the way in only: what the bands write stays 8 bit, 4:2:0, limited range, BT.601; chroma
+/* Every planar layout a `.y4m` clip can have, to RGB (the way in; pb_rgb_to_yuv below is the way out; chroma
  * siting is not acted on; the matrix is the caller's to name - it is not guessed from the frame size).  One rule, exact integers:
  *   chroma      400 (mono: no chroma planes), 420, 422 or 444;  (sx, sy) = (1, 1) for 420, (1, 0) for 422, (0, 0) for 444
  *   depth d     8 .. 16: one byte per sample at d = 8, else a 16-bit little-endian word, read whole and not masked
@@ -295,6 +295,42 @@ int pb_yuv_coeffs(const pb_yuv_fmt *fmt, int32_t out[7]);
 int pb_yuv_to_rgb(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out);
 int pb_yuv_to_rgb_dev(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb_out);
 int pb_set_frame_format(pb_ctx *ctx, const pb_yuv_fmt *fmt);
+
+/* RGB to every one of those layouts, the way out: what a written `.y4m` holds.  A format is the pb_yuv_fmt above; plane order, plane sizes, sample
+ * size (one byte at d = 8, else a 16-bit little-endian word), yoff and coff are those of the read direction.  One rule, exact integers, one table:
+ *   limited: ys = 219 2^(d - 8) / 255, cs = 224 2^(d - 8) / 255;   full: ys = cs = (2^d - 1) / 255;   F = 24 - d fractional bits
+ *   - the one exception: {d = 8, limited, BT.601} takes F = 8
+ *   yr = rhu(2^F ys Kr)     yb = rhu(2^F ys Kb)     yg = rhu(2^F ys) - yr - yb
+ *   h  = rhu(2^F cs / 2)    ur = rhu(2^F cs Kr / (2 (1 - Kb)))    ug = h - ur    vb = rhu(2^F cs Kb / (2 (1 - Kr)))    vg = h - vb
+ *   Y  = clamp((( yr R + yg G + yb B + 2^(F - 1)) >> F) + yoff)      per pixel
+ *   Cb = clamp(((-ur R - ug G + h  B + 2^(F - 1)) >> F) + coff)      per chroma sample
+ *   Cr = clamp((( h  R - vg G - vb B + 2^(F - 1)) >> F) + coff)
+ * rhu, Kr, Kb as above, `>>` an arithmetic shift on int32 (|coefficient| <= 2^24 / 255, so every intermediate is inside int32), clamp to
+ * 0 .. 2^d - 1.  The R, G, B of a chroma sample are the rounded mean of the pixels it covers, indices clamped to the frame: (sum of 4 + 2) >> 2
+ * for 420 (as pb_rgb_to_i420), (sum of 2 + 1) >> 1 for 422, the pixel itself for 444; 400 writes Y only.  The G coefficients are remainders, so a
+ * grey pixel gives Cb = Cr = coff exactly and white gives the top code.  With F = 8 the construction yields the published integers 66, 129, 25 /
+ * 38, 74, 112 / 112, 94, 18 of pb_rgb_to_i420 - which is why the exception is an F and not a second table: {420, 8, 0, PB_YUV_BT601} is
+ * pb_rgb_to_i420 byte for byte (and runs its kernel), and the other 8-bit limited BT.601 layouts share its luma.
+ * Outside the exception the result is within 0.5 + 510 / 2^F codes of the real-valued conversion of the same (block-mean) R, G, B: 0.5 for the
+ * final floor, and coefficient rounding of at most 0.5, 1 and 0.5 per unit on inputs up to 255 - under 0.51 codes at d = 8, under 2.5 codes of
+ * 65536 at d = 16.  Read back by the rule above (pb_yuv_to_rgb, same format): 444 at d = 12, 14, 16 returns every one of the 2^24 colours
+ * exactly, in both ranges and matrices; at d = 10 up to 2.2 % of them are off by 1, at d = 8 75 - 84 % by up to 2; a grey value through
+ * {400, 8, full} comes back exactly.
+ * pb_yuv_fwd_coeffs: out = yr, yg, yb, ur, ug, h, vg, vb, F, yoff, coff, 2^d - 1; needs no GPU.  pb_rgb_to_yuv: host pointers, blocking, in
+ * chunks of "host_chunk" frames (default 8) as pb_rgb_to_i420, page-locked arrays addressed directly; pb_rgb_to_yuv_dev: device pointers,
+ * asynchronous on the ctx stream, pb_sync() waits.  No alignment is needed (with W % 16 == 0 and 16-byte aligned device pointers a lane moves 16
+ * bytes per access).  Work on any ctx; a format outside the table or a size that is not positive is refused before any launch.
+ *   rgb : n x H x W x 3 uint8      yuv : n x pb_yuv_bytes(fmt, H, W) bytes
+ * Inside the bands: pb_set_out_format(ctx, fmt) makes the rgb_out of the host-pointer and submit entry points of the ctx (the mask band's
+ * mask_out) hold pb_yuv_bytes(fmt, h, w) bytes per frame in that layout, converted on the ctx stream out of the RGB buffer the band encodes into.
+ * fmt = NULL: RGB again.  pb_set_option(ctx, "rgb_out_i420", 1) is pb_set_out_format with {420, 8, 0, PB_YUV_BT601}, 0 is NULL.  With
+ * "rgb_out_full" (below) that format keeps the fused resize kernels; any other resizes to RGB into ctx scratch and then converts - two launches,
+ * the bytes of pb_rgb_to_yuv of pb_rgb_resize.  Refused while a submission is outstanding (PB_ERR_STATE), and for a format outside the table
+ * (PB_ERR_ARG) - the ctx is then left as it was.  The *_dev band entry points keep RGB. */
+int pb_yuv_fwd_coeffs(const pb_yuv_fmt *fmt, int32_t out[12]);
+int pb_rgb_to_yuv(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
+int pb_rgb_to_yuv_dev(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
+int pb_set_out_format(pb_ctx *ctx, const pb_yuv_fmt *fmt);
 
 /* Bilinear resize of RGB frames, 8 bit, exact integers, half-pixel centres (the geometry of swscale's SWS_BILINEAR, which the reference's
  * VideoWriter applies to every frame that is not of the video's size).  Per axis, for output index x of n_out from n_in samples:

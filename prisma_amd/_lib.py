@@ -112,6 +112,10 @@ SYMBOLS = {
     "pb_yuv_to_rgb": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_yuv_to_rgb_dev": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_set_frame_format": (C.c_int, [_P, C.POINTER(pb_yuv_fmt)]),
+    "pb_yuv_fwd_coeffs": (C.c_int, [C.POINTER(pb_yuv_fmt), C.POINTER(C.c_int32)]),
+    "pb_rgb_to_yuv": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_rgb_to_yuv_dev": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
+    "pb_set_out_format": (C.c_int, [_P, C.POINTER(pb_yuv_fmt)]),
     "pb_rgb_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "pb_rgb_resize_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "pb_depth_net_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),

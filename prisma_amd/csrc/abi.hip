@@ -373,9 +373,9 @@ static int depth_host_pipeline(pb_ctx *c, const uint8_t *frames, int n, int H, i
     // profiles/r06j_pcie_entry_points.txt; copies are hidden ACROSS calls by the asynchronous form instead.)
     const int mb = c->depth->max_batch();
     const int cap = std::min(n, c->host_chunk > 0 ? std::min(c->host_chunk, mb) : mb);
-    // "frames_i420" / "rgb_out_i420": the lane carries I420 frames, converted on the ctx stream into / out of the RGB buffer the band works on
+    // pb_set_frame_format / pb_set_out_format: the lane carries planar YUV frames, converted on the ctx stream into / out of the RGB buffer the band works on
     const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out;
-    const size_t fin = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : px * 3, fout = yout ? (size_t)i420_frame_bytes(H, W) : px * 3;
+    const size_t fin = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : px * 3, fout = yout ? (size_t)yuv_frame_bytes(c->out_fmt, H, W) : px * 3;
     const bool pin_in = pb_is_pinned(frames, (size_t)n * fin), pin_d = pb_is_pinned(depth_out, (size_t)n * px * 4),
                pin_r = pb_is_pinned(rgb_out, (size_t)n * fout);
     const bool pin_mm = (!min_out || pb_is_pinned(min_out, (size_t)n * 4)) && (!max_out || pb_is_pinned(max_out, (size_t)n * 4));
@@ -398,7 +398,7 @@ static int depth_host_pipeline(pb_ctx *c, const uint8_t *frames, int n, int H, i
         }
         uint8_t *enc = (uint8_t *)(rgb_out ? (yout ? c->yuv[1] : l[2].d[slot]) : nullptr);
         PB_TRY(c->depth->infer(in, m, H, W, (float *)(depth_out ? l[1].d[slot] : nullptr), enc, mn, mn + cap, flip));
-        return yout ? launch_rgb_to_i420(c->stream, enc, m, H, W, (uint8_t *)l[2].d[slot]) : 0;
+        return yout ? launch_rgb_to_yuv(c->stream, c->out_fmt, enc, m, H, W, (uint8_t *)l[2].d[slot]) : 0;
     });
 }
 
@@ -480,12 +480,14 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
     // through as it is and the engine refuses it
     cp = std::max(1, c->flow->chunk_pairs(cp, H, W, scale, dirs));
     const size_t px = (size_t)sh * sw * dirs, np = (size_t)pairs;      // px: result pixels of a pair, all directions
-    // "frames_i420" / "rgb_out_i420": I420 frames in, I420 frames of the output size out (dirs of them per pair), converted on the ctx stream
-    // "rgb_out_full": ... of the clip's H x W, resized on the ctx stream from the sh x sw frames the band encodes (nothing to do at scale 1)
+    // pb_set_frame_format / pb_set_out_format: planar YUV frames in, ... of the output size out (dirs of them per pair), converted on the ctx stream
+    // "rgb_out_full": ... of the clip's H x W, resized on the ctx stream from the sh x sw frames the band encodes (nothing to do at scale 1): I420
+    // by the fused resize kernel, any other layout by a resize into ctx scratch and a conversion out of it
     const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0 && rgb_out, full = c->rgb_out_full != 0 && rgb_out && (sh != H || sw != W);
     const int rh = full ? H : sh, rw = full ? W : sw;                  // the size of an rgb_out frame
+    const bool two = full && yout && !yuv_fmt_is_i420(c->out_fmt);
     const size_t fpx = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : (size_t)H * W * 3,
-                 rpx = (yout ? (size_t)i420_frame_bytes(rh, rw) : (size_t)rh * rw * 3) * dirs;
+                 rpx = (yout ? (size_t)yuv_frame_bytes(c->out_fmt, rh, rw) : (size_t)rh * rw * 3) * dirs;
     const bool pin_in = pb_is_pinned(frames, (size_t)F * fpx), pin_f = pb_is_pinned(flow_out, np * px * 8), pin_r = pb_is_pinned(rgb_out, np * rpx),
                pin_k = pb_is_pinned(mask_out, np * px), pin_m = !maxdisp_out || pb_is_pinned(maxdisp_out, np * dirs * 4);
     if (submit) PB_CHECK(pin_in && (!flow_out || pin_f) && (!rgb_out || pin_r) && (!mask_out || pin_k) && pin_m, PB_ERR_ARG,
@@ -497,6 +499,7 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
                                 {mask_out, mask_out ? px : 0, true, pin_k}};
     if (yin) PB_TRY(c->yuv_grow(0, (size_t)(cp + 1) * H * W * 3));
     if (yout || full) PB_TRY(c->yuv_grow(1, (size_t)cp * px * 3));
+    if (two) PB_TRY(c->yuv_grow(2, (size_t)cp * dirs * H * W * 3));
     TimerSpan span(c->flow->timer);
     const ChunkPipe::Lane *l = c->pipe.lane;
     return run_chunks(c, pairs, cp, 1, lanes, 5, submit, [&](int slot, int, int m) {
@@ -508,8 +511,12 @@ static int flow_host_pipeline(pb_ctx *c, const uint8_t *frames, int F, int H, in
         uint8_t *enc = (uint8_t *)(rgb_out ? (yout || full ? c->yuv[1] : l[2].d[slot]) : nullptr);
         PB_TRY(c->flow->infer(in, m + 1, H, W, scale, iters, backward, (float *)(flow_out ? l[1].d[slot] : nullptr), enc, (float *)l[3].d[slot],
                               (uint8_t *)(mask_out ? l[4].d[slot] : nullptr), alpha1, alpha2));
+        if (two) {
+            PB_TRY(launch_rgb_resize(c->stream, enc, m * dirs, sh, sw, H, W, (uint8_t *)c->yuv[2], false));
+            return launch_rgb_to_yuv(c->stream, c->out_fmt, (const uint8_t *)c->yuv[2], m * dirs, H, W, (uint8_t *)l[2].d[slot]);
+        }
         if (full) return launch_rgb_resize(c->stream, enc, m * dirs, sh, sw, H, W, (uint8_t *)l[2].d[slot], yout);
-        return yout ? launch_rgb_to_i420(c->stream, enc, m * dirs, sh, sw, (uint8_t *)l[2].d[slot]) : 0;
+        return yout ? launch_rgb_to_yuv(c->stream, c->out_fmt, enc, m * dirs, sh, sw, (uint8_t *)l[2].d[slot]) : 0;
     });
 }
 
@@ -586,13 +593,13 @@ int pb_mask_infer_batch(pb_ctx *c, const uint8_t *frames, int n, int H, int W, f
     PB_HIP(hipSetDevice(c->device));
     const size_t fb = (size_t)H * W * 3, bytes = (size_t)n * fb;
     const int cf = c->mask->frames_per_chunk(), chunks = (n + cf - 1) / cf;
-    // "frames_i420" / "rgb_out_i420": the copies move I420 frames (fi / fo bytes each) into / out of whole-batch I420 buffers (ctx yuv[0] / yuv[1]);
+    // pb_set_frame_format / pb_set_out_format: the copies move planar YUV frames (fi / fo bytes each) into / out of whole-batch buffers (ctx yuv[0] / yuv[1]);
     // the chunk's frames are converted into d_in once its copy has arrived, its id images out of d_out before they leave - both on the ctx stream
     const bool yin = c->frames_i420 != 0, yout = c->rgb_out_i420 != 0;
-    const size_t fi = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : fb, fo = yout ? (size_t)i420_frame_bytes(H, W) : fb;
+    const size_t fi = yin ? (size_t)yuv_frame_bytes(c->frame_fmt, H, W) : fb, fo = yout ? (size_t)yuv_frame_bytes(c->out_fmt, H, W) : fb;
     const bool pin_in = pb_is_pinned(frames, n * fi), pin_out = pb_is_pinned(mask_out, n * fo);
     MaskPipe &mp = c->mpipe;
-    PB_TRY(mp.ensure(bytes, n * fi, !pin_in, !pin_out, chunks));        // h_in by the frames' own size: up to 6 bytes per pixel, not RGB's 3
+    PB_TRY(mp.ensure(bytes, n * fi, n * fo, !pin_in, !pin_out, chunks));        // h_in / h_out by the frames' own size: up to 6 bytes per pixel, not RGB's 3
     if (yin) PB_TRY(c->yuv_grow(0, n * fi));
     if (yout) PB_TRY(c->yuv_grow(1, n * fo));
     PipeDrain drain{mp.s_in, c->stream, mp.s_out};              // no exit, error or not, leaves a copy into caller memory in flight
@@ -606,15 +613,15 @@ int pb_mask_infer_batch(pb_ctx *c, const uint8_t *frames, int n, int H, int W, f
     }
     hipStream_t st = c->stream;
     char *dst = pin_out ? (char *)mask_out : (char *)mp.h_out;
-    const pb_yuv_fmt ffmt = c->frame_fmt;
+    const pb_yuv_fmt ffmt = c->frame_fmt, ofmt = c->out_fmt;
     c->mask->chunk_begin = [&mp, st, cf, yin, up, fi, fb, H, W, ffmt](int first, int m) -> int {
         PB_HIP(hipStreamWaitEvent(st, mp.ev_in[first / cf], 0));
         if (yin) PB_TRY(launch_yuv_to_rgb(st, ffmt, (const uint8_t *)up + (size_t)first * fi, m, H, W, (uint8_t *)mp.d_in + (size_t)first * fb));
         return 0;
     };
-    c->mask->chunk_end = [&mp, st, cf, fb, fo, dst, yout, down, H, W](int first, int m) -> int {
+    c->mask->chunk_end = [&mp, st, cf, fb, fo, dst, yout, down, H, W, ofmt](int first, int m) -> int {
         const size_t off = (size_t)first * fo;
-        if (yout) PB_TRY(launch_rgb_to_i420(st, (const uint8_t *)mp.d_out + (size_t)first * fb, m, H, W, (uint8_t *)down + off));
+        if (yout) PB_TRY(launch_rgb_to_yuv(st, ofmt, (const uint8_t *)mp.d_out + (size_t)first * fb, m, H, W, (uint8_t *)down + off));
         PB_HIP(hipEventRecord(mp.ev_done[first / cf], st));
         PB_HIP(hipStreamWaitEvent(mp.s_out, mp.ev_done[first / cf], 0));
         PB_HIP(hipMemcpyAsync(dst + off, down + off, (size_t)m * fo, hipMemcpyDeviceToHost, mp.s_out));
@@ -725,6 +732,7 @@ int pb_set_option(pb_ctx *c, const char *key, int value) {
         PB_CHECK(c->pending.empty(), PB_ERR_STATE, "option '%s': a submission of this ctx is still outstanding (pb_wait first)", key);
         (key[0] == 'f' ? c->frames_i420 : key[8] == 'i' ? c->rgb_out_i420 : c->rgb_out_full) = value;
         if (key[0] == 'f') c->frame_fmt = pb_yuv_fmt{420, 8, 0, PB_YUV_BT601};      // pb_set_frame_format's special case
+        else if (key[8] == 'i') c->out_fmt = pb_yuv_fmt{420, 8, 0, PB_YUV_BT601};   // pb_set_out_format's
     }
     else if (!strcmp(key, "corr_layout")) {        // corr_layout.h: 1 = source-blocked volume (default), 0 = row-major; the next flow_raft call re-plans
         PB_CHECK(value == 0 || value == 1, PB_ERR_ARG, "option '%s' is 0 or 1, not %d", key, value);
@@ -991,6 +999,50 @@ int pb_set_frame_format(pb_ctx *c, const pb_yuv_fmt *fmt) {
     PB_CHECK(c->pending.empty(), PB_ERR_STATE, "set_frame_format: a submission of this ctx is still outstanding (pb_wait first)");
     c->frames_i420 = fmt != nullptr;
     if (fmt) c->frame_fmt = *fmt;
+    return 0;
+}
+
+// ---- RGB -> any .y4m layout (yuv_out.hip): on its own, and as the format of a band ctx's rgb_out ----------------------------------------------------
+#define PB_CHECK_FMT(what, fmt) \
+    PB_CHECK(yuv_fmt_ok(*(fmt)), PB_ERR_ARG, what ": no such format (chroma %d, depth %d, full_range %d, matrix %d)", (fmt)->chroma, (fmt)->depth, \
+             (fmt)->full_range, (fmt)->matrix)
+
+int pb_yuv_fwd_coeffs(const pb_yuv_fmt *fmt, int32_t out[12]) {
+    PB_CHECK(fmt && out, PB_ERR_ARG, "yuv_fwd_coeffs: bad arguments");
+    PB_CHECK_FMT("yuv_fwd_coeffs", fmt);
+    yuv_fwd_coeffs(*fmt, out);
+    return 0;
+}
+
+int pb_rgb_to_yuv_dev(pb_ctx *c, const pb_yuv_fmt *fmt, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out) {
+    PB_CHECK(c && fmt && rgb && yuv_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "rgb_to_yuv: bad arguments");
+    PB_CHECK_FMT("rgb_to_yuv", fmt);
+    PB_HIP(hipSetDevice(c->device));
+    return launch_rgb_to_yuv(c->stream, *fmt, rgb, n, H, W, yuv_out);
+}
+
+// Host-pointer variant: run_chunks over chunks of "host_chunk" (default 8) frames, as pb_rgb_to_i420.
+int pb_rgb_to_yuv(pb_ctx *c, const pb_yuv_fmt *fmt, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out) {
+    PB_CHECK(c && fmt && rgb && yuv_out && n > 0 && H > 0 && W > 0, PB_ERR_ARG, "rgb_to_yuv: bad arguments");
+    PB_CHECK_FMT("rgb_to_yuv", fmt);
+    PB_CHECK(c->pending.empty(), PB_ERR_STATE, "rgb_to_yuv: a submission of this ctx is still outstanding (pb_wait first)");
+    PB_HIP(hipSetDevice(c->device));
+    const pb_yuv_fmt f = *fmt;
+    const size_t fi = (size_t)H * W * 3, fo = (size_t)yuv_frame_bytes(f, H, W);
+    const int cap = std::min(n, c->host_chunk > 0 ? c->host_chunk : 8);
+    const ChunkLane lanes[2] = {{(void *)rgb, fi, false, pb_is_pinned(rgb, n * fi)}, {yuv_out, fo, true, pb_is_pinned(yuv_out, n * fo)}};
+    const ChunkPipe::Lane *l = c->pipe.lane;
+    return run_chunks(c, n, cap, 0, lanes, 2, false, [&](int slot, int, int m) {
+        return launch_rgb_to_yuv(c->stream, f, (const uint8_t *)l[0].d[slot], m, H, W, (uint8_t *)l[1].d[slot]);
+    });
+}
+
+int pb_set_out_format(pb_ctx *c, const pb_yuv_fmt *fmt) {
+    PB_CHECK(c, PB_ERR_ARG, "set_out_format: null ctx");
+    if (fmt) PB_CHECK_FMT("set_out_format", fmt);
+    PB_CHECK(c->pending.empty(), PB_ERR_STATE, "set_out_format: a submission of this ctx is still outstanding (pb_wait first)");
+    c->rgb_out_i420 = fmt != nullptr;
+    if (fmt) c->out_fmt = *fmt;
     return 0;
 }
 

@@ -76,8 +76,9 @@ struct MaskPipe {
     void *d_in = nullptr, *d_out = nullptr, *h_in = nullptr, *h_out = nullptr;
     size_t cap_d = 0, cap_hi = 0, cap_ho = 0;
     std::vector<hipEvent_t> ev_in, ev_done;
-    // bytes: the batch as RGB (d_in, d_out, h_out); in_bytes: the batch as the caller hands it over (h_in) - planar YUV frames may be larger than RGB
-    int ensure(size_t bytes, size_t in_bytes, bool host_in, bool host_out, int chunks) {
+    // bytes: the batch as RGB (d_in, d_out); in_bytes / out_bytes: the batch as the caller hands it over (h_in) / takes it back (h_out) - planar
+    // YUV frames may be larger than RGB
+    int ensure(size_t bytes, size_t in_bytes, size_t out_bytes, bool host_in, bool host_out, int chunks) {
         if (!s_in) {
             PB_HIP(hipStreamCreateWithFlags(&s_in, hipStreamNonBlocking));
             PB_HIP(hipStreamCreateWithFlags(&s_out, hipStreamNonBlocking));
@@ -96,11 +97,11 @@ struct MaskPipe {
             PB_HIP(hipHostMalloc(&h_in, in_bytes, hipHostMallocDefault));
             cap_hi = in_bytes;
         }
-        if (host_out && bytes > cap_ho) {
+        if (host_out && out_bytes > cap_ho) {
             if (h_out) PB_HIP(hipHostFree(h_out));
             h_out = nullptr; cap_ho = 0;
-            PB_HIP(hipHostMalloc(&h_out, bytes, hipHostMallocDefault));
-            cap_ho = bytes;
+            PB_HIP(hipHostMalloc(&h_out, out_bytes, hipHostMallocDefault));
+            cap_ho = out_bytes;
         }
         while ((int)ev_in.size() < chunks) {
             hipEvent_t a, b;
@@ -157,10 +158,12 @@ struct pb_ctx {
     // Work on one stream runs in order, so chunks and submissions share them; they grow only while the stream is idle.
     // pb_set_option("rgb_out_full"): the flow bands' rgb_out holds frames of the clip's size, resized (resize.hip) out of yuv[1] as well.
     // pb_set_frame_format: frames_i420 != 0 says the frames are planar YUV, frame_fmt which ("frames_i420" sets {420, 8, limited, BT.601}).
+    // pb_set_out_format: the same for rgb_out - rgb_out_i420 != 0 says it is planar YUV, out_fmt which ("rgb_out_i420" sets {420, 8, limited,
+    // BT.601}).  yuv[2]: the resized RGB frames of "rgb_out_full" on their way to a layout that has no fused resize kernel.
     int frames_i420 = 0, rgb_out_i420 = 0, rgb_out_full = 0;
-    pb_yuv_fmt frame_fmt = {420, 8, 0, PB_YUV_BT601};
-    void *yuv[2] = {};
-    size_t yuv_cap[2] = {};
+    pb_yuv_fmt frame_fmt = {420, 8, 0, PB_YUV_BT601}, out_fmt = {420, 8, 0, PB_YUV_BT601};
+    void *yuv[3] = {};
+    size_t yuv_cap[3] = {};
     int yuv_grow(int k, size_t need) {
         if (need <= yuv_cap[k]) return 0;
         PB_HIP(hipStreamSynchronize(stream));

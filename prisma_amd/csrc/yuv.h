@@ -20,6 +20,23 @@ int64_t yuv_frame_bytes(const pb_yuv_fmt &f, int H, int W);       // 0 for a bad
 void yuv_coeffs(const pb_yuv_fmt &f, int32_t out[7]);             // cy, crv, cgu, cgv, cbu, yoff, coff of a good format
 int launch_yuv_to_rgb(hipStream_t s, const pb_yuv_fmt &f, const uint8_t *yuv, int n, int H, int W, uint8_t *rgb);
 
+// yuv_out.hip: RGB to every one of those layouts, the way out (include/prisma_bands.h pb_rgb_to_yuv has the rule).  {420, 8, limited, BT.601} runs
+// launch_rgb_to_i420.
+void yuv_fwd_coeffs(const pb_yuv_fmt &f, int32_t out[12]);        // yr, yg, yb, ur, ug, h, vg, vb, F, yoff, coff, 2^d - 1 of a good format
+int launch_rgb_to_yuv(hipStream_t s, const pb_yuv_fmt &f, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv);
+
+// ---- what the kernels of yuv_formats.hip and yuv_out.hip share ------------------------------------------------------------------------------------
+struct YuvLayout {  // plane geometry of one frame: samples of BPS bytes, chroma planes subsampled by 2^SX x 2^SY (none with MONO)
+    int ch, cw;
+    size_t luma, chroma, bytes;
+    __host__ __device__ YuvLayout(int H, int W, int bps, int sx, int sy, bool mono)
+        : ch((H + (1 << sy) - 1) >> sy), cw((W + (1 << sx) - 1) >> sx) {
+        luma = (size_t)H * W * bps;
+        chroma = mono ? 0 : (size_t)ch * cw * bps;
+        bytes = luma + 2 * chroma;
+    }
+};
+
 // ---- what the kernels of yuv.hip and resize.hip share -------------------------------------------------------------------------------------------
 struct I420Frame {  // plane geometry of one I420 frame
     int H, W, ch, cw;

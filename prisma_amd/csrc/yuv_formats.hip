@@ -19,16 +19,7 @@ namespace {
 
 struct Coeffs { int cy, crv, cgu, cgv, cbu, yoff, coff, half, d; };
 
-struct Layout {  // plane geometry of one frame: samples of BPS bytes, chroma planes subsampled by 2^SX x 2^SY (none with MONO)
-    int ch, cw;
-    size_t luma, chroma, bytes;
-    __host__ __device__ Layout(int H, int W, int bps, int sx, int sy, bool mono)
-        : ch((H + (1 << sy) - 1) >> sy), cw((W + (1 << sx) - 1) >> sx) {
-        luma = (size_t)H * W * bps;
-        chroma = mono ? 0 : (size_t)ch * cw * bps;
-        bytes = luma + 2 * chroma;
-    }
-};
+using Layout = YuvLayout;
 
 // sample i of a run held in 32-bit words
 template <int BPS>

@@ -56,6 +56,14 @@ def yuv_coeffs(fmt: YuvFormat) -> Tuple[int, ...]:
     return tuple(out)
 
 
+def yuv_fwd_coeffs(fmt: YuvFormat) -> Tuple[int, ...]:
+    """(yr, yg, yb, ur, ug, h, vg, vb, F, yoff, coff, 2^d - 1) of the library's integer RGB -> YUV conversion to layout `fmt` (pb_yuv_fwd_coeffs,
+    needs no GPU)"""
+    out = (C.c_int32 * 12)()
+    check(_lib.load().pb_yuv_fwd_coeffs(C.byref(YuvFormat(*fmt).c()), out))
+    return tuple(int(v) for v in out)
+
+
 FORMATS = ("rgb", "i420")       # what `frames` / the encoded `rgb` results of a band context are: [..., H, W, 3] or [..., i420_bytes(H, W)] uint8
 
 
@@ -309,6 +317,27 @@ class _Ctx:
         """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_yuv_to_rgb_dev): sync() waits"""
         check(self.lib.pb_yuv_to_rgb_dev(self.ctx, C.byref(YuvFormat(*fmt).c()), C.c_void_p(yuv_ptr), n, H, W, C.c_void_p(rgb_ptr)))
 
+    # RGB -> any planar .y4m layout (pb_rgb_to_yuv: exact integers, tests/yuv_out_ref.py restates them)
+    def rgb_to_yuv(self, fmt: YuvFormat, rgb: np.ndarray, out: Optional[np.ndarray] = None) -> np.ndarray:
+        """RGB uint8 [n, H, W, 3] (or one frame [H, W, 3]) -> frames of layout `fmt`, uint8 [n, yuv_bytes(fmt, H, W)] ([yuv_bytes]; a 16-bit
+        sample is two bytes, little-endian); `out`: the caller's own (page-locked) array"""
+        fmt = YuvFormat(*fmt)
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert rgb.ndim in (3, 4) and rgb.shape[-1] == 3, rgb.shape
+        H, W = rgb.shape[-3:-1]
+        fb = yuv_bytes(fmt, H, W)
+        if fb <= 0:
+            raise ValueError("no such YUV format: %r" % (fmt,))
+        shape = rgb.shape[:-3] + (fb,)
+        yuv = np.empty(shape, np.uint8) if out is None else out
+        assert yuv.shape == shape and yuv.dtype == np.uint8 and yuv.flags.c_contiguous
+        check(self.lib.pb_rgb_to_yuv(self.ctx, C.byref(fmt.c()), _ptr(rgb), rgb.size // (H * W * 3), H, W, _ptr(yuv)))
+        return yuv
+
+    def rgb_to_yuv_dev(self, fmt: YuvFormat, rgb_ptr: int, n: int, H: int, W: int, yuv_ptr: int):
+        """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_rgb_to_yuv_dev): sync() waits"""
+        check(self.lib.pb_rgb_to_yuv_dev(self.ctx, C.byref(YuvFormat(*fmt).c()), C.c_void_p(rgb_ptr), n, H, W, C.c_void_p(yuv_ptr)))
+
     def i420_to_rgb_dev(self, yuv_ptr: int, n: int, H: int, W: int, rgb_ptr: int):
         """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_i420_to_rgb_dev): sync() waits"""
         check(self.lib.pb_i420_to_rgb_dev(self.ctx, C.c_void_p(yuv_ptr), n, H, W, C.c_void_p(rgb_ptr)))
@@ -338,6 +367,7 @@ class _Ctx:
     # "rgb" (the default) or "i420" - pb_set_option "frames_i420" / "rgb_out_i420".  With frame_format = "i420" those calls take
     # [n, i420_bytes(H, W)] arrays and need `size=(H, W)`; with rgb_format = "i420" their rgb arrays are [..., i420_bytes(h, w)] of the output size.
     # frame_format also takes a YuvFormat (pb_set_frame_format): the calls then take [n, yuv_bytes(fmt, H, W)] arrays of that layout's planes.
+    # rgb_format does too (pb_set_out_format): their rgb arrays are then [..., yuv_bytes(fmt, h, w)] of the output size.
     @property
     def frame_format(self):
         return self._formats[0]
@@ -352,12 +382,17 @@ class _Ctx:
         self._formats[0] = fmt
 
     @property
-    def rgb_format(self) -> str:
+    def rgb_format(self):
         return self._formats[1]
 
     @rgb_format.setter
-    def rgb_format(self, fmt: str):
-        self._set_format(1, "rgb_out_i420", fmt)
+    def rgb_format(self, fmt):
+        if isinstance(fmt, str):
+            self._set_format(1, "rgb_out_i420", fmt)
+            return
+        fmt = YuvFormat(*fmt)
+        check(self.lib.pb_set_out_format(self.ctx, C.byref(fmt.c())))       # a refusal leaves the context and this attribute as they were
+        self._formats[1] = fmt
 
     # flow bands: their `rgb` results have the clip's H x W instead of the band's sh x sw (pb_set_option "rgb_out_full": resized on the GPU, what
     # a video of the clip's size holds); flow, masks and max displacements stay at sh x sw
@@ -390,7 +425,9 @@ class _Ctx:
 
     def rgb_shape(self, h: int, w: int) -> tuple:
         """trailing shape of one encoded result frame in the context's rgb_format"""
-        return (i420_bytes(h, w),) if self.rgb_format == "i420" else (h, w, 3)
+        if self.rgb_format == "rgb":
+            return (h, w, 3)
+        return (i420_bytes(h, w),) if self.rgb_format == "i420" else (yuv_bytes(self.rgb_format, h, w),)
 
     def _flow_rgb_shape(self, H: int, W: int, sh: int, sw: int) -> tuple:
         """trailing shape of one encoded frame of a flow call: the band's sh x sw, or with rgb_full the clip's H x W"""

@@ -38,7 +38,7 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
-from bands.common.io import get_image_size, get_video_data  # noqa: E402
+from bands.common.io import get_image_size, get_video_data, y4m_out  # noqa: E402
 from bands.common.meta import (add_band, create_metadata, get_record3d_data, is_video, load_metadata,  # noqa: E402
                                set_default_band, update_metadata, write_metadata)
 
@@ -224,9 +224,22 @@ def main(argv=None):
     parser.add_argument("--jobs", "-j", help="Bands of one input run side by side, this many at a time", type=int, default=1)
     parser.add_argument("--gpus", "-g", help="GPUs of this node every video band shards its frames across (default $PRISMA_GPUS, else 1)",
                         type=int, default=int(os.environ.get("PRISMA_GPUS") or 1))
+    parser.add_argument("--y4m_out", help="Layout of the .y4m videos the bands write: a C tag, then ,full and / or ,bt709 (C444p12,full is lossless, "
+                        "Cmono,full for grey bands), or `source`; default 8-bit 4:2:0 limited BT.601 (sets PRISMA_Y4M_OUT for the bands)",
+                        type=str, default=None, metavar="FORMAT")
     args = parser.parse_args(argv)
     if args.jobs < 1 or args.gpus < 1:
         parser.error("--jobs and --gpus must be at least 1")
+    if args.y4m_out is not None:
+        before = os.environ.get("PRISMA_Y4M_OUT")
+        os.environ["PRISMA_Y4M_OUT"] = args.y4m_out        # the band subprocesses inherit it; the rgba band still copies a .y4m input as it is
+        try:
+            y4m_out()
+        except RuntimeError as e:
+            os.environ.pop("PRISMA_Y4M_OUT")
+            if before is not None:
+                os.environ["PRISMA_Y4M_OUT"] = before
+            parser.error("--y4m_out: %s" % e)
     del COMMANDS[:]
     del RESULTS[:]
 
