@@ -764,6 +764,10 @@ int pb_op_mask_band_accumulate(pb_ctx *ctx, const float *sig, const uint8_t *use
  *   holds token t.  lo_off: the rounding residual at half lo_off (lo8 = 0) or the e4m3 parts at bytes 2 lo_off / 3 lo_off (lo8 = 1, scale 2^*lo8_pa,
  *   the engine's); o8_off: e4m3(hi o8_scale) at byte o8_off of the row.
  * depth_attention: q, k, v [B, heads, N, 64] -> (B ntp + guard) rows of ldo halfs, ntp = N rounded up to 16; variant 1: the 8-wave kernel, 2: the 4-wave one.
+ * depth_preprocess: frames u8 [n, H, W, 3] -> one launch of the pre-process kernel for all n frames with both outputs: chw [n, 3, net_h, net_w] float32
+ *   and patch_raw, the fused 14 x 14 im2col: round_up(n P, 256) + guard_rows rows of 640 halfs (P = net_h / 14 x net_w / 14), row (b, gy, gx), column
+ *   c 196 + py 14 + px.  mode 0: the relative band (pb_depth_net_size, cubic taps); 1: the metric band (392 x 518, align-corners bilinear taps); the
+ *   tables are built by the engine's own functions, net_h / net_w must be the mode's.
  * depth_cls_rows: -> the residual stream (B ntp + guard) x D floats, of which only row 0 of every image is written.
  * depth_dpt_tail: z [B, H, W, 288] in pixels of ldz halfs, layout 0 [hi], 1 [hi | lo], 2 [hi | hi8 | lo8] (parts 320 wide) -> B OH OW + guard floats.
  * depth_resize_minmax: net [B, nh, nw] -> out B H W + guard floats, mnmx [B, 2] the decoded per-frame min / max.
@@ -774,6 +778,8 @@ int pb_op_depth_layernorm(pb_ctx *ctx, const float *x, const float *g, const flo
                           int o8_off, float o8_scale, int lo8, int guard_rows, void *out, int *lo8_pa);
 int pb_op_depth_attention(pb_ctx *ctx, const float *q, const float *k, const float *v, int B, int heads, int N, int variant, int ldo, int o8_off,
                           float o8_scale, int guard_rows, void *out);
+int pb_op_depth_preprocess(pb_ctx *ctx, const uint8_t *frames, int n, int H, int W, int mode, int net_h, int net_w, int guard_rows, float *chw,
+                           void *patch_raw);
 int pb_op_depth_cls_rows(pb_ctx *ctx, const float *cls, const float *pos, int B, int ntp, int D, int guard_rows, float *out);
 int pb_op_depth_dpt_tail(pb_ctx *ctx, const float *z, const float *bias, const float *w2, float b2, int B, int H, int W, int OH, int OW, int layout,
                          int ldz, int guard, float *out, int *lo8_pa);

@@ -218,7 +218,8 @@ SYMBOLS = {
     "pb_op_mask_band_accumulate": (C.c_int, [_P, _P, _P] + [C.c_int] * 7 + [C.c_float, C.c_int, _P, _P]),
     "pb_op_depth_layernorm": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 8 + [C.c_float, C.c_int, C.c_int, _P, _P]),
     "pb_op_depth_attention": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 6 + [C.c_float, C.c_int, _P]),
-    "pb_op_depth_cls_rows": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P]),
+    "pb_op_depth_preprocess": (C.c_int, [_P, _P] + [C.c_int] * 7 + [_P, _P]),
+    "pb_op_depth_cls_rows":(C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P]),
     "pb_op_depth_dpt_tail": (C.c_int, [_P, _P, _P, _P, C.c_float] + [C.c_int] * 8 + [_P, _P]),
     "pb_op_depth_resize_minmax": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
     "pb_op_zoe_softplus": (C.c_int, [_P, _P] + [C.c_int] * 4),

@@ -12,6 +12,7 @@
 #include "yuv.h"
 
 void pb_cubic_taps(int src, int dst, int *idx, float *wt);   // engine.hip
+void pb_bilinear_ac_taps(int src, int dst, int *idx, float *wt);   // engine.hip: the metric band's align-corners table, 4 taps of which two weigh 0
 
 #define PB_TRY(expr) do { int _r = (expr); if (_r) return _r; } while (0)
 

@@ -902,6 +902,30 @@ class DepthOpEngine : public MaskOpEngine {
         return finish(out, dout, bytes);
     }
 
+    // launch_preprocess as DepthEngine::run_chunk issues it - one launch for all n frames, the tap tables of DepthEngine::prepare (mode 0:
+    // pb_cubic_taps, mode 1: pb_bilinear_ac_taps) - with BOTH outputs: chw [n, 3, nh, nw] and the im2col rows of patchA_, 640 halfs wide,
+    // round_up(n P, 256) + guard of them, raw
+    int preprocess(const uint8_t *frames, int n, int H, int W, int mode, int nh, int nw, int guard, float *chw, void *patch) {
+        std::vector<int> xi((size_t)nw * 4), yi((size_t)nh * 4);
+        std::vector<float> xw((size_t)nw * 4), yw((size_t)nh * 4);
+        if (mode) { pb_bilinear_ac_taps(W, nw, xi.data(), xw.data()); pb_bilinear_ac_taps(H, nh, yi.data(), yw.data()); }
+        else { pb_cubic_taps(W, nw, xi.data(), xw.data()); pb_cubic_taps(H, nh, yi.data(), yw.data()); }
+        for (int v : xi) PB_CHECK(v >= 0 && v < W, PB_ERR_STATE, "op_depth_preprocess: x tap %d outside a row of %d pixels", v, W);
+        for (int v : yi) PB_CHECK(v >= 0 && v < H, PB_ERR_STATE, "op_depth_preprocess: y tap %d outside %d rows", v, H);
+        const int Kp = 640;
+        const int64_t P = (int64_t)(nh / 14) * (nw / 14), rows = round_up((int64_t)n * P, 256) + guard;
+        const size_t cb = (size_t)n * 3 * nh * nw * 4, pbytes = (size_t)rows * Kp * 2;
+        DevMem df, dxi, dxw, dyi, dyw, dchw, dpatch;
+        PB_TRY(up(df, frames, (size_t)n * H * W * 3));
+        PB_TRY(up(dxi, xi.data(), xi.size() * 4)); PB_TRY(up(dxw, xw.data(), xw.size() * 4));
+        PB_TRY(up(dyi, yi.data(), yi.size() * 4)); PB_TRY(up(dyw, yw.data(), yw.size() * 4));
+        PB_TRY(preset(dchw, cb)); PB_TRY(preset(dpatch, pbytes));
+        PB_TRY(launch_preprocess(stream, df.as<uint8_t>(), n, H, W, nh, nw, dxi.as<int>(), dxw.as<float>(), dyi.as<int>(), dyw.as<float>(), dpatch.as<f16>(), Kp,
+                                 dchw.as<float>()));
+        PB_TRY(finish(chw, dchw, cb));
+        return down(patch, dpatch, pbytes);
+    }
+
     int cls_rows(const float *cls, const float *pos, int B, int ntp, int D, int guard, float *out) {
         DevMem dc, dp, dr;
         PB_TRY(up(dc, cls, (size_t)D * 4)); PB_TRY(up(dp, pos, (size_t)D * 4));
@@ -2084,6 +2108,17 @@ int pb_op_depth_attention(pb_ctx *c, const float *q, const float *k, const float
              "op_depth_attention: fp8 copy at byte %d outside a row of %d halfs", o8_off, ldo);
     DEPTH_OP_ENGINE(e);
     return e.attention(q, k, v, B, heads, N, variant, ldo, o8_off, o8_scale, guard_rows, out);
+}
+int pb_op_depth_preprocess(pb_ctx *c, const uint8_t *frames, int n, int H, int W, int mode, int net_h, int net_w, int guard_rows, float *chw, void *patch_raw) {
+    PB_CHECK(c && frames && chw && patch_raw && n > 0 && H > 0 && W > 0 && (mode == 0 || mode == 1) && guard_rows >= 0, PB_ERR_ARG,
+             "op_depth_preprocess: bad arguments (mode 0: the relative band's cubic table, 1: the metric band's align-corners table)");
+    int nh = 392, nw = 518;
+    if (mode == 0) PB_TRY(pb_depth_net_size(H, W, &nh, &nw));
+    PB_CHECK(nh == net_h && nw == net_w, PB_ERR_ARG, "op_depth_preprocess: net size is %dx%d, caller passed %dx%d", nh, nw, net_h, net_w);
+    PB_CHECK((int64_t)n * H * W * 3 < (1LL << 31) && (int64_t)n * 3 * nh * nw < (1LL << 31), PB_ERR_ARG, "op_depth_preprocess: %d frames of %dx%d are too many for one launch",
+             n, H, W);
+    DEPTH_OP_ENGINE(e);
+    return e.preprocess(frames, n, H, W, mode, nh, nw, guard_rows, chw, patch_raw);
 }
 int pb_op_depth_cls_rows(pb_ctx *c, const float *cls, const float *pos, int B, int ntp, int D, int guard_rows, float *out) {
     PB_CHECK(c && cls && pos && out && B > 0 && ntp > 0 && D > 0 && guard_rows >= 0, PB_ERR_ARG, "op_depth_cls_rows: bad arguments");

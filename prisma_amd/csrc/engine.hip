@@ -275,6 +275,15 @@ void pb_cubic_taps(int src, int dst, int *idx, float *wt) {
     memcpy(wt, w.data(), w.size() * 4);
 }
 
+// (external linkage, as pb_cubic_taps: pb_op_depth_preprocess builds the metric band's table with the function prepare() uses)
+void pb_bilinear_ac_taps(int src, int dst, int *idx, float *wt) {
+    std::vector<int> i;
+    std::vector<float> w;
+    bilinear_ac_taps(src, dst, i, w);
+    memcpy(idx, i.data(), i.size() * 4);
+    memcpy(wt, w.data(), w.size() * 4);
+}
+
 int pb_depth_net_size(int H, int W, int *net_h, int *net_w) {
     PB_CHECK(H > 0 && W > 0 && net_h && net_w, PB_ERR_ARG, "net_size: bad arguments");
     // bands/d_anything/util/transform.py:100-166, lower_bound / keep_aspect_ratio / multiple of 14 / target 518

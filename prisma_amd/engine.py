@@ -1225,6 +1225,19 @@ class Ops(_Ctx):
         check(self.lib.pb_op_depth_attention(self.ctx, _ptr(q), _ptr(k), _ptr(v), B, Hh, N, variant, ldo, o8_off, o8_scale, guard_rows, _ptr(out)))
         return out
 
+    def depth_preprocess(self, frames, metric: bool = False, guard_rows: int = 8):
+        """frames uint8 [n, H, W, 3] -> (chw float32 [n, 3, nh, nw], raw uint8 [round_up(n P, 256) + guard, 1280]: the im2col rows of 640 halfs);
+        one launch with both outputs, the relative band's cubic table or (metric) the align-corners table to 392 x 518"""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, H, W, c = frames.shape
+        assert c == 3
+        nh, nw = (392, 518) if metric else net_size(H, W)
+        rows = -(-(n * (nh // 14) * (nw // 14)) // 256) * 256 + guard_rows
+        chw = np.empty((n, 3, nh, nw), np.float32)
+        raw = np.empty((rows, 1280), np.uint8)
+        check(self.lib.pb_op_depth_preprocess(self.ctx, _ptr(frames), n, H, W, int(metric), nh, nw, guard_rows, _ptr(chw), _ptr(raw)))
+        return chw, raw
+
     def depth_cls_rows(self, cls, pos, B: int, ntp: int, guard_rows: int = 2) -> np.ndarray:
         """-> raw float32 [B ntp + guard, D]: the residual stream, preset, after cls_rows"""
         cls, pos = _f32(cls), _f32(pos)

@@ -888,3 +888,202 @@ def pil_verify(what, raw, x, H, W, guard: int = GUARD):
     got = raw[:n].reshape(x.shape[0], H, W)
     same_bytes(what + ": bit-equal to PIL.Image.resize", got, pil_truth(x, H, W))
     same_bytes(what + ": bit-equal to zoe_oracle.pil_resize_f32", got, np.stack([Z.pil_resize_f32(m, H, W) for m in x]))
+
+
+# =====================================================================================================================
+# pre-process (elementwise.hip preprocess_kernel): u8 frames -> normalised CHW + the fused 14 x 14 im2col, both tap tables
+# =====================================================================================================================
+PREP_CASES = {              # mode -> frame sizes (H, W); two frames each, one at 2160 x 3840
+    "cubic": [(1, 1), (2, 3),           # every tap clamps
+              (7, 13), (96, 128),       # upscale
+              (600, 333),               # portrait, the network is not square
+              (1080, 1920)],
+    "metric": [(1, 1), (1, 7), (5, 1), (2, 3),      # scale 0 on one or both axes
+               (392, 518),              # the identity table: lambda = 0 everywhere
+               (393, 519), (360, 640), (1080, 1920), (2160, 3840)],
+}
+PREP_SAT = (7, 13)                      # the saturating frames: all 0, then all 255
+PREP_KP = 640                           # halfs per im2col row (DepthEngine's patchA_), 588 of them live
+PREP_ROUNDINGS = 13                     # product, 3 adds, product, 3 adds, 1 / 255 and its product, the subtract, 1 / std and its product
+PREP_MEAN = np.array([0.485, 0.456, 0.406])
+PREP_STD = np.array([0.229, 0.224, 0.225])
+PREP_BUGS = {"cubic": ["a_half", "no_half", "no_clamp", "swap_xy", "bgr", "norm_rot", "pypx"],
+             "metric": ["align", "coord64", "swap_xy", "bgr", "norm_rot", "pypx"]}
+
+
+def prep_net(mode: str, H: int, W: int):
+    if mode == "metric":
+        return Z.NET_H, Z.NET_W
+    from oracle import depth_oracle as O
+    nw, nh = O.net_size(W, H)
+    return nh, nw
+
+
+def prep_frames_n(H: int, W: int) -> int:
+    return 1 if H * W >= 2160 * 3840 else 2
+
+
+_PREP_CACHE = {}
+
+
+def prep_data(mode: str, H: int, W: int) -> np.ndarray:
+    """seeded uint8 frames [n, H, W, 3], every frame its own noise (the hardest content for a resize: no two taps agree), with a patch of
+    0 and a patch of 255 where there is room; shared, read-only"""
+    key = ("data", mode, H, W)
+    if key not in _PREP_CACHE:
+        g = rng(700 + 7 * H + W + (1 if mode == "metric" else 0))
+        f = g.integers(0, 256, (prep_frames_n(H, W), H, W, 3), dtype=np.uint8)
+        if H >= 6 and W >= 6:
+            f[0, :H // 3, :W // 3] = 0
+            f[-1, -(H // 3):, -(W // 3):] = 255
+        f.setflags(write=False)
+        _PREP_CACHE[key] = f
+    return _PREP_CACHE[key]
+
+
+def prep_sat_data() -> np.ndarray:
+    f = np.zeros((2,) + PREP_SAT + (3,), np.uint8)
+    f[1] = 255
+    return f
+
+
+def _cubic_table(src: int, dst: int, bug=None):
+    """oracle.depth_oracle.cubic_taps with room for the planted faults: A = -0.5, no half-pixel offset, taps that are not clamped (a tap
+    outside reads the other end of the row / column - some other pixel, as the memory next to the row would be)"""
+    from oracle import depth_oracle as O
+    if bug not in ("a_half", "no_half", "no_clamp"):
+        idx, w = O.cubic_taps(src, dst)
+        return idx.astype(np.int64), w.astype(F32)
+    scale = 1.0 / (dst / src)
+    d = np.arange(dst, dtype=np.float64)
+    fx = (d * scale if bug == "no_half" else (d + 0.5) * scale - 0.5).astype(F32)
+    sx = np.floor(fx).astype(np.int64)
+    fx = fx - sx.astype(F32)
+    raw = sx[:, None] + np.arange(-1, 3)[None, :]
+    idx = np.mod(raw, src) if bug == "no_clamp" else np.clip(raw, 0, src - 1)
+    if bug == "a_half":
+        A, one = F32(-0.5), F32(1)
+        c0 = ((A * (fx + one) - F32(5) * A) * (fx + one) + F32(8) * A) * (fx + one) - F32(4) * A
+        c1 = ((A + F32(2)) * fx - (A + F32(3))) * fx * fx + one
+        c2 = ((A + F32(2)) * (one - fx) - (A + F32(3))) * (one - fx) * (one - fx) + one
+        w = np.stack([c0, c1, c2, one - c0 - c1 - c2], -1).astype(F32)
+    else:
+        w = O._cubic_coeffs(fx)
+    return idx, w.astype(F32)
+
+
+def _ac_table(src: int, dst: int, bug=None):
+    """engine.hip bilinear_ac_taps: torch's align_corners=True rule for float32 input as four taps (i0, i1, i1, i1) weighing
+    (1 - lambda, lambda, 0, 0), the coordinate in float32.  bugs: 'align' (align_corners=False), 'coord64' (the coordinate in float64)"""
+    if bug == "coord64":
+        s = (src - 1) / (dst - 1) * np.arange(dst, dtype=np.float64) if dst > 1 else np.zeros(dst)
+        i0 = np.minimum(s.astype(np.int64), src - 1)
+        i1, l = i0 + (i0 < src - 1), (s - i0).astype(F32)
+    else:
+        i0, i1, l = ac_taps(dst, src, "align" if bug == "align" else None)
+        l = l.astype(F32)
+    idx = np.stack([i0, i1, i1, i1], -1).astype(np.int64)
+    w = np.zeros((dst, 4), F32)
+    w[:, 0] = F32(1) - l
+    w[:, 1] = l
+    return idx, w
+
+
+def prep_tables(mode: str, H: int, W: int, bug=None):
+    """-> (yi [nh, 4], yw float32 [nh, 4], xi [nw, 4], xw float32 [nw, 4]).  bug 'swap_xy': each axis' table built for the other axis'
+    source length (indices held inside the frame)"""
+    nh, nw = prep_net(mode, H, W)
+    tab = _cubic_table if mode == "cubic" else _ac_table
+    tb = bug if bug in ("a_half", "no_half", "no_clamp", "align", "coord64") else None
+    sh, sw = (W, H) if bug == "swap_xy" else (H, W)
+    yi, yw = tab(sh, nh, tb)
+    xi, xw = tab(sw, nw, tb)
+    return np.minimum(yi, H - 1), yw, np.minimum(xi, W - 1), xw
+
+
+def _prep_resize(p, tables, absw=False):
+    """p [n, H, W, 3] float64 -> [n, nh, nw, 3]: sum_ty sum_tx wy wx p in float64 with the float32 weights (their moduli with absw)"""
+    yi, yw, xi, xw = tables
+    yw, xw = yw.astype(np.float64), xw.astype(np.float64)
+    if absw:
+        yw, xw = np.abs(yw), np.abs(xw)
+    tmp = sum(p[:, :, xi[:, t]] * xw[None, None, :, t, None] for t in range(4))
+    return sum(tmp[:, yi[:, t]] * yw[None, :, t, None, None] for t in range(4))
+
+
+def prep_truth(frames, mode: str):
+    """-> (truth [n, 3, nh, nw] float64, tolerance of the same shape).  The tables are the reference's own - oracle.depth_oracle.cubic_taps
+    with float32 coefficients; torch's float32 align_corners=True index rule - every value operation is float64:
+    (sum w p / 255 - mean) / std.  tolerance = 13 x 2^-24 x (sum |w_y| |w_x| p / 255 + mean) / std, element-wise: 13 float32 roundings on the
+    kernel's longest path (PREP_ROUNDINGS), each no larger than 2^-24 of the magnitude it rounds; contraction into FMAs only removes some"""
+    n, H, W, _ = frames.shape
+    key = ("truth", mode, H, W) if frames is _PREP_CACHE.get(("data", mode, H, W)) else None
+    if key in _PREP_CACHE:
+        return _PREP_CACHE[key]
+    tables = prep_tables(mode, H, W)
+    p = frames.astype(np.float64) / 255.0
+    ref = ((_prep_resize(p, tables) - PREP_MEAN) / PREP_STD).transpose(0, 3, 1, 2)
+    mag = ((_prep_resize(p, tables, absw=True) + PREP_MEAN) / PREP_STD).transpose(0, 3, 1, 2)
+    out = (np.ascontiguousarray(ref), PREP_ROUNDINGS * U24 * np.ascontiguousarray(mag))
+    if key:
+        _PREP_CACHE[key] = out
+    return out
+
+
+def prep_patch_rows(chw, bug=None) -> np.ndarray:
+    """chw float32 [n, 3, nh, nw] -> float16 [n P, 588]: row (b, gy, gx), column c 196 + py 14 + px.  bug 'pypx': px 14 + py"""
+    n, _, nh, nw = chw.shape
+    gh, gw = nh // 14, nw // 14
+    t = chw.reshape(n, 3, gh, 14, gw, 14)                        # b c gy py gx px
+    t = t.transpose(0, 2, 4, 1, 5, 3) if bug == "pypx" else t.transpose(0, 2, 4, 1, 3, 5)
+    return np.ascontiguousarray(t).reshape(n * gh * gw, 588).astype(np.float16)
+
+
+def prep_raw_rows(n: int, nh: int, nw: int, guard: int = GUARD) -> int:
+    return -(-(n * (nh // 14) * (nw // 14)) // 256) * 256 + guard
+
+
+def prep_restated(frames, mode: str, guard: int = GUARD, bug=None):
+    """preprocess_kernel operation by operation in numpy float32 (no FMA): r = sum_tx float(p) wx, acc = sum_ty r wy, both from 0 in tap
+    order; v = (acc (1 / 255) - mean) (1 / std) with the three constants rounded to float32 -> (chw float32 [n, 3, nh, nw], raw uint8
+    [round_up(n P, 256) + guard, 1280]).  bugs: the table faults of prep_tables / _cubic_table / _ac_table, 'bgr' (channels reversed),
+    'norm_rot' (mean / std of the next channel), 'pypx' (the im2col column px 14 + py)"""
+    n, H, W, _ = frames.shape
+    nh, nw = prep_net(mode, H, W)
+    yi, yw, xi, xw = prep_tables(mode, H, W, bug)
+    acc = np.zeros((n, nh, nw, 3), F32)
+    for ty in range(4):
+        rows = frames[:, yi[:, ty]]                              # [n, nh, W, 3] uint8
+        r = np.zeros((n, nh, nw, 3), F32)
+        for tx in range(4):
+            r = (r + rows[:, :, xi[:, tx]].astype(F32) * xw[None, None, :, tx, None]).astype(F32)
+        acc = (acc + r * yw[None, :, ty, None, None]).astype(F32)
+    if bug == "bgr":
+        acc = acc[..., ::-1]
+    mean, istd = PREP_MEAN.astype(F32), (F32(1) / PREP_STD.astype(F32)).astype(F32)
+    if bug == "norm_rot":
+        mean, istd = np.roll(mean, -1), np.roll(istd, -1)
+    v = ((acc * (F32(1) / F32(255)) - mean).astype(F32) * istd).astype(F32)
+    chw = np.ascontiguousarray(v.transpose(0, 3, 1, 2))
+    raw = raw_rows(prep_raw_rows(n, nh, nw, guard), 2 * PREP_KP)
+    raw.view(np.float16)[:n * (nh // 14) * (nw // 14), :588] = prep_patch_rows(chw, bug)
+    return chw, raw
+
+
+def prep_verify(what, chw, raw, frames, mode: str, guard: int = GUARD, ref=None, tol=None) -> dict:
+    """chw against float64 truth within the derived bound; the im2col rows bit-equal to fp16 of the SAME chw (both are stores of one
+    register); columns 588 .. 639, the rows behind n P and the guard rows still 0xFF.  ref / tol: another truth for the same frames (the
+    saturating case's constants)"""
+    n, H, W, _ = frames.shape
+    nh, nw = prep_net(mode, H, W)
+    P = (nh // 14) * (nw // 14)
+    assert chw.shape == (n, 3, nh, nw) and chw.dtype == F32, (what, chw.shape, chw.dtype)
+    assert raw.shape == (prep_raw_rows(n, nh, nw, guard), 2 * PREP_KP) and raw.dtype == np.uint8, (what, raw.shape)
+    if ref is None:
+        ref, tol = prep_truth(frames, mode)
+    out = {"value": check(what + ": chw vs float64 (sum w p / 255 - mean) / std", chw, ref, tol)}
+    preset(what + ": rows behind the last patch and guard rows", raw[n * P:])
+    h = raw[:n * P].view(np.float16)
+    preset(what + ": columns 588 .. 639", h[:, 588:])
+    same_bytes(what + ": im2col [(b, gy, gx), c 196 + py 14 + px] = fp16 of the kernel's own chw", h[:, :588], prep_patch_rows(chw))
+    return out

@@ -167,3 +167,41 @@ def test_zoe_pil_resize(ops, size):
     measured: bits equal."""
     x = R.pil_data()
     R.pil_verify("zoe_pil_resize %dx%d" % size, ops.zoe_pil_resize(x, *size, R.GUARD), x, *size)
+
+
+# ---- pre-process ----
+@pytest.mark.parametrize("case", [(m, s) for m, sizes in R.PREP_CASES.items() for s in sizes], ids=lambda c: "%s-%dx%d" % ((c[0],) + c[1]))
+def test_preprocess_both_outputs(ops, case):
+    """launch_preprocess as DepthEngine::run_chunk issues it - one launch for both frames (one at 2160 x 3840), the tap tables of
+    DepthEngine::prepare (cubic: pb_cubic_taps to pb_depth_net_size; metric: bilinear_ac_taps to 392 x 518) - with BOTH outputs.  chw against
+    float64 truth on the reference's own tables at 13 x 2^-24 x (sum |w_y| |w_x| p / 255 + mean) / std, element-wise (13 roundings on the longest
+    path, depth_ref.prep_truth); the im2col rows of 640 halfs bit-equal to fp16 of the kernel's own chw; columns 588 .. 639, the rows behind
+    n P and the guard rows still 0xFF.  Sizes: every tap clamped (1 x 1, 2 x 3), scale 0 on an axis, the identity table, 4K.
+    measured: chw err / tol <= 0.306 (cubic: 4.0 of the 13 roundings), <= 0.224 (metric: 2.9 of 13); every byte check equal."""
+    mode, (H, W) = case
+    frames = R.prep_data(mode, H, W)
+    chw, raw = ops.depth_preprocess(frames, mode == "metric", R.GUARD)
+    R.prep_verify("preprocess %s %dx%d" % (mode, H, W), chw, raw, frames, mode)
+
+
+@pytest.mark.parametrize("mode", list(R.PREP_CASES))
+def test_preprocess_saturating_frames(ops, mode):
+    """a frame of 0 and a frame of 255, 7 x 13: every output is the constant (p / 255 - mean) / std of its channel within the same bound
+    (a tap set's float32 weights sum to 1 only to rounding), the im2col bytes as above.
+    measured: err / tol <= 0.216 (cubic), <= 0.219 (metric); bytes equal."""
+    frames = R.prep_sat_data()
+    _, tol = R.prep_truth(frames, mode)
+    ref = ((frames[:, 0, 0].astype("float64") / 255 - R.PREP_MEAN) / R.PREP_STD)[:, :, None, None] + 0 * tol
+    chw, raw = ops.depth_preprocess(frames, mode == "metric", R.GUARD)
+    R.prep_verify("preprocess %s saturated" % mode, chw, raw, frames, mode, ref=ref, tol=tol)
+
+
+def test_preprocess_refuses_bad_arguments(ops):
+    """a net size that is not the mode's, a mode that does not exist, no frames: PB_ERR_ARG before any launch"""
+    import numpy as np
+    frames = R.prep_sat_data()
+    chw, raw = np.empty((2, 3, 392, 518), np.float32), np.empty((R.prep_raw_rows(2, 392, 518), 1280), np.uint8)
+    call = lambda n, mode, nh, nw, guard: ops.lib.pb_op_depth_preprocess(ops.ctx, engine._ptr(frames), n, 7, 13, mode, nh, nw, guard, engine._ptr(chw), engine._ptr(raw))   # noqa: E731
+    assert call(2, 1, 392, 518, R.GUARD) == 0
+    for bad in ((2, 1, 518, 392, R.GUARD), (2, 0, 392, 518, R.GUARD), (2, 2, 392, 518, R.GUARD), (0, 1, 392, 518, R.GUARD), (2, 1, 392, 518, -1)):
+        assert call(*bad) == -1, bad
