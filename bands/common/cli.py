@@ -7,7 +7,7 @@ import sys
 from prisma_amd import shard
 
 from .io import check_overwrite
-from .meta import get_target, get_url, is_video, load_metadata, merge_metadata
+from .meta import band_video_ext, get_target, get_url, is_video, load_metadata, merge_metadata, video_out
 
 
 def begin(args, band, flow=False):
@@ -15,6 +15,10 @@ def begin(args, band, flow=False):
     depth and mask write a PNG for a still image and say that they found the metadata; the flow bands (flow=True) take videos only, resolve --mask
     to args.output_mask and make their --subpath / --subpath_mask dump folders absolute.  Returns (data, loaded, meta_path, ranks): the metadata, a
     deep copy of it as loaded (merge_metadata's base), where it lives, and shard.Ranks() after rank 0's check_overwrite."""
+    try:
+        video_out()         # a PRISMA_VIDEO_OUT nobody can write is refused here, before a model loads
+    except RuntimeError as e:
+        raise SystemExit(f"[{band}] {e}")
     meta_path = args.input
     data = load_metadata(meta_path)
     loaded = copy.deepcopy(data)
@@ -26,7 +30,7 @@ def begin(args, band, flow=False):
         if flow and args.mask:
             args.output_mask = get_target(args.input, data, band=band + "_mask")
     elif not args.output:
-        ext = os.path.basename(args.input).rsplit(".", 1)[1]
+        ext = band_video_ext(args.input)       # the clip's own, or PRISMA_VIDEO_OUT's
         args.output = os.path.join(os.path.dirname(args.input), band + "." + (ext if flow or is_video(args.input) else "png"))
     if flow and not is_video(args.output):
         raise SystemExit(f"[{band}] needs a video input")

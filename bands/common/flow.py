@@ -6,7 +6,7 @@ import numpy as np
 
 from prisma_amd import engine
 
-from .io import FrameReader, VideoWriter, is_y4m, write_flo, write_flow_png, y4m_out
+from .io import FrameReader, VideoWriter, is_planar, planar_out, write_flo, write_flow_png
 from .loop import Stream, frame_formats, run_sharded, stream_enabled
 from .yuv import yuv_bytes
 
@@ -41,12 +41,14 @@ def process_video(args, band, model, data, rk, chunk, subpath_needs_both, iterat
     # rescale: a .y4m has the clip's w x h like the reference's videos (its VideoWriter rescales every frame, io.py:297), not the band's sw x sh;
     # a .npy stack has no declared size and keeps the band's, an .mp4 is rescaled by PyAV as ever
     # the layout of every .y4m written: PRISMA_Y4M_OUT's (io.y4m_out), I420 when unset
-    ofmt = y4m_out(getattr(src, "format", None)) if any(is_y4m(f) for f in files.values()) else None
-    videos = {k: VideoWriter(width=w, height=h, frame_rate=src.rate, filename=f, rescale=True, fmt=ofmt) for k, f in files.items()} if rk.main else {}
+    # (an .avi / .mjpeg: the JPEG's planes, PRISMA_VIDEO_OUT's subsampling)
+    ofmt = planar_out(args.output, getattr(src, "format", None))
+    videos = ({k: VideoWriter(width=w, height=h, frame_rate=src.rate, filename=f, rescale=True, fmt=ofmt, device=rk.device) for k, f in files.items()}
+              if rk.main else {})
     # a .y4m on either side: its planes go to / come from the engine as they are - at --scale != 1 resized to the clip's size on the GPU, next
     # to the conversion (engine rgb_full).  The mask videos and the trailing zero frame are small and rare: they are converted, and
     # resized, on the host (VideoWriter.write)
-    yin, yout = src.i420, is_y4m(args.output)
+    yin, yout = src.i420, is_planar(args.output)
     fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None), ofmt)
     model.rgb_full = yout and (sh, sw) != (h, w)
     rh, rw = (h, w) if model.rgb_full else (sh, sw)      # the size of the engine's rgb frames

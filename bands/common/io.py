@@ -23,12 +23,18 @@ quantises it.  Properties of the two rules, checked over all 2^24 colours (tests
 either range and matrix, returns every RGB byte the band produced - C444p12,full is the lossless choice, 6 bytes per pixel; at 10 bits up to
 2.2 % of the colours come back off by 1, at 8 bits 75 - 84 % by up to 2; a grey value through Cmono,full comes back exactly - the choice for the
 mask videos, one byte per pixel.  A header has no tag for the matrix: a file written with `,bt709` is read back with PRISMA_Y4M_MATRIX=bt709.
+
+.avi / .mjpeg (Motion JPEG) is the compressed container that needs no library either: every frame a complete baseline .jpg, encoded on the GPU
+(pb_jpeg_encode; there is no host encoder), an AVI 1.0 file around them or nothing at all.  PRISMA_VIDEO_OUT (process.py --video_out; common/meta.py
+video_out) makes every derived band video one: `avi` or `mjpeg`, then `,q=NN` and one of `,444` `,420` `,mono`.  The frames are planes of JFIF's
+colour space - 8 bit, full range, BT.601 (jpeg_format) - which the engines deliver like a .y4m layout (planar_out).  Read back with Pillow.
 """
 import os
 from fractions import Fraction
 
 import numpy as np
 
+from .meta import VIDEO_OUT_EXTS, video_out
 from .resize import resize_rgb
 from .yuv import I420, Format, i420_bytes, rgb_to_yuv, yuv_bytes, yuv_to_rgb
 
@@ -121,6 +127,35 @@ def get_video_data(path):
 
 def is_y4m(path):
     return bool(path) and path.endswith(".y4m")
+
+
+def is_mjpeg(path):
+    """a Motion JPEG file of this writer: an AVI of JPEG frames, or their bare concatenation"""
+    return bool(path) and path.endswith(tuple("." + e for e in VIDEO_OUT_EXTS))
+
+
+def is_planar(path):
+    """the file's frames are planes a VideoWriter takes as they are (write_planes) and an engine delivers (rgb_format): .y4m, .avi, .mjpeg"""
+    return is_y4m(path) or is_mjpeg(path)
+
+
+JPEG_CHROMAS = (444, 420, 400)
+
+
+def jpeg_format(chroma=444):
+    """the layout of the planes a JPEG frame is made of - JFIF's colour space: 8 bit, full range, BT.601"""
+    return Format(int(chroma), 8, True, "bt601")
+
+
+def planar_out(path, source=None):
+    """the layout of the frames written to `path`: PRISMA_Y4M_OUT's for a .y4m (y4m_out), the JPEG planes of PRISMA_VIDEO_OUT's subsampling (4:4:4
+    when it names none) for an .avi / .mjpeg, None for every other file"""
+    if is_y4m(path):
+        return y4m_out(source)
+    if is_mjpeg(path):
+        vo = video_out()
+        return jpeg_format(vo.chroma if vo else 444)
+    return None
 
 
 def y4m_header(width, height, rate, fmt=None):
@@ -246,8 +281,187 @@ class Y4MFile:
             pass
 
 
+AVI_MAX = 2 ** 31 - 1       # an AVI 1.0 file is one RIFF chunk; readers take its 32-bit sizes and offsets as signed
+AVI_MOVI = 220              # where the `movi` fourcc lies in a file of this writer: idx1 offsets count from it
+
+
+def _avi_header(width, height, rate, frames=0, max_frame=0, movi_bytes=0, riff_bytes=0):
+    """the 224 bytes in front of the first frame chunk: RIFF AVI, LIST hdrl (avih, LIST strl (strh vids / MJPG, strf BITMAPINFOHEADER)), LIST movi"""
+    import struct
+    usec = (1000000 * rate.denominator + rate.numerator // 2) // rate.numerator
+    per_sec = (max_frame * rate.numerator + rate.denominator - 1) // rate.denominator
+    avih = struct.pack("<14I", usec, min(per_sec, 2 ** 32 - 1), 0, 0x10, frames, 0, 1, max_frame, width, height, 0, 0, 0, 0)
+    strh = struct.pack("<4s4sIHHIIIIIIII4h", b"vids", b"MJPG", 0, 0, 0, 0, rate.denominator, rate.numerator, 0, frames, max_frame, 0xFFFFFFFF, 0,
+                       0, 0, width, height)
+    strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+    chunk = lambda tag, body: tag + struct.pack("<I", len(body)) + body      # noqa: E731
+    strl = b"strl" + chunk(b"strh", strh) + chunk(b"strf", strf)
+    hdrl = b"hdrl" + chunk(b"avih", avih) + chunk(b"LIST", strl)
+    head = b"RIFF" + struct.pack("<I", riff_bytes) + b"AVI " + chunk(b"LIST", hdrl) + b"LIST" + struct.pack("<I", 4 + movi_bytes) + b"movi"
+    assert len(head) == AVI_MOVI + 4
+    return head
+
+
+class GpuJpegEncoder:
+    """The encoder a Motion JPEG VideoWriter makes for itself: a GPU context of its own (the band's is busy, and the writer runs on the sink
+    thread), pb_jpeg_encode on page-locked buffers.  encoder(planes [n, frame bytes] uint8, H, W, chroma, quality) -> the n frames' bytes, views
+    that hold until the next call.  There is no host fallback: without a GPU the context cannot be made."""
+
+    def __init__(self, device=0):
+        from prisma_amd import engine
+        self._engine, self._ctx, self._out = engine, engine.Ops(device=device), None
+
+    def host_empty(self, shape, dtype):
+        return self._ctx.host_empty(shape, dtype)
+
+    def _room(self, nbytes):
+        if self._out is None or self._out.size < nbytes:
+            if self._out is not None:
+                self._ctx.host_free(self._out)
+            self._out = self._ctx.host_empty(int(nbytes), np.uint8)
+        return self._out
+
+    def __call__(self, planes, H, W, chroma, quality):
+        n = len(planes)
+        out = self._room(max(1 << 16, planes.size // 2))      # frames are a fraction of their planes; grown to what they need when they are not
+        try:
+            out, offs = self._ctx.jpeg_encode(planes, H, W, chroma, quality, out=out)
+        except self._engine.JpegOverflow as e:
+            out, offs = self._ctx.jpeg_encode(planes, H, W, chroma, quality, out=self._room(e.needed + e.needed // 4))
+        return [out[offs[i]:offs[i + 1]] for i in range(n)]
+
+    def close(self):
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = self._out = None
+
+
+def _jpeg_end(buf, pos):
+    """the position behind the EOI of the JPEG frame that starts at buf[pos] (SOI): its segments walked by their lengths, its entropy-coded data
+    scanned for a marker that is neither a stuffed 0xFF nor RSTm - SOI / EOI byte pairs inside a segment's payload are not looked at"""
+    if buf[pos:pos + 2] != b"\xff\xd8":
+        raise RuntimeError("no JPEG frame (SOI) at byte %d" % pos)
+    pos += 2
+    while True:
+        if pos + 2 > len(buf) or buf[pos] != 0xFF:
+            raise RuntimeError("broken JPEG frame: no marker at byte %d" % pos)
+        m = buf[pos + 1]
+        if m == 0xD9:
+            return pos + 2
+        if pos + 4 > len(buf):
+            raise RuntimeError("broken JPEG frame: it ends inside the segment at byte %d" % pos)
+        pos += 2 + int.from_bytes(buf[pos + 2:pos + 4], "big")
+        if m != 0xDA:
+            continue
+        while True:                     # entropy-coded data
+            pos = buf.find(b"\xff", pos)
+            if pos < 0 or pos + 1 >= len(buf):
+                raise RuntimeError("broken JPEG frame: the entropy-coded data does not end")
+            if buf[pos + 1] == 0x00 or 0xD0 <= buf[pos + 1] <= 0xD7:
+                pos += 2
+                continue
+            break                       # a marker: EOI, or another segment (a further scan)
+
+
+class MjpegFile:
+    """The container side of an .avi (AVI 1.0 with an `MJPG` video stream and an idx1 index - what VideoWriter writes; anything else is refused by
+    name) or a bare .mjpeg stream: .width / .height / .rate (Fraction; None for a bare stream, which carries none) / len() / frame(i) -> the
+    JPEG's bytes."""
+
+    def __init__(self, path):
+        import mmap
+        import struct
+        self.path, self.rate = path, None
+        self._f = open(path, "rb")
+        self._buf = mmap.mmap(self._f.fileno(), 0, access=mmap.ACCESS_READ) if os.fstat(self._f.fileno()).st_size else b""
+        buf = self._buf
+        self._spans = []
+        if path.endswith(".avi"):
+            if buf[:4] != b"RIFF" or buf[8:12] != b"AVI ":
+                raise RuntimeError("%s: not an AVI file (no `RIFF ... AVI ` header)" % path)
+            chunks, movi = {}, None
+
+            def walk(lo, hi):
+                nonlocal movi
+                while lo + 8 <= hi:
+                    tag, size = bytes(buf[lo:lo + 4]), struct.unpack("<I", buf[lo + 4:lo + 8])[0]
+                    if tag == b"LIST":
+                        kind = bytes(buf[lo + 8:lo + 12])
+                        if kind == b"movi":
+                            movi = lo + 8
+                        else:
+                            walk(lo + 12, lo + 8 + size)
+                    else:
+                        chunks.setdefault(tag, (lo + 8, size))
+                    lo += 8 + size + (size & 1)
+            walk(12, len(buf))
+            if b"RIFF" in chunks or b"indx" in chunks:
+                raise RuntimeError("%s: an OpenDML AVI (AVIX / indx) - this reader has AVI 1.0 with an idx1 index only" % path)
+            if movi is None or b"strh" not in chunks or b"strf" not in chunks or b"idx1" not in chunks:
+                raise RuntimeError("%s: an AVI without a movi list, a stream header or an idx1 index - this reader has AVI 1.0 MJPG files with idx1 only" % path)
+            sh, sf = chunks[b"strh"][0], chunks[b"strf"][0]
+            kind, codec = bytes(buf[sh:sh + 4]), bytes(buf[sf + 16:sf + 20])
+            if kind != b"vids" or codec.upper() != b"MJPG":
+                raise RuntimeError("%s: the first stream is %r / %r - this reader decodes Motion JPEG (`vids` / `MJPG`) only" % (path, kind, codec))
+            scale, rate = struct.unpack("<II", buf[sh + 20:sh + 28])
+            self.rate = Fraction(rate, scale) if rate and scale else None
+            self.width, self.height = struct.unpack("<ii", buf[sf + 4:sf + 12])
+            at, size = chunks[b"idx1"]
+            for k in range(size // 16):
+                tag, _flags, off, ln = struct.unpack("<4sIII", buf[at + 16 * k:at + 16 * k + 16])
+                if tag != b"00dc":
+                    continue
+                if bytes(buf[movi + off:movi + off + 4]) != b"00dc" or struct.unpack("<I", buf[movi + off + 4:movi + off + 8])[0] != ln:
+                    raise RuntimeError("%s: idx1 entry %d does not point at a `00dc` chunk of its size (offsets count from the movi list)" % (path, k))
+                self._spans.append((movi + off + 8, ln))
+        else:
+            pos = 0
+            while pos < len(buf):
+                try:
+                    end = _jpeg_end(buf, pos)
+                except RuntimeError as e:
+                    raise RuntimeError("%s: frame %d: %s" % (path, len(self._spans), e)) from e
+                self._spans.append((pos, end - pos))
+                pos = end
+            if self._spans:
+                from PIL import Image
+                import io as _io
+                with Image.open(_io.BytesIO(self.frame(0))) as im:
+                    self.width, self.height = im.size
+            else:
+                self.width = self.height = 0
+
+    def __len__(self):
+        return len(self._spans)
+
+    def frame(self, i):
+        at, ln = self._spans[i]
+        return bytes(self._buf[at:at + ln])
+
+    def decode(self, i):
+        """frame i as uint8 [H, W, 3] RGB: Pillow's decode of the frame's bytes"""
+        import io as _io
+        from PIL import Image
+        with Image.open(_io.BytesIO(self.frame(i))) as im:
+            return np.asarray(im.convert("RGB"))
+
+    def close(self):
+        if self._f is not None:
+            if self._buf:
+                self._buf.close()
+            self._f.close()
+            self._f = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # noqa: BLE001
+            pass
+
+
 class FrameReader:
-    """len() / [i] -> uint8 HxWx3 RGB; fps.  decord for .mp4 (reference), numpy memmap for .npy, Y4MFile for .y4m.
+    """len() / [i] -> uint8 HxWx3 RGB; fps.  decord for .mp4 (reference), numpy memmap for .npy, Y4MFile for .y4m, MjpegFile for .avi /
+    .mjpeg (Motion JPEG as VideoWriter writes it, decoded with Pillow on the host).
     .rate is what a VideoWriter of the band's output takes: the exact Fraction of a .y4m source, else fps.
     .i420: the source holds planar YUV frames (.y4m) - then .width / .height are known without a decode, .format is their layout (common/yuv.py
     Format; I420 for the usual clip) and .frame_bytes their size, read_i420(i, out) copies frame i's planes as they are into the caller's
@@ -264,6 +478,11 @@ class FrameReader:
             self.read_i420 = self._y4m.read_i420
             self._n = len(self._y4m)
             self._get = lambda i: yuv_to_rgb(self.format, self._y4m.read_i420(i, np.empty(self.frame_bytes, np.uint8)), self.height, self.width)
+        elif is_mjpeg(path):
+            self._mj = MjpegFile(path)
+            self._n, self._get = len(self._mj), self._mj.decode
+            if self._mj.rate is not None:
+                self.fps = self._mj.rate.numerator / self._mj.rate.denominator
         elif path.endswith(".npy"):
             self._a = np.load(path, mmap_mode="r")
             assert self._a.ndim == 4 and self._a.shape[-1] == 3 and self._a.dtype == np.uint8
@@ -281,6 +500,9 @@ class FrameReader:
 
     @property
     def rate(self):
+        mj = getattr(self, "_mj", None)
+        if mj is not None and mj.rate is not None:
+            return mj.rate
         return self._y4m.rate if self.i420 else self.fps
 
     def __len__(self):
@@ -297,11 +519,32 @@ class VideoWriter:
     layout (the engines' rgb_format results; write_i420 is the same for an I420 writer).
     rescale=True (a .y4m writer's; the flow bands pass it, whose frames are `--scale` times the clip's): the video has the width and height
     the writer was opened with, as the reference's has (io.py:297 rescales every frame to them).  write() resizes a frame of another size
-    on the host (common/resize.py: bilinear with two taps, where PyAV's reformat runs swscale's), write_i420 takes frames of that size only."""
+    on the host (common/resize.py: bilinear with two taps, where PyAV's reformat runs swscale's), write_i420 takes frames of that size only.
 
-    def __init__(self, width, height, frame_rate, filename, rescale=False, fmt=None):
-        self.filename, self._frames, self._av, self._y4m = filename, None, None, None
+    .avi / .mjpeg -> Motion JPEG: baseline JPEG frames of `quality` (None: PRISMA_VIDEO_OUT's, 90 without one) made of planes of layout `fmt`
+    (None: planar_out's - 4:4:4 unless PRISMA_VIDEO_OUT says otherwise; always 8 bit, full range, BT.601: JFIF's colour space), which write_planes
+    takes as a .y4m writer does and write() converts to; rescale as above.  Frames are gathered `group` at a time and encoded in one call of
+    `encoder(planes [n, bytes], H, W, chroma, quality) -> n byte strings` - by default a GpuJpegEncoder on `device`, made with the first frame;
+    there is no host fallback (tests pass tests/jpeg_ref.py's).  .avi is AVI 1.0: RIFF AVI, hdrl (avih, one strl: vids / MJPG, dwRate / dwScale the
+    exact rate, BITMAPINFOHEADER), movi of `00dc` chunks padded to even, idx1; frames are appended as they come, 16 index bytes per frame are kept
+    and the counts and sizes patched into the headers by close().  The file is one RIFF: a frame that would take it past 2 GiB raises (OpenDML is
+    not written); the frames of its group that were not yet written are dropped with it, and close() still leaves a valid file of what fits.  .mjpeg is the bare concatenation of the frames, of any length (`ffmpeg -framerate R -i x.mjpeg`)."""
+
+    def __init__(self, width, height, frame_rate, filename, rescale=False, fmt=None, quality=None, encoder=None, group=8, device=0):
+        self.filename, self._frames, self._av, self._y4m, self._mj = filename, None, None, None, None
         self.i420 = is_y4m(filename)
+        if is_mjpeg(filename):
+            vo = video_out()
+            self.format = planar_out(filename) if fmt is None else Format(*fmt)
+            self.quality = int(quality if quality is not None else (vo.quality if vo else 90))
+            if self.format != jpeg_format(self.format[0]) or self.format[0] not in JPEG_CHROMAS or not 1 <= self.quality <= 100:
+                raise ValueError("%s: a JPEG frame is made of 8-bit full-range BT.601 planes, 4:4:4, 4:2:0 or mono, at quality 1 .. 100 - not %r at %r"
+                                 % (filename, tuple(self.format), self.quality))
+            self._rate, self._size, self._rescale = as_rate(frame_rate), (int(height), int(width)) if rescale else None, bool(rescale)
+            self._encoder, self._own_encoder, self._device, self._group, self._held, self._buf = encoder, False, device, max(1, int(group)), 0, None
+            self._avi, self._index, self._count, self._max_frame = filename.endswith(".avi"), bytearray(), 0, 0
+            self._mj = open(filename, "wb")
+            return
         self.format = I420 if fmt is None else Format(*fmt)
         yuv_bytes(self.format, 1, 1)        # an unknown layout is refused here
         if self.i420:
@@ -337,6 +580,8 @@ class VideoWriter:
 
     def write_planes(self, yuv, height, width):
         """one frame of the writer's layout (uint8, yuv_bytes(format, height, width) bytes: the Y plane, then Cb and Cr if the layout has them)"""
+        if self._mj is not None:
+            return self._mj_planes(yuv, height, width)
         if self._y4m is None:
             raise RuntimeError("%s: write_planes is a .y4m writer's" % self.filename)
         if self._size is None:
@@ -351,8 +596,74 @@ class VideoWriter:
         self._y4m.write(memoryview(yuv))
         self._y4m.flush()
 
+    # ---- Motion JPEG ----
+    def _tell(self):
+        return self._mj.tell()
+
+    def _mj_planes(self, yuv, height, width):
+        if self._size is None:
+            self._size = (height, width)
+        fb = yuv_bytes(self.format, height, width)
+        yuv = np.asarray(yuv, np.uint8).reshape(-1)
+        if (height, width) != self._size or yuv.size != fb:
+            raise ValueError("%s: a %d x %d frame of %d bytes in a %d x %d video" % ((self.filename, height, width, yuv.size) + self._size))
+        if self._buf is None:           # the first frame: the encoder (a GPU context of the writer's own) and the group's buffer, page-locked if it can be
+            if self._encoder is None:
+                self._encoder, self._own_encoder = GpuJpegEncoder(self._device), True
+            alloc = getattr(self._encoder, "host_empty", np.empty)
+            self._buf = alloc((self._group, fb), np.uint8)
+            if self._avi:
+                self._mj.write(_avi_header(width, height, self._rate))
+        self._buf[self._held] = yuv
+        self._held += 1
+        if self._held == self._group:
+            self._mj_flush()
+
+    def _mj_flush(self):
+        if not self._held:
+            return
+        h, w = self._size
+        frames = self._encoder(self._buf[:self._held], h, w, self.format[0], self.quality)
+        self._held = 0
+        for f in frames:
+            f = memoryview(f).cast("B")
+            n = len(f)
+            if self._avi:
+                at = self._tell()
+                # the chunk, its pad byte, the index with this frame's entry: what the file would end as
+                if at + 8 + n + (n & 1) + 8 + len(self._index) + 16 > AVI_MAX:
+                    raise RuntimeError("%s: frame %d would take the file past 2 GiB, the limit of an AVI 1.0 file (one RIFF chunk; OpenDML is not "
+                                       "written): write `.mjpeg` (PRISMA_VIDEO_OUT=mjpeg: a bare stream of any length) or lower the quality (,q=NN)"
+                                       % (self.filename, self._count))
+                self._index += b"00dc" + (0x10).to_bytes(4, "little") + (at - AVI_MOVI).to_bytes(4, "little") + n.to_bytes(4, "little")
+                self._mj.write(b"00dc" + n.to_bytes(4, "little"))
+            self._mj.write(f)
+            if self._avi and n & 1:
+                self._mj.write(b"\0")
+            self._count += 1
+            self._max_frame = max(self._max_frame, n)
+        self._mj.flush()
+
+    def _mj_close(self):
+        try:
+            self._mj_flush()
+            if self._avi:
+                if self._buf is None:       # no frame was written: an empty video of the writer's size, if it has one
+                    h, w = self._size or (0, 0)
+                    self._mj.write(_avi_header(w, h, self._rate))
+                end = self._tell()
+                self._mj.write(b"idx1" + len(self._index).to_bytes(4, "little") + bytes(self._index))
+                total = self._tell()
+                h, w = self._size or (0, 0)
+                self._mj.seek(0)
+                self._mj.write(_avi_header(w, h, self._rate, self._count, self._max_frame, end - (AVI_MOVI + 4), total - 8))
+        finally:
+            self._mj.close()
+            if self._own_encoder:
+                self._encoder.close()
+
     def write(self, rgb):
-        if self._y4m is not None:
+        if self._y4m is not None or self._mj is not None:
             if self._rescale and tuple(rgb.shape[:2]) != self._size:
                 rgb = resize_rgb(rgb, *self._size)
             self.write_planes(rgb_to_yuv(self.format, np.asarray(rgb, np.uint8)), rgb.shape[0], rgb.shape[1])
@@ -366,6 +677,9 @@ class VideoWriter:
             self._av.mux(pkt)
 
     def close(self):
+        if self._mj is not None:
+            self._mj_close()
+            return
         if self._y4m is not None:
             self._y4m.close()
             return

@@ -72,7 +72,8 @@ class Stream:
 
 def frame_formats(model, yin, yout, h, w, layout=None, out_layout=None):
     """Tells a band's engine what the loop will hand it (`yin`: the source is a .y4m, its frames are planes of `layout`, the reader's .format -
-    I420 without one) and wants back (`yout`: the output is a .y4m, its frames planes of `out_layout`, io.y4m_out()'s - I420 without one):
+    I420 without one) and wants back (`yout`: the output is a .y4m, its frames planes of `out_layout`, io.y4m_out()'s - I420 without one -, or an
+    .avi / .mjpeg, whose JPEG frames are made of the planes io.planar_out() names):
     engine.frame_format / rgb_format.  -> the extra keyword arguments of the
     engine's calls: the frame size, which plane arrays do not carry.  With neither, nothing is touched and nothing is passed: the calls are what
     they were before .y4m."""

@@ -5,6 +5,7 @@ create_metadata :35-58, is_video :65-67, get_target :70-93, get_url :96-104, add
 write_metadata :124-134, set_default_band :137-146, get_record3d_data :148-156) - same function names,
 arguments and JSON layout, so files written by either implementation are interchangeable.
 """
+import collections
 import copy
 import fcntl
 import json
@@ -42,9 +43,43 @@ def create_metadata(path):
     return load_metadata(mp)
 
 
+VIDEO_OUT_EXTS = ("avi", "mjpeg")          # Motion JPEG containers the bands write (common/io.py VideoWriter)
+VIDEO_OUT_CHROMAS = {"444": 444, "420": 420, "mono": 400}
+VideoOut = collections.namedtuple("VideoOut", "ext quality chroma")
+
+
+def video_out():
+    """PRISMA_VIDEO_OUT (process.py --video_out): the container every derived video band is written in instead of the clip's own.  `avi` or
+    `mjpeg`, then optionally `,q=NN` (JPEG quality 1 .. 100, default 90) and one of `,444` `,420` `,mono` (default 444: the bands carry data in
+    their colours).  -> VideoOut(ext, quality, chroma 444 | 420 | 400), None when unset or empty; anything else is refused."""
+    v = os.environ.get("PRISMA_VIDEO_OUT", "")
+    if not v:
+        return None
+    ext, *opts = v.split(",")
+    bad = RuntimeError("PRISMA_VIDEO_OUT=%s: `avi` or `mjpeg`, then optionally `,q=NN` (1 .. 100) and one of `,444` `,420` `,mono`" % v)
+    if ext not in VIDEO_OUT_EXTS:
+        raise bad
+    quality, chroma = None, None
+    for o in opts:
+        if o.startswith("q=") and quality is None and o[2:].isdigit() and 1 <= int(o[2:]) <= 100:
+            quality = int(o[2:])
+        elif o in VIDEO_OUT_CHROMAS and chroma is None:
+            chroma = VIDEO_OUT_CHROMAS[o]
+        else:
+            raise bad
+    return VideoOut(ext, 90 if quality is None else quality, 444 if chroma is None else chroma)
+
+
+def band_video_ext(path):
+    """the extension of a video band derived from the clip `path`: PRISMA_VIDEO_OUT's when set, else the clip's own"""
+    vo = video_out()
+    return vo.ext if vo is not None and is_video(path) else os.path.basename(path).rsplit(".", 1)[1]
+
+
 def is_video(path):
-    # the reference tests the suffix only (:65-67); .npy frame stacks are this repo's offline stand-in, .y4m the container that needs no library
-    return path.endswith(".mp4") or path.endswith(".npy") or path.endswith(".y4m")
+    # the reference tests the suffix only (:65-67); .npy frame stacks are this repo's offline stand-in, .y4m the container that needs no library,
+    # .avi / .mjpeg the Motion JPEG files of PRISMA_VIDEO_OUT
+    return path.endswith((".mp4", ".npy", ".y4m", ".avi", ".mjpeg"))
 
 
 def add_band(metadata, band, url="", folder=""):
@@ -57,7 +92,8 @@ def add_band(metadata, band, url="", folder=""):
 
 def get_target(path, metadata, band="rgba", target="", force_extension=None):
     folder = target if os.path.isdir(target) else os.path.dirname(path)
-    ext = os.path.basename(path).rsplit(".", 1)[1]
+    # rgba keeps the clip's container: the other bands read it
+    ext = os.path.basename(path).rsplit(".", 1)[1] if band == "rgba" else band_video_ext(path)
     if force_extension and (not is_video(path) or force_extension == "csv"):
         ext = force_extension
     name = band + "." + ext

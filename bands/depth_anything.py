@@ -17,7 +17,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, create_folder, is_y4m, open_rgb, write_ply, write_rgb, y4m_out  # noqa: E402
+from common.io import FrameReader, VideoWriter, create_folder, is_planar, open_rgb, planar_out, write_ply, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.cli import begin, end, synthetic_or_exit  # noqa: E402
 from common.loop import Stream, frame_formats, run_sharded, stream_enabled  # noqa: E402
@@ -138,9 +138,10 @@ def process_video(a):
     src = FrameReader(a.input)
     n = len(src)
     h, w = src[0].shape[:2]
-    yin, yout = src.i420, is_y4m(a.output)      # a .y4m on either side: its planes go to / come from the engine as they are
-    ofmt = y4m_out(getattr(src, "format", None)) if yout else None      # the layout written: PRISMA_Y4M_OUT's, I420 when unset
-    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=a.output, fmt=ofmt) if rk.main else None
+    # a .y4m on either side, an .avi / .mjpeg out: its planes go to / come from the engine as they are
+    yin, yout = src.i420, is_planar(a.output)
+    ofmt = planar_out(a.output, getattr(src, "format", None))      # the layout written: PRISMA_Y4M_OUT's (I420 when unset), or the JPEG's planes
+    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=a.output, fmt=ofmt, device=rk.device) if rk.main else None
     out_bytes = yuv_bytes(ofmt, h, w) if yout else h * w * 3
     out_folder = os.path.dirname(a.output)
     if a.subpath:

@@ -18,7 +18,7 @@ for _p in (_ROOT, os.path.dirname(os.path.abspath(__file__))):
     if _p not in sys.path:
         sys.path.insert(0, _p)
 
-from common.io import FrameReader, VideoWriter, create_folder, is_y4m, open_rgb, write_rgb, y4m_out  # noqa: E402
+from common.io import FrameReader, VideoWriter, create_folder, is_planar, open_rgb, planar_out, write_rgb  # noqa: E402
 from common.ckpt import load_checkpoint  # noqa: E402
 from common.cli import begin, end, synthetic_or_exit  # noqa: E402
 from common.loop import Stream, frame_formats, run_sharded, stream_enabled  # noqa: E402
@@ -92,12 +92,12 @@ def process_video(args):
         args.subpath = os.path.join(os.path.dirname(args.output), args.subpath)
         create_folder(args.subpath)
     first, last = rk.frames(n)
-    ofmt = y4m_out(getattr(src, "format", None)) if is_y4m(args.output) else None      # the layout written: PRISMA_Y4M_OUT's, I420 when unset
-    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=args.output, fmt=ofmt) if rk.main else None
+    ofmt = planar_out(args.output, getattr(src, "format", None))      # the layout written: PRISMA_Y4M_OUT's (I420 when unset), or an .avi / .mjpeg's JPEG planes
+    out = VideoWriter(width=w, height=h, frame_rate=src.rate, filename=args.output, fmt=ofmt, device=rk.device) if rk.main else None
     set_sdf(args.sdf)
     # a .y4m on either side: its planes go to / come from the engine as they are - but the COLMAP dump needs the id images' red channel, so
     # with --subpath they come back as RGB and the video's frames are converted on the host
-    yin, yout = src.i420, is_y4m(args.output) and not args.subpath
+    yin, yout = src.i420, is_planar(args.output) and not args.subpath
     fmt = frame_formats(model, yin, yout, h, w, getattr(src, "format", None), ofmt)
     out_bytes = yuv_bytes(ofmt, h, w) if yout else h * w * 3
     frame = ((src.frame_bytes,), np.uint8) if yin else (src[0].shape, np.uint8)       # a .y4m's planes, in the clip's own layout

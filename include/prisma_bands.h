@@ -108,7 +108,8 @@ int pb_version(void);
 /* ABI guard: bumped whenever a public struct's layout or an entry point's signature changes.  A binding compares
  * pb_abi_version() with the PB_ABI_VERSION it was written against and pb_struct_size(which) with its own sizeof before the first
  * call (prisma_amd/_lib.py load(); integration/depth_anything_stub.py) - a stale binding fails at load, not by reading shifted
- * fields.  which: 0 pb_tensor, 1 pb_depth_cfg, 2 pb_flow_cfg, 3 pb_mask_cfg, 4 pb_kernel_stat, 5 pb_comm_id, 6 pb_yuv_fmt; -1 for others. */
+ * fields.  which: 0 pb_tensor, 1 pb_depth_cfg, 2 pb_flow_cfg, 3 pb_mask_cfg, 4 pb_kernel_stat, 5 pb_comm_id, 6 pb_yuv_fmt, 7 pb_jpeg_cfg;
+ * -1 for others. */
 #define PB_ABI_VERSION 3
 int pb_abi_version(void);
 int pb_struct_size(int which);
@@ -331,6 +332,45 @@ int pb_yuv_fwd_coeffs(const pb_yuv_fmt *fmt, int32_t out[12]);
 int pb_rgb_to_yuv(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
 int pb_rgb_to_yuv_dev(pb_ctx *ctx, const pb_yuv_fmt *fmt, const uint8_t *rgb, int n, int H, int W, uint8_t *yuv_out);
 int pb_set_out_format(pb_ctx *ctx, const pb_yuv_fmt *fmt);
+
+/* Baseline JPEG frames - a Motion JPEG video is their concatenation (`.mjpeg`) or an AVI of them.  One rule, exact integers; tests/jpeg_ref.py
+ * restates it and the kernels (jpeg.hip) give its bytes.
+ *   input     a frame's planes as pb_rgb_to_yuv of {chroma, 8, full_range = 1, PB_YUV_BT601} lays them out - JFIF's colour space; chroma 444, 420 or
+ *             400 (one component)
+ *   padding   every plane to whole MCUs (8 x 8 samples; at 420 16 x 16 of Y, 8 x 8 of Cb and Cr) by repeating its last column and row; s = sample - 128
+ *   DCT       F[v][u] = sum_y sum_x C[v][y] C[u][x] s[y][x],  C[u][x] = round(2^13 c(u) / 2 cos((2x + 1) u pi / 16)),  c(0) = 1 / sqrt 2, c(u) = 1
+ *             (C[0][x] = 2896; the others +- 4017 3784 3406 2896 2276 1567 799); nothing is rounded between the passes, |F| < 2^37
+ *   quantise  sign(F) ((|F| + D / 2) div D),  D = 2^26 Q: round half away from zero in one integer division
+ *   tables    Q = clamp((base s + 50) div 100, 1, 255) with base ITU-T T.81 Annex K.1 (Y) / K.2 (Cb, Cr) and s = 5000 div quality below 50, else
+ *             200 - 2 quality (the IJG scaling, quality 1 .. 100); Huffman tables Annex K.3 - K.6
+ *   coding    zigzag, then T.81 F.1.2: the DC difference to the previous block of the component inside the restart interval (0 at its start),
+ *             AC as (run, size) with ZRL and EOB; the blocks of an MCU in the order Y00 Y01 Y10 Y11 Cb Cr at 420
+ *   stream    SOI, APP0 (JFIF 1.01, density 1 : 1), one DQT per table, SOF0 (8 bit; components 1 2 3; sampling 1x1, or 2x2 1x1 1x1), one DHT per table
+ *             (DC, AC of table 0, then of table 1; 400 has table 0 only), DRI = the MCUs of one MCU row, SOS, the intervals with RST(m mod 8) after
+ *             interval m except the last, each padded to a whole byte with 1-bits and a 0x00 after every 0xFF byte, EOI.  Every frame is a complete
+ *             .jpg; a restart interval per MCU row is what makes the rows independent.
+ * pb_jpeg_bound: the worst-case bytes of one frame - the header, every block at 20 + 63 x 26 bits (208 bytes), every byte stuffed, the markers;
+ * 0 for a cfg outside the table or a side outside 1 .. 65535.  Needs no GPU.  Real frames are a small fraction of it: a caller may pass less and
+ * grow on overflow.
+ * pb_jpeg_encode: host pointers, blocking, in chunks of "host_chunk" frames (default 8) whose copies overlap the kernels; page-locked arrays are
+ * addressed directly, and only the bytes produced are copied back.  planes: n x pb_yuv_bytes({chroma, 8, 1, BT601}, H, W) bytes; out: capacity
+ * bytes, the frames back to back; offsets: n + 1 values, frame i is out[offsets[i] .. offsets[i + 1]).
+ * Overflow: offsets[] always holds the positions the frames need, so offsets[n] is the capacity that would do; a frame is written whole if its end
+ * lies within capacity and not at all otherwise (nothing past out[capacity - 1] is touched); the call then returns PB_ERR_MEMORY.
+ * pb_jpeg_encode_dev: device pointers (offsets too), asynchronous on the ctx stream, pb_sync() waits; the same rule, the caller compares
+ * offsets[n] with capacity.  No alignment is needed (with plane rows that are multiples of 16 bytes and a 16-byte aligned `planes` a lane loads 16
+ * bytes per access).  Work on any ctx; a cfg outside the table or a side outside 1 .. 65535 is PB_ERR_ARG before any launch.  So is a call too large for the
+ * encoder's 32-bit positions: a frame whose pb_jpeg_bound reaches 2^31 bytes (about 5.1 million blocks: 110 Mpixel at 4:4:4, 330 Mpixel mono) or
+ * n frames of 2^25 blocks and more together (split the call).  The ctx keeps a
+ * workspace of 353 bytes per 8 x 8 block (coefficients, offsets, the unstuffed stream) for the frames of one chunk (of the call, for _dev). */
+typedef struct pb_jpeg_cfg {
+    int32_t chroma;         /* 444, 420, 400 */
+    int32_t quality;        /* 1 .. 100 */
+} pb_jpeg_cfg;
+int64_t pb_jpeg_bound(const pb_jpeg_cfg *cfg, int H, int W);
+int pb_jpeg_encode(pb_ctx *ctx, const pb_jpeg_cfg *cfg, const uint8_t *planes, int n, int H, int W, uint8_t *out, int64_t capacity, int64_t *offsets);
+int pb_jpeg_encode_dev(pb_ctx *ctx, const pb_jpeg_cfg *cfg, const uint8_t *planes, int n, int H, int W, uint8_t *out, int64_t capacity,
+                       int64_t *offsets);
 
 /* Bilinear resize of RGB frames, 8 bit, exact integers, half-pixel centres (the geometry of swscale's SWS_BILINEAR, which the reference's
  * VideoWriter applies to every frame that is not of the video's size).  Per axis, for output index x of n_out from n_in samples:

@@ -56,6 +56,10 @@ class pb_yuv_fmt(C.Structure):
     _fields_ = [("chroma", C.c_int32), ("depth", C.c_int32), ("full_range", C.c_int32), ("matrix", C.c_int32)]
 
 
+class pb_jpeg_cfg(C.Structure):
+    _fields_ = [("chroma", C.c_int32), ("quality", C.c_int32)]
+
+
 YUV_MATRICES = ("bt601", "bt709")       # pb_yuv_fmt.matrix: PB_YUV_BT601, PB_YUV_BT709
 
 
@@ -116,6 +120,9 @@ SYMBOLS = {
     "pb_rgb_to_yuv": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_rgb_to_yuv_dev": (C.c_int, [_P, C.POINTER(pb_yuv_fmt), _P, C.c_int, C.c_int, C.c_int, _P]),
     "pb_set_out_format": (C.c_int, [_P, C.POINTER(pb_yuv_fmt)]),
+    "pb_jpeg_bound": (C.c_int64, [C.POINTER(pb_jpeg_cfg), C.c_int, C.c_int]),
+    "pb_jpeg_encode": (C.c_int, [_P, C.POINTER(pb_jpeg_cfg), _P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
+    "pb_jpeg_encode_dev": (C.c_int, [_P, C.POINTER(pb_jpeg_cfg), _P, C.c_int, C.c_int, C.c_int, _P, C.c_int64, _P]),
     "pb_rgb_resize": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "pb_rgb_resize_dev": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, C.c_int]),
     "pb_depth_net_size": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -258,7 +265,7 @@ def load():
     if lib.pb_abi_version() != ABI_VERSION:
         raise PrismaBandsError(f"{LIB_PATH}: ABI version {lib.pb_abi_version()}, this binding expects {ABI_VERSION} - rebuild the library "
                                "(make -C prisma_amd/csrc) or update prisma_amd/_lib.py")
-    for which, st in ((0, pb_tensor), (1, pb_depth_cfg), (2, pb_flow_cfg), (3, pb_mask_cfg), (4, pb_kernel_stat), (6, pb_yuv_fmt)):
+    for which, st in ((0, pb_tensor), (1, pb_depth_cfg), (2, pb_flow_cfg), (3, pb_mask_cfg), (4, pb_kernel_stat), (6, pb_yuv_fmt), (7, pb_jpeg_cfg)):
         if lib.pb_struct_size(which) != C.sizeof(st):
             raise PrismaBandsError(f"{LIB_PATH}: sizeof({st.__name__}) is {lib.pb_struct_size(which)} in the library, {C.sizeof(st)} in the binding")
     _lib = lib

@@ -165,6 +165,7 @@ int pb_struct_size(int which) {
         case 4: return (int)sizeof(pb_kernel_stat);
         case 5: return (int)sizeof(pb_comm_id);
         case 6: return (int)sizeof(pb_yuv_fmt);
+        case 7: return (int)sizeof(pb_jpeg_cfg);
         default: return -1;
     }
 }
@@ -338,6 +339,7 @@ void pb_destroy(pb_ctx *c) {
     c->pipe.release();
     c->mpipe.release();
     for (void *p : c->yuv) if (p) { hipStreamSynchronize(c->stream); hipFree(p); }
+    if (c->jpeg.ws || c->jpeg.d_in[0]) { hipStreamSynchronize(c->stream); c->jpeg.release(); }
     // pb_host_alloc blocks: the submissions that wrote into them were waited for above and the copy streams are drained and gone
     for (void *p : c->host_blocks) hipHostFree(p);
     if (c->depth) delete c->depth;
@@ -1065,6 +1067,80 @@ int pb_rgb_resize(pb_ctx *c, const uint8_t *rgb, int n, int sh, int sw, int H, i
     return run_chunks(c, n, cap, 0, lanes, 2, false, [&](int slot, int, int m) {
         return launch_rgb_resize(c->stream, (const uint8_t *)l[0].d[slot], m, sh, sw, H, W, (uint8_t *)l[1].d[slot], out_i420 != 0);
     });
+}
+
+// ---- baseline JPEG frames out of planar YUV (jpeg.hip) ---------------------------------------------------------------------------------------------
+#define PB_CHECK_JPEG(what, cfg, H, W)                                                                                                              \
+    do {                                                                                                                                            \
+        PB_CHECK(jpeg_cfg_ok(*(cfg)), PB_ERR_ARG, what ": no such format (chroma %d: 444, 420 or 400; quality %d: 1 .. 100)", (cfg)->chroma,       \
+                 (cfg)->quality);                                                                                                                   \
+        PB_CHECK((H) >= 1 && (W) >= 1 && (H) <= 65535 && (W) <= 65535, PB_ERR_ARG, what ": a %d x %d frame (a side is 1 .. 65535)", (H), (W));      \
+    } while (0)
+
+int64_t pb_jpeg_bound(const pb_jpeg_cfg *cfg, int H, int W) { return cfg ? jpeg_frame_bound(*cfg, H, W) : 0; }
+
+int pb_jpeg_encode_dev(pb_ctx *c, const pb_jpeg_cfg *cfg, const uint8_t *planes, int n, int H, int W, uint8_t *out, int64_t capacity,
+                       int64_t *offsets) {
+    PB_CHECK(c && cfg && planes && out && offsets && n > 0 && capacity >= 0, PB_ERR_ARG, "jpeg_encode: bad arguments");
+    PB_CHECK_JPEG("jpeg_encode", cfg, H, W);
+    PB_HIP(hipSetDevice(c->device));
+    return jpeg_encode_dev(c->jpeg, c->stream, *cfg, planes, n, H, W, out, capacity, offsets);
+}
+
+// Host-pointer variant: chunks of "host_chunk" (default 8) frames through two slots.  A chunk's planes go up on the pipe's copy-in stream while
+// the chunk before is encoded; its offsets come back first, and then exactly the bytes of the frames that fit, on the copy-out stream.  Page-locked
+// caller arrays are addressed by the copy engines directly; pageable ones go through the runtime's own staging (the copy then blocks this thread).
+int pb_jpeg_encode(pb_ctx *c, const pb_jpeg_cfg *cfg, const uint8_t *planes, int n, int H, int W, uint8_t *out, int64_t capacity, int64_t *offsets) {
+    PB_CHECK(c && cfg && planes && offsets && n > 0 && capacity >= 0 && (out || capacity == 0), PB_ERR_ARG, "jpeg_encode: bad arguments");
+    PB_CHECK_JPEG("jpeg_encode", cfg, H, W);
+    PB_CHECK(c->pending.empty(), PB_ERR_STATE, "jpeg_encode: a submission of this ctx is still outstanding (pb_wait first)");
+    PB_HIP(hipSetDevice(c->device));
+    const pb_jpeg_cfg f = *cfg;
+    const pb_yuv_fmt yf = {f.chroma, 8, 1, PB_YUV_BT601};
+    const size_t fb = (size_t)yuv_frame_bytes(yf, H, W);
+    const int64_t bound = jpeg_frame_bound(f, H, W);
+    const int per = std::min(n, c->host_chunk > 0 ? c->host_chunk : 8);
+    const int64_t dcap = std::max<int64_t>(std::min<int64_t>((int64_t)per * bound, capacity), 16);
+    ChunkPipe &p = c->pipe;
+    PB_TRY(p.ensure_streams());
+    PB_HIP(hipStreamSynchronize(c->stream));        // the slots may grow: nothing of an earlier _dev call may be in flight
+    JpegState &j = c->jpeg;
+    PB_TRY(j.grow_host((size_t)per * fb, (size_t)dcap, per));
+    PipeDrain drain{p.s_in, c->stream, p.s_out};
+    const int chunks = (n + per - 1) / per;
+    auto copy_in = [&](int i) -> int {
+        const int slot = i & 1, u0 = i * per, m = std::min(per, n - u0);
+        PB_HIP(hipStreamWaitEvent(p.s_in, p.ev_comp[slot], 0));        // the encode that last read this slot
+        PB_HIP(hipMemcpyAsync(j.d_in[slot], planes + (size_t)u0 * fb, (size_t)m * fb, hipMemcpyHostToDevice, p.s_in));
+        PB_HIP(hipEventRecord(p.ev_h2d[slot], p.s_in));
+        return 0;
+    };
+    int64_t total = 0;
+    offsets[0] = 0;
+    PB_TRY(copy_in(0));
+    for (int i = 0; i < chunks; ++i) {
+        const int slot = i & 1, u0 = i * per, m = std::min(per, n - u0);
+        const int64_t room = std::min<int64_t>(dcap, std::max<int64_t>(capacity - total, 0));
+        PB_HIP(hipStreamWaitEvent(c->stream, p.ev_h2d[slot], 0));
+        PB_HIP(hipStreamWaitEvent(c->stream, p.ev_d2h[slot], 0));      // the copy that last emptied this slot's stream buffer
+        PB_TRY(jpeg_encode_dev(j, c->stream, f, (const uint8_t *)j.d_in[slot], m, H, W, (uint8_t *)j.d_out[slot], room, j.d_offs[slot]));
+        PB_HIP(hipMemcpyAsync(j.h_offs[slot], j.d_offs[slot], (size_t)(m + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+        PB_HIP(hipEventRecord(p.ev_comp[slot], c->stream));
+        if (i + 1 < chunks) PB_TRY(copy_in(i + 1));
+        PB_HIP(hipEventSynchronize(p.ev_comp[slot]));
+        int64_t fit = 0;        // bytes of the chunk's frames that end within the caller's capacity: a prefix, the positions only grow
+        for (int k = 0; k < m; ++k) {
+            offsets[u0 + k + 1] = total + j.h_offs[slot][k + 1];
+            if (offsets[u0 + k + 1] <= capacity) fit = j.h_offs[slot][k + 1];
+        }
+        if (fit > 0) PB_HIP(hipMemcpyAsync(out + total, j.d_out[slot], (size_t)fit, hipMemcpyDeviceToHost, p.s_out));
+        PB_HIP(hipEventRecord(p.ev_d2h[slot], p.s_out));
+        total = offsets[u0 + m];
+    }
+    PB_HIP(hipStreamSynchronize(p.s_out));
+    PB_CHECK(total <= capacity, PB_ERR_MEMORY, "jpeg_encode: %d frames of %d x %d need %lld bytes, the buffer holds %lld (offsets[n] has the need)", n, H,
+             W, (long long)total, (long long)capacity);
+    return 0;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 #include "engine.h"
 #include "mask_engine.h"
 #include "flow_engine.h"
+#include "jpeg.h"
 #include "resize.h"
 #include "yuv.h"
 
@@ -177,4 +178,6 @@ struct pb_ctx {
     // pb_depth_point_cloud_dev: the per-frame min / max words of the un-flip, on the ctx stream (the host variant keeps its own in still_buf)
     unsigned *pcl_mm = nullptr;
     int pcl_mm_cap = 0;
+    // pb_jpeg_encode / pb_jpeg_encode_dev: the encoder's workspace and the slots of its host pipeline, on the ctx stream
+    JpegState jpeg;
 };

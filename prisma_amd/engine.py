@@ -64,6 +64,28 @@ def yuv_fwd_coeffs(fmt: YuvFormat) -> Tuple[int, ...]:
     return tuple(int(v) for v in out)
 
 
+JPEG_CHROMAS = (444, 420, 400)
+
+
+def jpeg_format(chroma: int) -> YuvFormat:
+    """the layout of the planes a JPEG of `chroma` is made of: JFIF's colour space"""
+    return YuvFormat(int(chroma), 8, True, "bt601")
+
+
+def jpeg_bound(chroma: int, quality: int, H: int, W: int) -> int:
+    """worst-case bytes of one JPEG frame (pb_jpeg_bound, needs no GPU); 0 for a chroma / quality / size the encoder does not have"""
+    return int(_lib.load().pb_jpeg_bound(C.byref(_lib.pb_jpeg_cfg(int(chroma), int(quality))), int(H), int(W)))
+
+
+class JpegOverflow(_lib.PrismaBandsError):
+    """jpeg_encode: the caller's buffer is too small.  .needed: the bytes that would do; .offsets: where every frame would lie - the frames that
+    end within the capacity are in the buffer."""
+
+    def __init__(self, msg, needed, offsets):
+        super().__init__(msg)
+        self.needed, self.offsets = needed, offsets
+
+
 FORMATS = ("rgb", "i420")       # what `frames` / the encoded `rgb` results of a band context are: [..., H, W, 3] or [..., i420_bytes(H, W)] uint8
 
 
@@ -337,6 +359,42 @@ class _Ctx:
     def rgb_to_yuv_dev(self, fmt: YuvFormat, rgb_ptr: int, n: int, H: int, W: int, yuv_ptr: int):
         """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_rgb_to_yuv_dev): sync() waits"""
         check(self.lib.pb_rgb_to_yuv_dev(self.ctx, C.byref(YuvFormat(*fmt).c()), C.c_void_p(rgb_ptr), n, H, W, C.c_void_p(yuv_ptr)))
+
+    # planar full-range BT.601 YUV -> baseline JPEG frames (pb_jpeg_encode: exact integers, tests/jpeg_ref.py restates them)
+    def jpeg_encode(self, planes: np.ndarray, H: int, W: int, chroma: int = 444, quality: int = 90, out: Optional[np.ndarray] = None,
+                    capacity: Optional[int] = None):
+        """frames of layout jpeg_format(chroma), uint8 [n, yuv_bytes] (or one frame [yuv_bytes]) -> (out, offsets): frame i is
+        out[offsets[i]:offsets[i + 1]], a complete .jpg; offsets int64 [n + 1].  `out`: the caller's own (page-locked) uint8 array, of which
+        `capacity` bytes (default: all) may be written - too small raises JpegOverflow.  Without `out` the buffer is sized here and grown once
+        if the frames need more."""
+        planes = np.ascontiguousarray(planes, np.uint8)
+        fb = yuv_bytes(jpeg_format(chroma), H, W)
+        if fb <= 0 or jpeg_bound(chroma, quality, H, W) <= 0:
+            raise ValueError("no such JPEG: chroma %r (one of %r), quality %r (1 .. 100), %r x %r" % (chroma, JPEG_CHROMAS, quality, H, W))
+        assert planes.ndim in (1, 2) and planes.shape[-1] == fb, (planes.shape, fb)
+        n = planes.size // fb
+        cfg = _lib.pb_jpeg_cfg(int(chroma), int(quality))
+        offsets = np.zeros(n + 1, np.int64)
+        own = out is None
+        if own:
+            out = np.empty(int(capacity) if capacity is not None else n * (fb // 2 + 1024), np.uint8)
+        assert out.dtype == np.uint8 and out.ndim == 1 and out.flags.c_contiguous
+        cap = out.size if capacity is None else int(capacity)
+        assert 0 <= cap <= out.size
+        rc = self.lib.pb_jpeg_encode(self.ctx, C.byref(cfg), _ptr(planes), n, int(H), int(W), _ptr(out), cap, _ptr(offsets))
+        if rc < 0 and int(offsets[n]) > cap:
+            if not own:
+                raise JpegOverflow(self.lib.pb_last_error().decode(), int(offsets[n]), offsets)
+            out = np.empty(int(offsets[n]), np.uint8)
+            rc = self.lib.pb_jpeg_encode(self.ctx, C.byref(cfg), _ptr(planes), n, int(H), int(W), _ptr(out), out.size, _ptr(offsets))
+        check(rc)
+        return out, offsets
+
+    def jpeg_encode_dev(self, planes_ptr: int, n: int, H: int, W: int, chroma: int, quality: int, out_ptr: int, capacity: int, offsets_ptr: int):
+        """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_jpeg_encode_dev): sync() waits; offsets_ptr takes n + 1 int64,
+        of which the last is the bytes needed - more than `capacity` means the frames past it were not written"""
+        check(self.lib.pb_jpeg_encode_dev(self.ctx, C.byref(_lib.pb_jpeg_cfg(int(chroma), int(quality))), C.c_void_p(planes_ptr), n, int(H), int(W),
+                                          C.c_void_p(out_ptr), int(capacity), C.c_void_p(offsets_ptr)))
 
     def i420_to_rgb_dev(self, yuv_ptr: int, n: int, H: int, W: int, rgb_ptr: int):
         """the same on device pointers (dev_alloc), enqueued on the ctx stream (pb_i420_to_rgb_dev): sync() waits"""

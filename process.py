@@ -40,7 +40,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 from bands.common.io import get_image_size, get_video_data, y4m_out  # noqa: E402
 from bands.common.meta import (add_band, create_metadata, get_record3d_data, is_video, load_metadata,  # noqa: E402
-                               set_default_band, update_metadata, write_metadata)
+                               set_default_band, update_metadata, video_out, write_metadata)
 
 # Default BANDS & MODELS (reference :17-30; defaults narrowed to what is built here)
 BUILT = ("rgba", "depth_anything", "flow_raft", "flow_gmflow", "mask_mmdet")
@@ -227,9 +227,23 @@ def main(argv=None):
     parser.add_argument("--y4m_out", help="Layout of the .y4m videos the bands write: a C tag, then ,full and / or ,bt709 (C444p12,full is lossless, "
                         "Cmono,full for grey bands), or `source`; default 8-bit 4:2:0 limited BT.601 (sets PRISMA_Y4M_OUT for the bands)",
                         type=str, default=None, metavar="FORMAT")
+    parser.add_argument("--video_out", help="Container of the video bands derived from a clip: avi or mjpeg (Motion JPEG, encoded on the GPU), then "
+                        "optionally ,q=NN (quality, default 90) and one of ,444 ,420 ,mono (default 444); default the clip's own container "
+                        "(sets PRISMA_VIDEO_OUT for the bands; rgba keeps the clip's)", type=str, default=None, metavar="FORMAT")
     args = parser.parse_args(argv)
     if args.jobs < 1 or args.gpus < 1:
         parser.error("--jobs and --gpus must be at least 1")
+    before = os.environ.get("PRISMA_VIDEO_OUT")
+    if args.video_out is not None:
+        os.environ["PRISMA_VIDEO_OUT"] = args.video_out      # the band subprocesses inherit it
+    try:
+        video_out()         # from the option or the environment: refused here, before any band starts
+    except RuntimeError as e:
+        if args.video_out is not None:
+            os.environ.pop("PRISMA_VIDEO_OUT")
+            if before is not None:
+                os.environ["PRISMA_VIDEO_OUT"] = before
+        parser.error("--video_out: %s" % e)
     if args.y4m_out is not None:
         before = os.environ.get("PRISMA_Y4M_OUT")
         os.environ["PRISMA_Y4M_OUT"] = args.y4m_out        # the band subprocesses inherit it; the rgba band still copies a .y4m input as it is
