@@ -408,7 +408,9 @@ int pb_depth_net_size(int H, int W, int *net_h, int *net_w);
  *     flow_out   [F-1, dirs, sh, sw, 2] float32 (u, v) pixels at the scaled resolution, or NULL
  *     rgb_out    [F-1, dirs, sh, sw, 3] uint8 process_flow encoding, or NULL
  *     maxdisp_out[F-1, dirs] float32 max displacement (the band's CSV value), or NULL
- *   (sh, sw) = pb_flow_out_size(H, W, scale). */
+ *   (sh, sw) = pb_flow_out_size(H, W, scale).
+ *   scale      : the reference computes with Python's double; every call here takes the float's shortest round-trip decimal as that double
+ *                (0.6f -> 0.6, not 0.60000002384), so sizes and resize taps are the reference's for any scale of up to 7 significant digits. */
 int pb_flow_out_size(int H, int W, float scale, int *sh, int *sw);
 int pb_flow_infer_sequence(pb_ctx *ctx, const uint8_t *frames, int F, int H, int W, float scale, int iters, int backward,
                            float *flow_out, uint8_t *rgb_out, float *maxdisp_out);
@@ -683,6 +685,25 @@ int pb_op_raft_instnorm(pb_ctx *ctx, const float *a, const float *b, int B, int 
                         int guard_rows, float *stats, void *out);
 int pb_op_raft_state(pb_ctx *ctx, const float *ctx_rows, const float *flow, int rows, int ld, int inp_off, int guard_rows, float *h32, void *hx,
                      void *hx2, float *flow0);
+/* The flow bands' frame path outside the networks - the first kernel and the last kernels of every flow_raft / flow_gmflow call
+ * (tests/test_gpu_flow_io_ops.py).  Outputs are preset to 0xFF bytes and carry a guard, as above.
+ * pb_op_flow_geometry (no GPU needed): geo[0..8] = {sh, sw, Hp, Wp, pad_l, pad_t, h8, w8, P} of an H x W frame at `scale`, padded to a multiple
+ *   of `factor` (8, 16 or 32) - the function the engines plan with.
+ * pb_op_flow_taps (no GPU needed): the 8-bit cubic table of one axis the engines upload: idx, co [dst, 4] (co = coefficient x 2048).
+ * flow_prep: n uint8 frames [n, H, W, 3] through ONE launch of the prep kernel with the engines' arguments.  norm_mode 0: RAFT's 2 x / 255 - 1,
+ *   1: GMFlow's ImageNet mean / std.  isz_h, isz_w > 0: GMFlow's --inference_size (bilinear, align_corners, no padding; Hp x Wp = the
+ *   inference size).  out: (n Hp / 4 Wp / 4 + guard_rows) rows of one 4 x 4 block each - layout 0: 64 halfs (((y & 3) 4 + (x & 3)) 4 + c,
+ *   channel 3 zero), 1: [hi | lo] 128 halfs, 2: [hi (64 halfs) | hi8 (64 bytes) | lo8 (64 bytes)] with the e4m3 scales 2^*lo8_pa and
+ *   2^(*lo8_pa + 12).  scaled: the scaled uint8 frames [n, sh, sw, 3] + guard bytes (left preset with an inference size).
+ * flow_resize_back: in [n, ih, iw, 2] -> out [n, sh, sw, 2] + guard floats (bilinear, align_corners, u sw / iw, v sh / ih); maxd [n]: the
+ *   per-frame maximum displacement as the encode kernel decodes it.
+ * flow_encode: flow [n, sh, sw, 2] and the per-frame maximum maxd [n] -> rgb [n, sh, sw, 3] + guard bytes, max_out [n]. */
+int pb_op_flow_geometry(int H, int W, float scale, int factor, int *geo);
+int pb_op_flow_taps(int src, int dst, float scale, int *idx, int *co);
+int pb_op_flow_prep(pb_ctx *ctx, const uint8_t *frames, int n, int H, int W, float scale, int factor, int layout, int norm_mode, int isz_h,
+                    int isz_w, int guard_rows, int guard, void *out, uint8_t *scaled, int *lo8_pa);
+int pb_op_flow_resize_back(pb_ctx *ctx, const float *in, int n, int ih, int iw, int sh, int sw, int guard, float *out, float *maxd);
+int pb_op_flow_encode(pb_ctx *ctx, const float *flow, const float *maxd, int n, int sh, int sw, int guard, uint8_t *rgb, float *max_out);
 /* The flow_gmflow band's own kernels one by one, through the launchers and arguments GmflowEngine::infer uses (tests/test_gpu_gmflow_ops.py).
  * (h8, w8) is the 1/8-resolution token grid (both even, >= 4): P = h8 w8 tokens per image, 2 x 2 windows of Lw = P / 4 tokens, V^T row strides
  * ldv = Lw and ldvP = P rounded up to 32.  Raw buffers are preset to 0xFF bytes and carry guard_rows untouched rows, as above.

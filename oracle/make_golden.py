@@ -409,7 +409,7 @@ def gmflow_full_case(seed=61):
     """flow_gmflow at the size the bench times it: one 1920x1080 pair at the band's default --scale 0.75
     (810x1440 -> InputPadder(16) -> 816x1440: a 102 x 180 grid, 18 360 tokens, 18 360^2 global matching) through the REAL reference
     GMFlow, forward direction, committed as 1/8-strided samples + float64 sums (as raft_full).  cv2 is absent here, so the reference
-    network is fed the oracle's 8-bit cubic resize (unpinned; GPU == oracle bit for bit) - the golden pins the network at that size."""
+    network is fed the oracle's 8-bit cubic resize (unpinned; GPU == oracle bit for bit: tests/test_gpu_flow_io_ops.py::test_prep_direct) - the golden pins the network at that size."""
     import time
     sys.modules.setdefault("cv2", types.ModuleType("cv2"))
     from gmflow.gmflow import GMFlow

@@ -245,8 +245,8 @@ def atan2_rn(y: np.ndarray, x: np.ndarray) -> np.ndarray:
             p = p * u2 + _ATAN_COEF[i]
         r = _ATAN_C[np.where(np.isnan(k), 0, k).astype(np.int64)] + u * p
         r = np.where(ay > ax, 1.5707963267948966 - r, r)
-        r = np.where(x < 0.0, 3.141592653589793 - r, r)
-        r = np.where(y < 0.0, -r, r)
+        r = np.where(np.signbit(x), 3.141592653589793 - r, r)        # the sign BIT: atan2(+-0, -1) = +-pi, atan2(+0, -0) = pi
+        r = np.where(np.signbit(y), -r, r)
     return np.where(np.isnan(t), np.nan, r)
 
 

@@ -187,6 +187,11 @@ SYMBOLS = {
     "pb_op_raft_upsample": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),
     "pb_op_raft_instnorm": (C.c_int, [_P, _P, _P] + [C.c_int] * 8 + [_P, _P]),
     "pb_op_raft_state": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P, _P, _P, _P]),
+    "pb_op_flow_geometry": (C.c_int, [C.c_int, C.c_int, C.c_float, C.c_int, C.POINTER(C.c_int)]),
+    "pb_op_flow_taps": (C.c_int, [C.c_int, C.c_int, C.c_float, _P, _P]),
+    "pb_op_flow_prep": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float] + [C.c_int] * 7 + [_P, _P, C.POINTER(C.c_int)]),
+    "pb_op_flow_resize_back": (C.c_int, [_P, _P] + [C.c_int] * 6 + [_P, _P]),
+    "pb_op_flow_encode": (C.c_int, [_P, _P, _P] + [C.c_int] * 4 + [_P, _P]),
     "pb_op_gm_tables": (C.c_int, [C.c_int, C.c_int, _P, _P]),
     "pb_op_gm_tables_n": (C.c_int, [C.c_int, C.c_int, C.c_int, _P, _P]),
     "pb_op_gm_tokens_warped": (C.c_int, [_P, _P, _P, _P] + [C.c_int] * 4 + [_P, _P]),

@@ -15,6 +15,8 @@
 void pb_cubic_taps(int src, int dst, int *idx, float *wt);   // engine.hip
 void pb_bilinear_ac_taps(int src, int dst, int *idx, float *wt);   // engine.hip: the metric band's align-corners table, 4 taps of which two weigh 0
 
+void pb_flow_cubic_taps(int src, int dst, float scale, std::vector<int> &idx, std::vector<int> &co);   // flow_engine.hip: the flow bands' 8-bit cubic table
+
 #define PB_TRY(expr) do { int _r = (expr); if (_r) return _r; } while (0)
 
 // Streams, events and double-buffered slots of the chunked host-pointer entry points (pb_depth_infer_batch, pb_flow_infer_sequence and their

@@ -7,6 +7,7 @@
 
 #include "abi_ctx.h"
 #include "corr_layout.h"
+#include "flow_chunk.h"
 #include "gmflow_engine.h"
 #include "mask_kernels.h"
 #include "zoe_kernels.h"
@@ -302,6 +303,74 @@ class RaftOpEngine : public SplitOpEngine {
         PB_TRY(launch_flow_encode(stream, dup.as<float>(), n, sh, sw, dmax.as<unsigned>(), nullptr, dmx.as<float>()));     // decodes maxd, no colours
         PB_TRY(finish(upo, dup, (size_t)(px * 2 + guard) * 4));
         PB_HIP(hipMemcpy(maxd, dmx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+    // The flow bands' frame path outside the networks (pb_op_flow_*).  flow_prep: ONE launch_raft_prep as FlowEngine::prep_frames issues it -
+    // always space-to-depth, the geometry of flow_geometry (GmflowEngine::prepare_g's override with an inference size), the tap tables of
+    // upload_resize_tables - plus the scaled uint8 frame the engines never ask for.  layout 0: 64 halfs per 4 x 4 block, 1: [hi | lo],
+    // 2: [hi | hi8 | lo8] (128 halfs per block)
+    int flow_prep(const uint8_t *frames, int n, int H, int W, float scale, int factor, int layout, int norm_mode, int isz_h, int isz_w,
+                  int guard_rows, int guard, void *out, uint8_t *scaled, int *lo8_pa) {
+        FlowGeometry g = flow_geometry(H, W, scale, factor);
+        if (isz_h > 0) { g.padl = g.padt = 0; g.Hp = isz_h; g.Wp = isz_w; }
+        PB_CHECK(g.sh > 0 && g.sw > 0 && g.Hp % 4 == 0 && g.Wp % 4 == 0, PB_ERR_ARG, "op_flow_prep: %d x %d scaled, %d x %d padded", g.sh, g.sw, g.Hp, g.Wp);
+        const int resize = scale != 1.f;
+        DevMem df, dxi, dxc, dyi, dyc, dout, dsc;
+        if (resize) {
+            std::vector<int> xi, xc, yi, yc;
+            pb_flow_cubic_taps(W, g.sw, scale, xi, xc);
+            pb_flow_cubic_taps(H, g.sh, scale, yi, yc);
+            for (int v : xi) PB_CHECK(v >= 0 && v < W, PB_ERR_STATE, "op_flow_prep: x tap %d outside a row of %d pixels", v, W);
+            for (int v : yi) PB_CHECK(v >= 0 && v < H, PB_ERR_STATE, "op_flow_prep: y tap %d outside %d rows", v, H);
+            PB_TRY(up(dxi, xi.data(), xi.size() * 4)); PB_TRY(up(dxc, xc.data(), xc.size() * 4));
+            PB_TRY(up(dyi, yi.data(), yi.size() * 4)); PB_TRY(up(dyc, yc.data(), yc.size() * 4));
+        }
+        const int lo_off = layout ? 64 : 0, ld = layout ? 128 : 64;
+        const int64_t rows = (int64_t)n * (g.Hp / 4) * (g.Wp / 4);
+        const size_t ob = (size_t)(rows + guard_rows) * ld * 2, sb = (size_t)n * g.sh * g.sw * 3 + guard;
+        PB_TRY(up(df, frames, (size_t)n * H * W * 3));
+        PB_TRY(preset(dout, ob)); PB_TRY(preset(dsc, sb));
+        PB_TRY(launch_raft_prep(stream, df.as<uint8_t>(), n, H, W, g.sh, g.sw, g.Hp, g.Wp, g.padl, g.padt, resize, dxi.as<int>(), dxc.as<int>(), dyi.as<int>(),
+                                dyc.as<int>(), dout.as<f16>(), dsc.as<uint8_t>(), 1, lo_off, layout == 2 ? kLo8Pa : -1, norm_mode, isz_h > 0));
+        PB_TRY(finish(out, dout, ob));
+        PB_HIP(hipMemcpy(scaled, dsc.p, sb, hipMemcpyDeviceToHost));
+        if (lo8_pa) *lo8_pa = kLo8Pa;
+        return 0;
+    }
+
+    // in [n, ih, iw, 2] -> out [n, sh, sw, 2] + guard floats, maxd [n] as the encode kernel decodes it (its words preset, not zeroed)
+    int flow_resize_back(const float *in, int n, int ih, int iw, int sh, int sw, int guard, float *out, float *maxd) {
+        const int64_t px = (int64_t)n * sh * sw;
+        DevMem din, dout, dmax, dmx;
+        PB_TRY(up(din, in, (size_t)n * ih * iw * 8));
+        PB_TRY(preset(dout, (size_t)(px * 2 + guard) * 4));
+        PB_TRY(preset(dmax, (size_t)n * 4));
+        PB_TRY(dmx.alloc((size_t)n * 4));
+        PB_TRY(launch_flow_resize_back(stream, din.as<float>(), n, ih, iw, sh, sw, dout.as<float>(), dmax.as<unsigned>()));
+        PB_TRY(launch_flow_encode(stream, dout.as<float>(), n, sh, sw, dmax.as<unsigned>(), nullptr, dmx.as<float>()));
+        PB_TRY(finish(out, dout, (size_t)(px * 2 + guard) * 4));
+        PB_HIP(hipMemcpy(maxd, dmx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+        return 0;
+    }
+
+    // flow [n, sh, sw, 2], maxd [n] (stored in the ordered-unsigned form of the kernels' atomicMax) -> rgb [n, sh, sw, 3] + guard bytes, max_out [n]
+    int flow_encode(const float *flow, const float *maxd, int n, int sh, int sw, int guard, uint8_t *rgb, float *max_out) {
+        const int64_t px = (int64_t)n * sh * sw;
+        std::vector<unsigned> ord((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            unsigned u;
+            memcpy(&u, maxd + i, 4);
+            ord[i] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+        }
+        DevMem dflow, drgb, dmax, dmx;
+        PB_TRY(up(dflow, flow, (size_t)px * 8));
+        PB_TRY(up(dmax, ord.data(), (size_t)n * 4));
+        PB_TRY(preset(drgb, (size_t)px * 3 + guard));
+        PB_TRY(preset(dmx, (size_t)n * 4));
+        PB_TRY(launch_flow_encode(stream, dflow.as<float>(), n, sh, sw, dmax.as<unsigned>(), drgb.as<uint8_t>(), dmx.as<float>()));
+        PB_TRY(finish(rgb, drgb, (size_t)px * 3 + guard));
+        PB_HIP(hipMemcpy(max_out, dmx.p, (size_t)n * 4, hipMemcpyDeviceToHost));
         return 0;
     }
 
@@ -1818,6 +1887,41 @@ int pb_op_raft_state(pb_ctx *c, const float *ctx_rows, const float *flow, int ro
              guard_rows >= 0, PB_ERR_ARG, "op_raft_state: bad arguments");
     RAFT_OP_ENGINE(e);
     return e.state(ctx_rows, flow, rows, ld, inp_off, guard_rows, h32, hx, hx2, flow0);
+}
+
+// ---- the flow bands' frame prep and flow tail (RaftOpEngine above); geometry and taps need no GPU ----
+int pb_op_flow_geometry(int H, int W, float scale, int factor, int *geo) {
+    PB_CHECK(geo && H > 0 && W > 0 && scale > 0.f && (factor == 8 || factor == 16 || factor == 32), PB_ERR_ARG, "op_flow_geometry: bad arguments");
+    const FlowGeometry g = flow_geometry(H, W, scale, factor);
+    const int v[9] = {g.sh, g.sw, g.Hp, g.Wp, g.padl, g.padt, g.h8, g.w8, g.P};
+    memcpy(geo, v, sizeof(v));
+    return 0;
+}
+int pb_op_flow_taps(int src, int dst, float scale, int *idx, int *co) {
+    PB_CHECK(idx && co && src > 0 && dst > 0 && scale > 0.f, PB_ERR_ARG, "op_flow_taps: bad arguments");
+    std::vector<int> i, c;
+    pb_flow_cubic_taps(src, dst, scale, i, c);
+    memcpy(idx, i.data(), i.size() * 4);
+    memcpy(co, c.data(), c.size() * 4);
+    return 0;
+}
+int pb_op_flow_prep(pb_ctx *c, const uint8_t *frames, int n, int H, int W, float scale, int factor, int layout, int norm_mode, int isz_h, int isz_w,
+                    int guard_rows, int guard, void *out, uint8_t *scaled, int *lo8_pa) {
+    PB_CHECK(c && frames && out && scaled && n > 0 && H > 0 && W > 0 && scale > 0.f && (factor == 8 || factor == 16 || factor == 32) && layout >= 0 &&
+             layout <= 2 && (norm_mode == 0 || norm_mode == 1) && isz_h >= 0 && (isz_h > 0) == (isz_w > 0) && guard_rows >= 0 && guard >= 0, PB_ERR_ARG,
+             "op_flow_prep: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.flow_prep(frames, n, H, W, scale, factor, layout, norm_mode, isz_h, isz_w, guard_rows, guard, out, scaled, lo8_pa);
+}
+int pb_op_flow_resize_back(pb_ctx *c, const float *in, int n, int ih, int iw, int sh, int sw, int guard, float *out, float *maxd) {
+    PB_CHECK(c && in && out && maxd && n > 0 && ih > 0 && iw > 0 && sh > 0 && sw > 0 && guard >= 0, PB_ERR_ARG, "op_flow_resize_back: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.flow_resize_back(in, n, ih, iw, sh, sw, guard, out, maxd);
+}
+int pb_op_flow_encode(pb_ctx *c, const float *flow, const float *maxd, int n, int sh, int sw, int guard, uint8_t *rgb, float *max_out) {
+    PB_CHECK(c && flow && maxd && rgb && max_out && n > 0 && sh > 0 && sw > 0 && guard >= 0, PB_ERR_ARG, "op_flow_encode: bad arguments");
+    RAFT_OP_ENGINE(e);
+    return e.flow_encode(flow, maxd, n, sh, sw, guard, rgb, max_out);
 }
 
 // ---- the flow_gmflow band's kernels one by one (GmOpEngine above) ----

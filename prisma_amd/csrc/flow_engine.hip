@@ -31,6 +31,12 @@ void cubic_taps_u8(int src, int dst, double scale, std::vector<int> &idx, std::v
 }
 }  // namespace
 
+// The tap table of one axis as upload_resize_tables builds it, with external linkage (as pb_cubic_taps, engine.hip): pb_op_flow_prep and
+// pb_op_flow_taps hand the tests the table the engines upload.  scale: the call's float, taken through flow_scale_exact (flow_chunk.h)
+void pb_flow_cubic_taps(int src, int dst, float scale, std::vector<int> &idx, std::vector<int> &co) {
+    cubic_taps_u8(src, dst, flow_scale_exact(scale), idx, co);
+}
+
 void FlowEngine::out_size(int H, int W, float scale, int *sh, int *sw) {
     const FlowGeometry g = flow_geometry(H, W, scale, 8);
     *sh = g.sh; *sw = g.sw;
@@ -110,8 +116,8 @@ void FlowEngine::carve_encoder(int F) {
 int FlowEngine::upload_resize_tables(int H, int W, float scale) {
     if (scale != 1.f) {
         std::vector<int> xi, xc, yi, yc;
-        cubic_taps_u8(W, sw_, scale, xi, xc);
-        cubic_taps_u8(H, sh_, scale, yi, yc);
+        pb_flow_cubic_taps(W, sw_, scale, xi, xc);
+        pb_flow_cubic_taps(H, sh_, scale, yi, yc);
         PB_HIP(hipMemcpyAsync(xi_, xi.data(), xi.size() * 4, hipMemcpyHostToDevice, stream));
         PB_HIP(hipMemcpyAsync(xc_, xc.data(), xc.size() * 4, hipMemcpyHostToDevice, stream));
         PB_HIP(hipMemcpyAsync(yi_, yi.data(), yi.size() * 4, hipMemcpyHostToDevice, stream));

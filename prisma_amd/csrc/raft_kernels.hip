@@ -68,7 +68,9 @@ __global__ __launch_bounds__(256) void raft_prep_kernel(const uint8_t *__restric
         // the scaled frame as float - no padding; torch's arithmetic: src = dst * (in - 1) / (out - 1), weights (1 - l, l), rows of the
         // horizontal blends
         const float ry = Hp > 1 ? (float)(sh - 1) / (float)(Hp - 1) : 0.f, rx = Wp > 1 ? (float)(sw - 1) / (float)(Wp - 1) : 0.f;
-        const float fy = ry * (float)y, fx = rx * (float)x;
+        // the products rounded on their own (ex_fmul): contracted into the subtractions below, the weights would come from the unrounded
+        // product while the indices come from the rounded one - where ry y rounds up to an integer, a weight of -8e-7 instead of torch's 0
+        const float fy = ex_fmul(ry, (float)y), fx = ex_fmul(rx, (float)x);
         const int y0 = (int)fy, x0 = (int)fx;
         const int y1 = y0 + (y0 < sh - 1 ? 1 : 0), x1 = x0 + (x0 < sw - 1 ? 1 : 0);
         const float ly = fy - (float)y0, lx = fx - (float)x0;
@@ -857,8 +859,8 @@ __device__ __forceinline__ double atan2_rn(double y, double x) {
     p = ex_dadd(ex_dmul(p, u2), 1.0);
     double r = ex_dadd(ATAN_C[(int)k], ex_dmul(u, p));
     if (ay > ax) r = ex_dsub(1.5707963267948966, r);
-    if (x < 0.0) r = ex_dsub(3.141592653589793, r);
-    if (y < 0.0) r = -r;
+    if (__builtin_signbit(x)) r = ex_dsub(3.141592653589793, r);     // the sign BIT, as atan2 takes it: (+-0, -1) -> +-pi, (+0, -0) -> pi
+    if (__builtin_signbit(y)) r = -r;
     return r;
 }
 
@@ -1109,7 +1111,7 @@ __global__ __launch_bounds__(256) void flow_resize_back_kernel(const float *__re
     float dmax = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)sh * sw; i += (int64_t)gridDim.x * 256) {
         const int y = (int)(i / sw), x = (int)(i - (int64_t)y * sw);
-        const float fy = ry * (float)y, fx = rx * (float)x;
+        const float fy = ex_fmul(ry, (float)y), fx = ex_fmul(rx, (float)x);       // rounded on their own, as in raft_prep_kernel
         const int y0 = (int)fy, x0 = (int)fx;
         const int y1 = y0 + (y0 < ih - 1 ? 1 : 0), x1 = x0 + (x0 < iw - 1 ? 1 : 0);
         const float ly = fy - (float)y0, lx = fx - (float)x0;

@@ -544,6 +544,24 @@ def raft_geometry(h8: int, w8: int) -> List[dict]:
     return [dict(h=geo[l * 5], w=geo[l * 5 + 1], wp=geo[l * 5 + 2], hp=geo[l * 5 + 3], ld=geo[l * 5 + 4]) for l in range(4)]
 
 
+FLOW_GEO = ("sh", "sw", "Hp", "Wp", "padl", "padt", "h8", "w8", "P")
+
+
+def flow_geometry(H: int, W: int, scale: float, factor: int = 8) -> dict:
+    """the flow bands' plan of an H x W frame (csrc flow_chunk.h flow_geometry; needs no GPU): the scaled size, its padding to a multiple of
+    `factor` (8 RAFT, 16 GMFlow, 32 two-scale GMFlow) and the 1/8 grid"""
+    geo = (C.c_int * 9)()
+    check(_lib.load().pb_op_flow_geometry(H, W, C.c_float(scale), factor, geo))
+    return dict(zip(FLOW_GEO, geo))
+
+
+def flow_taps(src: int, dst: int, scale: float):
+    """one axis of the flow bands' 8-bit cubic resize table, as the engines upload it (needs no GPU) -> (idx [dst, 4], co [dst, 4] int32)"""
+    idx, co = np.empty((dst, 4), np.int32), np.empty((dst, 4), np.int32)
+    check(_lib.load().pb_op_flow_taps(src, dst, C.c_float(scale), _ptr(idx), _ptr(co)))
+    return idx, co
+
+
 def corr_layout_index(layout: int, P: int, pld: int) -> np.ndarray:
     """[P, pld] int64: where entry c of source row p sits in a level of flow_raft's correlation volume, layout 0 row-major / 1 source-blocked
     (csrc/corr_layout.h, the function the kernels compile; needs no GPU)"""
@@ -924,6 +942,49 @@ class Ops(_Ctx):
         f0 = np.empty((rows + guard_rows, 2), np.float32)
         check(self.lib.pb_op_raft_state(self.ctx, _ptr(ctx_rows), _ptr(flow), rows, ld, inp_off, guard_rows, _ptr(h32), _ptr(hx), _ptr(hx2), _ptr(f0)))
         return h32, hx, hx2, f0
+
+    # ---- the flow bands' frame prep and flow tail (pb_op_flow_*; tests/test_gpu_flow_io_ops.py) ----
+    def flow_prep(self, frames, scale: float, factor: int, layout: int, norm_mode: int, inference_size=None, guard_rows: int = 8, guard: int = 64):
+        """frames uint8 [n, H, W, 3] through one launch of the prep kernel -> (geo dict (flow_geometry; Hp, Wp the inference size when given),
+        raw uint8 [n Hp/4 Wp/4 + guard_rows, 128 (layout 0) | 256] one 4 x 4 block per row, scaled uint8 [n, sh, sw, 3], the guard bytes behind
+        it, lo8_pa)"""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        n, H, W, _ = frames.shape
+        geo = flow_geometry(H, W, scale, factor)
+        ih, iw = inference_size if inference_size else (0, 0)
+        if inference_size:
+            geo.update(Hp=ih, Wp=iw, padl=0, padt=0, h8=ih // 8, w8=iw // 8, P=(ih // 8) * (iw // 8))
+        rows = n * (geo["Hp"] // 4) * (geo["Wp"] // 4)
+        raw = np.empty((rows + guard_rows, 256 if layout else 128), np.uint8)
+        sc = np.empty(n * geo["sh"] * geo["sw"] * 3 + guard, np.uint8)
+        pa = C.c_int(-1)
+        check(self.lib.pb_op_flow_prep(self.ctx, _ptr(frames), n, H, W, C.c_float(scale), factor, layout, norm_mode, ih, iw, guard_rows, guard,
+                                       _ptr(raw), _ptr(sc), C.byref(pa)))
+        cut = n * geo["sh"] * geo["sw"] * 3
+        return geo, raw, sc[:cut].reshape(n, geo["sh"], geo["sw"], 3), sc[cut:], pa.value
+
+    def flow_resize_back(self, flow, sh: int, sw: int, guard: int = 64):
+        """flow [n, ih, iw, 2] -> (out [n, sh, sw, 2], guard floats behind it, maxd [n])"""
+        flow = _f32(flow)
+        n, ih, iw, _ = flow.shape
+        buf = np.empty(n * sh * sw * 2 + guard, np.float32)
+        mx = np.empty(n, np.float32)
+        check(self.lib.pb_op_flow_resize_back(self.ctx, _ptr(flow), n, ih, iw, sh, sw, guard, _ptr(buf), _ptr(mx)))
+        return buf[:n * sh * sw * 2].reshape(n, sh, sw, 2), buf[n * sh * sw * 2:], mx
+
+    def flow_encode(self, flow, maxd, guard: int = 64):
+        """flow [n, sh, sw, 2], maxd [n] -> (rgb uint8 [n, sh, sw, 3], guard bytes behind it, max_out [n])"""
+        flow, maxd = _f32(flow), _f32(maxd)
+        n, sh, sw, _ = flow.shape
+        assert maxd.shape == (n,)
+        buf = np.empty(n * sh * sw * 3 + guard, np.uint8)
+        mx = np.empty(n, np.float32)
+        check(self.lib.pb_op_flow_encode(self.ctx, _ptr(flow), _ptr(maxd), n, sh, sw, guard, _ptr(buf), _ptr(mx)))
+        return buf[:n * sh * sw * 3].reshape(n, sh, sw, 3), buf[n * sh * sw * 3:], mx
+
+    def flow_fwdbwd_mask(self, flows, alpha_1: float = 0.05, alpha_2: float = 0.5) -> np.ndarray:
+        """pb_flow_fwdbwd_mask on an ops context: flows [n, 2, sh, sw, 2] -> bool [n, 2, sh, sw]"""
+        return _fwdbwd_mask(self, flows, alpha_1, alpha_2)
 
     # ---- the flow_gmflow band's kernels one by one (pb_op_gm_*, pb_op_attention128_cfg; tests/test_gpu_gmflow_ops.py) ----
     # raw buffers come back as uint8 [rows + guard_rows, bytes per row]: 0xFF wherever the kernel did not write
@@ -1478,6 +1539,16 @@ class DepthAnything(_Ctx):
                                                 v(min_ptr), v(max_ptr), int(flip)))
 
 
+def _fwdbwd_mask(ctx: "_Ctx", flows, alpha_1: float, alpha_2: float) -> np.ndarray:
+    """pb_flow_fwdbwd_mask on any context (it needs a device and a stream, no band): flows f32 [n, 2, sh, sw, 2] -> bool [n, 2, sh, sw]"""
+    flows = np.ascontiguousarray(flows, np.float32)
+    n, d, sh, sw, two = flows.shape
+    assert d == 2 and two == 2
+    mask = np.empty((n, 2, sh, sw), np.uint8)
+    check(ctx.lib.pb_flow_fwdbwd_mask(ctx.ctx, _ptr(flows), n, sh, sw, C.c_float(alpha_1), C.c_float(alpha_2), _ptr(mask)))
+    return mask.view(np.bool_)
+
+
 def flow_out_size(H: int, W: int, scale: float) -> Tuple[int, int]:
     sh, sw = C.c_int(), C.c_int()
     check(_lib.load().pb_flow_out_size(H, W, C.c_float(scale), C.byref(sh), C.byref(sw)))
@@ -1584,12 +1655,7 @@ class FlowRaft(_Ctx):
 
     def fwdbwd_mask(self, flows: np.ndarray, alpha_1: float = 0.05, alpha_2: float = 0.5) -> np.ndarray:
         """flows f32 [n,2,sh,sw,2] (forward, backward) -> bool [n,2,sh,sw] (bands/common/flow.py:28-40)."""
-        flows = np.ascontiguousarray(flows, np.float32)
-        n, d, sh, sw, two = flows.shape
-        assert d == 2 and two == 2
-        mask = np.empty((n, 2, sh, sw), np.uint8)
-        check(self.lib.pb_flow_fwdbwd_mask(self.ctx, _ptr(flows), n, sh, sw, C.c_float(alpha_1), C.c_float(alpha_2), _ptr(mask)))
-        return mask.view(np.bool_)
+        return _fwdbwd_mask(self, flows, alpha_1, alpha_2)
 
     def infer_sequence_dev(self, frames_ptr: int, F: int, H: int, W: int, scale: float, iters: int, backward: bool,
                            flow_ptr: int = 0, rgb_ptr: int = 0, max_ptr: int = 0):

@@ -22,6 +22,10 @@ int main(int argc, char **argv) {
         }
         return 0;
     }
+    if (argc > 1 && !strcmp(argv[1], "exact")) {        // exact scale ...: flow_scale_exact of every scale, narrowed to float as the C ABI carries it
+        for (int i = 2; i < argc; ++i) printf("%.17g\n", flow_scale_exact((float)atof(argv[i])));
+        return 0;
+    }
     for (int i = 1; i + 3 < argc; i += 4)
         printf("%d\n", flow_chunk_pairs(atoi(argv[i]), atoi(argv[i + 1]), atoll(argv[i + 2]), atoll(argv[i + 3])));
     return 0;
@@ -88,6 +92,32 @@ def test_flow_geometry_against_brute_force_padder(exe):
     # the ragged grids the GPU tests run on, and no padding where the size is a multiple of the factor already
     assert (got[0]["h8"], got[0]["w8"]) == (16, 20) and (got[1]["h8"], got[1]["w8"]) == (17, 23)
     assert all(g["Hp"] == 96 and g["Wp"] == 128 and g["padl"] == 0 and g["padt"] == 0 for g in got[5:])
+
+
+def test_scale_exact_is_the_double_the_caller_typed(exe):
+    """the C ABI carries --scale as a float, the reference computes with Python's double: flow_scale_exact gives that double back - for every
+    scale of EXPERIMENTS 6.30's table, for two- to seven-digit literals, and unchanged where the float is the number itself (dyadic scales)"""
+    scales = [0.75, 0.5, 0.25, 0.4, 0.8, 1.25, 1.5, 0.6, 0.3, 0.9, 0.7, 0.35, 1.0, 2.0, 0.1, 0.05, 0.333, 0.6667, 1.23456, 0.1234567, 3.0, 0.0625]
+    out = subprocess.run([exe, "exact"] + [repr(s) for s in scales], check=True, capture_output=True, text=True).stdout.split()
+    assert [float(o) for o in out] == scales
+    # plain arithmetic (no text, no locale): held against numpy's shortest round-trip decimal of the float on 4000 literals of 1 - 7 digits
+    # between 1e-3 and 1e3, and against the widened float where the helper steps aside
+    import numpy as np
+    g = np.random.default_rng(3)
+    lits = [float("%.*e" % (int(d), v)) for d, v in zip(g.integers(0, 7, 4000), 10.0 ** g.uniform(-3, 3, 4000))]
+    out = subprocess.run([exe, "exact"] + [repr(v) for v in lits], check=True, capture_output=True, text=True).stdout.split()
+    want = [float(np.format_float_positional(np.float32(v), unique=True)) for v in lits]
+    assert [float(o) for o in out] == want == lits
+    out = subprocess.run([exe, "exact", "1e-20", "3e15"], check=True, capture_output=True, text=True).stdout.split()
+    assert [float(o) for o in out] == [float(np.float32(1e-20)), float(np.float32(3e15))]
+    import struct
+    widened = lambda s: struct.unpack("f", struct.pack("f", s))[0]
+    assert all(widened(s) == s for s in (0.75, 0.5, 1.0)) and all(widened(s) != s for s in (0.6, 0.3, 0.9, 0.7, 0.35))
+    # sizes the widened float gets wrong - the double's products are half-even ties (4.5, 10.5, 3.5, 17.5), the widened float's fall beside
+    # them - and a tie of a dyadic scale
+    got = geometry(exe, [(15, 35, 0.3, 8), (5, 25, 0.7, 8), (2, 6, 0.75, 8)])
+    assert [(g["sh"], g["sw"]) for g in got] == [(4, 10), (4, 18), (2, 4)]
+    assert [(round(15 * widened(0.3)), round(35 * widened(0.3))), (round(5 * widened(0.7)), round(25 * widened(0.7)))] == [(5, 11), (3, 17)]
 
 
 def test_chunk_pairs_against_brute_force(exe):
